@@ -1,13 +1,26 @@
 #!/usr/bin/env python
 """bench.py -- rating-nonzeros/sec per CAVI iteration (steps A-F) on MI355X.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--config C2]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--config C2] [--full] [--dump-outputs DIR]
   python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 
 A "step" is one full CAVI iteration (phi passes + row sweeps; report steps
 excluded) over one synthetic ratings matrix that is resident in HBM before the
 timed region starts (generated on the GPU, handed over with
 hpf_upload_csr_device / hpf_set_state_device: no PCIe inside or before `value`).
+
+A plain run sets up, warms up, times K steps and prints the line: the contract's fields, the
+per-kernel hipEvent times of the timed steps, the work lists, the hand-over times and the
+`roofline` block from the algorithmic bytes of those times.  Every check and side measurement
+listed below (self_check, the PMC passes behind roofline.traffic, the gather-only and copy
+probes, other_configs, cpu_baseline, w48_opt_in, and for N > 1 the replica check, both exchange
+orders, the rccl block and the one-GPU reference) runs only with --full.
+
+  --dump-outputs DIR   after the timed steps, the state a caller of hpf_iterate receives after
+                       the last of them (rank 0's handle), one DIR/<state>.npy per array of the
+                       model (float64): factor rows of a side with more rows than its share of
+                       64 MB are a fixed, seeded sample of them (dump_outputs).  The inputs are
+                       a pure function of the arguments, so two builds compare output for output.
 
   N = 1   BASELINE config C2 (1M x 100K, 5e7 nnz, K=100, -hier) on one GPU.
   N > 1   BASELINE config C3 (10M x 1M, 1e9 nnz, K=100, -hier), STRONG scaling:
@@ -23,7 +36,7 @@ hpf_upload_csr_device / hpf_set_state_device: no PCIe inside or before `value`).
           stored number; `rccl` says what the communicator saw.
   --weak  the round-1 mode: every rank owns a C2-sized shard (weak scaling).
 
-Rank 0 prints one JSON line.  Beside the contract's fields (round 4):
+Rank 0 prints one JSON line.  Beside the contract's fields (round 4; all of these with --full only):
 
   roofline        the dominant kernel against the HBM peak.  `frac` is the MEMORY-SIDE fraction:
                   bytes that crossed from the fabric into the L2s per launch -- read from the PMC
@@ -315,6 +328,42 @@ def mass_check(D, cfg, nnz_loc, val, dev):
     return {"mass_rel_err": abs(got - want_k) / want_k, "ok": bool(abs(got - want_k) / want_k < 1e-9)}
 
 
+DUMP_BYTES = 60_000_000          # --dump-outputs: all files together stay below 64 MB
+
+
+def dump_outputs(D, cfg, directory):
+    """--dump-outputs DIR: every state array of the model -- the ones the CLI's save_model reads (theta, beta; xi, eta with
+    -hier; the biases with -bias; shape, rate, E, Elog each) -- as DIR/<state>.npy in float64, from the handle just timed.
+    A side (users: theta, xi, user bias; items: beta, eta, item bias) whose rows take more than half of DUMP_BYTES is
+    written for a sample of its rows, the same in every array of that side: drawn with a fixed seed from the row count
+    alone and sorted, so two runs with the same arguments hold the same rows.  -> summary for the log"""
+    import torch
+    from hgaprec_amd.capi import STATE, STATE_NAMES
+    directory = Path(directory)
+    directory.mkdir(parents=True, exist_ok=True)
+    objs = {0, 1} | ({2, 3} if cfg["hier"] else set()) | ({4, 5} if cfg["bias"] else set())
+    names = [w for w in STATE_NAMES if STATE[w] // 4 in objs]
+    # without -hier the theta / beta rates are one K-vector each (state_shape), not rows
+    per_row = {w: not (STATE[w] // 4 <= 1 and STATE[w] % 4 == 1 and not cfg["hier"]) for w in names}
+    rows = {}
+    for side, n in ((0, D.n_users), (1, D.n_items)):
+        row_bytes = sum(int(np.prod(D.state_shape(w)[1:])) * 8 for w in names if per_row[w] and STATE[w] // 4 % 2 == side)
+        keep = min(n, max(1, DUMP_BYTES // 2 // max(row_bytes, 1)))
+        rows[side] = None if keep >= n else np.sort(np.random.default_rng(20261016 + side).choice(n, keep, replace=False))
+    nbytes = 0
+    for w in names:
+        t = D.get_state_device(w)
+        idx = rows[STATE[w] // 4 % 2] if per_row[w] else None
+        if idx is not None:
+            t = t.index_select(0, torch.from_numpy(idx).to(t.device))
+        a = t.cpu().numpy()
+        del t
+        np.save(directory / f"{w.lower()}.npy", a)
+        nbytes += a.nbytes
+    return {"dir": str(directory), "files": len(names), "bytes": nbytes,
+            "rows": {nm: (D.n_users, D.n_items)[s] if rows[s] is None else len(rows[s]) for s, nm in ((0, "users"), (1, "items"))}}
+
+
 def sampled_rows(D, cfg, rowptr, col, val, n_users, n_items):
     """value check of the handle just timed: ONE more iteration, the phi sums of a sample of owner
     rows recomputed in plain fp64 from the exported Elog arrays (tests/rowcheck.py; outside `value`)"""
@@ -449,6 +498,14 @@ def main():
     ap.add_argument("--weak", action="store_true",
                     help="N > 1: weak scaling -- every rank owns its own C2-sized user shard")
     ap.add_argument("--scale", type=float, default=1.0, help="shrink n, m, nnz (debug only)")
+    ap.add_argument("--full", action="store_true",
+                    help="every check and side measurement beside the headline: self_check, the in-run PMC passes, "
+                         "gather-only and copy probes, other configs, 48-bit block, CPU baseline; N > 1: replica check, "
+                         "both exchange orders, rccl block, one-GPU reference.  Without it: set-up, warm-up, the timed "
+                         "steps, --dump-outputs and the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the state of the model they computed as DIR/<state>.npy "
+                         "(float64; a fixed, seeded sample of the rows of a large side; under 64 MB in all)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--lean", action="store_true",
                     help="the timed region and the mass check only: no gather-only probe, copy rate, 48-bit block, "
@@ -488,8 +545,15 @@ def main():
     ap.add_argument("--same-device", action="store_true",
                     help="debug: put every rank on cuda:0 (use with --backend gloo)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if args.lean:
         args.no_pmc = args.no_other_configs = args.no_cpu_baseline = True
+    elif not args.full:
+        # a plain run: set-up, warm-up, the timed steps, --dump-outputs and the line, nothing else
+        args.no_pmc = args.no_other_configs = args.no_cpu_baseline = args.no_1gpu_reference = True
+    checks = args.full or args.lean          # mass check, and for N > 1 replica check, exchange orders, rccl block
+    side = args.full and not args.lean       # the side measurements --lean leaves out as well
 
     # RCCL prints a version banner through C stdio on stdout (flushed at process
     # exit when stdout is a pipe).  Keep the real stdout for the ONE JSON line:
@@ -530,7 +594,7 @@ def main():
     force_dist = os.environ.get("HPF_BENCH_FORCE_DIST") == "1"
     use_dist = world > 1 or force_dist
     rccl_log = None
-    if use_dist and args.backend == "nccl" and rank == 0:
+    if use_dist and args.backend == "nccl" and rank == 0 and checks:
         # what RCCL itself reports (ranks, channels, transports, algorithm / protocol of the
         # big all-reduce) goes to a file that the `rccl` block of the JSON line quotes
         rccl_log = f"/tmp/hpf_rccl_{os.getpid()}.log"
@@ -709,6 +773,11 @@ def main():
     dt = time.perf_counter() - t0
     tm = D.mean_timing(min(args.steps, 64))
     it_ms = D.iteration_times(min(args.steps, 64))          # hipEvents on the handle's stream, one figure per timed iteration
+    if args.dump_outputs and rank == 0:
+        # before anything else touches the handle: what the last timed step left
+        t0 = time.perf_counter()
+        dumped = dump_outputs(D, cfg, args.dump_outputs)
+        log(f"[dump-outputs] {dumped} in {time.perf_counter() - t0:.1f}s")
     per_rank = None
     if use_dist:
         tt = torch.tensor([dt], dtype=torch.float64, device=dev)
@@ -728,7 +797,7 @@ def main():
         nnz_total = nnz_loc
 
     modes_ms = None
-    if use_dist:
+    if use_dist and checks:
         # both exchange orders in the same run, outside `value` (the first hardware run decides the default with data): a few more
         # iterations each way, max over ranks of the wall time per iteration, and what the stream had to wait for
         modes_ms = {}
@@ -746,8 +815,8 @@ def main():
         modes_ms["timed_region_used"] = "single_fused" if args.single_allreduce else "pair_overlapped"
         modes_ms["iterations_each"] = k2
 
-    replica_check = None
-    if use_dist:
+    replica_check = beta_checksum = None
+    if use_dist and checks:
         # every rank must hold bit-identical item-side state after the same
         # all-reduced sums: a cheap end-of-run guard against an ordering race
         be = D.get_state_device("BETA_E", dev)
@@ -760,7 +829,7 @@ def main():
         del be
 
     rccl = None
-    if use_dist:
+    if use_dist and checks:
         # what the communicator really was: ranks RCCL saw, its version, and
         # the big all-reduce on its own -- same tensor size, nothing else on the GPU
         scratch = torch.zeros_like(x_items)
@@ -807,7 +876,7 @@ def main():
                 rccl["log"] = {"error": str(ex)}
 
     # the timed iterations did the work: mass conservation on the handle that was timed ...
-    self_check = mass_check(D, cfg, nnz_loc, val, dev)
+    self_check = mass_check(D, cfg, nnz_loc, val, dev) if checks else None
     if args.lean and m > n_loc:
         # the PMC passes calibrate FETCH_SIZE / WRITE_SIZE on materialize_es_kernel over the LARGER side (known bytes):
         # the mass check above exported the user side only
@@ -818,14 +887,14 @@ def main():
     # the ceiling of each phi pass's ACCESS PATTERN on this GPU, measured now: the same work list,
     # index stream and rows with the arithmetic taken out (hpf_gather_only).  Outside the timed region.
     gather_only = None
-    if not args.lean:
+    if side:
         try:
             gather_only = {"phi_user": D.gather_only_ms(0, 3), "phi_item": D.gather_only_ms(1, 3)}
         except Exception as ex:
             gather_only = {"error": str(ex)}
     # ... and the VALUES of a sample of its rows (one more iteration, outside the timed region): a gather of
     # the wrong row conserves mass; this does not pass it
-    if world == 1 and not force_dist and not args.lean:
+    if world == 1 and not force_dist and side:
         self_check["sampled_rows"] = sampled_rows(D, cfg, rowptr, col, val, 48, 16)
         self_check["ok"] = bool(self_check["ok"] and self_check["sampled_rows"].get("ok"))
 
@@ -868,7 +937,7 @@ def main():
         del rp_h, col_h, val_h, a
 
     copy_gbs = None
-    if rank == 0 and not args.lean:
+    if rank == 0 and side:
         # context for the roofline: what a plain device-to-device copy reaches on
         # this GPU right now (read + write bytes / time), outside the timed region
         src = torch.empty(1 << 27, dtype=torch.float64, device=dev)        # 1 GiB
@@ -928,6 +997,9 @@ def main():
             "iteration_cache_inclusive_algorithmic_GBps":
                 (ab["phi_user"] + ab["phi_item"] + ab["rows"]) / (dt / args.steps) / 1e9,
         }
+        if not checks:                   # not run (plain run): no key, rather than a null that reads like a failed check
+            for k in ("replica_check", "self_check", "beta_e_checksum"):
+                del out[k]
         if per_rank is not None:
             comp = [r["phi_item_ms"] + r["combine_item_ms"] + r["phi_user_ms"] + r["combine_user_ms"]
                     + r["sweep_user_ms"] + r["sweep_item_ms"] for r in per_rank]
@@ -935,10 +1007,11 @@ def main():
             out["exposed_allreduce_ms"] = {"max": max(r["exchange_wait_ms"] for r in per_rank),
                                            "mean": sum(r["exchange_wait_ms"] for r in per_rank) / world}
             out["compute_ms"] = {"max": max(comp), "min": min(comp)}
-            out["allreduce_modes_ms"] = modes_ms
+            if modes_ms is not None:
+                out["allreduce_modes_ms"] = modes_ms
         if rccl is not None:
             out["rccl"] = rccl
-        if (world == 1 and not custom and not force_dist and not args.lean
+        if (world == 1 and not custom and not force_dist and side
                 and (n_loc + m) * wi["ld"] * 8 * 5 + nnz_loc * 12 < 0.4 * free_b):
             # context, never `value`: the same workload with W stored in 48 bits (hpf_config.w_storage = 2,
             # opt-in): the passes are bound by bytes per gathered row, this is what shorter rows buy
@@ -1072,7 +1145,8 @@ def main():
         alg_gbs = kbytes / (kms * 1e-3) / 1e9
         traffic = None
         pmc = None
-        traffic_note = "hipGraph replay: no per-kernel times" if graph else "--lean / --no-pmc"
+        traffic_note = ("hipGraph replay: no per-kernel times" if graph else "--lean / --no-pmc" if checks
+                        else "plain run: the counter passes run with --full")
         if not args.no_pmc and not graph:
             # N > 1 (and HPF_BENCH_FORCE_DIST): the child is ONE rank that generates exactly rank 0's user range of the
             # same matrix and runs whole iterations on it -- the item pass walks the work list rank 0 just timed; the

@@ -252,6 +252,23 @@ def full_fixtures():
         print("wrote", cdir)
 
 
+def live_cases():
+    """refpart's output for the inputs of the two tests that run it live (tests/test_oracle_pins.py: live_softmax_input,
+    live_rows_inputs), keyed by command and input hash: what those tests compare against where refpart is not built"""
+    sys.path.insert(0, str(ROOT))
+    from tests import test_oracle_pins as t
+    runs = {}
+    with tempfile.TemporaryDirectory() as td:
+        fin, fout = Path(td) / "in.bin", Path(td) / "out.bin"
+        for cmd, payload in [("softmax", t.live_softmax_input()[1])] + [("rows", p) for _, p in t.live_rows_inputs()]:
+            fin.write_bytes(payload)
+            subprocess.run([str(REFPART), cmd, str(fin), str(fout)], check=True)
+            runs[t.live_key(cmd, payload)] = hexl(np.fromfile(fout, "<f8"))
+    return {"source": "oracle/_ref/refpart softmax / rows on the inputs of tests/test_oracle_pins.py "
+                      "(test_oracle_against_live_reference_build, test_sweep_steps_against_live_reference_build)",
+            "runs": runs}
+
+
 def main():
     if "--full" in sys.argv:
         if not REFBIN.exists():
@@ -264,7 +281,7 @@ def main():
     GOLD.mkdir(parents=True, exist_ok=True)
     only = [a for a in sys.argv[1:] if not a.startswith("-")]
     for name, fn in (("softmax", softmax_cases), ("accumulate", accumulate_cases), ("arrays", arrays_cases),
-                     ("rows", rows_cases), ("save", save_cases), ("env", env_cases)):
+                     ("rows", rows_cases), ("save", save_cases), ("env", env_cases), ("live", live_cases)):
         if only and name not in only:
             continue
         (GOLD / f"{name}.json").write_text(json.dumps(fn(), indent=1))

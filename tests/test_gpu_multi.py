@@ -233,7 +233,7 @@ def test_two_gpus_bench_strong_scaling_line():
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2",
                         "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), str(ROOT / "bench.py"),
-                        "--gpus", "2", "--steps", "3", "--warmup", "1", "--scale", "0.01"],
+                        "--gpus", "2", "--steps", "3", "--warmup", "1", "--scale", "0.01", "--full"],
                        capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     line = [l for l in r.stdout.splitlines() if l.startswith("{")][-1]
@@ -314,7 +314,7 @@ def test_two_ranks_on_one_gpu_bench_strong_scaling_over_gloo(single):
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2",
                         "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), str(ROOT / "bench.py"),
-                        "--gpus", "2", "--steps", "3", "--warmup", "1", "--scale", "0.005",
+                        "--gpus", "2", "--steps", "3", "--warmup", "1", "--scale", "0.005", "--full",
                         "--backend", "gloo", "--same-device"] + (["--single-allreduce"] if single else []),
                        capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -351,7 +351,7 @@ def test_one_gpu_bench_takes_the_distributed_path():
     overlapped all-reduces) on one rank -- HPF_BENCH_FORCE_DIST=1 -- at 1 % of C2"""
     env = dict(os.environ, HPF_BENCH_FORCE_DIST="1", MASTER_PORT=str(_free_port()),
                HSA_ENABLE_IPC_MODE_LEGACY="0")
-    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--steps", "3", "--warmup", "1", "--scale", "0.01"],
+    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--steps", "3", "--warmup", "1", "--scale", "0.01", "--full"],
                        capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
@@ -379,7 +379,7 @@ def test_eight_ranks_through_the_launcher_on_one_gpu():
     def launch():
         return subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=8",
                                "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), str(ROOT / "bench.py"),
-                               "--gpus", "8", "--steps", "3", "--warmup", "1", "--scale", "0.005",
+                               "--gpus", "8", "--steps", "3", "--warmup", "1", "--scale", "0.005", "--full",
                                "--backend", "gloo", "--same-device"],
                               capture_output=True, text=True, timeout=1800, env=env, cwd=ROOT)
     r = launch()
@@ -430,7 +430,7 @@ def test_one_gpu_bench_library_comm_path():
     outs = {}
     for comm in ("torch", "library"):
         env = dict(os.environ, HPF_BENCH_FORCE_DIST="1", MASTER_PORT=str(_free_port()), HSA_ENABLE_IPC_MODE_LEGACY="0")
-        r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--steps", "3", "--warmup", "1", "--scale", "0.01",
+        r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--steps", "3", "--warmup", "1", "--scale", "0.01", "--full",
                             "--no-cpu-baseline", "--no-pmc", "--comm", comm],
                            capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
         assert r.returncode == 0, r.stderr[-3000:]
@@ -452,7 +452,7 @@ def test_two_gpus_bench_library_comm_equals_torch_comm():
         env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
         r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2",
                             "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), str(ROOT / "bench.py"),
-                            "--gpus", "2", "--steps", "3", "--warmup", "1", "--scale", "0.01", "--no-cpu-baseline", "--no-pmc",
+                            "--gpus", "2", "--steps", "3", "--warmup", "1", "--scale", "0.01", "--full", "--no-cpu-baseline", "--no-pmc",
                             "--no-1gpu-reference", "--comm", comm],
                            capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
         assert r.returncode == 0, r.stderr[-3000:]

@@ -8,6 +8,7 @@
  * digamma against mpmath at 50 digits.
 The end-to-end path stays "parity unpinned" (the full reference needs GSL).
 """
+import hashlib
 import json
 import struct
 import subprocess
@@ -103,22 +104,56 @@ def test_tsv_writers_golden(orc, tmp_path):
         assert (tmp_path / "v.tsv").read_text() == c["vector_tsv"]
 
 
-def test_oracle_against_live_reference_build(orc, tmp_path):
-    """fresh random vectors through oracle/_ref/refpart (present in this
-    container and shipped prebuilt to the GPU box; skipped if absent)"""
-    if not orc.REFPART.exists():
-        pytest.skip("oracle/_ref/refpart not built")
+def live_softmax_input():
+    """the records of test_oracle_against_live_reference_build and refpart's `softmax` input file holding them"""
     rng = np.random.default_rng(1234)
     recs = [(rng.normal(size=n) * s - 3.0, int(rng.integers(0, 6)))
             for n in (2, 5, 22, 100, 202) for s in (1.0, 20.0)]
-    fin, fout = tmp_path / "i.bin", tmp_path / "o.bin"
-    with open(fin, "wb") as f:
-        f.write(struct.pack("<I", len(recs)))
-        for x, y in recs:
-            f.write(struct.pack("<II", x.size, y))
-            f.write(x.astype("<f8").tobytes())
-    subprocess.run([str(orc.REFPART), "softmax", str(fin), str(fout)], check=True)
-    raw, pos = np.fromfile(fout, "<f8"), 0
+    payload = struct.pack("<I", len(recs))
+    for x, y in recs:
+        payload += struct.pack("<II", x.size, y) + x.astype("<f8").tobytes()
+    return recs, payload
+
+
+def live_rows_inputs():
+    """the cases of test_sweep_steps_against_live_reference_build: (mode, sn, ev, u, v) and refpart's `rows` input file"""
+    rng = np.random.default_rng(99)
+    out = []
+    for mode, rows, k in ((0, 11, 22), (1, 5, 22), (2, 13, 1), (3, 13, 1)):
+        sn = 0.3 + rng.gamma(0.5, 3.0, size=(rows, k))
+        ev, u, v = rng.gamma(2.0, 0.2, size=rows), rng.gamma(1.0, 30.0, size=rows if mode == 2 else k), 6.3
+        payload = (struct.pack("<IIIddd", mode, rows, k, 0.3, 0.3, v) + sn.astype("<f8").tobytes()
+                   + ev.astype("<f8").tobytes() + u.astype("<f8").tobytes())
+        out.append(((mode, sn, ev, u, v), payload))
+    return out
+
+
+def live_key(cmd, payload):
+    return f"{cmd}:{hashlib.sha256(payload).hexdigest()[:16]}"
+
+
+def refpart_output(orc, cmd, payload, tmp_path):
+    """refpart's output for this input: run live where oracle/_ref/refpart is built (and then equal to the stored copy),
+    elsewhere the copy tests/golden/live.json keeps of the same input (tests/golden/make_golden.py live)"""
+    stored = json.loads((GOLD / "live.json").read_text())["runs"].get(live_key(cmd, payload))
+    if orc.REFPART.exists():
+        fin, fout = tmp_path / "i.bin", tmp_path / "o.bin"
+        fin.write_bytes(payload)
+        r = subprocess.run([str(orc.REFPART), cmd, str(fin), str(fout)])
+        if r.returncode == 0:
+            raw = np.fromfile(fout, "<f8")
+            assert stored is None or np.array_equal(raw, unhex(stored)), f"refpart {cmd} disagrees with its stored output"
+            return raw
+        assert r.returncode == 2 and stored is not None, f"refpart {cmd} failed (rc {r.returncode})"   # 2: predates `cmd`
+    assert stored is not None, f"no stored refpart output for {live_key(cmd, payload)}: tests/golden/make_golden.py live"
+    return unhex(stored)
+
+
+def test_oracle_against_live_reference_build(orc, tmp_path):
+    """fresh random vectors through oracle/_ref/refpart (where it is built; elsewhere its stored output for the same
+    vectors, tests/golden/live.json)"""
+    recs, payload = live_softmax_input()
+    raw, pos = refpart_output(orc, "softmax", payload, tmp_path), 0
     for x, y in recs:
         phi = orc.lognormalize(x)
         if y > 1:
@@ -209,21 +244,11 @@ def test_sweep_steps_golden_bit_exact(orc):
 
 
 def test_sweep_steps_against_live_reference_build(orc, tmp_path):
-    """fresh random arrays through oracle/_ref/refpart rows (skipped where it is not built)"""
-    if not orc.REFPART.exists():
-        pytest.skip("oracle/_ref/refpart not built")
-    rng = np.random.default_rng(99)
-    for mode, rows, k in ((0, 11, 22), (1, 5, 22), (2, 13, 1), (3, 13, 1)):
-        sn = 0.3 + rng.gamma(0.5, 3.0, size=(rows, k))
-        ev, u, v = rng.gamma(2.0, 0.2, size=rows), rng.gamma(1.0, 30.0, size=rows if mode == 2 else k), 6.3
-        fin, fout = tmp_path / "i.bin", tmp_path / "o.bin"
-        with open(fin, "wb") as f:
-            f.write(struct.pack("<IIIddd", mode, rows, k, 0.3, 0.3, v))
-            f.write(sn.astype("<f8").tobytes()); f.write(ev.astype("<f8").tobytes()); f.write(u.astype("<f8").tobytes())
-        r = subprocess.run([str(orc.REFPART), "rows", str(fin), str(fout)])
-        if r.returncode == 2:
-            pytest.skip("prebuilt refpart predates the rows command")
-        raw = np.fromfile(fout, "<f8")
+    """fresh random arrays through oracle/_ref/refpart rows (where it is built; elsewhere its stored output for the same
+    arrays, tests/golden/live.json)"""
+    for (mode, sn, ev, u, v), payload in live_rows_inputs():
+        rows, k = sn.shape
+        raw = refpart_output(orc, "rows", payload, tmp_path)
         ns, nr = rows * k, (k if mode == 1 else rows * k)
         got = orc.sweep_steps(mode, sn, ev, u, v)
         want = (raw[:ns], raw[ns:ns + nr], raw[ns + nr:2 * ns + nr], raw[2 * ns + nr:])

@@ -18,18 +18,18 @@ for pmc in "FETCH_SIZE" "WRITE_SIZE" "TCC_HIT_sum TCC_MISS_sum" "TCC_EA0_RDREQ_s
   name=$(echo $pmc | tr ' ' '_' | tr 'A-Z' 'a-z' | cut -c1-40)
   rocprofv3 --kernel-trace --pmc $pmc --output-format csv -d $OUT/pmc_$name -o c2 -- $LEAN > /dev/null 2> $OUT/pmc_$name.log
 done
-# 3. the plain bench line: in-run PMC passes, other_configs, CPU baseline, host hand-over
-python bench.py --host-handover > $OUT/bench.json 2> $OUT/bench.log
+# 3. the full bench line: in-run PMC passes, other_configs, CPU baseline, host hand-over
+python bench.py --full --host-handover > $OUT/bench.json 2> $OUT/bench.log
 # 4. the same line with the tiles switched off, and the L2 hit rate / fabric bytes of the item pass either way
-HPF_EXPERIMENTAL=1 HPF_TILE=0 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-other-configs > $OUT/bench_c2_untiled.json 2> $OUT/bench_c2_untiled.log
+HPF_EXPERIMENTAL=1 HPF_TILE=0 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-other-configs > $OUT/bench_c2_untiled.json 2> $OUT/bench_c2_untiled.log
 HPF_EXPERIMENTAL=1 HPF_TILE=0 rocprofv3 --kernel-trace --pmc TCC_HIT_sum TCC_MISS_sum --output-format csv -d $OUT/pmc_tcc_untiled -o c2 -- $LEAN > /dev/null 2> $OUT/pmc_tcc_untiled.log
 # 5. the other configs on one GPU, each with its own in-run PMC passes; C1 and C4 WITH their CPU baseline
-python bench.py --config C1 --steps 20 --warmup 5 > $OUT/bench_c1.json 2> $OUT/bench_c1.log
-python bench.py --config C4 --steps 5 --warmup 2 > $OUT/bench_c4.json 2> $OUT/bench_c4.log
-python bench.py --config C3 --steps 5 --warmup 2 --no-cpu-baseline > $OUT/bench_c3_full_1gpu.json 2> $OUT/bench_c3_full_1gpu.log
-HPF_EXPERIMENTAL=1 HPF_TILE=0 python bench.py --config C3 --steps 5 --warmup 2 --no-cpu-baseline --no-pmc > $OUT/bench_c3_full_1gpu_untiled.json 2> $OUT/bench_c3_full_1gpu_untiled.log
-HPF_EXPERIMENTAL=1 HPF_TILE=0 python bench.py --config C4 --steps 5 --warmup 2 --no-cpu-baseline --no-pmc > $OUT/bench_c4_untiled.json 2> $OUT/bench_c4_untiled.log
-python bench.py --config C5 --steps 3 --warmup 1 --no-cpu-baseline --no-pmc > $OUT/bench_c5_full_1gpu.json 2> $OUT/bench_c5_full_1gpu.log
+python bench.py --full --config C1 --steps 20 --warmup 5 > $OUT/bench_c1.json 2> $OUT/bench_c1.log
+python bench.py --full --config C4 --steps 5 --warmup 2 > $OUT/bench_c4.json 2> $OUT/bench_c4.log
+python bench.py --full --config C3 --steps 5 --warmup 2 --no-cpu-baseline > $OUT/bench_c3_full_1gpu.json 2> $OUT/bench_c3_full_1gpu.log
+HPF_EXPERIMENTAL=1 HPF_TILE=0 python bench.py --full --config C3 --steps 5 --warmup 2 --no-cpu-baseline --no-pmc > $OUT/bench_c3_full_1gpu_untiled.json 2> $OUT/bench_c3_full_1gpu_untiled.log
+HPF_EXPERIMENTAL=1 HPF_TILE=0 python bench.py --full --config C4 --steps 5 --warmup 2 --no-cpu-baseline --no-pmc > $OUT/bench_c4_untiled.json 2> $OUT/bench_c4_untiled.log
+python bench.py --full --config C5 --steps 3 --warmup 1 --no-cpu-baseline --no-pmc > $OUT/bench_c5_full_1gpu.json 2> $OUT/bench_c5_full_1gpu.log
 # 6. what 8 GPUs would hold (compute and load balance only: nothing crosses xGMI)
 for n in 2 4 8; do python tools/emulate_shards.py C3 $n > $OUT/emulate_c3_$n.json 2> $OUT/emulate_c3_$n.log; done
 for n in 2 4 8; do python tools/emulate_shards.py C4 $n > $OUT/emulate_c4_$n.json 2> $OUT/emulate_c4_$n.log; done
@@ -70,7 +70,7 @@ cfgprof() {
     rocprofv3 --kernel-trace --pmc $pmc --output-format csv -d $D/pmc_$name -o k -- $L > /dev/null 2> $D/pmc_$name.log
   done
   # the pass with its arithmetic taken out, in the same shape (roofline.gather_only_ms of the full line)
-  python bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-other-configs --no-pmc $* > $D/bench.json 2> $D/bench.log
+  python bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-other-configs --no-pmc $* > $D/bench.json 2> $D/bench.log
 }
 cfgprof c4 --config C4
 cfgprof c3_shard --config C3 --user-range 0 1250000
