@@ -84,7 +84,8 @@ __device__ __forceinline__ double group_max(double v)
 }
 
 // 1/x to ~1 ulp: v_rcp_f64 seed + two Newton steps (5 instructions instead
-// of the ~15 of an IEEE-exact fp64 division); x is a positive normal number
+// of the ~15 of an IEEE-exact fp64 division); x is a positive normal number.
+// Measured against mpmath on [1e-300, 1e300] (tests/test_gpu_special.py): relative error <= 1.0 u, u = 2^-53 (asserted: 2 u)
 __device__ __forceinline__ double fast_rcp(double x)
 {
   double r = __builtin_amdgcn_rcp(x);
@@ -326,9 +327,12 @@ __global__ __launch_bounds__(256) void phi_pass_kernel(PhiArgs a)
 // A row is L 16-byte pieces per lane for G lanes, INTERLEAVED: piece t of lane g sits at byte
 // (t*G + g)*16, so that one load instruction of a lane group reads G*16 contiguous bytes.  The
 // 4L dwords of a lane hold E elements; lane g owns columns e*G + g.  Layout of a lane's dwords
-//   p59: d[0..E)  low 32 mantissa bits of each element; then a stream of 27-bit fields
-//        (7 exponent bits above 20 mantissa bits; the all-zero element stands for 0 and reads
-//        back as 2^-127), element e at bit 27 e of the stream
+//   p59: LOGICAL dwords k = 0 .. E + S - 1: k < E is the low 32 mantissa bits of element k; the S dwords from E on are
+//        a stream of 27-bit fields (7 exponent bits above 20 mantissa bits; the all-zero element stands for 0 and
+//        reads back as 2^-127), element e at bit 27 e of the stream.  PHYSICALLY, logical dword k sits at place
+//        codec_p59<L>::pos(k) of the lane's 4L (p59_pos at run time): since round 6 the low word of element e at the
+//        even place 2e beside stream dword e at the odd place 2e + 1 (HPF_P59_PAIRED; 0 = the logical order itself).
+//        pos is one-to-one into [0, 4L) for every L in both orders (static_assert in hpf_probe.hip)
 //   f48: d[0..E)  high dwords; then the 16-bit low parts, two per dword
 // Row stride of the fp64 matrices (S, E, Elog) and of the exchange buffer: ld = G*E columns.
 // Arithmetic and accumulators are fp64 in every mode.
@@ -372,11 +376,14 @@ template <int L> struct codec_p59 {
   // first, so that stream dword e has been consumed by the elements above e when element e overwrites it.  In the round-5
   // order (all low words, then the stream) every other low word had to be copied into a fresh pair first: 11 v_mov per batch
   // of 93 VALU instructions and 12 more registers (tools/count_isa.py; profiles/r06/experiments.md 1).
-  static constexpr __host__ __device__ int pos(int k)
+  // pos_as names the order explicitly (hpf_probe.hip asserts at compile time that BOTH orders place the E + S logical dwords
+  // one-to-one into [0, 4L)); pos is the order this build uses.
+  static constexpr __host__ __device__ int pos_as(bool paired, int k)
   {
-    if (!HPF_P59_PAIRED) return k;
+    if (!paired) return k;
     return k < E ? (k < 2 * L ? 2 * k : 2 * (S + k - 2 * L) + 1) : 2 * (k - E) + 1;
   }
+  static constexpr __host__ __device__ int pos(int k) { return pos_as(HPF_P59_PAIRED != 0, k); }
   static __device__ __forceinline__ double get(const uint32_t (&d)[4 * L], int e)
   {
     const int o = 27 * e, i = E + o / 32, sh = o % 32;    // compile-time after unrolling
@@ -418,23 +425,36 @@ __device__ __forceinline__ uint32_t p59_pos(const PackedRow &pk, uint32_t k)
   return k < pk.E ? (k < 2u * pk.L ? 2u * k : 2u * (S + k - 2u * pk.L) + 1u) : 2u * (k - pk.E) + 1u;
 }
 
+// What an element w puts into a p59 lane: its low word and its 27-bit field (both writers, p59_put and the register form of
+// the row sweep).  Representable: exponent field 897..1023, i.e. 2^-126 <= w < 2.  Anything else -- zero, a smaller
+// value, and what a valid state never holds: w >= 2, infinities, NaN, negative numbers -- is stored as
+// the all-zero element; only an exact +0 does so without being reported (flushed).  live = false: a slot past the end of
+// the row, which holds the all-zero element whatever w is
+struct P59Words { uint32_t lo, f; bool flushed; };
+__device__ __forceinline__ P59Words p59_words(double w, bool live = true)
+{
+  const uint32_t hi = (uint32_t)__double2hiint(w), lo = (uint32_t)__double2loint(w);
+  const bool tiny = hi < 0x38100000u || hi >= 0x40000000u;
+  P59Words r;
+  r.flushed = live && tiny && !(hi == 0u && lo == 0u);
+  r.f = (tiny || !live) ? 0u : hi - 0x38000000u;
+  r.lo = (tiny || !live) ? 0u : lo;
+  return r;
+}
+
 // returns true when a nonzero w had to be flushed (below 2^-126)
 __device__ __forceinline__ bool p59_put(uint32_t *buf, const PackedRow &pk, uint32_t c, double w)
 {
   const uint32_t g = c & (pk.G - 1u), e = c >> pk.lgG;
-  const uint32_t hi = (uint32_t)__double2hiint(w), lo = (uint32_t)__double2loint(w);
-  // representable: exponent field 897..1023, i.e. 2^-126 <= w < 2.  Anything else -- zero, a smaller
-  // value, and what a valid state never holds: w >= 2, infinities, NaN, negative numbers -- is stored as
-  // the all-zero element; only an exact +0 does so without being reported
-  const bool tiny = hi < 0x38100000u || hi >= 0x40000000u;
-  const uint32_t f = tiny ? 0u : hi - 0x38000000u;
-  buf[packed_dword_index(pk, g, p59_pos(pk, e))] = tiny ? 0u : lo;
+  const P59Words pw = p59_words(w);
+  const uint32_t f = pw.f;
+  buf[packed_dword_index(pk, g, p59_pos(pk, e))] = pw.lo;
   const uint32_t o = 27u * e, i = pk.E + o / 32u, sh = o % 32u;
   if (f) {
     atomicOr(&buf[packed_dword_index(pk, g, p59_pos(pk, i))], f << sh);
     if (sh > 5u) atomicOr(&buf[packed_dword_index(pk, g, p59_pos(pk, i + 1))], f >> (32u - sh));
   }
-  return tiny && !(hi == 0u && lo == 0u);
+  return pw.flushed;
 }
 
 __device__ __forceinline__ void f48_put(uint32_t *buf, const PackedRow &pk, uint32_t c, double w)
@@ -873,7 +893,14 @@ __global__ __launch_bounds__(256) void combine_partials_wg_kernel(const LongRow 
 // x < 10 is shifted by exactly 10 with psi(x) = psi(x+10) - P'(x)/P(x),
 // P(x) = prod_{j<10}(x+j) (one reciprocal instead of ten), then the asymptotic
 // series (A&S 6.3.18) through x^-14 at xs >= 10.  Stands where the reference
-// calls gsl_sf_psi (gpbase.hh:260).  |err| <~ 4e-15 abs on [1e-30, inf).
+// calls gsl_sf_psi (gpbase.hh:260).
+// Accuracy.  No absolute figure holds on the whole range (psi(1e-30) = -1e30; one ulp of psi(1e18) is 7e-15).  The
+// rounding model tests/test_gpu_special.py asserts against mpmath is, with u = 2^-53,
+//     |psi_dev - psi| <= u (3 log xs + 16 corr + |psi|)        (1.1e-15 at x = 10, 1.2e-14 at x = 0.3)
+// and the largest error / bound measured on an MI355X (digamma_pos; 4000 log-uniform x in [1e-30, 1e18], 6000 uniform
+// in [0.3, 12], both neighbours of 10, the root 1.4616..., 1e30, 1e100, 1e300) is, per band of x,
+//     [1e-30, 0.3) 0.35    [0.3, 10) 0.34    [10, 1e3) 0.49    [1e3, 1e300] 0.50
+// Every output is finite up to x = 1e300, where t, p and dp below are inf: the selects drop them.
 // ---------------------------------------------------------------------
 struct PsiParts { double xs, corr; };
 
@@ -914,7 +941,13 @@ __device__ __forceinline__ PsiParts psi_parts(double x)
 // reciprocals of five instructions each (C2 user sweep 0.445 -> 0.425 ms, profiles/r04/experiments.md 8).  P(x) <= 19^10,
 // the shifted x <= 20 and any rate a model can take keep the product far inside the range; where x >= 10 (no shift) P is
 // replaced by 1, so that an overflowed product never enters.  ri = 1 / rt to ~2 ulp (the exported E is an IEEE
-// division, materialize_es_kernel; this one feeds the column sums and W); corr as in psi_parts to a few 1e-16.
+// division, materialize_es_kernel; this one feeds the column sums and W).  What does enter is xs * rt, which has to stay
+// finite and normal: a shape of 1e300 takes rates up to 1e8 only.
+// Measured against mpmath on an MI355X (tests/test_gpu_special.py; x as for psi_parts, rt log-uniform in [1e-6, 1e12],
+// the make_nonzero floor 1e-30 against x in [0.3, 100], rt <= 1 for x >= 1e100), u = 2^-53:
+//     ri                          relative error <= 2.2 u                                      (asserted: 4 u)
+//     W = xs exp_neg(corr) ri     against exp(psi(x)) / rt, relative error / (u (16 corr + 10)), per band of x:
+//                                 [1e-30, 0.3) 0.31    [0.3, 10) 0.31    [10, 1e3) 0.39    [1e3, 1e300] 0.31   (asserted: 1)
 struct PsiRate { double xs, corr, ri; };
 
 __device__ __forceinline__ PsiRate psi_parts_rate(double x, double rt)
@@ -958,8 +991,12 @@ __device__ __forceinline__ double fma_uc(double a, double b, double c)
 // exp(-c) for c >= 0 (the sweep's exp(psi(shape)) = xs * exp(-corr)): n = rint(-c log2 e),
 // r = -c - n ln2 in two pieces, a degree-13 Taylor polynomial on |r| <= ln2/2 (remainder
 // 4e-18), scaled by 2^n with v_ldexp_f64 (which also delivers the gradual underflow);
-// c > 745 gives 0.  ~1 ulp, like the library exp it replaces, without that routine's
+// c >= 746 gives exactly 0 (c = 745 the smallest denormal).  Without the library exp's
 // special-case selects for positive arguments, infinities and NaN.
+// Measured against mpmath on an MI355X (tests/test_gpu_special.py; 20 000 c uniform in [0, 708], 2000 log-uniform
+// down to 1e-20, 500 in [708, 746], ln2/2 and its neighbours, ln2): relative error <= 1.22 u, u = 2^-53, wherever
+// the result is normal (asserted: 4 u); every denormal result equal to the correctly rounded one (asserted: within
+// one denormal spacing).
 __device__ __forceinline__ double exp_neg(double c)
 {
   const double z = -fmin(c, 750.0);
@@ -1182,12 +1219,10 @@ __global__ __launch_bounds__(256) void row_sweep_kernel(SweepArgs a)
         for (int t = 0; t < R; ++t) {
           const bool pair = 2 * t + 1 < E;                // element 2t + 1 exists (E odd: the last slot of h = 1 is past the row)
           const double v = w[t] * inv;
-          const uint32_t vhi = (uint32_t)__double2hiint(v), vlo = (uint32_t)__double2loint(v);
           const bool live = pair || !h;
-          // representable: exponent field 897..1023, i.e. 2^-126 <= w < 2 (see p59_put)
-          const bool tiny = vhi < 0x38100000u || vhi >= 0x40000000u;
-          flushed |= live && tiny && !(vhi == 0u && vlo == 0u);
-          const uint32_t of = (tiny || !live) ? 0u : vhi - 0x38000000u, ol = (tiny || !live) ? 0u : vlo;
+          const P59Words pw = p59_words(v, live);         // representable: 2^-126 <= w < 2
+          flushed |= pw.flushed;
+          const uint32_t of = pw.f, ol = pw.lo;
           const uint32_t pf = lane_xor<GP>(of), pl = lane_xor<GP>(ol);
           p59_place<E, L>(D, 2 * t, h ? pl : ol, h ? pf : of);
           if (pair) p59_place<E, L>(D, 2 * t + 1, h ? ol : pl, h ? of : pf);

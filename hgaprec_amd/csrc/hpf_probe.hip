@@ -1,0 +1,326 @@
+// hpf_probe.hip -- TEST-ONLY entry points onto the inline device functions of hpf_kernels.hpp
+// (libhpf_probe.so; tests/devprobe.py loads it, the library and the CLI do not link it).
+//
+// Every kernel here calls the very function the hot path calls -- fast_rcp, psi_parts / digamma_pos,
+// psi_parts_rate, exp_neg, p59_put / packed_copy_out, p59_place, codec_p59<L>::get -- on one array element
+// per thread, so that tests/test_gpu_special.py can hold each of them against mpmath on its own.  Nothing is
+// re-implemented: a change of a coefficient in the header changes what these return.
+//
+// All entry points take HOST pointers, allocate, copy, launch one small kernel, synchronise, copy back and
+// return the hipError_t (0 = success).  Arrays hold at most PROBE_MAX_N elements.
+#include "hpf_kernels.hpp"
+
+using namespace hpf;
+
+namespace {
+
+constexpr int PROBE_MAX_N = 100000;
+
+// ---- codec_p59<L>::pos maps the E + S logical dwords one-to-one into the lane's 4L, in BOTH dword orders
+template <int L, bool PAIRED>
+constexpr bool p59_pos_is_injective()
+{
+  using C = codec_p59<L>;
+  bool seen[4 * L] = {};
+  for (int k = 0; k < C::E + C::S; ++k) {
+    const int p = C::pos_as(PAIRED, k);
+    if (p < 0 || p >= 4 * L || seen[p]) return false;
+    seen[p] = true;
+  }
+  return true;
+}
+template <int L> constexpr bool p59_pos_ok() { return p59_pos_is_injective<L, true>() && p59_pos_is_injective<L, false>(); }
+static_assert(p59_pos_ok<1>() && p59_pos_ok<2>() && p59_pos_ok<3>() && p59_pos_ok<4>() && p59_pos_ok<5>() &&
+              p59_pos_ok<6>() && p59_pos_ok<7>() && p59_pos_ok<8>(),
+              "codec_p59<L>::pos must place the E + S logical dwords of a lane one-to-one into [0, 4L)");
+
+// ---- device buffers that free themselves, and the copy / launch / copy skeleton
+struct DevBuf {
+  void *p = nullptr;
+  ~DevBuf() { if (p) (void)hipFree(p); }
+  hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 1); }
+  template <typename T> T *as() const { return static_cast<T *>(p); }
+};
+
+#define PROBE_TRY(expr) do { const hipError_t e_ = (expr); if (e_ != hipSuccess) return (int)e_; } while (0)
+
+int finish_launch()
+{
+  PROBE_TRY(hipGetLastError());
+  PROBE_TRY(hipDeviceSynchronize());
+  return 0;
+}
+
+inline dim3 grid_for(int n) { return dim3((unsigned)((n + 255) / 256)); }
+
+// ---- the special functions, one element per thread
+__global__ void rcp_kernel(const double *x, double *out, int n)
+{
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) out[i] = fast_rcp(x[i]);
+}
+
+__global__ void psi_kernel(const double *x, double *psi, double *xs, double *corr, int n)
+{
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const PsiParts r = psi_parts(x[i]);
+  xs[i] = r.xs;
+  corr[i] = r.corr;
+  psi[i] = digamma_pos(x[i]);
+}
+
+__global__ void sweep_elem_kernel(const double *x, const double *rt, double *w, double *ri, double *corr, int n)
+{
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const PsiRate ps = psi_parts_rate(x[i], rt[i]);
+  ri[i] = ps.ri;
+  corr[i] = ps.corr;
+  w[i] = ps.xs * exp_neg(ps.corr) * ps.ri;      // row_sweep_kernel: exp(psi(shape) - log(rate))
+}
+
+__global__ void exp_neg_kernel(const double *c, double *out, int n)
+{
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) out[i] = exp_neg(c[i]);
+}
+
+// ---- p59 rows.  One workgroup of G threads per row; thread g is packed lane g and owns the columns e * G + g.
+// Columns from ncols on are "past the row's length": the LDS writer never puts them (row_sweep_kernel tests the
+// column against the stride), the register writer places the all-zero element (its `live` test).
+__global__ void p59_write_lds_kernel(PackedRow pk, uint32_t ncols, const double *w, unsigned char *rows, uint32_t *flushed)
+{
+  __shared__ uint32_t buf[64 * 8 * 4];             // G <= 64 lanes x L <= 8 pieces x 4 dwords
+  const uint32_t g = threadIdx.x, G = pk.G, ld = G * pk.E;
+  const size_t row = blockIdx.x;
+  packed_clear(buf, pk, g, G);
+  __syncthreads();
+  for (uint32_t e = 0; e < pk.E; ++e) {
+    const uint32_t c = g + G * e;
+    uint32_t fl = 0u;
+    if (c < ncols) fl = p59_put(buf, pk, c, w[row * ld + c]) ? 1u : 0u;
+    flushed[row * ld + c] = fl;
+  }
+  __syncthreads();
+  packed_copy_out(buf, rows, row, pk, g, G);
+}
+
+// the slot count R of the register-building sweep that serves p59 rows of L pieces (p59_of_slots)
+template <int L> struct slots_of_p59 {
+  static constexpr int E = codec_p59<L>::E;
+  static constexpr int R = E <= 10 ? E / 2 : (E + 1) / 2;
+  static_assert(p59_of_slots<R>::valid && p59_of_slots<R>::E == E && p59_of_slots<R>::L == L,
+                "every p59 shape L = 1..8 has a register-building sweep");
+};
+
+template <int L>
+__global__ void p59_write_reg_kernel(uint32_t G, uint32_t ncols, const double *w, unsigned char *rows, uint32_t *flushed)
+{
+  using P = p59_of_slots<slots_of_p59<L>::R>;
+  constexpr int E = P::E;
+  const uint32_t g = threadIdx.x, ld = G * (uint32_t)E;
+  const size_t row = blockIdx.x;
+  uint32_t D[4 * L];
+#pragma unroll
+  for (int i = 0; i < 4 * L; ++i) D[i] = 0u;
+#pragma unroll
+  for (int e = 0; e < E; ++e) {
+    const uint32_t c = g + G * (uint32_t)e;
+    const bool live = c < ncols;
+    const P59Words pw = p59_words(live ? w[row * ld + c] : 0.0, live);
+    flushed[row * ld + c] = pw.flushed ? 1u : 0u;
+    p59_place<E, L>(D, e, pw.lo, pw.f);
+  }
+  // piece t of lane g at byte (t * G + g) * 16 of the row
+  uint4 *dst = reinterpret_cast<uint4 *>(rows + row * (size_t)(G * L * 16)) + g;
+#pragma unroll
+  for (int t = 0; t < L; ++t) dst[(size_t)t * G] = make_uint4(D[4 * t], D[4 * t + 1], D[4 * t + 2], D[4 * t + 3]);
+}
+
+// the reader, as phi_segments loads and decodes a row: L 16-byte pieces per lane, elements from the last to the first
+template <int L>
+__global__ void p59_read_kernel(uint32_t G, const unsigned char *rows, double *out)
+{
+  using C = codec_p59<L>;
+  const uint32_t g = threadIdx.x, ld = G * (uint32_t)C::E;
+  const size_t row = blockIdx.x;
+  const unsigned char *base = rows + row * (size_t)(G * L * 16) + (size_t)g * 16;
+  uint32_t d[4 * L];
+#pragma unroll
+  for (int t = 0; t < L; ++t) {
+    const uint4 v = *reinterpret_cast<const uint4 *>(base + (size_t)t * G * 16);
+    d[4 * t] = v.x; d[4 * t + 1] = v.y; d[4 * t + 2] = v.z; d[4 * t + 3] = v.w;
+  }
+#pragma unroll
+  for (int e = C::E - 1; e >= 0; --e) out[row * ld + (uint32_t)e * G + g] = C::get(d, e);
+}
+
+__global__ void p59_pos_kernel(PackedRow pk, uint32_t n, uint32_t *out)
+{
+  const uint32_t k = threadIdx.x;
+  if (k < n) out[k] = p59_pos(pk, k);
+}
+
+PackedRow packed_row(int G, int L)
+{
+  PackedRow pk;
+  pk.G = (uint32_t)G; pk.L = (uint32_t)L; pk.E = (uint32_t)((128 * L) / 59); pk.row_bytes = (uint32_t)(G * L) * 16u;
+  pk.lgG = 0; while ((1u << pk.lgG) < (uint32_t)G) ++pk.lgG;
+  return pk;
+}
+
+template <int L>
+int p59_round_trip(int G, int writer, uint32_t nrows, uint32_t ncols, const double *w_in, double *w_out,
+                   uint32_t *flushed_out, unsigned char *rows_out)
+{
+  const PackedRow pk = packed_row(G, L);
+  const size_t n = (size_t)nrows * pk.G * pk.E, row_bytes = (size_t)nrows * pk.row_bytes;
+  DevBuf w, out, fl, rows;
+  PROBE_TRY(w.alloc(n * sizeof(double)));
+  PROBE_TRY(out.alloc(n * sizeof(double)));
+  PROBE_TRY(fl.alloc(n * sizeof(uint32_t)));
+  PROBE_TRY(rows.alloc(row_bytes));
+  PROBE_TRY(hipMemcpy(w.p, w_in, n * sizeof(double), hipMemcpyHostToDevice));
+  PROBE_TRY(hipMemset(rows.p, 0xa5, row_bytes));           // a writer must store every byte of the row
+  if (writer == 0)
+    hipLaunchKernelGGL(p59_write_lds_kernel, dim3(nrows), dim3((unsigned)G), 0, 0, pk, ncols, w.as<double>(),
+                       rows.as<unsigned char>(), fl.as<uint32_t>());
+  else
+    hipLaunchKernelGGL((p59_write_reg_kernel<L>), dim3(nrows), dim3((unsigned)G), 0, 0, (uint32_t)G, ncols, w.as<double>(),
+                       rows.as<unsigned char>(), fl.as<uint32_t>());
+  if (const int rc = finish_launch()) return rc;
+  hipLaunchKernelGGL((p59_read_kernel<L>), dim3(nrows), dim3((unsigned)G), 0, 0, (uint32_t)G, rows.as<unsigned char>(),
+                     out.as<double>());
+  if (const int rc = finish_launch()) return rc;
+  PROBE_TRY(hipMemcpy(w_out, out.p, n * sizeof(double), hipMemcpyDeviceToHost));
+  PROBE_TRY(hipMemcpy(flushed_out, fl.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  if (rows_out) PROBE_TRY(hipMemcpy(rows_out, rows.p, row_bytes, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+template <int L>
+void p59_static_pos(uint32_t *out, uint32_t *n)
+{
+  using C = codec_p59<L>;
+  *n = (uint32_t)(C::E + C::S);
+  for (int k = 0; k < C::E + C::S; ++k) out[k] = (uint32_t)C::pos(k);
+}
+
+bool array_ok(int n) { return n >= 0 && n <= PROBE_MAX_N; }
+
+}  // namespace
+
+#define PROBE_API extern "C" __attribute__((visibility("default")))
+
+PROBE_API int probe_max_n(void) { return PROBE_MAX_N; }
+
+// out[i] = fast_rcp(x[i])
+PROBE_API int probe_rcp(int n, const double *x, double *out)
+{
+  if (!array_ok(n)) return (int)hipErrorInvalidValue;
+  if (n == 0) return 0;
+  DevBuf dx, dout;
+  PROBE_TRY(dx.alloc(n * sizeof(double)));
+  PROBE_TRY(dout.alloc(n * sizeof(double)));
+  PROBE_TRY(hipMemcpy(dx.p, x, n * sizeof(double), hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(rcp_kernel, grid_for(n), dim3(256), 0, 0, dx.as<double>(), dout.as<double>(), n);
+  if (const int rc = finish_launch()) return rc;
+  PROBE_TRY(hipMemcpy(out, dout.p, n * sizeof(double), hipMemcpyDeviceToHost));
+  return 0;
+}
+
+// psi_out[i] = digamma_pos(x[i]);  (xs_out[i], corr_out[i]) = psi_parts(x[i])
+PROBE_API int probe_psi(int n, const double *x, double *psi_out, double *xs_out, double *corr_out)
+{
+  if (!array_ok(n)) return (int)hipErrorInvalidValue;
+  if (n == 0) return 0;
+  DevBuf dx, d[3];
+  PROBE_TRY(dx.alloc(n * sizeof(double)));
+  for (DevBuf &b : d) PROBE_TRY(b.alloc(n * sizeof(double)));
+  PROBE_TRY(hipMemcpy(dx.p, x, n * sizeof(double), hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(psi_kernel, grid_for(n), dim3(256), 0, 0, dx.as<double>(), d[0].as<double>(), d[1].as<double>(),
+                     d[2].as<double>(), n);
+  if (const int rc = finish_launch()) return rc;
+  PROBE_TRY(hipMemcpy(psi_out, d[0].p, n * sizeof(double), hipMemcpyDeviceToHost));
+  PROBE_TRY(hipMemcpy(xs_out, d[1].p, n * sizeof(double), hipMemcpyDeviceToHost));
+  PROBE_TRY(hipMemcpy(corr_out, d[2].p, n * sizeof(double), hipMemcpyDeviceToHost));
+  return 0;
+}
+
+// (xs, corr, ri) = psi_parts_rate(x[i], rt[i]);  w_out[i] = xs * exp_neg(corr) * ri -- one element of the row sweep
+PROBE_API int probe_sweep_elem(int n, const double *x, const double *rt, double *w_out, double *ri_out, double *corr_out)
+{
+  if (!array_ok(n)) return (int)hipErrorInvalidValue;
+  if (n == 0) return 0;
+  DevBuf dx, drt, d[3];
+  PROBE_TRY(dx.alloc(n * sizeof(double)));
+  PROBE_TRY(drt.alloc(n * sizeof(double)));
+  for (DevBuf &b : d) PROBE_TRY(b.alloc(n * sizeof(double)));
+  PROBE_TRY(hipMemcpy(dx.p, x, n * sizeof(double), hipMemcpyHostToDevice));
+  PROBE_TRY(hipMemcpy(drt.p, rt, n * sizeof(double), hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(sweep_elem_kernel, grid_for(n), dim3(256), 0, 0, dx.as<double>(), drt.as<double>(), d[0].as<double>(),
+                     d[1].as<double>(), d[2].as<double>(), n);
+  if (const int rc = finish_launch()) return rc;
+  PROBE_TRY(hipMemcpy(w_out, d[0].p, n * sizeof(double), hipMemcpyDeviceToHost));
+  PROBE_TRY(hipMemcpy(ri_out, d[1].p, n * sizeof(double), hipMemcpyDeviceToHost));
+  PROBE_TRY(hipMemcpy(corr_out, d[2].p, n * sizeof(double), hipMemcpyDeviceToHost));
+  return 0;
+}
+
+// out[i] = exp_neg(c[i])
+PROBE_API int probe_exp_neg(int n, const double *c, double *out)
+{
+  if (!array_ok(n)) return (int)hipErrorInvalidValue;
+  if (n == 0) return 0;
+  DevBuf dc, dout;
+  PROBE_TRY(dc.alloc(n * sizeof(double)));
+  PROBE_TRY(dout.alloc(n * sizeof(double)));
+  PROBE_TRY(hipMemcpy(dc.p, c, n * sizeof(double), hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(exp_neg_kernel, grid_for(n), dim3(256), 0, 0, dc.as<double>(), dout.as<double>(), n);
+  if (const int rc = finish_launch()) return rc;
+  PROBE_TRY(hipMemcpy(out, dout.p, n * sizeof(double), hipMemcpyDeviceToHost));
+  return 0;
+}
+
+// nrows p59 rows of G lanes x L pieces (E = 128 L / 59 elements per lane, G * E columns): the first ncols columns of
+// every row of w_in are encoded by `writer` -- 0: p59_put into LDS + packed_copy_out, 1: p59_place<E, L> in registers --
+// and ALL G * E columns are decoded with codec_p59<L>::get into w_out.  flushed_out[row][column]: the writer reported
+// the element as flushed.  rows_out (may be NULL): the nrows * G * L * 16 bytes of the rows as written.
+PROBE_API int probe_p59(int L, int G, int writer, uint32_t nrows, uint32_t ncols, const double *w_in, double *w_out,
+                        uint32_t *flushed_out, unsigned char *rows_out)
+{
+  if (L < 1 || L > 8 || (G != 4 && G != 8 && G != 16 && G != 32 && G != 64) || (writer != 0 && writer != 1))
+    return (int)hipErrorInvalidValue;
+  const uint32_t ld = (uint32_t)(G * ((128 * L) / 59));
+  if (nrows == 0 || ncols > ld || (size_t)nrows * ld > (size_t)PROBE_MAX_N) return (int)hipErrorInvalidValue;
+  switch (L) {
+#define P59_L(LL) case LL: return p59_round_trip<LL>(G, writer, nrows, ncols, w_in, w_out, flushed_out, rows_out);
+    P59_L(1) P59_L(2) P59_L(3) P59_L(4) P59_L(5) P59_L(6) P59_L(7) P59_L(8)
+#undef P59_L
+  }
+  return (int)hipErrorInvalidValue;
+}
+
+// the place of each of the E + S logical dwords of a p59 lane of L pieces: run_time_out from p59_pos on the device (what
+// the LDS writer uses, shape from PackedRow), compile_time_out from codec_p59<L>::pos (the reader and the register writer).
+// Both arrays hold 4 L entries at most; *n_out = E + S.
+PROBE_API int probe_p59_pos(int L, int G, uint32_t *run_time_out, uint32_t *compile_time_out, uint32_t *n_out)
+{
+  if (L < 1 || L > 8 || (G != 4 && G != 8 && G != 16 && G != 32 && G != 64)) return (int)hipErrorInvalidValue;
+  switch (L) {
+#define POS_L(LL) case LL: p59_static_pos<LL>(compile_time_out, n_out); break;
+    POS_L(1) POS_L(2) POS_L(3) POS_L(4) POS_L(5) POS_L(6) POS_L(7) POS_L(8)
+#undef POS_L
+  }
+  const PackedRow pk = packed_row(G, L);
+  DevBuf d;
+  PROBE_TRY(d.alloc(32 * sizeof(uint32_t)));
+  hipLaunchKernelGGL(p59_pos_kernel, dim3(1), dim3(64), 0, 0, pk, *n_out, d.as<uint32_t>());
+  if (const int rc = finish_launch()) return rc;
+  PROBE_TRY(hipMemcpy(run_time_out, d.p, *n_out * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  return 0;
+}
+
+// whether the library was built with the paired dword order (HPF_P59_PAIRED)
+PROBE_API int probe_p59_paired(void) { return HPF_P59_PAIRED ? 1 : 0; }
