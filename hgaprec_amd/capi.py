@@ -41,6 +41,7 @@ EXPORTS = [
     "hpf_get_work_info", "hpf_upload_csr_device", "hpf_get_csc", "hpf_set_state_device", "hpf_get_state_device",
     "hpf_iteration_times", "hpf_debug_poke_index", "hpf_start_sums", "hpf_host_alloc", "hpf_host_free",
     "hpf_heldout_bind", "hpf_heldout_ll_bound",
+    "hpf_predict", "hpf_loo_ranks",
 ]
 
 
@@ -180,6 +181,9 @@ def load_library(path: os.PathLike | None = None) -> C.CDLL:
     lib.hpf_scores.argtypes = [vp, u32p, C.c_uint32, dp]
     lib.hpf_rank_topn.argtypes = [vp, u32p, C.c_uint32, u64p, u32p, C.c_uint32, u32p, dp]
     lib.hpf_item_ranks.argtypes = [vp, u32p, C.c_uint32, u64p, u32p, u32p, u32p, C.c_uint32, u32p, dp]
+    if hasattr(lib, "hpf_predict"):               # (v8 additions: absent from an older build loaded through HPF_LIB)
+        lib.hpf_predict.argtypes = [vp, u32p, u32p, C.c_size_t, dp]
+        lib.hpf_loo_ranks.argtypes = [vp, u32p, C.c_uint32, u64p, u32p, u32p, C.c_uint32, u32p, dp, u32p]
     lib.hpf_comm_unique_id.argtypes = [vp]
     lib.hpf_comm_init.argtypes = [vp, vp]
     lib.hpf_allreduce_exchange.argtypes = [vp]
@@ -514,6 +518,34 @@ class Hpf:
                                             _ptr(q_sel, C.c_uint32), _ptr(q_item, C.c_uint32), q_sel.size,
                                             _ptr(rank, C.c_uint32), _ptr(sc, C.c_double)))
         return rank, sc
+
+    def predict(self, u, i) -> np.ndarray:
+        """E_theta[u] . E_beta[i] (+ both biases) per pair (hpf_predict); u is a local user index"""
+        u = np.ascontiguousarray(u, dtype=np.uint32)
+        i = np.ascontiguousarray(i, dtype=np.uint32)
+        if u.shape != i.shape or u.ndim != 1:
+            raise ValueError("u and i: one-dimensional arrays of the same length")
+        out = np.empty(u.size, dtype=np.float64)
+        self._check(self.lib.hpf_predict(self._h, _ptr(u, C.c_uint32), _ptr(i, C.c_uint32), u.size, _ptr(out, C.c_double)))
+        return out
+
+    def loo_ranks(self, users, q_item, mask_ptr=None, mask_items=None, item_limit=0):
+        """position of q_item[b] among the items [0, item_limit) of selected user b (hpf_loo_ranks; 0: all items)
+        -> (rank, score, masked)"""
+        users = np.ascontiguousarray(users, dtype=np.uint32)
+        q_item = np.ascontiguousarray(q_item, dtype=np.uint32)
+        if users.shape != q_item.shape or users.ndim != 1:
+            raise ValueError("users and q_item: one-dimensional arrays of the same length")
+        mp, mi, pmp, pmi = self._mask(mask_ptr, mask_items)
+        if mp is not None and mp.size != users.size + 1:
+            raise ValueError("mask_ptr must have len(users) + 1 entries")
+        rank = np.empty(users.size, dtype=np.uint32)
+        sc = np.empty(users.size, dtype=np.float64)
+        masked = np.empty(users.size, dtype=np.uint32)
+        self._check(self.lib.hpf_loo_ranks(self._h, _ptr(users, C.c_uint32), users.size, pmp, pmi, _ptr(q_item, C.c_uint32),
+                                           int(item_limit), _ptr(rank, C.c_uint32), _ptr(sc, C.c_double),
+                                           _ptr(masked, C.c_uint32)))
+        return rank, sc, masked
 
     def synchronize(self):
         self._check(self.lib.hpf_synchronize(self._h))

@@ -62,11 +62,14 @@ int Env::parse(int argc, char **argv, bool echo, std::string *bad)
     else if (!strcmp(s, "-bias")) { bias = true; }
     else if (!strcmp(s, "-hier")) { hier = true; }
     else if (!strcmp(s, "-mle-user") || !strcmp(s, "-mle-item") || !strcmp(s, "-canny") ||
-             !strcmp(s, "-gen-ranking") || !strcmp(s, "-rmse") || !strcmp(s, "-msr") ||
              !strcmp(s, "-nmf") || !strcmp(s, "-nmfload") || !strcmp(s, "-vwload") ||
              !strcmp(s, "-lda") || !strcmp(s, "-vwlda") || !strcmp(s, "-write-training") ||
              !strcmp(s, "-chi") || !strcmp(s, "-chinmf") || !strcmp(s, "-als") ||
              !strcmp(s, "-wals") || !strcmp(s, "-climf") || !strcmp(s, "-ctr")) { out_of_scope(s); }
+    else if (!strcmp(s, "-gen-ranking")) { gen_ranking = true; }
+    else if (!strcmp(s, "-rmse")) { rmse = true; }
+    else if (!strcmp(s, "-msr")) { msr = true; }
+    else if (!strcmp(s, "-model-dir")) { model_dir = next(); }   // extension: where a score mode finds the factor files
     else if (!strcmp(s, "-novb")) { vb = false; }
     else if (!strcmp(s, "-wals_l") || !strcmp(s, "-wals_C")) { next(); }
     else if (!strcmp(s, "-rating-threshold")) { rating_threshold = (uint32_t)atoi(next()); }
@@ -1117,6 +1120,125 @@ int save_vector(const std::string &path, const double *a, uint32_t rows,
   }
   w.flush();
   return close_rewrite(tf, path, ferror(tf) == 0) ? 0 : -1;
+}
+
+// ======================================================================
+// model reader: the inverse of save_matrix / save_vector
+// ======================================================================
+// The reference's rules (D2Array<double>::load matrix.hh:1198-1266, D1Array<double>::load 767-803, called by
+// GPMatrix::load / GPMatrixGR::load / GPArray::load, gpbase.hh:410-415,755-764,983-990): a line is read field by
+// field with strtod until a field does not parse; the first two fields (seq, id) are skipped as values; rows are
+// taken in line order; lines beyond the expected row count are never looked at.
+// STRICTER than the reference, on purpose -- there a missing file is an assert, and a short file, a short row or
+// the model of another data set load without a word (the array keeps its zeros, the ids are never compared):
+//   a file that cannot be opened, a file with fewer rows than the model has, a row with fewer than `cols` values
+//   and (ids != NULL) a row whose id column is not the expected one are ERRORS; the message names the file and,
+//   where there is one, the line (the first one in file order).
+// Values beyond the first `cols` of a row are ignored.  Like the TSV reader, a large file is mapped and parsed in
+// pieces by the host's threads (HGAPREC_READ_THREADS, HGAPREC_READ_PARALLEL_MIN): a 10^6 x 100 htheta.tsv is 1.1 GB.
+namespace {
+// one line [p, e) (e: its '\n' or the end of the text, where a NUL or '\n' stands) into dst[cols]
+bool load_row(const char *p, const char *e, double *dst, uint32_t cols, bool check_id, uint32_t want_id, std::string *why)
+{
+  uint32_t f = 0;
+  for (; f < cols + 2; ++f) {
+    // everything strtod itself would skip ('\f' and '\v' too), so that it never runs past e into the next line
+    while (p < e && *p != '\n' && isspace((unsigned char)*p)) ++p;
+    if (p >= e || *p == '\n') break;
+    char *q = nullptr;
+    const double d = strtod(p, &q);
+    if (q == p) break;                                          // not a number: the reference stops the line here
+    p = q;
+    if (f == 1 && check_id && d != (double)want_id) {
+      char buf[96]; snprintf(buf, sizeof buf, "id %.0f where the ratings have %u (the model of another data set?)", d, want_id);
+      *why = buf; return false;
+    }
+    if (f >= 2) dst[f - 2] = d;
+  }
+  if (f < cols + 2) {
+    char buf[96]; snprintf(buf, sizeof buf, "%u values where %u are expected", f >= 2 ? f - 2 : 0u, cols);
+    *why = buf; return false;
+  }
+  return true;
+}
+}  // namespace
+
+int load_matrix(const std::string &path, double *out, uint32_t rows, uint32_t cols,
+                const uint32_t *ids, uint32_t nids, std::string *err)
+{
+  auto fail = [&](const std::string &msg) { if (err) *err = path + ": " + msg; return -1; };
+  const int fd = ::open(path.c_str(), O_RDONLY | O_CLOEXEC);
+  if (fd < 0) return fail(std::string("cannot open: ") + strerror(errno));
+  struct FdClose { int fd; ~FdClose() { ::close(fd); } } fdc{fd};
+  struct stat st;
+  if (fstat(fd, &st) != 0) return fail(std::string("cannot stat: ") + strerror(errno));
+  if (rows == 0) return 0;
+  const size_t size = S_ISREG(st.st_mode) ? (size_t)st.st_size : 0;
+  if (size == 0) return fail("0 rows where the model has " + std::to_string(rows));
+  void *map = mmap(nullptr, size, PROT_READ, MAP_PRIVATE, fd, 0);
+  if (map == MAP_FAILED) return fail(std::string("cannot map: ") + strerror(errno));
+  struct Unmap { void *p; size_t n; ~Unmap() { munmap(p, n); } } unmap{map, size};
+  const char *d = (const char *)map;
+  // strtod needs a character that ends the number behind it: a last line without '\n' is parsed from a copy
+  size_t body = size;                                           // the text up to and including the last '\n'
+  while (body > 0 && d[body - 1] != '\n') --body;
+  const std::string last(d + body, size - body);
+
+  unsigned nt = std::thread::hardware_concurrency();
+  if (const char *e = getenv("HGAPREC_READ_THREADS")) { const int v = atoi(e); nt = v < 1 ? 1u : (unsigned)v; }
+  nt = std::min(std::max(nt, 1u), 64u);
+  size_t min_bytes = (size_t)8 << 20;
+  if (const char *e = getenv("HGAPREC_READ_PARALLEL_MIN")) min_bytes = (size_t)strtoull(e, nullptr, 0);
+  if (body < std::max<size_t>(min_bytes, 1)) nt = 1;
+  nt = (unsigned)std::max<size_t>(1, std::min<size_t>(nt, body / 64 + 1));
+
+  // pieces that start behind a '\n'; lines per piece; then every piece knows the row of its first line
+  std::vector<size_t> cut(nt + 1, body);
+  cut[0] = 0;
+  for (unsigned t = 1; t < nt; ++t) {
+    size_t p = std::max(cut[t - 1], body / nt * t);
+    while (p < body && p > 0 && d[p - 1] != '\n') ++p;
+    cut[t] = p;
+  }
+  std::vector<uint64_t> first(nt + 1, 0);
+  on_threads(nt, [&](unsigned t) {
+    uint64_t cnt = 0;
+    for (const char *p = d + cut[t], *e = d + cut[t + 1]; p < e;) {
+      const char *nl = (const char *)memchr(p, '\n', (size_t)(e - p));
+      if (!nl) break;
+      ++cnt; p = nl + 1;
+    }
+    first[t + 1] = cnt;
+  });
+  for (unsigned t = 0; t < nt; ++t) first[t + 1] += first[t];
+  const uint64_t lines = first[nt] + (last.empty() ? 0 : 1);
+  if (lines < rows) return fail(std::to_string(lines) + " rows where the model has " + std::to_string(rows));
+
+  std::vector<uint64_t> bad_line(nt + 1, ~0ull);
+  std::vector<std::string> bad_why(nt + 1);
+  auto row_of = [&](uint64_t r, const char *p, const char *e, unsigned slot) {
+    const uint32_t want = (ids && r < nids) ? ids[r] : (uint32_t)r;
+    if (load_row(p, e, out + (size_t)r * cols, cols, ids != nullptr, want, &bad_why[slot])) return true;
+    bad_line[slot] = r + 1;
+    return false;
+  };
+  on_threads(nt, [&](unsigned t) {
+    uint64_t r = first[t];
+    for (const char *p = d + cut[t], *e = d + cut[t + 1]; p < e && r < rows; ++r) {
+      const char *nl = (const char *)memchr(p, '\n', (size_t)(e - p));
+      if (!nl || !row_of(r, p, nl, t)) break;
+      p = nl + 1;
+    }
+  });
+  if (!last.empty() && first[nt] < rows) row_of(first[nt], last.c_str(), last.c_str() + last.size(), nt);
+  for (unsigned t = 0; t <= nt; ++t)
+    if (bad_line[t] != ~0ull) return fail("line " + std::to_string(bad_line[t]) + ": " + bad_why[t]);   // pieces are in file order
+  return 0;
+}
+
+int load_vector(const std::string &path, double *out, uint32_t rows, const uint32_t *ids, uint32_t nids, std::string *err)
+{
+  return load_matrix(path, out, rows, 1, ids, nids, err);
 }
 
 // ======================================================================

@@ -49,6 +49,12 @@ struct Env {
   // <dir>/hgaprec.cache.bin and loads it instead of the three TSVs while their
   // sizes / mtimes and -n -m -binary-data -rating-threshold are unchanged
   bool data_cache = false;
+  // score a saved model instead of training one (main.cc:233-257; hgaprec.cc:2087-2112, 1579-1604, 1993-2085): read the
+  // data, load the factor files the writers left, run ONE report, exit.  -model-dir DIR (extension): where those files
+  // are; default the current directory, like the reference (name() + ".tsv")
+  bool gen_ranking = false, rmse = false, msr = false;
+  std::string model_dir;
+  bool score_mode() const { return gen_ranking || rmse || msr; }
 
   std::string prefix;          // output directory (Env::prefix)
   FILE *plogf = nullptr;       // param.txt
@@ -197,6 +203,17 @@ int save_matrix(const std::string &path, const double *a, uint32_t rows, uint32_
                 const uint32_t *seq2id, uint32_t nids, uint32_t row0 = 0, unsigned threads = 0);
 int save_vector(const std::string &path, const double *a, uint32_t rows,
                 const uint32_t *seq2id, uint32_t nids, uint32_t row0 = 0);
+
+// ------------------------------------------------------------ readers -----
+// the inverse of save_matrix / save_vector with the reference's reading rules (matrix.hh:767-803,1198-1266): strtod per
+// field, the first two columns (seq, id) skipped as values, rows in line order, lines beyond `rows` ignored.  Stricter
+// than the reference (hgaprec_host.cpp): a missing file, fewer rows than `rows`, a row with fewer than `cols` values and
+// -- when ids is given -- an id column that differs from ids[row] (row >= nids: the row index) return -1 with
+// *err = "<path>: ..." naming the line.  out: rows x cols doubles, row-major.
+int load_matrix(const std::string &path, double *out, uint32_t rows, uint32_t cols,
+                const uint32_t *ids, uint32_t nids, std::string *err);
+int load_vector(const std::string &path, double *out, uint32_t rows,
+                const uint32_t *ids, uint32_t nids, std::string *err);
 
 // ------------------------------------------- held-out series / stopping ---
 // HGAPRec::compute_likelihood bookkeeping (hgaprec.cc:1466-1500)

@@ -13,13 +13,18 @@
 // stand-in (`-comm host`, for tests on a single GPU).  The output files are
 // the same as in a single-GPU run.
 //
-// Out of scope: competitor bridges, MLE/Canny ablations,
-// -gen-ranking/-msr/-rmse report modes; their flags are recognised and refused.
+// Scoring a saved model: -gen-ranking / -rmse / -msr read the data like a training run, load
+// the factor files a run has written (from the current directory like the reference, or from
+// -model-dir DIR) into the handle's expectations, write ONE report and exit (Driver::score).
+//
+// Out of scope: competitor bridges, MLE/Canny ablations, -test; their
+// flags are recognised and refused.
 #include "../../../include/hpf.h"
 #include "hgaprec_host.hpp"
 
 #include <algorithm>
 #include <cassert>
+#include <cmath>
 #include <chrono>
 #include <cerrno>
 #include <csignal>
@@ -247,7 +252,7 @@ struct Driver {
                  wi.tiles_user ? "tiled" : "row-major", wi.tiles_user, wi.tiles_item ? "tiled" : "row-major", wi.tiles_item);
     }
 
-    save_prealloc = std::thread([this]() {
+    if (!env.score_mode()) save_prealloc = std::thread([this]() {     // (a score mode never saves the model)
       for (int j = 0; j < 3; ++j) {
         save_u[j].reserve((size_t)(hi - lo) * k);
         if (root()) save_i[j].reserve((size_t)m * k);
@@ -659,6 +664,134 @@ struct Driver {
 
   void do_on_stop() { save_model(); gen_ranking_for_users(); }          // hgaprec.cc:1572-1577
 
+  // ---- scoring a saved model: -gen-ranking, -rmse, -msr (one GPU) --------
+  std::string model_path(const char *name) const { return (env.model_dir.empty() ? std::string(".") : env.model_dir) + "/" + name; }
+  [[noreturn]] void model_die(const std::string &msg) {
+    fprintf(stderr, "error: cannot load the model: %s\n", msg.c_str());
+    exit(1);
+  }
+  // HGAPRec::load_beta_and_theta (hgaprec.cc:2114-2135): the expectations of the factor files into the handle's *_E.
+  // -hier: htheta.tsv / hbeta.tsv hold E; without: E = shape / rate[k], as GPMatrixGR::load -> compute_expectations
+  // does (gpbase.hh:755-764); -bias: the one value column of thetabias.tsv / betabias.tsv.  thetarate.tsv / betarate.tsv
+  // are read when they are there (scoring never touches them).  Stricter than the reference (hgaprec_host.cpp,
+  // load_matrix): a missing file, a short file, a short row, or ids that are not those of the ratings just read stop the run.
+  void load_model() {
+    auto put = [&](hpf_state w, const std::vector<double> &v) {
+      int rc = hpf_set_state(h, w, v.data(), v.size());
+      if (rc) die("hpf_set_state", rc);
+    };
+    std::string err;
+    auto side = [&](bool user_side) {
+      const uint32_t rows = user_side ? n : m;
+      const std::vector<uint32_t> &ids = user_side ? rt.seq2user : rt.seq2item;
+      const std::string base = env.hier ? (user_side ? "htheta" : "hbeta") : (user_side ? "theta" : "beta");
+      std::vector<double> E((size_t)rows * k);
+      if (env.hier) {
+        if (load_matrix(model_path((base + ".tsv").c_str()), E.data(), rows, k, ids.data(), (uint32_t)ids.size(), &err)) model_die(err);
+      } else {
+        std::vector<double> rate(k);
+        if (load_matrix(model_path((base + "_shape.tsv").c_str()), E.data(), rows, k, ids.data(), (uint32_t)ids.size(), &err)) model_die(err);
+        if (load_vector(model_path((base + "_rate.tsv").c_str()), rate.data(), k, nullptr, 0, &err)) model_die(err);   // a K-vector: its id column is seq2id[k]
+        for (size_t r = 0; r < rows; ++r)
+          for (uint32_t c = 0; c < k; ++c) E[r * k + c] = E[r * k + c] / rate[c];
+      }
+      put(user_side ? HPF_THETA_E : HPF_BETA_E, E);
+      if (env.hier) {
+        const std::string rp = model_path(user_side ? "thetarate.tsv" : "betarate.tsv");
+        if (access(rp.c_str(), R_OK) == 0) {
+          std::vector<double> v(rows);
+          if (load_vector(rp, v.data(), rows, ids.data(), (uint32_t)ids.size(), &err)) model_die(err);
+          put(user_side ? HPF_XI_E : HPF_ETA_E, v);
+        }
+      }
+      if (env.bias) {
+        std::vector<double> v(rows);
+        if (load_vector(model_path(user_side ? "thetabias.tsv" : "betabias.tsv"), v.data(), rows, ids.data(), (uint32_t)ids.size(), &err)) model_die(err);
+        put(user_side ? HPF_UBIAS_E : HPF_IBIAS_E, v);
+      }
+    };
+    side(false);
+    side(true);
+    env.lerr("loaded the model from %s", env.model_dir.empty() ? "." : env.model_dir.c_str());
+  }
+
+  // HGAPRec::compute_rmse (hgaprec.cc:1579-1604).  DEVIATION: the reference's -rmse never loads the model (main.cc:254-257
+  // constructs and calls compute_rmse; load_beta_and_theta() is commented out at hgaprec.cc:1587), so it scores the empty
+  // start objects.  This build loads the model first.
+  void compute_rmse() {
+    const HeldOut &ho = rt.test;
+    std::vector<double> pred(ho.u.size());
+    int rc = hpf_predict(h, ho.u.data(), ho.i.data(), ho.u.size(), pred.data());
+    if (rc) die("hpf_predict", rc);
+    const std::string spath = env.file_str("/test_scores.tsv");
+    FILE *f = open_or_die(spath, "w");
+    double s = .0;
+    for (size_t p = 0; p < pred.size(); ++p) {                // map order, summed serially
+      const uint8_t v = (uint8_t)ho.y[p];                     // yval_t v = i->second
+      const double u = pred[p];
+      s += (u - v) * (u - v);
+      fprintf(f, "%d\t%.5f\n", v, u);
+    }
+    close_or_die(f, spath);
+    const std::string rpath = env.file_str("/rmse.txt");
+    FILE *rf = open_or_die(rpath, "w");
+    fprintf(rf, "%.5f\n", sqrt(s / pred.size()));
+    close_or_die(rf, rpath);
+  }
+
+  // HGAPRec::gen_msr_csv (hgaprec.cc:1993-2085): per user, where the held-out item -- the LAST test pair of the user in
+  // (user, item) order, hgaprec.cc:140-145 -- stands among the items [0, m - 1) (the reference's loop never scores item
+  // m - 1).  The reference asserts on a user without a test pair; here the run stops before pred.csv exists.
+  void gen_msr_csv() {
+    std::vector<uint32_t> heldout(n, 0xffffffffu);
+    for (size_t p = 0; p < rt.test.u.size(); ++p) heldout[rt.test.u[p]] = rt.test.i[p];     // sorted by (user, item): the last one stays
+    for (uint32_t u = 0; u < n; ++u)
+      if (heldout[u] == 0xffffffffu) {
+        fprintf(stderr, "error: -msr: user %u (seq %u) has no pair in test.tsv\n", rt.seq2user[u], u);
+        exit(1);
+      }
+    if (item_deg.empty()) { item_deg.assign(m, 0); for (uint32_t c : rt.col) item_deg[c]++; }
+    std::vector<uint32_t> valid_users(m, 0);                 // _validation_users_of_movie
+    for (uint32_t it : rt.validation.i) valid_users[it]++;
+    std::vector<uint32_t> rank(n), masked(n);                // O(n) results; the scores of a chunk never leave the device
+    std::vector<double> sc;
+    const uint32_t limit = m - 1, CH = 1u << 16;
+    std::vector<uint32_t> us; std::vector<uint64_t> mptr; std::vector<uint32_t> mitems;
+    // m == 1: the reference's loop over [0, m - 1) scores nothing and leaves rank 0 (a limit of 0 would mean "all items")
+    for (uint32_t u0 = 0; u0 < n && limit > 0; u0 += CH) {
+      const uint32_t u1 = std::min(n, u0 + CH);
+      us.clear(); mitems.clear(); mptr.assign(1, 0);
+      for (uint32_t u = u0; u < u1; ++u) {
+        us.push_back(u);
+        for (size_t a = lower(rt.validation, u, 0); a < rt.validation.u.size() && rt.validation.u[a] == u; ++a)
+          mitems.push_back(rt.validation.i[a]);
+        mptr.push_back(mitems.size());
+      }
+      sc.resize(us.size());
+      int rc = hpf_loo_ranks(h, us.data(), (uint32_t)us.size(), mptr.data(), mitems.data(), heldout.data() + u0, limit,
+                             rank.data() + u0, sc.data(), masked.data() + u0);
+      if (rc) die("hpf_loo_ranks", rc);
+    }
+    const std::string path = env.file_str("/pred.csv");
+    FILE *f = open_or_die(path, "w");
+    fprintf(f, "User\tHeldOutItem\tHeldOutItemIndex\tUserNegatives\tUserCount\tItemCount\n");
+    for (uint32_t u = 0; u < n; ++u) {
+      const uint32_t t = heldout[u], training = masked[u], negatives = limit - masked[u];
+      fprintf(f, "%d\t%d\t%d\t%d\t%d\t%d\n", rt.seq2user[u], rt.seq2item[t], rank[u], negatives, training,
+              valid_users[t] + item_deg[t]);
+    }
+    close_or_die(f, path);
+  }
+
+  // one report on the loaded state, in the reference's order of tests (main.cc:254-285, then -gen-ranking)
+  void score() {
+    load_model();
+    if (env.rmse) compute_rmse();
+    else if (env.msr) gen_msr_csv();
+    else gen_ranking_for_users();
+    finish(0);
+  }
+
   // the library moved the rows of W from the packed form to plain doubles (a state p59 cannot hold): say so once
   void note_fallback() {
     hpf_work_info wi;
@@ -894,8 +1027,26 @@ int main(int argc, char **argv)
   if (!env.unsupported.empty()) {
     fprintf(stderr, "error: option %s selects a mode outside the MI355X hot-path build "
                     "(supported: -dir -n -m -k -hier -bias -binary-data -rfreq -max-iterations "
-                    "-seed -label -rating-threshold -logl -novb -a -b -c -d, -ngpus -comm -single-allreduce -device)\n", env.unsupported.c_str());
+                    "-seed -label -rating-threshold -logl -novb -a -b -c -d, -gen-ranking -rmse -msr -model-dir, "
+                    "-ngpus -comm -single-allreduce -device)\n", env.unsupported.c_str());
     return 2;
+  }
+  if (env.score_mode()) {
+    if (env.ngpus > 1 || world > 1) {
+      fprintf(stderr, "error: -gen-ranking / -rmse / -msr score a saved model on ONE GPU: run them without -ngpus\n");
+      return 1;
+    }
+    // the start of a run truncates validation.txt, precision.txt and friends in its output directory: that directory
+    // must not be the one the model is read from.  Nothing has been opened yet.
+    char *pm = realpath(env.model_dir.empty() ? "." : env.model_dir.c_str(), nullptr);
+    char *po = realpath(env.make_prefix().c_str(), nullptr);
+    const bool same = pm && po && !strcmp(pm, po);
+    free(pm); free(po);
+    if (same) {
+      fprintf(stderr, "error: the output directory %s is the model directory: the run would overwrite the files next to the model. "
+                      "Give another -label, or run from inside the model directory like the reference\n", env.make_prefix().c_str());
+      return 1;
+    }
   }
   if (world == 1 && env.ngpus > 1) return spawn_ranks(env.ngpus, argv);
 
@@ -1007,6 +1158,7 @@ int main(int argc, char **argv)
   Driver d(env, ratings, comm);
   d.use_rccl = world > 1 && env.comm_mode != "host";
   d.construct();
+  if (env.score_mode()) { d.score(); return 0; }             // one report on the loaded model: never the training loop
   d.run();
   return 0;
 }

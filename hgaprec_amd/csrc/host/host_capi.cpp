@@ -115,6 +115,23 @@ int hg_save_matrix(const char *path, const double *a, uint32_t rows, uint32_t co
 int hg_save_vector(const char *path, const double *a, uint32_t rows, const uint32_t *ids, uint32_t nids)
 { return save_vector(path, a, rows, ids, nids); }
 
+// the model reader: 0, or -1 with the message ("<path>: ...") in err
+int hg_load_matrix(const char *path, double *out, uint32_t rows, uint32_t cols, const uint32_t *ids, uint32_t nids,
+                   char *err, size_t errcap)
+{
+  std::string e;
+  const int rc = load_matrix(path, out, rows, cols, ids, nids, &e);
+  if (err && errcap) { strncpy(err, e.c_str(), errcap - 1); err[errcap - 1] = 0; }
+  return rc;
+}
+int hg_load_vector(const char *path, double *out, uint32_t rows, const uint32_t *ids, uint32_t nids, char *err, size_t errcap)
+{
+  std::string e;
+  const int rc = load_vector(path, out, rows, ids, nids, &e);
+  if (err && errcap) { strncpy(err, e.c_str(), errcap - 1); err[errcap - 1] = 0; }
+  return rc;
+}
+
 // user ranges of a multi-process run: out[2*r], out[2*r+1] = [lo, hi) of rank r
 void hg_partition_users(const int64_t *rowptr, uint32_t n, int world, uint32_t *out)
 {

@@ -355,6 +355,46 @@ static void test_threads()
   unsetenv("HGAPREC_SAVE_THREADS");
 }
 
+// ---- model reader: what the writers wrote, hostile text, pieces on threads ----
+static void test_loader()
+{
+  const uint32_t rows = 257, cols = 9;
+  std::vector<double> mtx((size_t)rows * cols), back((size_t)rows * cols, -1.0);
+  std::vector<uint32_t> ids(rows);
+  for (size_t e = 0; e < mtx.size(); ++e) mtx[e] = (double)((e * 2654435761u) % 1000003u) / 1024.0;
+  for (uint32_t r = 0; r < rows; ++r) ids[r] = 7u * r + 3u;
+  CHECK(save_matrix(path("load.tsv"), mtx.data(), rows, cols, ids.data(), rows, 0, 1) == 0);
+  std::string err;
+  for (int threaded = 0; threaded < 2; ++threaded) {
+    if (threaded) { setenv("HGAPREC_READ_PARALLEL_MIN", "1", 1); setenv("HGAPREC_READ_THREADS", "5", 1); }
+    std::fill(back.begin(), back.end(), -1.0);
+    CHECK(load_matrix(path("load.tsv"), back.data(), rows, cols, ids.data(), rows, &err) == 0);
+    bool close = true;
+    for (size_t e = 0; e < mtx.size(); ++e) close = close && std::fabs(back[e] - mtx[e]) <= 5.001e-9;        // %.8f, plus the rounding of the parsed decimal
+    CHECK(close);
+    CHECK(load_matrix(path("load.tsv"), back.data(), rows + 1, cols, nullptr, 0, &err) != 0 && err.find("257 rows") != std::string::npos);
+    CHECK(load_matrix(path("load.tsv"), back.data(), rows, cols + 1, nullptr, 0, &err) != 0 && err.find("line 1:") != std::string::npos);
+    ids[200] ^= 1u;
+    CHECK(load_matrix(path("load.tsv"), back.data(), rows, cols, ids.data(), rows, &err) != 0 && err.find("line 201:") != std::string::npos);
+    ids[200] ^= 1u;
+  }
+  unsetenv("HGAPREC_READ_PARALLEL_MIN"); unsetenv("HGAPREC_READ_THREADS");
+  CHECK(load_matrix(path("no-such-model.tsv"), back.data(), 1, 1, nullptr, 0, &err) != 0 && err.find("cannot open") != std::string::npos);
+  // text the writers never produce: no final newline, a lone sign, letters, an empty file, only newlines
+  double v[4] = {0, 0, 0, 0};
+  write_text(path("tail.tsv"), "0\t5\t1.5\n1\t6\t2.5");
+  CHECK(load_vector(path("tail.tsv"), v, 2, nullptr, 0, &err) == 0 && v[0] == 1.5 && v[1] == 2.5);
+  write_text(path("sign.tsv"), "0\t5\t-");
+  CHECK(load_vector(path("sign.tsv"), v, 1, nullptr, 0, &err) != 0);
+  write_text(path("junk.tsv"), "0\t5\tabc\n\n\n");
+  CHECK(load_vector(path("junk.tsv"), v, 1, nullptr, 0, &err) != 0 && err.find("line 1:") != std::string::npos);
+  CHECK(load_vector(path("junk.tsv"), v, 3, nullptr, 0, &err) != 0);
+  write_text(path("empty.tsv"), "");
+  CHECK(load_vector(path("empty.tsv"), v, 1, nullptr, 0, &err) != 0 && load_vector(path("empty.tsv"), v, 0, nullptr, 0, &err) == 0);
+  write_text(path("nl.tsv"), "\n\n");
+  CHECK(load_vector(path("nl.tsv"), v, 2, nullptr, 0, &err) != 0 && err.find("line 1:") != std::string::npos);
+}
+
 int main(int argc, char **argv)
 {
   char tmpl[] = "/tmp/hgaprec_selftest_XXXXXX";
@@ -368,6 +408,7 @@ int main(int argc, char **argv)
   test_writers();
   test_state();
   test_threads();
+  test_loader();
   test_comm();
   if (g_fail) { fprintf(stderr, "host_selftest: %d check(s) failed\n", g_fail); return 1; }
   printf("host_selftest ok\n");

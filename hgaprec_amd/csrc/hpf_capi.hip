@@ -2862,6 +2862,118 @@ int hpf_item_ranks(hpf_handle *h, const uint32_t *users, uint32_t n_sel, const u
   return rc;
 }
 
+// ---- scoring a saved model: per-pair predictions, fused leave-one-out ranks ----
+int hpf_predict(hpf_handle *h, const uint32_t *u, const uint32_t *i, size_t cnt, double *out)
+{
+  if (!h) return HPF_ERR_INVALID;
+  if (cnt == 0) return HPF_OK;
+  if (!u || !i || !out) return HPF_ERR_INVALID;
+  if (!(h->u.have_E && h->it.have_E) && h->iterations == 0) { h->err = "E state not set"; return HPF_ERR_STATE; }
+  for (size_t p = 0; p < cnt; ++p)
+    if (u[p] >= h->u.rows || i[p] >= h->it.rows) { h->err = "hpf_predict: index out of range"; return HPF_ERR_INVALID; }
+  uint32_t *du = nullptr, *di = nullptr; double *dout = nullptr;
+  int rc = HPF_OK;
+  do {
+    if ((rc = check_flags(h))) break;
+    if ((rc = refresh_es(h, h->u)) || (rc = refresh_es(h, h->it))) break;
+    if ((rc = dalloc(h, &du, cnt)) || (rc = dalloc(h, &di, cnt)) || (rc = dalloc(h, &dout, cnt))) break;
+    if ((rc = h2d(h, du, u, cnt * 4)) || (rc = h2d(h, di, i, cnt * 4))) break;
+    PredictArgs a;
+    a.u = du; a.i = di; a.cnt = cnt; a.Et = h->u.E; a.Eb = h->it.E; a.out = dout; a.ld = h->ld; a.K = h->K;
+    a.ubias_col = h->cfg.bias ? h->u.bias_col : -1;
+    a.ibias_col = h->cfg.bias ? h->it.bias_col : -1;
+    const uint32_t blocks = (uint32_t)std::min<size_t>((cnt + 15) / 16, 4096);
+    hipLaunchKernelGGL(predict_kernel, dim3(blocks), dim3(256), 0, h->stream, a);
+    if ((rc = check_launch(h, "predict_kernel"))) break;
+    hipError_t e = hipMemcpyAsync(out, dout, cnt * 8, hipMemcpyDeviceToHost, h->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    if (e != hipSuccess) { h->err = hipGetErrorString(e); rc = HPF_ERR_HIP; }
+  } while (0);
+  dfree(du); dfree(di); dfree(dout);
+  return rc;
+}
+
+int hpf_loo_ranks(hpf_handle *h, const uint32_t *users, uint32_t n_sel, const uint64_t *mask_ptr,
+                  const uint32_t *mask_items, const uint32_t *q_item, uint32_t item_limit,
+                  uint32_t *out_rank, double *out_score, uint32_t *out_masked)
+{
+  if (!h || (n_sel && (!users || !q_item || !out_rank || !out_score))) return HPF_ERR_INVALID;
+  if (!n_sel) return HPF_OK;
+  if (h->iterations == 0 && !(h->u.have_E && h->it.have_E)) { h->err = "E state not set"; return HPF_ERR_STATE; }
+  if (!h->have_csr) { h->err = "hpf_upload_csr has not been called"; return HPF_ERR_STATE; }
+  const uint32_t m = h->it.rows;
+  if (item_limit > m) { h->err = "item_limit beyond n_items"; return HPF_ERR_INVALID; }
+  const uint32_t limit = item_limit ? item_limit : m;
+  if (h->ld & 1u) { h->err = "hpf_loo_ranks: odd row stride"; return HPF_ERR_UNSUPPORTED; }
+  for (uint32_t b = 0; b < n_sel; ++b) {
+    if (users[b] >= h->u.rows) { h->err = "user index out of range"; return HPF_ERR_INVALID; }
+    if (q_item[b] >= m) { h->err = "query item out of range"; return HPF_ERR_INVALID; }
+  }
+  const uint64_t nmask = mask_ptr ? mask_ptr[n_sel] : 0;
+  if (mask_ptr) {
+    if (mask_ptr[0] != 0) { h->err = "mask_ptr[0] must be 0"; return HPF_ERR_INVALID; }
+    for (uint32_t b = 0; b < n_sel; ++b) if (mask_ptr[b + 1] < mask_ptr[b]) { h->err = "mask_ptr not monotone"; return HPF_ERR_INVALID; }
+    if (nmask && !mask_items) return HPF_ERR_INVALID;
+    for (uint64_t j = 0; j < nmask; ++j) if (mask_items[j] >= m) { h->err = "mask item out of range"; return HPF_ERR_INVALID; }
+  }
+  int rc;
+  if ((rc = check_flags(h))) return rc;
+  if ((rc = refresh_es(h, h->u)) || (rc = refresh_es(h, h->it))) return rc;
+
+  // users per batch: the bit rows of a batch stay under 256 MB; a multiple of the 64 users of a workgroup.
+  // HPF_LOO_BATCH (users, rounded up to the 16 users of a wave's block; a TEST knob, so that a handful of users
+  // crosses a batch boundary) makes it smaller.
+  const uint32_t words = (m + 63) / 64;
+  uint64_t batch = std::max<uint64_t>(64, (((uint64_t)256 << 20) / ((uint64_t)words * 8)) & ~63ull);
+  if (const char *e = getenv("HPF_LOO_BATCH")) { const long v = atol(e); if (v > 0) batch = std::min<uint64_t>(batch, ((uint64_t)v + 15) & ~15ull); }
+  batch = std::min<uint64_t>(batch, ((uint64_t)n_sel + 15) & ~15ull);
+
+  uint32_t *d_users = nullptr, *d_q = nullptr, *d_mitems = nullptr, *d_rank = nullptr, *d_masked = nullptr;
+  uint64_t *d_mptr = nullptr, *d_bits = nullptr; double *d_sc = nullptr;
+  do {
+    if ((rc = dalloc(h, &d_users, n_sel)) || (rc = dalloc(h, &d_q, n_sel)) || (rc = dalloc(h, &d_rank, n_sel)) ||
+        (rc = dalloc(h, &d_masked, n_sel)) || (rc = dalloc(h, &d_sc, n_sel)) || (rc = dalloc(h, &d_bits, (size_t)batch * words))) break;
+    if ((rc = h2d(h, d_users, users, (size_t)n_sel * 4)) || (rc = h2d(h, d_q, q_item, (size_t)n_sel * 4))) break;
+    if (mask_ptr) {
+      if ((rc = dalloc(h, &d_mptr, (size_t)n_sel + 1)) || (rc = dalloc(h, &d_mitems, (size_t)nmask))) break;
+      if ((rc = h2d(h, d_mptr, mask_ptr, ((size_t)n_sel + 1) * 8))) break;
+      if (nmask && (rc = h2d(h, d_mitems, mask_items, (size_t)nmask * 4))) break;
+    }
+    const uint32_t ntiles = (limit + 63) / 64;
+    for (uint32_t b0 = 0; b0 < n_sel && !rc; b0 += (uint32_t)batch) {
+      const uint32_t b1 = (uint32_t)std::min<uint64_t>(n_sel, (uint64_t)b0 + batch), rows = b1 - b0;
+      if (b0) { hipError_t e = hipMemsetAsync(d_bits, 0, (size_t)rows * words * 8, h->stream); if (e != hipSuccess) { h->err = hipGetErrorString(e); rc = HPF_ERR_HIP; break; } }
+      hipLaunchKernelGGL(loo_mask_kernel, dim3(std::min<uint32_t>((rows + 3) / 4, 4096)), dim3(256), 0, h->stream,
+                         d_users + b0, rows, h->rowptr_dev, h->u.idx, h->u.val, d_mptr ? d_mptr + b0 : nullptr, d_mitems,
+                         (uint32_t *)d_bits, words);
+      LooArgs a;
+      a.users = d_users + b0; a.q_item = d_q + b0; a.Et = h->u.E; a.Eb = h->it.E; a.bits = d_bits;
+      a.rank = d_rank + b0; a.masked = d_masked + b0; a.score = d_sc + b0;
+      a.n_sel = rows; a.limit = limit; a.ld = h->ld; a.K = h->K; a.words = words;
+      a.ubias_col = h->cfg.bias ? h->u.bias_col : -1; a.ibias_col = h->cfg.bias ? h->it.bias_col : -1;
+      // few user blocks: the item range is cut so that some 1024 workgroups exist; many: one sweep per block
+      const uint32_t blocks = (rows + 63) / 64;
+      uint32_t splits = std::max<uint32_t>(1, std::min<uint32_t>(ntiles, (1024 + blocks - 1) / blocks));
+      a.tiles_per_split = (ntiles + splits - 1) / splits;
+      splits = (ntiles + a.tiles_per_split - 1) / a.tiles_per_split;
+      if (h->K <= 32) hipLaunchKernelGGL(loo_rank_kernel<1>, dim3(blocks, splits), dim3(256), 0, h->stream, a);
+      else if (h->K <= 64) hipLaunchKernelGGL(loo_rank_kernel<2>, dim3(blocks, splits), dim3(256), 0, h->stream, a);
+      else if (h->K <= 128) hipLaunchKernelGGL(loo_rank_kernel<4>, dim3(blocks, splits), dim3(256), 0, h->stream, a);
+      else hipLaunchKernelGGL(loo_rank_kernel<0>, dim3(blocks, splits), dim3(256), 0, h->stream, a);
+      rc = check_launch(h, "loo_rank_kernel");
+    }
+    if (rc) break;
+    hipError_t e = hipMemcpyAsync(out_rank, d_rank, (size_t)n_sel * 4, hipMemcpyDeviceToHost, h->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(out_score, d_sc, (size_t)n_sel * 8, hipMemcpyDeviceToHost, h->stream);
+    if (e == hipSuccess && out_masked) e = hipMemcpyAsync(out_masked, d_masked, (size_t)n_sel * 4, hipMemcpyDeviceToHost, h->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    if (e != hipSuccess) { h->err = hipGetErrorString(e); rc = HPF_ERR_HIP; }
+  } while (0);
+  if (rc) (void)hipStreamSynchronize(h->stream);
+  dfree(d_users); dfree(d_q); dfree(d_mitems); dfree(d_rank); dfree(d_masked); dfree(d_mptr); dfree(d_bits); dfree(d_sc);
+  return rc;
+}
+
 int hpf_get_work_info(hpf_handle *h, hpf_work_info *out)
 {
   if (!h || !out) return HPF_ERR_INVALID;

@@ -1884,6 +1884,266 @@ __global__ __launch_bounds__(256) void rank_query_kernel(const double *scores, u
   }
 }
 
+// ---------------------------------------------------------------------
+// Scoring a saved model (-rmse, -msr).
+//   predict_kernel      the rate of one (user, item) pair per 16-lane group: the dot product of
+//                       heldout_ll_kernel, handed out instead of its likelihood
+//   loo_mask_kernel     training (rating > 0) and mask-list items of a batch of users as BITS
+//   loo_rank_kernel     fused score-and-count: where ONE item per user stands among all items.
+//                       Scores a 16 x 64 tile per wave on the fp64 matrix cores with the MFMA sequence
+//                       of score_tile_kernel (so every score carries the same bits), compares it in
+//                       registers with the user's threshold and counts; no score reaches memory.
+// ---------------------------------------------------------------------
+struct PredictArgs {
+  const uint32_t *u, *i;
+  uint64_t        cnt;
+  const double   *Et, *Eb;     // [n x ld], [m x ld]
+  double         *out;         // [cnt]
+  uint32_t        ld, K;
+  int32_t         ubias_col, ibias_col;   // -1 without -bias
+};
+
+__global__ __launch_bounds__(256) void predict_kernel(PredictArgs a)
+{
+  constexpr int G = 16;
+  const int lane = threadIdx.x & 63, g = lane % G;
+  const uint64_t grp = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) / G;
+  const uint64_t ngrp = ((uint64_t)gridDim.x * blockDim.x) / G;
+  for (uint64_t p0 = 0; p0 < a.cnt; p0 += ngrp) {
+    const uint64_t p = p0 + grp;
+    const bool ok = p < a.cnt;
+    const uint32_t u = ok ? a.u[p] : 0u, it = ok ? a.i[p] : 0u;
+    const double *et = a.Et + (size_t)u * a.ld, *eb = a.Eb + (size_t)it * a.ld;
+    double s = 0.0;
+    if (ok)
+      for (uint32_t c = g; c < a.K; c += G) s = fma(et[c], eb[c], s);
+    s = group_sum<G>(s);
+    if (ok && g == 0) {
+      if (a.ubias_col >= 0) s += et[a.ubias_col] + eb[a.ibias_col];
+      a.out[p] = s;
+    }
+  }
+}
+
+// one wave per user of the batch: bit i of row b is set when item i is zeroed for that user
+// (mask_scores_kernel's rules).  Rows are `words` 64-bit words, written as dwords.
+__global__ void loo_mask_kernel(const uint32_t *users, uint32_t n_sel, const int64_t *rowptr,
+                                const uint32_t *col, const uint8_t *val, const uint64_t *mask_ptr,
+                                const uint32_t *mask_items, uint32_t *bits, uint32_t words)
+{
+  const int lane = threadIdx.x & 63;
+  const uint32_t wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  const uint32_t nwaves = (gridDim.x * blockDim.x) >> 6;
+  for (uint32_t b = wave; b < n_sel; b += nwaves) {
+    const uint32_t u = users[b];
+    uint32_t *row = bits + (size_t)b * words * 2;
+    if (rowptr)
+      for (int64_t j = rowptr[u] + lane; j < rowptr[u + 1]; j += 64)
+        if (!val || val[j] > 0) atomicOr(&row[col[j] >> 5], 1u << (col[j] & 31u));
+    if (mask_ptr)
+      for (uint64_t j = mask_ptr[b] + lane; j < mask_ptr[b + 1]; j += 64)
+        atomicOr(&row[mask_items[j] >> 5], 1u << (mask_items[j] & 31u));
+  }
+}
+
+struct LooArgs {
+  const uint32_t *users;    // [n_sel] user rows of this batch
+  const uint32_t *q_item;   // [n_sel] the item whose position is asked for
+  const double   *Et, *Eb;  // [n x ld], [m x ld]
+  const uint64_t *bits;     // [n_sel x words] masked items
+  uint32_t       *rank;     // [n_sel] zeroed; counts are added
+  uint32_t       *masked;   // [n_sel] zeroed; distinct masked items below limit
+  double         *score;    // [n_sel]
+  uint32_t        n_sel, limit, ld, K, words;
+  uint32_t        tiles_per_split;   // 64-item tiles per blockIdx.y
+  int32_t         ubias_col, ibias_col;
+};
+
+constexpr int LOO_KC = 32;            // columns of an item tile staged at once
+constexpr int LOO_LDS_STRIDE = 34;    // doubles per staged row: the 16 rows x 2 k of a half wave fall into 32 different bank pairs
+
+// Workgroup = 4 waves = 64 users (16 per wave) x one split of the item range.  The 64 x 32 pieces of the
+// item rows go through LDS (16-byte loads, the next piece on its way while this one is multiplied) and are
+// shared by the four waves.  NCH > 0: the wave's A fragments (its 16 users, K <= 32 * NCH <= 128) stay in
+// registers; NCH == 0: they are read per step like score_tile_kernel does (K up to HPF_MAX_COLUMNS).
+// Per output ONE accumulator chain over k0 = 0, 4, 8, ... with the tail padded by zeros -- exactly the MFMAs
+// score_tile_kernel issues -- then + (E_ubias + E_ibias).  The threshold s(b, t) comes from the same
+// arithmetic: a 16 x 16 tile whose column j is the row of user j's query item, of which the diagonal is kept.
+template <int NCH>
+__global__ __launch_bounds__(256) void loo_rank_kernel(LooArgs a)
+{
+  __shared__ double tile[64 * LOO_LDS_STRIDE];
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int r16 = lane & 15, kq = lane >> 4;
+  const uint32_t ub0 = blockIdx.x * 64 + wv * 16;              // first user of this wave
+  const uint32_t usel = ub0 + r16;
+  const bool uok = usel < a.n_sel;
+  const uint32_t urow = uok ? a.users[usel] : 0u;
+  const double *pa = a.Et + (size_t)urow * a.ld;
+  const uint32_t nsteps = (a.K + 3) / 4;                       // MFMAs per output, as in score_tile_kernel
+
+  double areg[NCH > 0 ? NCH * 8 : 1];
+  if (NCH > 0) {
+#pragma unroll
+    for (int s = 0; s < NCH * 8; ++s) {
+      const uint32_t k = 4u * s + kq;
+      areg[s] = (uok && k < a.K) ? pa[k] : 0.0;
+    }
+  }
+  auto a_of = [&](int s) -> double {                           // A[i = lane%16][k = 4 s + lane/16]
+    if (NCH > 0) return areg[s];
+    const uint32_t k = 4u * (uint32_t)s + kq;
+    return (uok && k < a.K) ? pa[k] : 0.0;
+  };
+
+  // ---- thresholds: D[i][j] = E_theta[user i] . E_beta[query item of user j], diagonal kept
+  const uint32_t myq = uok ? a.q_item[usel] : 0u;
+  double thr[4]; uint32_t tq[4]; bool live[4];
+  {
+    const double *pq = a.Eb + (size_t)myq * a.ld;
+    double4_t acc = (double4_t){0.0, 0.0, 0.0, 0.0};
+    if (NCH > 0) {
+#pragma unroll
+      for (int s = 0; s < NCH * 8; ++s)
+        if ((uint32_t)s < nsteps) {
+          const uint32_t k = 4u * s + kq;
+          const double bv = (uok && k < a.K) ? pq[k] : 0.0;
+          acc = __builtin_amdgcn_mfma_f64_16x16x4f64(areg[s], bv, acc, 0, 0, 0);
+        }
+    } else {
+      for (uint32_t s = 0; s < nsteps; ++s) {
+        const uint32_t k = 4u * s + kq;
+        const double bv = (uok && k < a.K) ? pq[k] : 0.0;
+        acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a_of((int)s), bv, acc, 0, 0, 0);
+      }
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int src = (kq + 4 * r) + 16 * kq;                  // the lane that holds D[i][i] for i = kq + 4 r, in register r
+      double v = __shfl(acc[r], src);
+      const uint32_t us = ub0 + kq + 4 * r;
+      live[r] = us < a.n_sel;
+      tq[r] = live[r] ? a.q_item[us] : 0u;
+      if (live[r] && a.ubias_col >= 0)
+        v += a.Et[(size_t)a.users[us] * a.ld + a.ubias_col] + a.Eb[(size_t)tq[r] * a.ld + a.ibias_col];
+      if (live[r] && ((a.bits[(size_t)us * a.words + (tq[r] >> 6)] >> (tq[r] & 63u)) & 1ull)) v = 0.0;
+      if (tq[r] >= a.limit) live[r] = false;                   // outside the ranked range: rank 0, score 0.0
+      thr[r] = v;
+    }
+  }
+
+  // ---- item sweep
+  const uint32_t ntiles = (a.limit + 63) / 64;
+  const uint32_t t0 = blockIdx.y * a.tiles_per_split, t1 = min(ntiles, t0 + a.tiles_per_split);
+  const uint32_t nchunks = (a.K + LOO_KC - 1) / LOO_KC;
+  uint32_t cnt[4] = {0, 0, 0, 0}, msk[4] = {0, 0, 0, 0};
+  double ubv[4];
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const uint32_t us = ub0 + kq + 4 * r;
+    ubv[r] = (us < a.n_sel && a.ubias_col >= 0) ? a.Et[(size_t)a.users[us] * a.ld + a.ubias_col] : 0.0;
+  }
+
+  // this thread's four 16-byte pieces of a 64 x 32 chunk: piece p = tid + 256 j -> row p / 16, columns 2 (p % 16), +1
+  double2 pre[4];
+  auto fetch = [&](uint32_t tile_i, uint32_t chunk) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const uint32_t p = (uint32_t)tid + 256u * j, row = p >> 4, c = chunk * LOO_KC + 2u * (p & 15u);
+      const uint32_t it = tile_i * 64 + row;
+      double2 v = make_double2(0.0, 0.0);
+      if (it < a.limit && c < a.K) {                           // c is even and ld is even: c + 1 < ld
+        v = *(const double2 *)(a.Eb + (size_t)it * a.ld + c);
+        if (c + 1 >= a.K) v.y = 0.0;
+      }
+      pre[j] = v;
+    }
+  };
+  if (t0 < t1) fetch(t0, 0);
+  for (uint32_t tl = t0; tl < t1; ++tl) {
+    double4_t acc[4];
+#pragma unroll
+    for (int t = 0; t < 4; ++t) acc[t] = (double4_t){0.0, 0.0, 0.0, 0.0};
+    auto stage = [&](uint32_t ch) {
+      __syncthreads();                                         // the previous chunk has been read
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const uint32_t p = (uint32_t)tid + 256u * j;
+        *(double2 *)&tile[(p >> 4) * LOO_LDS_STRIDE + 2u * (p & 15u)] = pre[j];
+      }
+      __syncthreads();
+      if (ch + 1 < nchunks) fetch(tl, ch + 1);
+      else if (tl + 1 < t1) fetch(tl + 1, 0);
+    };
+    if (NCH > 0) {
+#pragma unroll
+      for (int ch = 0; ch < NCH; ++ch)
+        if ((uint32_t)ch < nchunks) {
+          stage((uint32_t)ch);
+#pragma unroll
+          for (int s = 0; s < 8; ++s)
+            if ((uint32_t)(ch * 8 + s) < nsteps) {
+#pragma unroll
+              for (int t = 0; t < 4; ++t) {
+                const double bv = tile[(16 * t + r16) * LOO_LDS_STRIDE + 4 * s + kq];   // B[k = lane/16][j = lane%16]
+                acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(areg[ch * 8 + s], bv, acc[t], 0, 0, 0);
+              }
+            }
+        }
+    } else {
+      for (uint32_t ch = 0; ch < nchunks; ++ch) {
+        stage(ch);
+        for (uint32_t s = 0; s < 8 && ch * 8 + s < nsteps; ++s) {
+          const double av = a_of((int)(ch * 8 + s));
+#pragma unroll
+          for (int t = 0; t < 4; ++t) {
+            const double bv = tile[(16 * t + r16) * LOO_LDS_STRIDE + 4 * s + kq];
+            acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(av, bv, acc[t], 0, 0, 0);
+          }
+        }
+      }
+    }
+    // epilogue: register r of tile t holds user kq + 4 r, item 64 tl + 16 t + r16
+    const uint32_t i0 = tl * 64;
+    unsigned long long w[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const uint32_t us = ub0 + kq + 4 * r;
+      w[r] = us < a.n_sel ? a.bits[(size_t)us * a.words + tl] : 0ull;
+      if (r16 == 0) {
+        const uint32_t left = a.limit - i0;                    // > 0: the tile starts below the limit
+        msk[r] += (uint32_t)__popcll(left >= 64 ? w[r] : (w[r] & ((1ull << left) - 1ull)));
+      }
+    }
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      const uint32_t it = i0 + 16 * t + r16;
+      const bool iok = it < a.limit;
+      const double bi = (iok && a.ibias_col >= 0) ? a.Eb[(size_t)it * a.ld + a.ibias_col] : 0.0;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        double v = acc[t][r];
+        if (a.ubias_col >= 0) v += ubv[r] + bi;                // s += Eb_u + Eb_i
+        if ((w[r] >> (16 * t + r16)) & 1ull) v = 0.0;
+        const unsigned long long k = score_key(v), kt = score_key(thr[r]);
+        cnt[r] += (iok && live[r] && it != tq[r] && (k > kt || (k == kt && it < tq[r]))) ? 1u : 0u;
+      }
+    }
+  }
+  // one reduction per user block: over the 16 lanes that share kq
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    uint32_t c = cnt[r];
+    for (int o = 8; o > 0; o >>= 1) c += __shfl_xor(c, o);
+    const uint32_t us = ub0 + kq + 4 * r;
+    if (r16 == 0 && us < a.n_sel) {
+      if (c) atomicAdd(&a.rank[us], c);
+      if (msk[r]) atomicAdd(&a.masked[us], msk[r]);
+      if (blockIdx.y == 0) a.score[us] = live[r] ? thr[r] : 0.0;
+    }
+  }
+}
+
 // materialise the per-element rate matrix for export (htheta_rate.tsv):
 // rate[row,k] = prior_used[row] + colsum[k]   (gpbase.hh:163-173,218-223)
 __global__ void build_rate_kernel(const double *prior_used, const double *colsum,

@@ -59,6 +59,8 @@ def lib():
     L.hg_state_get.argtypes = [vp, C.c_int, C.POINTER(dp)]; L.hg_state_get.restype = C.c_size_t
     L.hg_save_matrix.argtypes = [C.c_char_p, dp, C.c_uint32, C.c_uint32, u32p, C.c_uint32]
     L.hg_save_vector.argtypes = [C.c_char_p, dp, C.c_uint32, u32p, C.c_uint32]
+    L.hg_load_matrix.argtypes = [C.c_char_p, dp, C.c_uint32, C.c_uint32, u32p, C.c_uint32, C.c_char_p, C.c_size_t]
+    L.hg_load_vector.argtypes = [C.c_char_p, dp, C.c_uint32, u32p, C.c_uint32, C.c_char_p, C.c_size_t]
     L.hg_format_fixed8.argtypes = [dp, C.c_size_t, C.c_char_p]
     L.hg_format_fixed8.restype = C.c_size_t
     L.hg_partition_users.argtypes = [C.POINTER(C.c_int64), C.c_uint32, C.c_int, u32p]
@@ -207,6 +209,34 @@ def save_vector(path, a, ids=None):
     return lib().hg_save_vector(str(path).encode(), a.ctypes.data_as(C.POINTER(C.c_double)), a.shape[0],
                                 None if i is None else i.ctypes.data_as(C.POINTER(C.c_uint32)),
                                 0 if i is None else i.size)
+
+
+def load_matrix(path, rows, cols, ids=None) -> np.ndarray:
+    """read back what save_matrix wrote: (rows, cols) float64.  ids: the id expected in the second column of each row
+    (the ratings' seq2user / seq2item); None: the column is not compared.  Raises ValueError with the reader's message
+    ("<path>: line N: ...") for a missing or short file, a short row or an id that differs."""
+    out = np.empty((int(rows), int(cols)), np.float64)
+    i = None if ids is None else np.ascontiguousarray(ids, np.uint32)
+    err = C.create_string_buffer(1024)
+    rc = lib().hg_load_matrix(str(path).encode(), out.ctypes.data_as(C.POINTER(C.c_double)), int(rows), int(cols),
+                              None if i is None else i.ctypes.data_as(C.POINTER(C.c_uint32)), 0 if i is None else i.size,
+                              err, 1024)
+    if rc:
+        raise ValueError(err.value.decode())
+    return out
+
+
+def load_vector(path, rows, ids=None) -> np.ndarray:
+    """read back what save_vector wrote (or a one-column matrix such as thetabias.tsv): (rows,) float64"""
+    out = np.empty(int(rows), np.float64)
+    i = None if ids is None else np.ascontiguousarray(ids, np.uint32)
+    err = C.create_string_buffer(1024)
+    rc = lib().hg_load_vector(str(path).encode(), out.ctypes.data_as(C.POINTER(C.c_double)), int(rows),
+                              None if i is None else i.ctypes.data_as(C.POINTER(C.c_uint32)), 0 if i is None else i.size,
+                              err, 1024)
+    if rc:
+        raise ValueError(err.value.decode())
+    return out
 
 
 def format_fixed8(values):

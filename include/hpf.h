@@ -326,6 +326,32 @@ int  hpf_item_ranks(hpf_handle *h, const uint32_t *users, uint32_t n_sel,
                     const uint32_t *q_sel, const uint32_t *q_item, uint32_t nq,
                     uint32_t *out_rank, double *out_score);
 
+/* ---- scoring a saved model (v8 additions: new functions only, no struct changed) ---- */
+/* replaces: prediction_score_hier / prediction_score (hgaprec.cc:1966-1991, 1850-1877;
+ * _use_rate_as_score) for a list of pairs: out[p] = E_theta[u[p]] . E_beta[i[p]]
+ * (+ E_ubias[u[p]] + E_ibias[i[p]]).  u is a LOCAL user index.  Needs E on both sides
+ * (hpf_set_state(*_E) or an iteration) and no CSR.  An index out of range is
+ * HPF_ERR_INVALID before anything is launched; cnt = 0 is HPF_OK.  Synchronous. */
+int  hpf_predict(hpf_handle *h, const uint32_t *u, const uint32_t *i, size_t cnt, double *out);
+/* replaces: the scoring loop, qsort and walk of HGAPRec::gen_msr_csv (hgaprec.cc:2024-2055):
+ * for selected user b, where item t = q_item[b] stands among the items [0, item_limit)
+ * (0 => n_items) under score descending, item ascending -- scores as hpf_scores gives them,
+ * replaced by +0.0 for the user's training items with a stored rating > 0 (all of them when the
+ * handle has no values) and for the items of the mask list (CSR over the selected users), like
+ * hpf_rank_topn.  out_rank[b] counts the items i != t below item_limit that come before t,
+ * out_score[b] = s(b, t), out_masked[b] (may be NULL) the DISTINCT masked items below
+ * item_limit.  t >= item_limit gives rank 0 and score 0.0 (the reference's loop never scores
+ * item m - 1 and leaves rank = 0); t >= n_items is HPF_ERR_INVALID.
+ * With item_limit = 0, out_rank and out_score equal, bit for bit, what hpf_item_ranks returns
+ * for q_sel = 0 .. n_sel - 1 on the same handle: the scores come out of the same MFMA chain.
+ * No n_sel x n_items array exists anywhere: a tile of scores is compared and counted in
+ * registers; the masked items are one BIT per (user, item) for a batch of users at a time
+ * (<= 256 MB; HPF_LOO_BATCH=<users> makes the batches smaller -- a test knob). */
+int  hpf_loo_ranks(hpf_handle *h, const uint32_t *users, uint32_t n_sel,
+                   const uint64_t *mask_ptr, const uint32_t *mask_items,
+                   const uint32_t *q_item, uint32_t item_limit,
+                   uint32_t *out_rank, double *out_score, uint32_t *out_masked);
+
 /* how the uploaded matrix was cut into work (diagnostics, tests, bench):
  * a "segment" is <= 512 consecutive nonzeros of one row; rows longer than that
  * are "long" (their segment sums are combined by a second kernel) and rows with
