@@ -13,6 +13,7 @@
 #include "../../include/hpf.h"
 #include "hpf_kernels.hpp"
 #include "hpf_build.hpp"
+#include "hpf_plan.hpp"
 
 #include <dlfcn.h>
 
@@ -23,11 +24,23 @@
 #include <cstring>
 #include <string>
 #include <thread>
+#include <utility>
 #include <vector>
 
 using namespace hpf;
+using hpf_plan::Knobs;
+using hpf_plan::Plan;
+
+// hpf_plan.hpp spells the layout codes, the sweep modes and the packed row on its own (it includes no HIP header)
+static_assert(hpf_plan::WL_PLAIN == WL_PLAIN && hpf_plan::WL_F48 == WL_F48 && hpf_plan::WL_P59 == WL_P59 && hpf_plan::WL_F64 == WL_F64, "layout codes");
+static_assert(hpf_plan::SW_PLAIN == SW_PLAIN && hpf_plan::SW_LDS_F48 == SW_LDS_F48 && hpf_plan::SW_LDS_P59 == SW_LDS_P59 &&
+              hpf_plan::SW_F64 == SW_F64 && hpf_plan::SW_REG_P59 == SW_REG_P59, "sweep modes");
+static_assert(sizeof(hpf_plan::Row) == sizeof(PackedRow) && offsetof(hpf_plan::Row, G) == offsetof(PackedRow, G) && offsetof(hpf_plan::Row, E) == offsetof(PackedRow, E) &&
+              offsetof(hpf_plan::Row, L) == offsetof(PackedRow, L) && offsetof(hpf_plan::Row, row_bytes) == offsetof(PackedRow, row_bytes) && offsetof(hpf_plan::Row, lgG) == offsetof(PackedRow, lgG), "packed row");
 
 namespace {
+
+PackedRow packed_row(const hpf_plan::Row &r) { return {r.G, r.E, r.L, r.row_bytes, r.lgG}; }
 
 struct Side {
   uint32_t rows = 0;
@@ -74,16 +87,10 @@ struct Side {
 
 }  // namespace
 
-struct hpf_handle {
+// the shapes (ld, wl, pk, phiG ...) are the Plan, the tuning values (seg_max, tile_mode ...) the Knobs: hpf_plan.hpp
+struct hpf_handle : Plan, Knobs {
   hpf_config cfg;
-  uint32_t K = 0, C = 0, ld = 0;
-  bool w32 = false;                     // W stored as float (hpf_config.w_storage = 1)
-  int wl = WL_PLAIN;                    // layout of W rows: plain, WL_P59 (lossless packing, default where it shortens
-                                        // the row), WL_F48 (w_storage = 2) or WL_F64 (w_storage = 3, or after a fall-back); rows in pieces: phiR = 16-byte pieces per lane
-  PackedRow pk = {0, 0, 0, 0, 0};
-  PackedRow pks = {0, 0, 0, 0, 0};      // plain-fp64 rows in pieces for the same columns (codec_f64): what the rows become when p59
-                                        // cannot hold a state (recover_flush)
-  int sw_mode = SW_PLAIN;               // how the sweep writes W (row_sweep_kernel MODE)
+  uint32_t K = 0, C = 0;
   uint32_t fallbacks = 0;               // automatic moves from p59 rows to plain fp64 rows so far
   uint32_t notes = 0;                   // hpf_work_info.notes
   uint64_t iters_counted = 0;           // iterations launched since the device counter flags[1] was last reset
@@ -112,37 +119,11 @@ struct hpf_handle {
   void *stage[2] = {nullptr, nullptr};
   hipEvent_t stage_ev[2] = {nullptr, nullptr};
   size_t stage_bytes = 0;
-  int xfer_mode = 1;               // 0 plain, 1 staged, 2 hipHostRegister
-  unsigned xfer_threads = 4;
   bool have_csr = false, derived_dirty = true;
   bool sums_dirty = true;               // a state array was handed in since the start state's column sums were taken: prepare_derived
                                         // takes them again.  derived_dirty without it = only W has to be written again (recover_flush):
                                         // the sums in place -- on several ranks the all-reduced ones -- stay
   uint32_t iterations = 0;
-  int phiG = 0, phiR = 0, phiV = 0, swG = 0, swR = 0;
-  uint32_t sweep_blocks_max = 2048;     // 8 waves per SIMD (HPF_SWEEP_BLOCKS); 1024 -> 2048: C2 user sweep 0.587 -> 0.544 ms
-  uint32_t seg_max = 512;
-  uint32_t huge_slots = 256, group_slots = 64;  // two-level combine above huge_slots segments (HPF_HUGE_SLOTS)
-  // tiled pass: 2 auto, 0 never, 1 forced with every row regrouped (HPF_TILE); bytes of gathered rows per tile
-  // (HPF_TILE_BYTES), segments per workgroup (HPF_TILE_CHUNK), the mean run a heavy row must reach in a
-  // tile (HPF_TILE_RUN), the share of the nonzeros the heavy rows must hold (HPF_TILE_SHARE, per cent)
-  // order of an XCD's queue (HPF_TILE_ORDER): 1 = the row-major rest in front on the even XCDs and behind on the
-  // odd ones, so that half the chip pulls over the fabric while the other half runs from its L2 (C2 item pass
-  // 4.39 ms; 0 = in front everywhere 4.75; 2 = dealt between the tiles 4.58)
-  int tile_order = 1;
-  uint32_t tile_split_below = 8;       // with fewer tiles than this EVERY tile is cut eight ways, a piece per XCD queue (round 4: below 32 tiles; C4's seven tiles of
-                                       // items are 2 % faster that way than levelled); from here on whole tiles are dealt eight at a time and the remainder levels
-                                       // the queues (build_tiled_side)
-  int tile_sides = 3;                   // HPF_TILE_SIDES: bit 0 the user pass, bit 1 the item pass (experiments)
-  int tile_mode = 2; uint64_t tile_bytes = 4u << 20; uint32_t tile_chunk = 0 /* 0: two segments per wave of the workgroup */, tile_min_run = 0; double tile_min_share = 0.15;
-  uint32_t phi_blocks = 65536;      // ~one wave per few segments; the dispatcher balances
-  // Threads per workgroup of a packed phi pass.  0 (default): 256 -- four waves, grid-stride -- for a ROW-MAJOR side, 64 -- one
-  // wave, a chunk of two segments -- for a TILED side (round 5).  A workgroup's wave slots come back one SIMD at a time but a
-  // new workgroup needs one on each of the four SIMDs at once: with the uneven runs of a tiled list a third of the slots stood
-  // empty (SQ_WAVE_CYCLES: ~2 of 3 waves per SIMD resident on average) -- which a pass that lives on its L2 hits and on issue
-  // pays for (C4 18.65 -> 17.45 ms, a C5 shard 44.8 -> 41.5; experiments.md) and a pass bound by the fabric does not (C2's
-  // user pass, a C3 shard: unchanged).  Same segments, same order inside each: the same bits.  HPF_PHI_WG forces 64 | 128 | 256.
-  uint32_t phi_wg = 0;
   uint32_t wg_of(bool tiled) const { return wl == WL_PLAIN ? 256u : phi_wg ? phi_wg : (tiled ? 64u : 256u); }   // (plain rows: phi_pass_kernel, always 256)
   uint32_t nz_per_batch() const { return phiG > 0 ? 64u / (uint32_t)phiG : 8u; }
   static constexpr uint32_t RING = 64;          // timed iterations kept
@@ -158,7 +139,6 @@ struct hpf_handle {
   // hipGraph replay of one whole iteration for launch-bound problems (hpf_iterate,
   // n_ranks == 1).  HPF_GRAPH=0/1 forces it off/on; default: on when the phi passes
   // are short enough that the ~10 launches per iteration dominate (nnz <= graph_nnz_max).
-  int graph_mode = -1;                  // -1 auto, 0 off, 1 on
   uint64_t graph_nnz_max = 4u << 20;
   hipGraphExec_t graph_exec = nullptr;
   // the same for a rank of several (round 6): the iteration is cut by its two collectives, so it is THREE graphs -- the item
@@ -297,191 +277,79 @@ size_t w_bytes(const hpf_handle *h, uint32_t rows)
   return (size_t)std::max<uint32_t>(rows, 1u) * row;
 }
 
-// pick (G,R[,V]) with G*R*V >= ld, R <= 8.  Cost = padded row length, +20 % when a lane
-// group spans less than one 128-byte line per load although the row is at least two
-// lines long (K=50: (4,7,2) loses to the wider, more padded (8,4,2): user pass 2.58
-// vs 2.29 ms).  Ties (row lengths that several shapes cover exactly, e.g. K = 64,
-// 128) are decided by what the K sweep on MI355X showed: keep
-// 2..7 loads per lane in flight (R = 1 has no ILP: K=64 user pass 3.30 ms vs 2.35 ms
-// at R = 4; R = 8 costs registers), span a line, and among equals be narrow (more
-// nonzeros per wave).
-bool choose_cfg(uint32_t ld, int V, int *G, int *R, int rmax64 = 8, long *cost_out = nullptr, bool gather = true)
-{
-  int bestG = 0, bestR = 0; long bestc = -1; int bestp = 0;
-  const int Gs[5] = {4, 8, 16, 32, 64};
-  for (int gi = 0; gi < 5; ++gi) {
-    const int g = Gs[gi];
-    const int r = (int)((ld + (uint32_t)(g * V) - 1) / (uint32_t)(g * V));
-    if (r < 1 || r > (g == 64 ? rmax64 : 8)) continue;
-    const bool narrow = g * V * 8 < 128;
-    const long c = (long)g * r * V * ((gather && narrow && ld * 8 >= 256) ? 12 : 10);   // the sweep streams: padding only
-    const int p = (r == 1 ? 3 : 0) + (r > 7 ? 2 : 0) + (narrow ? 1 : 0);
-    if (bestc < 0 || c < bestc || (c == bestc && p < bestp)) { bestc = c; bestG = g; bestR = r; bestp = p; }
-  }
-  if (bestc < 0) return false;
-  *G = bestG; *R = bestR;
-  if (cost_out) *cost_out = bestc;
-  return true;
-}
-
 // ---- kernel dispatch over the template grid -------------------------------
-template <typename WT, int G, int R, int V>
-void launch_phi_t(int side, const PhiArgs &a, uint32_t blocks, hipStream_t st)
-{
-  if (side & 1) hipLaunchKernelGGL((phi_pass_kernel<WT, G, R, V, 1>), dim3(blocks), dim3(256), 0, st, a);
-  else          hipLaunchKernelGGL((phi_pass_kernel<WT, G, R, V, 0>), dim3(blocks), dim3(256), 0, st, a);
-}
-template <typename WT, int G, int V>
-bool launch_phi_r(int R, int side, const PhiArgs &a, uint32_t blocks, hipStream_t st)
-{
-  switch (R) {
-    case 1: launch_phi_t<WT, G, 1, V>(side, a, blocks, st); return true;
-    case 2: launch_phi_t<WT, G, 2, V>(side, a, blocks, st); return true;
-    case 3: launch_phi_t<WT, G, 3, V>(side, a, blocks, st); return true;
-    case 4: launch_phi_t<WT, G, 4, V>(side, a, blocks, st); return true;
-    case 5: launch_phi_t<WT, G, 5, V>(side, a, blocks, st); return true;
-    case 6: launch_phi_t<WT, G, 6, V>(side, a, blocks, st); return true;
-    case 7: launch_phi_t<WT, G, 7, V>(side, a, blocks, st); return true;
-    case 8: launch_phi_t<WT, G, 8, V>(side, a, blocks, st); return true;
-  }
-  return false;
-}
-template <typename WT, int V>
-bool launch_phi_g(int G, int R, int side, const PhiArgs &a, uint32_t blocks, hipStream_t st)
-{
-  switch (G) {
-    case 4:  return launch_phi_r<WT, 4, V>(R, side, a, blocks, st);
-    case 8:  return launch_phi_r<WT, 8, V>(R, side, a, blocks, st);
-    case 16: return launch_phi_r<WT, 16, V>(R, side, a, blocks, st);
-    case 32: return launch_phi_r<WT, 32, V>(R, side, a, blocks, st);
-    case 64: return launch_phi_r<WT, 64, V>(R, side, a, blocks, st);
-  }
-  return false;
-}
-// V = elements per load: 1 or 2 doubles, 2 or 4 floats (8- or 16-byte accesses)
-bool launch_phi(bool w32, int G, int R, int V, int side, const PhiArgs &a, uint32_t blocks, hipStream_t st)
-{
-  if (w32) return V == 4 ? launch_phi_g<float, 4>(G, R, side, a, blocks, st)
-                         : launch_phi_g<float, 2>(G, R, side, a, blocks, st);
-  return V == 2 ? launch_phi_g<double, 2>(G, R, side, a, blocks, st)
-                : launch_phi_g<double, 1>(G, R, side, a, blocks, st);
-}
+// The instances that exist are the ones hpf_plan.hpp's has_* predicates name: a shape they reject instantiates nothing
+// and launches nothing (false), a shape they accept cannot be left out.
+// pick: calls f(std::integral_constant<int, v>()) for the v among Vs that equals x; false where none does
+template <int... Vs, typename F>
+bool pick(int x, std::integer_sequence<int, Vs...>, F &&f) { return ((x == Vs && f(std::integral_constant<int, Vs>())) || ...); }
+using Groups = std::integer_sequence<int, 4, 8, 16, 32, 64>;
+using Counts = std::integer_sequence<int, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16>;
+#define PICKED(x) decltype(x)::value
 
-template <int G, int MODE>
-bool launch_sweep_r(int R, const SweepArgs &a, uint32_t blocks, hipStream_t st)
-{
-#define SW(RR) case RR: hipLaunchKernelGGL((row_sweep_kernel<G, RR, MODE>), dim3(blocks), dim3(256), 0, st, a); return true;
-  if (MODE == SW_REG_P59) {                  // the slot counts p59 shapes have (p59_of_slots): 6 is none; G = 2 x the pass's lanes <= 64
-    switch (R) { SW(1) SW(2) SW(3) SW(4) SW(5) SW(7) SW(8) SW(9) }
-    return false;
-  }
-  switch (R) { SW(1) SW(2) SW(3) SW(4) SW(5) SW(6) SW(7) SW(8) }
-  if (MODE == SW_F64 && R == 9) { hipLaunchKernelGGL((row_sweep_kernel<G, 9, MODE>), dim3(blocks), dim3(256), 0, st, a); return true; }
-  if (G == 64) switch (R) { SW(9) SW(10) SW(11) SW(12) SW(13) SW(14) SW(15) SW(16) }   // 513..1024 columns
-#undef SW
-  return false;
-}
-template <int MODE>
-bool launch_sweep_g(int G, int R, const SweepArgs &a, uint32_t blocks, hipStream_t st)
-{
-  switch (G) {
-    case 4:  return MODE == SW_REG_P59 ? false : launch_sweep_r<4, MODE == SW_REG_P59 ? SW_PLAIN : MODE>(R, a, blocks, st);
-    case 8:  return launch_sweep_r<8, MODE>(R, a, blocks, st);
-    case 16: return launch_sweep_r<16, MODE>(R, a, blocks, st);
-    case 32: return launch_sweep_r<32, MODE>(R, a, blocks, st);
-    case 64: return launch_sweep_r<64, MODE>(R, a, blocks, st);
-  }
-  return false;
-}
-bool launch_sweep(int mode, int G, int R, const SweepArgs &a, uint32_t blocks, hipStream_t st)
-{
-  switch (mode) {
-    case SW_REG_P59: return launch_sweep_g<SW_REG_P59>(G, R, a, blocks, st);
-    case SW_LDS_P59: return G == 64 ? launch_sweep_r<64, SW_LDS_P59>(R, a, blocks, st) : false;   // narrower groups build in registers
-    case SW_LDS_F48: return launch_sweep_g<SW_LDS_F48>(G, R, a, blocks, st);
-    case SW_F64:     return launch_sweep_g<SW_F64>(G, R, a, blocks, st);
-  }
-  return launch_sweep_g<SW_PLAIN>(G, R, a, blocks, st);
-}
-
-// how a packed phi pass is launched: workgroups x threads (256 = four waves that share a chunk of segments, 64 = one wave: a
+// how a phi pass is launched: workgroups x threads (256 = four waves that share a chunk of segments, 64 = one wave: a
 // tiled side) on a stream -- handed down explicitly (until round 5 the thread count travelled in a thread_local)
 struct PhiLaunch { uint32_t blocks, wg; hipStream_t st; };
 
+// plain rows: G lanes per nonzero, R loads of V elements per lane (phi_pass_kernel, always 256 threads)
+bool launch_phi(bool w32, int G, int R, int V, int side, const PhiArgs &a, const PhiLaunch &pl)
+{
+  return pick(w32, std::integer_sequence<int, 0, 1>(), [&](auto f32) { return pick(V, std::integer_sequence<int, 1, 2, 4>(), [&](auto v) {
+    return pick(G, Groups(), [&](auto g) { return pick(R, Counts(), [&](auto r) { return pick(side & 1, std::integer_sequence<int, 0, 1>(), [&](auto sd) {
+      if constexpr (hpf_plan::has_phi(PICKED(f32), PICKED(g), PICKED(r), PICKED(v))) {
+        using WT = std::conditional_t<PICKED(f32) != 0, float, double>;
+        hipLaunchKernelGGL((phi_pass_kernel<WT, PICKED(g), PICKED(r), PICKED(v), PICKED(sd)>), dim3(pl.blocks), dim3(256), 0, pl.st, a);
+        return true;
+      } else return false;
+    }); }); }); }); });
+}
+
 // packed W rows: G lanes per nonzero, L 16-byte pieces per lane (phi_pass_packed_kernel)
-template <template <int> class C, int G, int L>
-void launch_phipk_t(int side, const PhiArgs &a, const PhiLaunch &pl)
+template <template <int> class C, int WL>
+bool launch_phipk(int G, int L, int side, const PhiArgs &a, const PhiLaunch &pl)
 {
-  if (side & 1) hipLaunchKernelGGL((phi_pass_packed_kernel<C, G, L, 1>), dim3(pl.blocks), dim3(pl.wg), 0, pl.st, a);
-  else          hipLaunchKernelGGL((phi_pass_packed_kernel<C, G, L, 0>), dim3(pl.blocks), dim3(pl.wg), 0, pl.st, a);
-}
-template <template <int> class C, int G>
-bool launch_phipk_l(int L, int side, const PhiArgs &a, const PhiLaunch &pl)
-{
-  switch (L) {
-    case 1: launch_phipk_t<C, G, 1>(side, a, pl); return true;
-    case 2: launch_phipk_t<C, G, 2>(side, a, pl); return true;
-    case 3: launch_phipk_t<C, G, 3>(side, a, pl); return true;
-    case 4: launch_phipk_t<C, G, 4>(side, a, pl); return true;
-    case 5: launch_phipk_t<C, G, 5>(side, a, pl); return true;
-    case 6: launch_phipk_t<C, G, 6>(side, a, pl); return true;
-    case 7: launch_phipk_t<C, G, 7>(side, a, pl); return true;
-    case 8: launch_phipk_t<C, G, 8>(side, a, pl); return true;
-  }
-  return false;
-}
-template <template <int> class C>
-bool launch_phipk_g(int G, int L, int side, const PhiArgs &a, const PhiLaunch &pl)
-{
-  switch (G) {
-    case 4:  return launch_phipk_l<C, 4>(L, side, a, pl);
-    case 8:  return launch_phipk_l<C, 8>(L, side, a, pl);
-    case 16: return launch_phipk_l<C, 16>(L, side, a, pl);
-    case 32: return launch_phipk_l<C, 32>(L, side, a, pl);
-    case 64: return launch_phipk_l<C, 64>(L, side, a, pl);
-  }
-  return false;
-}
-template <int G>
-bool launch_phif64_l(int L, int side, const PhiArgs &a, const PhiLaunch &pl)
-{
-  if (L == 9) { launch_phipk_t<codec_f64, G, 9>(side, a, pl); return true; }      // stands in for p59 rows of 17 elements
-  return launch_phipk_l<codec_f64, G>(L, side, a, pl);
+  return pick(G, Groups(), [&](auto g) { return pick(L, Counts(), [&](auto l) { return pick(side & 1, std::integer_sequence<int, 0, 1>(), [&](auto sd) {
+    if constexpr (hpf_plan::has_phi_packed(WL, PICKED(g), PICKED(l))) {
+      hipLaunchKernelGGL((phi_pass_packed_kernel<C, PICKED(g), PICKED(l), PICKED(sd)>), dim3(pl.blocks), dim3(pl.wg), 0, pl.st, a);
+      return true;
+    } else return false;
+  }); }); });
 }
 bool launch_phi_packed(int wl, int G, int L, int side, const PhiArgs &a, const PhiLaunch &pl)
 {
-  if (wl == WL_F64) {
-    switch (G) {
-      case 4:  return launch_phif64_l<4>(L, side, a, pl);
-      case 8:  return launch_phif64_l<8>(L, side, a, pl);
-      case 16: return launch_phif64_l<16>(L, side, a, pl);
-      case 32: return launch_phif64_l<32>(L, side, a, pl);
-      case 64: return launch_phif64_l<64>(L, side, a, pl);
-    }
-    return false;
+  switch (wl) {
+    case WL_P59: return launch_phipk<codec_p59, WL_P59>(G, L, side, a, pl);
+    case WL_F48: return launch_phipk<codec_f48, WL_F48>(G, L, side, a, pl);
+    case WL_F64: return launch_phipk<codec_f64, WL_F64>(G, L, side, a, pl);
   }
-  return wl == WL_P59 ? launch_phipk_g<codec_p59>(G, L, side, a, pl) : launch_phipk_g<codec_f48>(G, L, side, a, pl);
+  return false;
 }
 
-template <int G>
-bool launch_gather_only_l(int L, const PhiArgs &a, uint32_t *sink, const PhiLaunch &pl)
-{
-#define GO(LL) case LL: hipLaunchKernelGGL((gather_only_kernel<G, LL>), dim3(pl.blocks), dim3(pl.wg), 0, pl.st, a, sink); return true;
-  switch (L) { GO(1) GO(2) GO(3) GO(4) GO(5) GO(6) GO(7) GO(8) GO(9) }
-#undef GO
-  return false;
-}
 bool launch_gather_only(int G, int L, const PhiArgs &a, uint32_t *sink, const PhiLaunch &pl)
 {
-  switch (G) {
-    case 4:  return launch_gather_only_l<4>(L, a, sink, pl);
-    case 8:  return launch_gather_only_l<8>(L, a, sink, pl);
-    case 16: return launch_gather_only_l<16>(L, a, sink, pl);
-    case 32: return launch_gather_only_l<32>(L, a, sink, pl);
-    case 64: return launch_gather_only_l<64>(L, a, sink, pl);
-  }
-  return false;
+  return pick(G, Groups(), [&](auto g) { return pick(L, Counts(), [&](auto l) {
+    if constexpr (hpf_plan::has_gather_only(PICKED(g), PICKED(l))) {
+      hipLaunchKernelGGL((gather_only_kernel<PICKED(g), PICKED(l)>), dim3(pl.blocks), dim3(pl.wg), 0, pl.st, a, sink);
+      return true;
+    } else return false;
+  }); });
 }
+
+// The ladders this replaced also compiled sweeps behind tests that were never true (R = 9..16 below 64 lanes, the slot counts
+// p59 has no shape for): nothing launches them, they stay only so that the library's kernels are the ones it had
+constexpr bool unreachable_sweep(int mode, int G, int R) { return mode != SW_LDS_P59 && (mode != SW_REG_P59 || G >= 8) && !hpf_plan::has_sweep(mode, G, R); }
+bool launch_sweep(int mode, int G, int R, const SweepArgs &a, uint32_t blocks, hipStream_t st)
+{
+  return pick(mode, std::integer_sequence<int, SW_PLAIN, SW_LDS_F48, SW_LDS_P59, SW_F64, SW_REG_P59>(), [&](auto m) {
+    return pick(G, Groups(), [&](auto g) { return pick(R, Counts(), [&](auto r) {
+      if constexpr (hpf_plan::has_sweep(PICKED(m), PICKED(g), PICKED(r))) {
+        hipLaunchKernelGGL((row_sweep_kernel<PICKED(g), PICKED(r), PICKED(m)>), dim3(blocks), dim3(256), 0, st, a);
+        return true;
+      } else if constexpr (unreachable_sweep(PICKED(m), PICKED(g), PICKED(r))) (void)&row_sweep_kernel<PICKED(g), PICKED(r), PICKED(m)>;
+      return false;
+    }); }); });
+}
+#undef PICKED
 
 int recover_flush(hpf_handle *h, uint32_t fl0, uint32_t begun);
 
@@ -1305,7 +1173,7 @@ int prepare_derived(hpf_handle *h)
       const uint32_t blocks = std::min<uint32_t>((s->rows + 3) / 4, 4096);
       hipLaunchKernelGGL(derive_w_kernel, dim3(blocks), dim3(256), 0, h->stream, s->L, s->W,
                          h->wl != WL_PLAIN ? (uint32_t)h->wl : (uint32_t)h->w32,
-                         s->rows, h->ld, h->K, s->bias_col, s->junk_col, h->pk, h->flags);
+                         s->rows, h->ld, h->K, s->bias_col, s->junk_col, packed_row(h->pk), h->flags);
     }
     if (!derived || h->wl != WL_P59 || h->capturing) break;
     // an Elog spread above 88 inside a row: p59 cannot hold the state -- plain rows then, derived again (recover_flush)
@@ -1344,20 +1212,25 @@ int prepare_derived(hpf_handle *h)
 
 // rows of W in 16-byte pieces?
 bool rows_in_pieces(const hpf_handle *h) { return h->wl != WL_PLAIN; }
+// the arguments of a pass over own's segments and its workgroups (run_phi; hpf_gather_only, which sums nothing)
+PhiLaunch phi_setup(const hpf_handle *h, const Side &own, const Side &oth, bool sums, PhiArgs &a)
+{
+  a.segs = own.segs; a.nseg = own.nseg; a.idx = own.pass_idx(); a.val = own.pass_val();
+  a.W_own = own.W; a.W_oth = oth.W; a.S_own = sums ? own.S : nullptr; a.partial = sums ? own.partial : nullptr; a.flags = h->flags;
+  a.chunks = own.chunks; a.ld = h->ld;
+  const uint32_t wpb = rows_in_pieces(h) ? h->wg_of(own.chunks != nullptr) / 64 : 4;      // waves per workgroup
+  const uint32_t blocks = own.chunks ? own.nchunk_blocks : std::min<uint32_t>((a.nseg + wpb - 1) / wpb, h->phi_blocks * (4 / wpb));
+  return {blocks, wpb * 64, h->stream};
+}
 int run_phi(hpf_handle *h, Side &own, Side &oth, hipEvent_t after_kernel)
 {
   const int side = &own == &h->it ? 1 : 0;
   hipStream_t st = h->stream;
   PhiArgs a;
-  a.segs = own.segs; a.nseg = own.nseg; a.idx = own.pass_idx(); a.val = own.pass_val();
-  a.W_own = own.W; a.W_oth = oth.W; a.S_own = own.S; a.partial = own.partial; a.flags = h->flags;
-  a.chunks = own.chunks; a.ld = h->ld;
+  const PhiLaunch pl = phi_setup(h, own, oth, true, a);
   if (a.nseg) {
-    const uint32_t wpb = rows_in_pieces(h) ? h->wg_of(own.chunks != nullptr) / 64 : 4;      // waves per workgroup
-    const uint32_t blocks = own.chunks ? own.nchunk_blocks : std::min<uint32_t>((a.nseg + wpb - 1) / wpb, h->phi_blocks * (4 / wpb));
-    const PhiLaunch pl = {blocks, wpb * 64, st};
     const bool ok = rows_in_pieces(h) ? launch_phi_packed(h->wl, h->phiG, h->phiR, side, a, pl)
-                                      : launch_phi(h->w32, h->phiG, h->phiR, h->phiV, side, a, blocks, st);
+                                      : launch_phi(h->w32, h->phiG, h->phiR, h->phiV, side, a, pl);
     if (!ok) { h->err = "no phi kernel for this configuration"; return HPF_ERR_UNSUPPORTED; }
   } else if (side == 1) {
     // the item-major pass opens an iteration (phi_pass_skips keeps the books of the fallback protocol): an empty one still does
@@ -1383,7 +1256,7 @@ int run_phi(hpf_handle *h, Side &own, Side &oth, hipEvent_t after_kernel)
 void sweep_args(hpf_handle *h, Side &s, SweepArgs &a)
 {
   a.S = s.S; a.W = s.W; a.w32 = h->w32;
-  a.pk = h->pk; a.flags = h->flags;
+  a.pk = packed_row(h->pk); a.flags = h->flags;
   a.prior_E = s.prior_E; a.prior_rate = s.prior_rate;
   a.psi_prior_shape = host_digamma(h->cfg.s_prior + (double)h->K * h->cfg.s_prior);
   a.colsum_part = s.colsum_part; a.colsum_used = s.colsum_used;
@@ -1573,8 +1446,7 @@ int set_rows_f64(hpf_handle *h)
 {
   int rc;
   drop_graph(h);
-  h->wl = WL_F64; h->pk = h->pks; h->phiR = (int)h->pks.L;
-  h->sw_mode = SW_F64;
+  static_cast<Plan &>(*h) = h->as_plain_doubles();
   Side *sides[2] = {&h->u, &h->it};
   for (Side *s : sides) {
     dfree(s->W); s->W = nullptr;
@@ -1723,21 +1595,20 @@ int hpf_create(const hpf_config *cfg, hpf_handle **out)
   if (cfg->device < 0 || cfg->device >= ndev) return HPF_ERR_NO_DEVICE;
   if (hipSetDevice(cfg->device) != hipSuccess) return HPF_ERR_NO_DEVICE;
 
+  if (cfg->w_storage > 3 || cfg->tiling > 1) return HPF_ERR_INVALID;
+  const Knobs knobs = hpf_plan::read_knobs();
+  Plan plan;
+  if (int rc = hpf_plan::plan_shapes(C, cfg->w_storage, knobs, &plan)) return rc;
+
   hpf_handle *h = new (std::nothrow) hpf_handle();
   if (!h) return HPF_ERR_OOM;
+  static_cast<Plan &>(*h) = plan;
+  static_cast<Knobs &>(*h) = knobs;
   h->cfg = *cfg;
   if (h->cfg.n_users_total == 0) h->cfg.n_users_total = cfg->n_users;
   if (h->cfg.s_prior <= 0) h->cfg.s_prior = 0.3;
   if (h->cfg.r_prior <= 0) h->cfg.r_prior = 0.3;
-  h->w32 = cfg->w_storage == 1;          // only ever chosen by the caller's hpf_config
-  if (cfg->w_storage > 3 || cfg->tiling > 1) { delete h; return HPF_ERR_INVALID; }
   h->K = cfg->K; h->C = C;
-  // Tuning knobs are read from the environment ONLY under HPF_EXPERIMENTAL=1 (tests, tools/):
-  // a stray variable must not change the layout or the summation order of a production run.
-  const bool experimental = [] { const char *e = getenv("HPF_EXPERIMENTAL"); return e && atoi(e) == 1; }();
-  auto knob = [&](const char *name) -> const char * { return experimental ? getenv(name) : nullptr; };
-  if (const char *e = knob("HPF_H2D")) h->xfer_mode = !strcmp(e, "plain") ? 0 : !strcmp(e, "register") ? 2 : 1;
-  if (const char *e = knob("HPF_H2D_THREADS")) { int v = atoi(e); if (v >= 1 && v <= 64) h->xfer_threads = (unsigned)v; }
 
   auto fail = [&](int rc) { hpf_destroy(h); return rc; };
   if (cfg->stream) h->stream = (hipStream_t)cfg->stream;
@@ -1748,132 +1619,6 @@ int hpf_create(const hpf_config *cfg, hpf_handle **out)
   for (uint32_t r = 0; r < hpf_handle::RING; ++r)
     for (int e = 0; e < 8; ++e)
       if (hipEventCreate(&h->evr[r][e]) != hipSuccess) return fail(HPF_ERR_HIP);
-
-  // Kernel shape and row stride.  The phi pass gives G lanes to a nonzero, each with R loads
-  // of V elements; the row stride of every device matrix is EXACTLY ld = G*R*V elements
-  // (round 3): the live columns K + 2*bias are padded with zero columns, so the kernels carry
-  // no column test (K=100: 800-byte rows become 896 = seven whole 128-byte lines, the
-  // number of lines a gather of an unaligned 800-byte row touched anyway).
-  {
-    // 16-byte loads when they pad no worse than 8-byte ones (measured: C2
-    // phi_user 4.36 ms vs 4.52 ms).  Elements per load: doubles 1|2, floats 2|4.
-    bool phi_cfg_forced = false;
-    const int Vs = h->w32 ? 2 : 1, Vl = 2 * Vs;
-    int g1 = 0, r1 = 0, g2 = 0, r2 = 0;
-    long w1 = 1L << 40, w2 = 1L << 40;
-    const bool ok1 = choose_cfg(C, Vs, &g1, &r1, 8, &w1), ok2 = choose_cfg(C, Vl, &g2, &r2, 8, &w2);
-    if (!ok1 && !ok2) return fail(HPF_ERR_UNSUPPORTED);
-    if (!ok1) w1 = 1L << 40;
-    if (!ok2) w2 = 1L << 40;
-    if (w2 <= w1) { h->phiG = g2; h->phiR = r2; h->phiV = Vl; }
-    else { h->phiG = g1; h->phiR = r1; h->phiV = Vs; }
-    if (h->w32) {
-      // f32 rows are half as long: measured at C2 (K=100) the passes want 256
-      // contiguous bytes per nonzero-group -- (G,R,V) = (16,2,4): 3.7 + 3.4 ms
-      // against 5.0 + 3.8 ms for (8,4,4) and 9.8 + 5.3 ms for the least-padding (4,7,4)
-      const int g = C > 512 ? 32 : C > 32 ? 16 : C > 16 ? 8 : 4;
-      h->phiG = g; h->phiV = 4; h->phiR = (int)((C + (uint32_t)(4 * g) - 1) / (uint32_t)(4 * g));
-    }
-    if (const char *e = knob("HPF_PHI_CFG")) {           // "G,R,V"
-      int g = 0, r = 0, v = 0;
-      if (sscanf(e, "%d,%d,%d", &g, &r, &v) == 3 && (h->w32 ? (v == 2 || v == 4) : (v == 1 || v == 2)) && r >= 1 && r <= 8 &&
-          (g == 4 || g == 8 || g == 16 || g == 32 || g == 64) && (uint32_t)(g * r * v) >= C && g * r * v <= 2048) {
-        h->phiG = g; h->phiR = r; h->phiV = v;
-        phi_cfg_forced = true;                             // an explicit plain shape: no packing
-      }
-    }
-    h->ld = (uint32_t)(h->phiG * h->phiR * h->phiV);
-    {
-      // Packed rows: G lanes x L 16-byte pieces, E elements per lane (p59: 128L/59, f48: 8L/3); fewest
-      // row bytes G*L*16 with G*E >= C.  w_storage 0 takes the lossless p59 packing when it saves
-      // at least one 128-byte line per row against the plain fp64 row (K = 100: 6 instead of 7,
-      // K = 50: 3 instead of 4 -- measured on a C5 shard: 65.6 -> 51.7 ms); 2 asks for f48; 3 keeps
-      // plain rows.  HPF_W_PACK=1 (experimental) packs whenever a shape exists.
-      const bool force_pack = knob("HPF_W_PACK") && atoi(knob("HPF_W_PACK")) == 1;
-      // w_storage 3 asks for plain doubles: where the default would pack, the rows keep the packed SHAPE (lanes per nonzero,
-      // columns, row stride of S) and hold plain doubles in its pieces (WL_F64) -- the layout a packed handle falls back to
-      // when a state turns up that p59 cannot hold, so that the two give the same bits
-      const int want = cfg->w_storage == 2 ? WL_F48 : (cfg->w_storage == 0 || cfg->w_storage == 3 || force_pack) && cfg->w_storage != 1 ? WL_P59 : WL_PLAIN;
-      if (want != WL_PLAIN && !(phi_cfg_forced && want == WL_P59)) {
-        long bestb = -1; int bg = 0, bl = 0;
-        const int Gq[5] = {8, 16, 32, 64, 4};
-        for (int g : Gq)
-          for (int l = 1; l <= 8; ++l) {
-            const int e = want == WL_F48 ? (8 * l) / 3 : (128 * l) / 59;
-            if ((uint32_t)(g * e) < C) continue;
-            const long b = (long)g * l * 16;
-            if (bestb < 0 || b < bestb) { bestb = b; bg = g; bl = l; }
-            break;                                                                   // larger l only adds bytes
-          }
-        const long plain_lines = ((long)h->ld * 8 + 127) / 128, packed_lines = (bestb + 127) / 128;
-        bool take = bestb > 0 && (want == WL_F48 || force_pack || packed_lines < plain_lines);
-        if (want == WL_F48 && bestb < 0) return fail(HPF_ERR_UNSUPPORTED);
-        // the sweep must have a shape for the packed stride too
-        if (take) {
-          const int e = want == WL_F48 ? (8 * bl) / 3 : (128 * bl) / 59;
-          const uint32_t pld = (uint32_t)(bg * e);
-          bool fits = false;
-          if (want == WL_F48) for (int g : {64, 32, 16, 8, 4}) { const uint32_t r = (pld + (uint32_t)g - 1) / (uint32_t)g; fits |= r >= 1 && r <= (g == 64 ? 16u : 8u); }
-          else fits = bg <= 32 || e <= 16;      // p59: groups of twice the pass's lanes (<= 9 slots), or 64 lanes with a slot per element
-          if (!fits && want == WL_F48) return fail(HPF_ERR_UNSUPPORTED);
-          if (!fits) take = false;                         // e.g. 961..1024 columns: 1088 packed columns have none; rows stay plain
-        }
-        if (take) {
-          const int e = want == WL_F48 ? (8 * bl) / 3 : (128 * bl) / 59;
-          h->wl = want;
-          h->phiG = bg; h->phiR = bl; h->phiV = 0;
-          h->pk.G = (uint32_t)bg; h->pk.L = (uint32_t)bl; h->pk.E = (uint32_t)e; h->pk.row_bytes = (uint32_t)(bg * bl) * 16u;
-          h->pk.lgG = 0; while ((1u << h->pk.lgG) < (uint32_t)bg) ++h->pk.lgG;
-          h->ld = (uint32_t)(bg * e);
-          if (want == WL_P59) {
-            const uint32_t ls = ((uint32_t)e + 1u) / 2u;
-            h->pks = h->pk; h->pks.L = ls; h->pks.E = 2u * ls; h->pks.row_bytes = (uint32_t)bg * ls * 16u;
-            if (cfg->w_storage == 3) { h->wl = WL_F64; h->pk = h->pks; h->phiR = (int)ls; }
-          }
-        }
-      }
-    }
-    // The row sweep gives G' lanes to a row with R' columns each.  Plain rows: G'*R' == ld exactly.  p59 rows (and the plain
-    // doubles in their shape): G' is TWICE the pass's lanes -- the two lanes that share a packed lane swap their halves and
-    // build the row in registers (row_sweep_kernel, SW_REG_P59) -- or the pass's 64.  48-bit rows: G'*R' >= ld, built in LDS.
-    h->swG = h->swR = 0;
-    if (h->wl == WL_P59 || h->wl == WL_F64) {
-      const uint32_t ep = h->ld / (uint32_t)h->phiG;                 // elements per lane of the p59 shape
-      if (h->phiG <= 32) { h->swG = 2 * h->phiG; h->swR = (int)((ep + 1) / 2); h->sw_mode = h->wl == WL_P59 ? SW_REG_P59 : SW_F64; }
-      else { h->swG = 64; h->swR = (int)ep; h->sw_mode = h->wl == WL_P59 ? SW_LDS_P59 : SW_F64; }
-    } else {
-      h->sw_mode = h->wl == WL_F48 ? SW_LDS_F48 : SW_PLAIN;
-      const int Gs[5] = {64, 32, 16, 8, 4};
-      int best = 1 << 30;
-      for (int g : Gs) {
-        if (h->wl == WL_PLAIN && h->ld % (uint32_t)g) continue;
-        const int r = (int)((h->ld + (uint32_t)g - 1) / (uint32_t)g);
-        if (r < 1 || r > (g == 64 ? 16 : 8)) continue;
-        const int p = (r == 1 ? 3 : 0) + (r > 7 ? 2 : 0) + (g * 8 < 128 ? 1 : 0);   // same preferences as round 1's K sweep
-        if (p < best || (p == best && g < h->swG)) { best = p; h->swG = g; h->swR = r; }
-      }
-      if (!h->swG) return fail(HPF_ERR_UNSUPPORTED);
-      if (const char *e = knob("HPF_SWEEP_CFG")) {         // "G,R" with G*R == ld (plain rows)
-        int g = 0, r = 0;
-        if (h->wl == WL_PLAIN && sscanf(e, "%d,%d", &g, &r) == 2 && r >= 1 && r <= (g == 64 ? 16 : 8) && (g == 4 || g == 8 || g == 16 || g == 32 || g == 64) &&
-            (uint32_t)(g * r) == h->ld) { h->swG = g; h->swR = r; }
-      }
-    }
-  }
-  if (const char *e = knob("HPF_SWEEP_BLOCKS")) { int v = atoi(e); if (v >= 1 && v <= 65536) h->sweep_blocks_max = (uint32_t)v; }
-  if (const char *e = knob("HPF_GRAPH")) h->graph_mode = atoi(e) != 0;
-  if (const char *e = knob("HPF_SEG_MAX")) { int v = atoi(e); if (v >= 16) h->seg_max = (uint32_t)v; }
-  if (const char *e = knob("HPF_HUGE_SLOTS")) { int v = atoi(e); if (v >= 2) { h->huge_slots = (uint32_t)v; h->group_slots = std::max<uint32_t>(2, std::min<uint32_t>(64, (uint32_t)v / 2)); } }
-  if (const char *e = knob("HPF_TILE")) { int v = atoi(e); if (v >= 0 && v <= 2) h->tile_mode = v; }
-  if (const char *e = knob("HPF_TILE_SIDES")) { int v = atoi(e); if (v >= 0 && v <= 3) h->tile_sides = v; }
-  if (const char *e = knob("HPF_TILE_SPLIT_BELOW")) { int v = atoi(e); if (v >= 0) h->tile_split_below = (uint32_t)v; }
-  if (const char *e = knob("HPF_TILE_ORDER")) { int v = atoi(e); if (v >= 0 && v <= 2) h->tile_order = v; }
-  if (const char *e = knob("HPF_TILE_BYTES")) { long long v = atoll(e); if (v >= 1024) h->tile_bytes = (uint64_t)v; }
-  if (const char *e = knob("HPF_TILE_CHUNK")) { int v = atoi(e); if (v >= 1) h->tile_chunk = (uint32_t)v; }       // default: two per wave of the workgroup
-  if (const char *e = knob("HPF_TILE_RUN")) { int v = atoi(e); if (v >= 1) h->tile_min_run = (uint32_t)v; }
-  if (const char *e = knob("HPF_TILE_SHARE")) { int v = atoi(e); if (v >= 0 && v <= 100) h->tile_min_share = v / 100.0; }
-  if (const char *e = knob("HPF_PHI_BLOCKS")) { int v = atoi(e); if (v >= 1) h->phi_blocks = (uint32_t)v; }
-  if (const char *e = knob("HPF_PHI_WG")) { int v = atoi(e); if (v == 64 || v == 128 || v == 256) h->phi_wg = (uint32_t)v; }
 
   const uint32_t n = cfg->n_users, m = cfg->n_items, ld = h->ld;
   h->u.rows = n; h->it.rows = m;
@@ -3010,16 +2755,11 @@ int hpf_gather_only(hpf_handle *h, int side, int reps, float *ms_out)
   if ((rc = prepare_derived(h))) return rc;
   Side &own = side ? h->it : h->u, &oth = side ? h->u : h->it;
   PhiArgs a;
-  a.segs = own.segs; a.nseg = own.nseg; a.idx = own.pass_idx(); a.val = own.pass_val();
-  a.W_own = own.W; a.W_oth = oth.W; a.S_own = nullptr; a.partial = nullptr; a.flags = h->flags;
-  a.chunks = own.chunks; a.ld = h->ld;
+  const PhiLaunch pl = phi_setup(h, own, oth, false, a);         // the pass's own workgroups
   *ms_out = 0.0f;
   if (!a.nseg) return HPF_OK;
   uint32_t *sink = nullptr;
   if ((rc = dalloc(h, &sink, 1))) return rc;
-  const uint32_t wpb = rows_in_pieces(h) ? h->wg_of(own.chunks != nullptr) / 64 : 4;        // the pass's own workgroups (run_phi)
-  const uint32_t blocks = own.chunks ? own.nchunk_blocks : std::min<uint32_t>((a.nseg + wpb - 1) / wpb, h->phi_blocks * (4 / wpb));
-  const PhiLaunch pl = {blocks, wpb * 64, h->stream};
   hipEvent_t e0 = nullptr, e1 = nullptr;
   hipError_t e = hipEventCreate(&e0);
   if (e == hipSuccess) e = hipEventCreate(&e1);

@@ -1,0 +1,255 @@
+// hpf_plan.hpp -- what the GPU will run, decided on the host: the experimental knobs, the shapes of the phi pass, of the rows
+// of W and of the row sweep for a column count (plan_shapes), and which kernel instances exist for them (has_*).
+// Plain C++17 without a HIP header: hpf_capi.hip builds its handle and its dispatcher from it, host/plan_selftest.cpp
+// walks every column count on a CPU.
+#pragma once
+#include "../../include/hpf.h"
+
+#include <algorithm>
+#include <cstdint>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+
+namespace hpf_plan {
+
+// The codes of hpf_kernels.hpp in plain int (hpf_capi.hip pins each with a static_assert): layout of the rows of W
+// (hpf_work_info.w_layout) and how the sweep writes them (row_sweep_kernel MODE)
+enum { WL_PLAIN = 0, WL_F48 = 2, WL_P59 = 3, WL_F64 = 4 };
+enum { SW_PLAIN = 0, SW_LDS_F48 = 2, SW_LDS_P59 = 3, SW_F64 = 4, SW_REG_P59 = 5 };
+
+// Tuning knobs, read from the environment ONLY under HPF_EXPERIMENTAL=1 (tests, tools/): a stray variable must not change
+// the layout or the summation order of a production run.  The values here are the defaults.
+struct Knobs {
+  int xfer_mode = 1;               // HPF_H2D=plain|staged|register: 0 plain, 1 staged, 2 hipHostRegister
+  unsigned xfer_threads = 4;       // HPF_H2D_THREADS
+  int phi_cfg[3] = {0, 0, 0};      // HPF_PHI_CFG "G,R,V": an explicit plain shape of the phi pass (zeros: none given)
+  bool w_pack = false;             // HPF_W_PACK=1: pack whenever a shape exists
+  int sweep_cfg[2] = {0, 0};       // HPF_SWEEP_CFG "G,R" with G*R == ld (plain rows)
+  uint32_t sweep_blocks_max = 2048;     // 8 waves per SIMD (HPF_SWEEP_BLOCKS); 1024 -> 2048: C2 user sweep 0.587 -> 0.544 ms
+  int graph_mode = -1;                  // HPF_GRAPH: -1 auto, 0 off, 1 on
+  uint32_t seg_max = 512;               // HPF_SEG_MAX
+  uint32_t huge_slots = 256, group_slots = 64;  // two-level combine above huge_slots segments (HPF_HUGE_SLOTS)
+  // tiled pass: 2 auto, 0 never, 1 forced with every row regrouped (HPF_TILE); bytes of gathered rows per tile
+  // (HPF_TILE_BYTES), segments per workgroup (HPF_TILE_CHUNK), the mean run a heavy row must reach in a
+  // tile (HPF_TILE_RUN), the share of the nonzeros the heavy rows must hold (HPF_TILE_SHARE, per cent)
+  // order of an XCD's queue (HPF_TILE_ORDER): 1 = the row-major rest in front on the even XCDs and behind on the
+  // odd ones, so that half the chip pulls over the fabric while the other half runs from its L2 (C2 item pass
+  // 4.39 ms; 0 = in front everywhere 4.75; 2 = dealt between the tiles 4.58)
+  int tile_order = 1;
+  uint32_t tile_split_below = 8;       // with fewer tiles than this EVERY tile is cut eight ways, a piece per XCD queue (round 4: below 32 tiles; C4's seven tiles of
+                                       // items are 2 % faster that way than levelled); from here on whole tiles are dealt eight at a time and the remainder levels
+                                       // the queues (build_tiled_side)
+  int tile_sides = 3;                   // HPF_TILE_SIDES: bit 0 the user pass, bit 1 the item pass (experiments)
+  int tile_mode = 2; uint64_t tile_bytes = 4u << 20; uint32_t tile_chunk = 0 /* 0: two segments per wave of the workgroup */, tile_min_run = 0; double tile_min_share = 0.15;
+  uint32_t phi_blocks = 65536;      // ~one wave per few segments; the dispatcher balances (HPF_PHI_BLOCKS)
+  // Threads per workgroup of a packed phi pass.  0 (default): 256 -- four waves, grid-stride -- for a ROW-MAJOR side, 64 -- one
+  // wave, a chunk of two segments -- for a TILED side (round 5).  A workgroup's wave slots come back one SIMD at a time but a
+  // new workgroup needs one on each of the four SIMDs at once: with the uneven runs of a tiled list a third of the slots stood
+  // empty (SQ_WAVE_CYCLES: ~2 of 3 waves per SIMD resident on average) -- which a pass that lives on its L2 hits and on issue
+  // pays for (C4 18.65 -> 17.45 ms, a C5 shard 44.8 -> 41.5; experiments.md) and a pass bound by the fabric does not (C2's
+  // user pass, a C3 shard: unchanged).  Same segments, same order inside each: the same bits.  HPF_PHI_WG forces 64 | 128 | 256.
+  uint32_t phi_wg = 0;
+};
+
+// the one place that reads the knobs from the environment
+inline Knobs read_knobs()
+{
+  Knobs k;
+  const char *x = getenv("HPF_EXPERIMENTAL");
+  if (!x || atoi(x) != 1) return k;
+  if (const char *e = getenv("HPF_H2D")) k.xfer_mode = !strcmp(e, "plain") ? 0 : !strcmp(e, "register") ? 2 : 1;
+  if (const char *e = getenv("HPF_H2D_THREADS")) { int v = atoi(e); if (v >= 1 && v <= 64) k.xfer_threads = (unsigned)v; }
+  if (const char *e = getenv("HPF_PHI_CFG")) { int c[3] = {0, 0, 0}; if (sscanf(e, "%d,%d,%d", &c[0], &c[1], &c[2]) == 3) std::copy(c, c + 3, k.phi_cfg); }
+  if (const char *e = getenv("HPF_W_PACK")) k.w_pack = atoi(e) == 1;
+  if (const char *e = getenv("HPF_SWEEP_CFG")) { int c[2] = {0, 0}; if (sscanf(e, "%d,%d", &c[0], &c[1]) == 2) std::copy(c, c + 2, k.sweep_cfg); }
+  if (const char *e = getenv("HPF_SWEEP_BLOCKS")) { int v = atoi(e); if (v >= 1 && v <= 65536) k.sweep_blocks_max = (uint32_t)v; }
+  if (const char *e = getenv("HPF_GRAPH")) k.graph_mode = atoi(e) != 0;
+  if (const char *e = getenv("HPF_SEG_MAX")) { int v = atoi(e); if (v >= 16) k.seg_max = (uint32_t)v; }
+  if (const char *e = getenv("HPF_HUGE_SLOTS")) { int v = atoi(e); if (v >= 2) { k.huge_slots = (uint32_t)v; k.group_slots = std::max<uint32_t>(2, std::min<uint32_t>(64, (uint32_t)v / 2)); } }
+  if (const char *e = getenv("HPF_TILE")) { int v = atoi(e); if (v >= 0 && v <= 2) k.tile_mode = v; }
+  if (const char *e = getenv("HPF_TILE_SIDES")) { int v = atoi(e); if (v >= 0 && v <= 3) k.tile_sides = v; }
+  if (const char *e = getenv("HPF_TILE_SPLIT_BELOW")) { int v = atoi(e); if (v >= 0) k.tile_split_below = (uint32_t)v; }
+  if (const char *e = getenv("HPF_TILE_ORDER")) { int v = atoi(e); if (v >= 0 && v <= 2) k.tile_order = v; }
+  if (const char *e = getenv("HPF_TILE_BYTES")) { long long v = atoll(e); if (v >= 1024) k.tile_bytes = (uint64_t)v; }
+  if (const char *e = getenv("HPF_TILE_CHUNK")) { int v = atoi(e); if (v >= 1) k.tile_chunk = (uint32_t)v; }       // default: two per wave of the workgroup
+  if (const char *e = getenv("HPF_TILE_RUN")) { int v = atoi(e); if (v >= 1) k.tile_min_run = (uint32_t)v; }
+  if (const char *e = getenv("HPF_TILE_SHARE")) { int v = atoi(e); if (v >= 0 && v <= 100) k.tile_min_share = v / 100.0; }
+  if (const char *e = getenv("HPF_PHI_BLOCKS")) { int v = atoi(e); if (v >= 1) k.phi_blocks = (uint32_t)v; }
+  if (const char *e = getenv("HPF_PHI_WG")) { int v = atoi(e); if (v == 64 || v == 128 || v == 256) k.phi_wg = (uint32_t)v; }
+  return k;
+}
+
+// ---- which kernel instances exist: the dispatcher of hpf_capi.hip instantiates exactly these ---------------------------
+constexpr bool is_group(int G) { return G == 4 || G == 8 || G == 16 || G == 32 || G == 64; }   // lanes per nonzero / per row
+
+// phi_pass_kernel: plain rows, R loads of V elements per lane -- V = 1 or 2 doubles, 2 or 4 floats (8- or 16-byte accesses)
+constexpr bool has_phi(bool w32, int G, int R, int V) { return is_group(G) && R >= 1 && R <= 8 && (w32 ? V == 2 || V == 4 : V == 1 || V == 2); }
+// phi_pass_packed_kernel: G lanes per nonzero, L 16-byte pieces per lane; nine pieces of plain doubles stand in for p59
+// rows of 17 elements
+constexpr bool has_phi_packed(int wl, int G, int L) { return (wl == WL_P59 || wl == WL_F48 || wl == WL_F64) && is_group(G) && L >= 1 && (L <= 8 || (wl == WL_F64 && L == 9)); }
+// gather_only_kernel: the loads of a pass over rows of 16-byte pieces (plain rows of doubles read in pairs are such rows)
+constexpr bool has_gather_only(int G, int L) { return is_group(G) && L >= 1 && L <= 9; }
+// row_sweep_kernel: G lanes per row with R columns each
+constexpr bool has_sweep(int mode, int G, int R)
+{
+  if (!is_group(G) || R < 1) return false;
+  switch (mode) {
+    case SW_REG_P59: return G >= 8 && R <= 9 && R != 6;     // the slot counts p59 shapes have (p59_of_slots): 6 is none; G = 2 x the pass's lanes <= 64
+    case SW_LDS_P59: return G == 64 && R <= 16;             // narrower groups build in registers
+    case SW_F64:     if (R == 9) return true;               // otherwise the shapes of plain rows
+                     [[fallthrough]];
+    case SW_LDS_F48:
+    case SW_PLAIN:   return R <= (G == 64 ? 16 : 8);        // G = 64 up to R = 16: 513..1024 columns
+  }
+  return false;
+}
+
+// ---- the plan ---------------------------------------------------------------------------------------------------------
+struct Row { uint32_t G, E, L, row_bytes, lgG; };     // PackedRow of hpf_kernels.hpp: G lanes x L 16-byte pieces, E elements per lane
+
+struct Plan {
+  uint32_t ld = 0;                      // row stride of every device matrix, columns
+  bool w32 = false;                     // W stored as float (hpf_config.w_storage = 1)
+  int wl = WL_PLAIN;                    // layout of W rows: plain, WL_P59 (lossless packing, default where it shortens
+                                        // the row), WL_F48 (w_storage = 2) or WL_F64 (w_storage = 3, or after a fall-back); rows in pieces: phiR = 16-byte pieces per lane
+  Row pk = {0, 0, 0, 0, 0};
+  Row pks = {0, 0, 0, 0, 0};            // plain-fp64 rows in pieces for the same columns (codec_f64): what the rows become when p59
+                                        // cannot hold a state (recover_flush)
+  int phiG = 0, phiR = 0, phiV = 0, swG = 0, swR = 0;
+  int sw_mode = SW_PLAIN;               // how the sweep writes W (row_sweep_kernel MODE)
+
+  // p59 rows -> plain doubles in the same shape (codec_f64): what a handle falls back to, and what w_storage = 3 asks for
+  Plan as_plain_doubles() const { Plan p = *this; p.wl = WL_F64; p.pk = pks; p.phiR = (int)pks.L; p.sw_mode = SW_F64; return p; }
+};
+
+// pick (G,R) with G*R*V >= ld, R <= 8.  Cost = padded row length, +20 % when a lane
+// group spans less than one 128-byte line per load although the row is at least two
+// lines long (K=50: (4,7,2) loses to the wider, more padded (8,4,2): user pass 2.58
+// vs 2.29 ms).  Ties (row lengths that several shapes cover exactly, e.g. K = 64,
+// 128) are decided by what the K sweep on MI355X showed: keep
+// 2..7 loads per lane in flight (R = 1 has no ILP: K=64 user pass 3.30 ms vs 2.35 ms
+// at R = 4; R = 8 costs registers), span a line, and among equals be narrow (more
+// nonzeros per wave).
+inline bool choose_cfg(uint32_t ld, int V, int *G, int *R, long *cost)
+{
+  int bestG = 0, bestR = 0; long bestc = -1; int bestp = 0;
+  for (int g : {4, 8, 16, 32, 64}) {
+    const int r = (int)((ld + (uint32_t)(g * V) - 1) / (uint32_t)(g * V));
+    if (r < 1 || r > 8) continue;
+    const bool narrow = g * V * 8 < 128;
+    const long c = (long)g * r * V * ((narrow && ld * 8 >= 256) ? 12 : 10);
+    const int p = (r == 1 ? 3 : 0) + (r > 7 ? 2 : 0) + (narrow ? 1 : 0);
+    if (bestc < 0 || c < bestc || (c == bestc && p < bestp)) { bestc = c; bestG = g; bestR = r; bestp = p; }
+  }
+  if (bestc < 0) return false;
+  *G = bestG; *R = bestR; *cost = bestc;
+  return true;
+}
+
+// Kernel shape and row stride for C = K + 2*bias live columns.  The phi pass gives G lanes to a nonzero, each with R loads
+// of V elements; the row stride of every device matrix is EXACTLY ld = G*R*V elements
+// (round 3): the live columns K + 2*bias are padded with zero columns, so the kernels carry
+// no column test (K=100: 800-byte rows become 896 = seven whole 128-byte lines, the
+// number of lines a gather of an unaligned 800-byte row touched anyway).
+inline int plan_shapes(uint32_t C, uint32_t w_storage, const Knobs &kn, Plan *out)
+{
+  if (C < 1 || C > HPF_MAX_COLUMNS || w_storage > 3) return HPF_ERR_UNSUPPORTED;
+  Plan p;
+  p.w32 = w_storage == 1;          // only ever chosen by the caller's hpf_config
+  // 16-byte loads when they pad no worse than 8-byte ones (measured: C2
+  // phi_user 4.36 ms vs 4.52 ms).  Elements per load: doubles 1|2, floats 2|4.
+  bool phi_cfg_forced = false;
+  const int Vs = p.w32 ? 2 : 1, Vl = 2 * Vs;
+  int g1 = 0, r1 = 0, g2 = 0, r2 = 0;
+  long w1 = 1L << 40, w2 = 1L << 40;            // stay so where no shape exists
+  const bool ok1 = choose_cfg(C, Vs, &g1, &r1, &w1), ok2 = choose_cfg(C, Vl, &g2, &r2, &w2);
+  if (!ok1 && !ok2) return HPF_ERR_UNSUPPORTED;
+  if (w2 <= w1) { p.phiG = g2; p.phiR = r2; p.phiV = Vl; }
+  else { p.phiG = g1; p.phiR = r1; p.phiV = Vs; }
+  if (p.w32) {
+    // f32 rows are half as long: measured at C2 (K=100) the passes want 256
+    // contiguous bytes per nonzero-group -- (G,R,V) = (16,2,4): 3.7 + 3.4 ms
+    // against 5.0 + 3.8 ms for (8,4,4) and 9.8 + 5.3 ms for the least-padding (4,7,4)
+    const int g = C > 512 ? 32 : C > 32 ? 16 : C > 16 ? 8 : 4;
+    p.phiG = g; p.phiV = 4; p.phiR = (int)((C + (uint32_t)(4 * g) - 1) / (uint32_t)(4 * g));
+  }
+  {
+    const int g = kn.phi_cfg[0], r = kn.phi_cfg[1], v = kn.phi_cfg[2];          // "G,R,V"
+    if (has_phi(p.w32, g, r, v) && (uint32_t)(g * r * v) >= C && g * r * v <= 2048) {
+      p.phiG = g; p.phiR = r; p.phiV = v;
+      phi_cfg_forced = true;                             // an explicit plain shape: no packing
+    }
+  }
+  p.ld = (uint32_t)(p.phiG * p.phiR * p.phiV);
+  // Packed rows: G lanes x L 16-byte pieces, E elements per lane (p59: 128L/59, f48: 8L/3); fewest
+  // row bytes G*L*16 with G*E >= C.  w_storage 0 takes the lossless p59 packing when it saves
+  // at least one 128-byte line per row against the plain fp64 row (K = 100: 6 instead of 7,
+  // K = 50: 3 instead of 4 -- measured on a C5 shard: 65.6 -> 51.7 ms); 2 asks for f48; 3 keeps
+  // plain rows.  HPF_W_PACK=1 (experimental) packs whenever a shape exists.
+  // w_storage 3 asks for plain doubles: where the default would pack, the rows keep the packed SHAPE (lanes per nonzero,
+  // columns, row stride of S) and hold plain doubles in its pieces (WL_F64) -- the layout a packed handle falls back to
+  // when a state turns up that p59 cannot hold, so that the two give the same bits
+  const int want = w_storage == 2 ? WL_F48 : w_storage == 1 ? WL_PLAIN : WL_P59;
+  if (want != WL_PLAIN && !(phi_cfg_forced && want == WL_P59)) {
+    auto per_lane = [&](int l) { return want == WL_F48 ? (8 * l) / 3 : (128 * l) / 59; };
+    long bestb = -1; int bg = 0, bl = 0;
+    for (int g : {8, 16, 32, 64, 4})
+      for (int l = 1; l <= 8; ++l) {
+        if ((uint32_t)(g * per_lane(l)) < C) continue;
+        const long b = (long)g * l * 16;
+        if (bestb < 0 || b < bestb) { bestb = b; bg = g; bl = l; }
+        break;                                                                   // larger l only adds bytes
+      }
+    const long plain_lines = ((long)p.ld * 8 + 127) / 128, packed_lines = (bestb + 127) / 128;
+    bool take = bestb > 0 && (want == WL_F48 || kn.w_pack || packed_lines < plain_lines);
+    if (want == WL_F48 && bestb < 0) return HPF_ERR_UNSUPPORTED;
+    const int e = per_lane(bl);
+    // the sweep must have a shape for the packed stride too
+    if (take) {
+      const uint32_t pld = (uint32_t)(bg * e);
+      bool fits = false;
+      if (want == WL_F48) for (int g : {64, 32, 16, 8, 4}) { const uint32_t r = (pld + (uint32_t)g - 1) / (uint32_t)g; fits |= r >= 1 && r <= (g == 64 ? 16u : 8u); }
+      else fits = bg <= 32 || e <= 16;      // p59: groups of twice the pass's lanes (<= 9 slots), or 64 lanes with a slot per element
+      if (!fits && want == WL_F48) return HPF_ERR_UNSUPPORTED;
+      if (!fits) take = false;                         // e.g. 961..1024 columns: 1088 packed columns have none; rows stay plain
+    }
+    if (take) {
+      p.wl = want;
+      p.phiG = bg; p.phiR = bl; p.phiV = 0;
+      p.pk.G = (uint32_t)bg; p.pk.L = (uint32_t)bl; p.pk.E = (uint32_t)e; p.pk.row_bytes = (uint32_t)(bg * bl) * 16u;
+      p.pk.lgG = 0; while ((1u << p.pk.lgG) < (uint32_t)bg) ++p.pk.lgG;
+      p.ld = (uint32_t)(bg * e);
+      if (want == WL_P59) {
+        const uint32_t ls = ((uint32_t)e + 1u) / 2u;
+        p.pks = p.pk; p.pks.L = ls; p.pks.E = 2u * ls; p.pks.row_bytes = (uint32_t)bg * ls * 16u;
+      }
+    }
+  }
+  // The row sweep gives G' lanes to a row with R' columns each.  Plain rows: G'*R' == ld exactly.  p59 rows (and the plain
+  // doubles in their shape): G' is TWICE the pass's lanes -- the two lanes that share a packed lane swap their halves and
+  // build the row in registers (row_sweep_kernel, SW_REG_P59) -- or the pass's 64.  48-bit rows: G'*R' >= ld, built in LDS.
+  if (p.wl == WL_P59) {
+    const uint32_t ep = p.ld / (uint32_t)p.phiG;                 // elements per lane of the p59 shape
+    if (p.phiG <= 32) { p.swG = 2 * p.phiG; p.swR = (int)((ep + 1) / 2); p.sw_mode = SW_REG_P59; }
+    else { p.swG = 64; p.swR = (int)ep; p.sw_mode = SW_LDS_P59; }
+    if (w_storage == 3) p = p.as_plain_doubles();
+  } else {
+    p.sw_mode = p.wl == WL_F48 ? SW_LDS_F48 : SW_PLAIN;
+    int best = 1 << 30;
+    for (int g : {64, 32, 16, 8, 4}) {
+      if (p.wl == WL_PLAIN && p.ld % (uint32_t)g) continue;
+      const int r = (int)((p.ld + (uint32_t)g - 1) / (uint32_t)g);
+      if (r < 1 || r > (g == 64 ? 16 : 8)) continue;
+      const int pen = (r == 1 ? 3 : 0) + (r > 7 ? 2 : 0) + (g * 8 < 128 ? 1 : 0);   // same preferences as round 1's K sweep
+      if (pen < best || (pen == best && g < p.swG)) { best = pen; p.swG = g; p.swR = r; }
+    }
+    if (!p.swG) return HPF_ERR_UNSUPPORTED;
+    const int g = kn.sweep_cfg[0], r = kn.sweep_cfg[1];
+    if (p.wl == WL_PLAIN && has_sweep(SW_PLAIN, g, r) && (uint32_t)(g * r) == p.ld) { p.swG = g; p.swR = r; }
+  }
+  *out = p;
+  return HPF_OK;
+}
+
+}  // namespace hpf_plan

@@ -216,3 +216,23 @@ def test_page_locked_host_buffers_take_the_direct_route():
         D.get_state("THETA_SHAPE", out=np.empty((n, K), np.float32))
     D.close()
     assert got_pin[0, 0] == sh[0, 0]                    # the pinned block is still there after the handle is gone
+
+
+def test_a_handle_reports_the_planned_shapes(monkeypatch):
+    """tests/data/plan_table.txt (what tests/test_plan.py holds the planner of hpf_plan.hpp to, on a CPU) is what a handle
+    reports: at the first and the last column count of every run of w_storage 0 and 3, without knobs, a handle of one
+    user and one item with K = C and nothing uploaded shows exactly that row in its work info"""
+    from pathlib import Path
+    from hgaprec_amd.capi import Hpf
+    monkeypatch.delenv("HPF_EXPERIMENTAL", raising=False)
+    names = ("w_layout", "phi_G", "phi_R", "phi_V", "sweep_G", "sweep_R", "ld")
+    rows = [ln.split() for ln in (Path(__file__).parent / "data" / "plan_table.txt").read_text().splitlines() if ln and ln[0] != "#"]
+    rows = [[int(x) for x in r] for r in rows if r[0] in ("0", "3") and r[1] == "0"]
+    assert len(rows) > 50 and all(len(r) == 11 for r in rows)         # (no column count is unsupported)
+    for ws, _, first, last, *shape in rows:
+        for cols in {first, last}:
+            D = Hpf(1, 1, cols, hier=True, bias=False, w_storage=ws)
+            w = D.work_info()
+            D.close()
+            assert [w[k] for k in names] == shape, (ws, cols, w)
+
