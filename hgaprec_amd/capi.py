@@ -41,8 +41,12 @@ EXPORTS = [
     "hpf_get_work_info", "hpf_upload_csr_device", "hpf_get_csc", "hpf_set_state_device", "hpf_get_state_device",
     "hpf_iteration_times", "hpf_debug_poke_index", "hpf_start_sums", "hpf_host_alloc", "hpf_host_free",
     "hpf_heldout_bind", "hpf_heldout_ll_bound",
-    "hpf_predict", "hpf_loo_ranks",
+    "hpf_predict", "hpf_loo_ranks", "hpf_rank_queries",
 ]
+
+# queries of one row of rank_queries_kernel (RQ_QCAP in csrc/hpf_kernels.hpp): hpf_rank_queries cuts a user with more
+# into several rows; tests put their query counts around it
+RANK_QUERIES_QCAP = 32
 
 
 
@@ -184,6 +188,8 @@ def load_library(path: os.PathLike | None = None) -> C.CDLL:
     if hasattr(lib, "hpf_predict"):               # (v8 additions: absent from an older build loaded through HPF_LIB)
         lib.hpf_predict.argtypes = [vp, u32p, u32p, C.c_size_t, dp]
         lib.hpf_loo_ranks.argtypes = [vp, u32p, C.c_uint32, u64p, u32p, u32p, C.c_uint32, u32p, dp, u32p]
+    if hasattr(lib, "hpf_rank_queries"):
+        lib.hpf_rank_queries.argtypes = [vp, u32p, C.c_uint32, u64p, u32p, u64p, u32p, u32p, dp]
     lib.hpf_comm_unique_id.argtypes = [vp]
     lib.hpf_comm_init.argtypes = [vp, vp]
     lib.hpf_allreduce_exchange.argtypes = [vp]
@@ -546,6 +552,26 @@ class Hpf:
                                            int(item_limit), _ptr(rank, C.c_uint32), _ptr(sc, C.c_double),
                                            _ptr(masked, C.c_uint32)))
         return rank, sc, masked
+
+    def rank_queries(self, users, q_ptr, q_items, mask_ptr=None, mask_items=None):
+        """position of EVERY queried item of every selected user (hpf_rank_queries): selected user b asks for
+        q_items[q_ptr[b]:q_ptr[b + 1]]; the user's scores are computed once -> (rank, score), one per entry of q_items"""
+        users = np.ascontiguousarray(users, dtype=np.uint32)
+        q_ptr = np.ascontiguousarray(q_ptr, dtype=np.uint64)
+        q_items = np.ascontiguousarray(q_items, dtype=np.uint32)
+        if users.ndim != 1 or q_ptr.ndim != 1 or q_items.ndim != 1 or q_ptr.size != users.size + 1:
+            raise ValueError("q_ptr must have len(users) + 1 entries")
+        if users.size and int(q_ptr[-1]) > q_items.size:
+            raise ValueError("q_ptr[-1] beyond len(q_items)")
+        mp, mi, pmp, pmi = self._mask(mask_ptr, mask_items)
+        if mp is not None and mp.size != users.size + 1:
+            raise ValueError("mask_ptr must have len(users) + 1 entries")
+        nq = int(q_ptr[-1]) if users.size else 0
+        rank = np.empty(nq, dtype=np.uint32)
+        sc = np.empty(nq, dtype=np.float64)
+        self._check(self.lib.hpf_rank_queries(self._h, _ptr(users, C.c_uint32), users.size, pmp, pmi, _ptr(q_ptr, C.c_uint64),
+                                              _ptr(q_items, C.c_uint32), _ptr(rank, C.c_uint32), _ptr(sc, C.c_double)))
+        return rank, sc
 
     def synchronize(self):
         self._check(self.lib.hpf_synchronize(self._h))

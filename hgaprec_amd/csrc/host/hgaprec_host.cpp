@@ -69,6 +69,7 @@ int Env::parse(int argc, char **argv, bool echo, std::string *bad)
     else if (!strcmp(s, "-gen-ranking")) { gen_ranking = true; }
     else if (!strcmp(s, "-rmse")) { rmse = true; }
     else if (!strcmp(s, "-msr")) { msr = true; }
+    else if (!strcmp(s, "-eval-all")) { eval_all = true; }       // extension: every user's every test item, from a saved model
     else if (!strcmp(s, "-model-dir")) { model_dir = next(); }   // extension: where a score mode finds the factor files
     else if (!strcmp(s, "-novb")) { vb = false; }
     else if (!strcmp(s, "-wals_l") || !strcmp(s, "-wals_C")) { next(); }
@@ -1256,6 +1257,39 @@ bool StopRule::update(uint32_t iter, double a, int *why)
   }
   prev_h = a;
   return stop;
+}
+
+// ======================================================================
+// metrics from ranks (-eval-all)
+// ======================================================================
+void eval_from_ranks(const uint64_t *q_ptr, const uint32_t *rank, const uint32_t *nranked, size_t n_users,
+                     EvalUser *per_user, EvalMeans *means)
+{
+  EvalMeans t = {0, 0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  for (size_t b = 0; b < n_users; ++b) {
+    EvalUser e = {0, 0, 0, 0, 0};
+    for (uint64_t q = q_ptr[b]; q < q_ptr[b + 1]; ++q) {
+      const uint32_t j = rank[q];
+      if (e.ntest == 0 || j < e.best_rank) e.best_rank = j;
+      e.ntest++;
+      if (j < 10) e.hits10++;
+      if (j < 100) e.hits100++;
+      e.sum_rank += (uint64_t)j + 1;
+    }
+    if (per_user) per_user[b] = e;
+    t.users++; t.pairs += e.ntest;
+    if (e.ntest) {
+      t.precision10 += (double)e.hits10 / 10;
+      t.precision100 += (double)e.hits100 / 100;
+      t.recall100 += (double)e.hits100 / e.ntest;
+      t.mrr += 1.0 / ((double)e.best_rank + 1.0);               // real division (see the header)
+      if (nranked[b] > 0) t.meanrank += ((double)e.sum_rank / nranked[b]) / e.ntest;
+    }
+  }
+  if (t.users) {
+    t.precision10 /= t.users; t.precision100 /= t.users; t.recall100 /= t.users; t.mrr /= t.users; t.meanrank /= t.users;
+  }
+  if (means) *means = t;
 }
 
 

@@ -54,7 +54,10 @@ struct Env {
   // are; default the current directory, like the reference (name() + ".tsv")
   bool gen_ranking = false, rmse = false, msr = false;
   std::string model_dir;
-  bool score_mode() const { return gen_ranking || rmse || msr; }
+  // extension: -eval-all ranks EVERY hit test item of EVERY user of a saved model (compute_itemrank judges a sample of at
+  // most 1000 users) and writes itemrank_all.tsv, eval_users.tsv and eval_all.txt; a score mode like the three above
+  bool eval_all = false;
+  bool score_mode() const { return gen_ranking || rmse || msr || eval_all; }
 
   std::string prefix;          // output directory (Env::prefix)
   FILE *plogf = nullptr;       // param.txt
@@ -222,6 +225,25 @@ struct StopRule {
   // returns true when the run must stop; *why as written to max.txt
   bool update(uint32_t iter, double a, int *why);
 };
+
+// ------------------------------------------------- metrics from ranks -----
+// -eval-all: what the ranks of a user's test items say about the user, and the means over the users.
+// Integers per user (eval_users.tsv): hitsN = queries with rank < N, best_rank = the smallest rank, sum_rank = the sum
+// of (rank + 1).
+struct EvalUser { uint32_t ntest, hits10, hits100, best_rank; uint64_t sum_rank; };
+// eval_all.txt: means over the users, each summed serially in the order given
+struct EvalMeans { uint64_t users, pairs; double precision10, precision100, recall100, mrr, meanrank; };
+// User b's ranks (0-based positions in its full item order) are rank[q_ptr[b] .. q_ptr[b+1]), in any order; every user
+// given has at least one.  nranked[b]: the items the reference counts as ranked for the user (n_items minus the
+// distinct training items with a rating > 0; compute_itemrank, hgaprec.cc:1628-1680).  Per user:
+//   precision@N = hitsN / N, recall@100 = hits100 / ntest,
+//   mrr = 1.0 / (best_rank + 1) -- REAL division: the reference's reciprocal_rank_ui divides integers (1 / (j + 1) is 0
+//         for every j > 0; Driver::compute_itemrank keeps that for parity), this report is an extension and does not,
+//   meanrank = (sum_rank / nranked) / ntest, the first figure of meanrank.txt (0 for a user with nranked = 0, whom
+//         compute_itemrank leaves out).
+// A user without a query (q_ptr[b] == q_ptr[b+1]) gets zeros and best_rank = 0 and adds 0 to every mean.
+void eval_from_ranks(const uint64_t *q_ptr, const uint32_t *rank, const uint32_t *nranked, size_t n_users,
+                     EvalUser *per_user, EvalMeans *means);
 
 // ------------------------------------------------------------- Comm --------
 // Host-side collectives of a multi-process run (one process per GPU): a TCP

@@ -13,7 +13,7 @@
 // stand-in (`-comm host`, for tests on a single GPU).  The output files are
 // the same as in a single-GPU run.
 //
-// Scoring a saved model: -gen-ranking / -rmse / -msr read the data like a training run, load
+// Scoring a saved model: -gen-ranking / -rmse / -msr / -eval-all read the data like a training run, load
 // the factor files a run has written (from the current directory like the reference, or from
 // -model-dir DIR) into the handle's expectations, write ONE report and exit (Driver::score).
 //
@@ -783,11 +783,77 @@ struct Driver {
     close_or_die(f, path);
   }
 
+  // -eval-all (extension): compute_itemrank's question -- where does each test item that is a hit stand in its user's
+  // full item order, training items with a rating > 0 and validation items zeroed -- for EVERY user with such an item
+  // instead of a sample, through hpf_rank_queries (the user's scores are computed once for all its items, and no score
+  // reaches memory).  itemrank_all.tsv has itemrank.tsv's lines; eval_users.tsv the integers per user; eval_all.txt the
+  // means (eval_from_ranks, hgaprec_host.hpp).
+  void eval_all_report() {
+    if (item_deg.empty()) { item_deg.assign(m, 0); for (uint32_t c : rt.col) item_deg[c]++; }
+    std::vector<uint32_t> eu;                                 // evaluated users, seq order
+    std::vector<uint64_t> qptr(1, 0); std::vector<uint32_t> qi;
+    for (uint32_t u = 0; u < n; ++u) {
+      for (size_t a = lower(rt.test, u, 0); a < rt.test.u.size() && rt.test.u[a] == u; ++a)
+        if (test_hit(rt.test.y[a])) qi.push_back(rt.test.i[a]);
+      if (qi.size() > qptr.back()) { eu.push_back(u); qptr.push_back(qi.size()); }
+    }
+    std::vector<uint32_t> rank(qi.size()); std::vector<double> pred(qi.size());
+    const uint32_t CH = 1u << 16;
+    std::vector<uint64_t> mptr, cq; std::vector<uint32_t> mitems;
+    for (size_t b0 = 0; b0 < eu.size(); b0 += CH) {
+      const size_t b1 = std::min(eu.size(), b0 + CH);
+      mitems.clear(); mptr.assign(1, 0); cq.clear();
+      for (size_t b = b0; b < b1; ++b) {
+        const uint32_t u = eu[b];
+        for (size_t a = lower(rt.validation, u, 0); a < rt.validation.u.size() && rt.validation.u[a] == u; ++a)
+          mitems.push_back(rt.validation.i[a]);
+        mptr.push_back(mitems.size());
+        cq.push_back(qptr[b] - qptr[b0]);
+      }
+      cq.push_back(qptr[b1] - qptr[b0]);
+      int rc = hpf_rank_queries(h, eu.data() + b0, (uint32_t)(b1 - b0), mptr.data(), mitems.data(), cq.data(),
+                                qi.data() + qptr[b0], rank.data() + qptr[b0], pred.data() + qptr[b0]);
+      if (rc) die("hpf_rank_queries", rc);
+    }
+    std::vector<uint32_t> nranked(eu.size()), seen;
+    for (size_t b = 0; b < eu.size(); ++b) {                  // Ratings::r(n,m) == 0, as in compute_itemrank
+      const uint32_t u = eu[b];
+      seen.clear();
+      for (int64_t j = rt.rowptr[u]; j < rt.rowptr[u + 1]; ++j) if (rt.val[(size_t)j] > 0) seen.push_back(rt.col[(size_t)j]);
+      std::sort(seen.begin(), seen.end());
+      nranked[b] = m - (uint32_t)(std::unique(seen.begin(), seen.end()) - seen.begin());
+    }
+    std::vector<EvalUser> pu(eu.size()); EvalMeans mean;
+    eval_from_ranks(qptr.data(), rank.data(), nranked.data(), eu.size(), pu.data(), &mean);
+
+    const std::string ipath = env.file_str("/itemrank_all.tsv"), upath = env.file_str("/eval_users.tsv"),
+                      apath = env.file_str("/eval_all.txt");
+    FILE *f = open_or_die(ipath, "w"), *uf = open_or_die(upath, "w");
+    std::vector<uint64_t> ord;
+    for (size_t b = 0; b < eu.size(); ++b) {
+      const uint32_t u = eu[b];
+      ord.resize(qptr[b + 1] - qptr[b]);
+      for (size_t t = 0; t < ord.size(); ++t) ord[t] = qptr[b] + t;
+      std::stable_sort(ord.begin(), ord.end(), [&](uint64_t x, uint64_t y) { return rank[x] < rank[y]; });
+      for (uint64_t q : ord) fprintf(f, "%d\t%d\t%.5f\t%d\t%d\n", u, qi[q], pred[q], rank[q], item_deg[qi[q]]);
+      fprintf(uf, "%u\t%u\t%u\t%u\t%u\t%u\t%llu\n", u, rt.seq2user[u], pu[b].ntest, pu[b].hits10, pu[b].hits100,
+              pu[b].best_rank, (unsigned long long)pu[b].sum_rank);
+    }
+    close_or_die(f, ipath);
+    close_or_die(uf, upath);
+    FILE *af = open_or_die(apath, "w");
+    fprintf(af, "%llu\t%llu\t%.5f\t%.5f\t%.5f\t%.5f\t%.5f\n", (unsigned long long)mean.users, (unsigned long long)mean.pairs,
+            mean.precision10, mean.precision100, mean.recall100, mean.mrr, mean.meanrank);
+    close_or_die(af, apath);
+    env.lerr("-eval-all: %llu users, %llu test items ranked", (unsigned long long)mean.users, (unsigned long long)mean.pairs);
+  }
+
   // one report on the loaded state, in the reference's order of tests (main.cc:254-285, then -gen-ranking)
   void score() {
     load_model();
     if (env.rmse) compute_rmse();
     else if (env.msr) gen_msr_csv();
+    else if (env.eval_all) eval_all_report();
     else gen_ranking_for_users();
     finish(0);
   }
@@ -1027,13 +1093,13 @@ int main(int argc, char **argv)
   if (!env.unsupported.empty()) {
     fprintf(stderr, "error: option %s selects a mode outside the MI355X hot-path build "
                     "(supported: -dir -n -m -k -hier -bias -binary-data -rfreq -max-iterations "
-                    "-seed -label -rating-threshold -logl -novb -a -b -c -d, -gen-ranking -rmse -msr -model-dir, "
+                    "-seed -label -rating-threshold -logl -novb -a -b -c -d, -gen-ranking -rmse -msr -eval-all -model-dir, "
                     "-ngpus -comm -single-allreduce -device)\n", env.unsupported.c_str());
     return 2;
   }
   if (env.score_mode()) {
     if (env.ngpus > 1 || world > 1) {
-      fprintf(stderr, "error: -gen-ranking / -rmse / -msr score a saved model on ONE GPU: run them without -ngpus\n");
+      fprintf(stderr, "error: -gen-ranking / -rmse / -msr / -eval-all score a saved model on ONE GPU: run them without -ngpus\n");
       return 1;
     }
     // the start of a run truncates validation.txt, precision.txt and friends in its output directory: that directory

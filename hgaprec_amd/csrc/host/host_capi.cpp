@@ -132,6 +132,21 @@ int hg_load_vector(const char *path, double *out, uint32_t rows, const uint32_t 
   return rc;
 }
 
+// -eval-all's arithmetic from ranks to metrics.  per_user: n_users x 6 integers (ntest, hits10, hits100, best_rank,
+// sum_rank, nranked as given); means: users, pairs, precision@10, precision@100, recall@100, mrr, meanrank
+void hg_eval_from_ranks(const uint64_t *q_ptr, const uint32_t *rank, const uint32_t *nranked, uint64_t n_users,
+                        uint64_t *per_user, double *means)
+{
+  std::vector<EvalUser> pu(n_users); EvalMeans t;
+  eval_from_ranks(q_ptr, rank, nranked, (size_t)n_users, pu.data(), &t);
+  for (uint64_t b = 0; b < n_users; ++b) {
+    uint64_t *o = per_user + 6 * b;
+    o[0] = pu[b].ntest; o[1] = pu[b].hits10; o[2] = pu[b].hits100; o[3] = pu[b].best_rank; o[4] = pu[b].sum_rank; o[5] = nranked[b];
+  }
+  means[0] = (double)t.users; means[1] = (double)t.pairs; means[2] = t.precision10; means[3] = t.precision100;
+  means[4] = t.recall100; means[5] = t.mrr; means[6] = t.meanrank;
+}
+
 // user ranges of a multi-process run: out[2*r], out[2*r+1] = [lo, hi) of rank r
 void hg_partition_users(const int64_t *rowptr, uint32_t n, int world, uint32_t *out)
 {

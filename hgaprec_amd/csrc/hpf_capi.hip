@@ -2719,6 +2719,112 @@ int hpf_loo_ranks(hpf_handle *h, const uint32_t *users, uint32_t n_sel, const ui
   return rc;
 }
 
+int hpf_rank_queries(hpf_handle *h, const uint32_t *users, uint32_t n_sel, const uint64_t *mask_ptr,
+                     const uint32_t *mask_items, const uint64_t *q_ptr, const uint32_t *q_items,
+                     uint32_t *out_rank, double *out_score)
+{
+  if (!h || (n_sel && (!users || !q_ptr))) return HPF_ERR_INVALID;
+  if (!n_sel) return HPF_OK;
+  if (h->iterations == 0 && !(h->u.have_E && h->it.have_E)) { h->err = "E state not set"; return HPF_ERR_STATE; }
+  if (!h->have_csr) { h->err = "hpf_upload_csr has not been called"; return HPF_ERR_STATE; }
+  const uint32_t m = h->it.rows;
+  if (h->ld & 1u) { h->err = "hpf_rank_queries: odd row stride"; return HPF_ERR_UNSUPPORTED; }
+  if (q_ptr[0] != 0) { h->err = "q_ptr[0] must be 0"; return HPF_ERR_INVALID; }
+  for (uint32_t b = 0; b < n_sel; ++b) {
+    if (users[b] >= h->u.rows) { h->err = "user index out of range"; return HPF_ERR_INVALID; }
+    if (q_ptr[b + 1] < q_ptr[b]) { h->err = "q_ptr not monotone"; return HPF_ERR_INVALID; }
+  }
+  const uint64_t nq = q_ptr[n_sel];
+  if (nq > 0xffffffffull) { h->err = "hpf_rank_queries: more than 2^32 - 1 queries in one call"; return HPF_ERR_INVALID; }
+  if (nq && (!q_items || !out_rank || !out_score)) return HPF_ERR_INVALID;
+  for (uint64_t q = 0; q < nq; ++q) if (q_items[q] >= m) { h->err = "query item out of range"; return HPF_ERR_INVALID; }
+  const uint64_t nmask = mask_ptr ? mask_ptr[n_sel] : 0;
+  if (mask_ptr) {
+    if (mask_ptr[0] != 0) { h->err = "mask_ptr[0] must be 0"; return HPF_ERR_INVALID; }
+    for (uint32_t b = 0; b < n_sel; ++b) if (mask_ptr[b + 1] < mask_ptr[b]) { h->err = "mask_ptr not monotone"; return HPF_ERR_INVALID; }
+    if (nmask && !mask_items) return HPF_ERR_INVALID;
+    for (uint64_t j = 0; j < nmask; ++j) if (mask_items[j] >= m) { h->err = "mask item out of range"; return HPF_ERR_INVALID; }
+  }
+  if (!nq) return HPF_OK;
+  int rc;
+  if ((rc = check_flags(h))) return rc;
+  if ((rc = refresh_es(h, h->u)) || (rc = refresh_es(h, h->it))) return rc;
+
+  // users per batch as in hpf_loo_ranks (bit rows under 256 MB, HPF_LOO_BATCH)
+  const uint32_t words = (m + 63) / 64;
+  uint64_t batch = std::max<uint64_t>(64, (((uint64_t)256 << 20) / ((uint64_t)words * 8)) & ~63ull);
+  if (const char *e = getenv("HPF_LOO_BATCH")) { const long v = atol(e); if (v > 0) batch = std::min<uint64_t>(batch, ((uint64_t)v + 15) & ~15ull); }
+  batch = std::min<uint64_t>(batch, ((uint64_t)n_sel + 15) & ~15ull);
+
+  // rows: a selected user with at most RQ_QCAP of its queries (a query's rank does not depend on the user's other
+  // queries, so cutting a user is exact); in the order of the selected users, so a batch owns a run of them
+  std::vector<uint32_t> row_sel, row_q0, row_nq, first_row;   // first_row[batch index] -> its first row
+  for (uint32_t b = 0; b < n_sel; ++b) {
+    if (b % batch == 0) first_row.push_back((uint32_t)row_sel.size());
+    for (uint64_t q = q_ptr[b]; q < q_ptr[b + 1]; q += RQ_QCAP) {
+      row_sel.push_back((uint32_t)(b % batch)); row_q0.push_back((uint32_t)q);
+      row_nq.push_back((uint32_t)std::min<uint64_t>(RQ_QCAP, q_ptr[b + 1] - q));
+    }
+  }
+  first_row.push_back((uint32_t)row_sel.size());
+  const size_t nrows = row_sel.size();
+
+  uint32_t *d_users = nullptr, *d_q = nullptr, *d_mitems = nullptr, *d_rank = nullptr, *d_rsel = nullptr, *d_rq0 = nullptr,
+           *d_rnq = nullptr, *d_sitem = nullptr, *d_sperm = nullptr;
+  uint64_t *d_mptr = nullptr, *d_bits = nullptr, *d_skey = nullptr; double *d_sc = nullptr;
+  do {
+    if ((rc = dalloc(h, &d_users, n_sel)) || (rc = dalloc(h, &d_q, (size_t)nq)) || (rc = dalloc(h, &d_rank, (size_t)nq)) ||
+        (rc = dalloc(h, &d_sc, (size_t)nq)) || (rc = dalloc(h, &d_skey, (size_t)nq)) || (rc = dalloc(h, &d_sitem, (size_t)nq)) ||
+        (rc = dalloc(h, &d_sperm, (size_t)nq)) || (rc = dalloc(h, &d_rsel, nrows)) || (rc = dalloc(h, &d_rq0, nrows)) ||
+        (rc = dalloc(h, &d_rnq, nrows)) || (rc = dalloc(h, &d_bits, (size_t)batch * words))) break;
+    if ((rc = h2d(h, d_users, users, (size_t)n_sel * 4)) || (rc = h2d(h, d_q, q_items, (size_t)nq * 4)) ||
+        (rc = h2d(h, d_rsel, row_sel.data(), nrows * 4)) || (rc = h2d(h, d_rq0, row_q0.data(), nrows * 4)) ||
+        (rc = h2d(h, d_rnq, row_nq.data(), nrows * 4))) break;
+    if (mask_ptr) {
+      if ((rc = dalloc(h, &d_mptr, (size_t)n_sel + 1)) || (rc = dalloc(h, &d_mitems, (size_t)nmask))) break;
+      if ((rc = h2d(h, d_mptr, mask_ptr, ((size_t)n_sel + 1) * 8))) break;
+      if (nmask && (rc = h2d(h, d_mitems, mask_items, (size_t)nmask * 4))) break;
+    }
+    const uint32_t ntiles = (m + 63) / 64;
+    size_t bi = 0;
+    for (uint32_t b0 = 0; b0 < n_sel && !rc; b0 += (uint32_t)batch, ++bi) {
+      const uint32_t b1 = (uint32_t)std::min<uint64_t>(n_sel, (uint64_t)b0 + batch), urows = b1 - b0;
+      const uint32_t r0 = first_row[bi], rows = first_row[bi + 1] - r0;
+      if (!rows) continue;
+      if (b0) { hipError_t e = hipMemsetAsync(d_bits, 0, (size_t)urows * words * 8, h->stream); if (e != hipSuccess) { h->err = hipGetErrorString(e); rc = HPF_ERR_HIP; break; } }   // (dalloc zeroes)
+      hipLaunchKernelGGL(loo_mask_kernel, dim3(std::min<uint32_t>((urows + 3) / 4, 4096)), dim3(256), 0, h->stream,
+                         d_users + b0, urows, h->rowptr_dev, h->u.idx, h->u.val, d_mptr ? d_mptr + b0 : nullptr, d_mitems,
+                         (uint32_t *)d_bits, words);
+      RqArgs a;
+      a.users = d_users + b0; a.row_sel = d_rsel + r0; a.row_q0 = d_rq0 + r0; a.row_nq = d_rnq + r0; a.q_item = d_q;
+      a.Et = h->u.E; a.Eb = h->it.E; a.bits = d_bits; a.skey = (unsigned long long *)d_skey; a.sitem = d_sitem;
+      a.sperm = d_sperm; a.rank = d_rank; a.score = d_sc;
+      a.nrows = rows; a.m = m; a.ld = h->ld; a.K = h->K; a.words = words;
+      a.ubias_col = h->cfg.bias ? h->u.bias_col : -1; a.ibias_col = h->cfg.bias ? h->it.bias_col : -1;
+      // hpf_loo_ranks' policy, over rows: few blocks of rows: the item range is cut so that some 1024 workgroups exist
+      const uint32_t blocks = (rows + 63) / 64;
+      uint32_t splits = std::max<uint32_t>(1, std::min<uint32_t>(ntiles, (1024 + blocks - 1) / blocks));
+      a.tiles_per_split = (ntiles + splits - 1) / splits;
+      splits = (ntiles + a.tiles_per_split - 1) / a.tiles_per_split;
+      hipLaunchKernelGGL(rq_threshold_kernel, dim3((rows + 3) / 4), dim3(256), 0, h->stream, a);
+      if (h->K <= 32) hipLaunchKernelGGL(rank_queries_kernel<1>, dim3(blocks, splits), dim3(256), 0, h->stream, a);
+      else if (h->K <= 64) hipLaunchKernelGGL(rank_queries_kernel<2>, dim3(blocks, splits), dim3(256), 0, h->stream, a);
+      else if (h->K <= 128) hipLaunchKernelGGL(rank_queries_kernel<4>, dim3(blocks, splits), dim3(256), 0, h->stream, a);
+      else hipLaunchKernelGGL(rank_queries_kernel<0>, dim3(blocks, splits), dim3(256), 0, h->stream, a);
+      rc = check_launch(h, "rank_queries_kernel");
+    }
+    if (rc) break;
+    hipError_t e = hipMemcpyAsync(out_rank, d_rank, (size_t)nq * 4, hipMemcpyDeviceToHost, h->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(out_score, d_sc, (size_t)nq * 8, hipMemcpyDeviceToHost, h->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    if (e != hipSuccess) { h->err = hipGetErrorString(e); rc = HPF_ERR_HIP; }
+  } while (0);
+  if (rc) (void)hipStreamSynchronize(h->stream);
+  dfree(d_users); dfree(d_q); dfree(d_mitems); dfree(d_rank); dfree(d_rsel); dfree(d_rq0); dfree(d_rnq); dfree(d_sitem);
+  dfree(d_sperm); dfree(d_mptr); dfree(d_bits); dfree(d_skey); dfree(d_sc);
+  return rc;
+}
+
 int hpf_get_work_info(hpf_handle *h, hpf_work_info *out)
 {
   if (!h || !out) return HPF_ERR_INVALID;

@@ -2144,6 +2144,255 @@ __global__ __launch_bounds__(256) void loo_rank_kernel(LooArgs a)
   }
 }
 
+// ---------------------------------------------------------------------
+// Every test item of a user in one pass (hpf_rank_queries, -eval-all).
+//   rq_threshold_kernel  s(b, t) of every query of a ROW (one selected user with <= RQ_QCAP of its queries) from the
+//                        MFMA chain of score_tile_kernel, masked like loo_rank_kernel's threshold; the row's
+//                        thresholds sorted best first, with the permutation back to the caller's order
+//   rank_queries_kernel  loo_rank_kernel's sweep; each score finds by binary search how many of its row's sorted
+//                        thresholds come before or equal it and counts into an LDS histogram; prefix sums are the ranks
+// ---------------------------------------------------------------------
+constexpr int RQ_QCAP = 32;           // queries of one row (hgaprec_amd/capi.py mirrors it as RANK_QUERIES_QCAP)
+static_assert(RQ_QCAP <= 64 && RQ_QCAP % 16 == 0, "a row's thresholds are sorted by one wave, 16 per MFMA chain");
+
+struct RqArgs {
+  const uint32_t *users;    // [batch] user rows of this batch of selected users
+  const uint32_t *row_sel;  // [nrows] selected user of the row, relative to the batch
+  const uint32_t *row_q0;   // [nrows] first query of the row (index into q_item and the arrays below)
+  const uint32_t *row_nq;   // [nrows] 1 .. RQ_QCAP
+  const uint32_t *q_item;   // [queries]
+  const double   *Et, *Eb;  // [n x ld], [m x ld]
+  const uint64_t *bits;     // [batch x words] masked items
+  unsigned long long *skey; // [queries] a row's thresholds, best first, at row_q0 + s
+  uint32_t       *sitem;    // [queries] ... their items
+  uint32_t       *sperm;    // [queries] ... and the query each came from
+  uint32_t       *rank;     // [queries] zeroed; counts are added
+  double         *score;    // [queries]
+  uint32_t        nrows, m, ld, K, words;
+  uint32_t        tiles_per_split;   // 64-item tiles per blockIdx.y
+  int32_t         ubias_col, ibias_col;
+};
+
+// One wave per row.  A 16 x 16 tile whose 16 rows are ALL the row's user and whose column j is the item of query
+// 16 c + j: every output row holds the 16 thresholds, no shuffle needed (loo_rank_kernel has one query per user and
+// keeps a diagonal instead; a row's queries are consecutive, so here one chain serves 16 of them).  Same chain per
+// output as score_tile_kernel: k0 = 0, 4, 8, ... with the tail padded by zeros, then + (E_ubias + E_ibias).
+__global__ __launch_bounds__(256) void rq_threshold_kernel(RqArgs a)
+{
+  __shared__ unsigned long long sk[4][RQ_QCAP];
+  __shared__ uint32_t si[4][RQ_QCAP];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int r16 = lane & 15, kq = lane >> 4;
+  const uint32_t row = blockIdx.x * 4 + wv;
+  const bool rok = row < a.nrows;
+  const uint32_t sel = rok ? a.row_sel[row] : 0u, q0 = rok ? a.row_q0[row] : 0u, Q = rok ? a.row_nq[row] : 0u;
+  const uint32_t urow = rok ? a.users[sel] : 0u;
+  const double *pa = a.Et + (size_t)urow * a.ld;
+  for (uint32_t c = 0; 16 * c < Q; ++c) {
+    const uint32_t j = 16 * c + r16;
+    const bool ok = j < Q;
+    const uint32_t it = ok ? a.q_item[q0 + j] : 0u;
+    const double *pq = a.Eb + (size_t)it * a.ld;
+    double4_t acc = (double4_t){0.0, 0.0, 0.0, 0.0};
+    for (uint32_t k0 = 0; k0 < a.K; k0 += 4) {
+      const uint32_t k = k0 + kq;
+      const double av = k < a.K ? pa[k] : 0.0;                   // A[i][k]: the same user in every row i
+      const double bv = (ok && k < a.K) ? pq[k] : 0.0;           // B[k = lane/16][j = lane%16]
+      acc = __builtin_amdgcn_mfma_f64_16x16x4f64(av, bv, acc, 0, 0, 0);
+    }
+    if (kq == 0 && ok) {                                         // register 0 of lane j: D[0][j]
+      double v = acc[0];
+      if (a.ubias_col >= 0) v += pa[a.ubias_col] + pq[a.ibias_col];
+      if ((a.bits[(size_t)sel * a.words + (it >> 6)] >> (it & 63u)) & 1ull) v = 0.0;
+      sk[wv][j] = score_key(v); si[wv][j] = it;
+      a.score[q0 + j] = v;
+    }
+  }
+  __syncthreads();
+  if ((uint32_t)lane < Q) {                                      // rank sort: key descending, item ascending, then query
+    const unsigned long long ke = sk[wv][lane]; const uint32_t ie = si[wv][lane];
+    uint32_t pos = 0;
+    for (uint32_t f = 0; f < Q; ++f) {
+      const unsigned long long kf = sk[wv][f]; const uint32_t jf = si[wv][f];
+      pos += (kf > ke || (kf == ke && (jf < ie || (jf == ie && f < (uint32_t)lane)))) ? 1u : 0u;
+    }
+    a.skey[q0 + pos] = ke; a.sitem[q0 + pos] = ie; a.sperm[q0 + pos] = q0 + (uint32_t)lane;
+  }
+}
+
+constexpr int RQ_CNT_STRIDE = RQ_QCAP + 1;
+
+// Workgroup = 4 waves = 64 rows (16 per wave) x one split of the item range; staging, A fragments and MFMA order are
+// loo_rank_kernel's.  The 64 rows' sorted thresholds and a histogram [row][p] live in LDS.  A score (key, item) adds 1
+// at p = the number of its row's thresholds that come before or equal it; p = Q (it precedes none: one comparison
+// with the row's worst threshold, kept in registers) adds nothing.  "Before or equal" puts a queried item behind its
+// own threshold and behind every duplicate of it.  The rank of the threshold at sorted position s is the sum of the
+// histogram over 0 .. s.
+template <int NCH>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void rank_queries_kernel(RqArgs a)
+{
+  __shared__ double tile[64 * LOO_LDS_STRIDE];
+  __shared__ unsigned long long tk[64 * RQ_QCAP];
+  __shared__ uint32_t ti[64 * RQ_QCAP];
+  __shared__ uint32_t cn[64 * RQ_CNT_STRIDE];
+  __shared__ uint32_t s_nq[64], s_sel[64];                         // per row: its queries (0: no such row), its user of the batch
+  __shared__ double s_ub[64];                                       // ... and E_ubias of that user
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int r16 = lane & 15, kq = lane >> 4;
+  const uint32_t rb0 = blockIdx.x * 64;                          // first row of this workgroup
+  const uint32_t rsel = rb0 + wv * 16 + r16;
+  const bool uok = rsel < a.nrows;
+  const uint32_t urow = uok ? a.users[a.row_sel[rsel]] : 0u;
+  const double *pa = a.Et + (size_t)urow * a.ld;
+  const uint32_t nsteps = (a.K + 3) / 4;                         // MFMAs per output, as in score_tile_kernel
+
+  double areg[NCH > 0 ? NCH * 8 : 1];
+  if (NCH > 0) {
+#pragma unroll
+    for (int s = 0; s < NCH * 8; ++s) {
+      const uint32_t k = 4u * s + kq;
+      areg[s] = (uok && k < a.K) ? pa[k] : 0.0;
+    }
+  }
+  auto a_of = [&](int s) -> double {                             // A[i = lane%16][k = 4 s + lane/16]
+    const uint32_t k = 4u * (uint32_t)s + kq;
+    return (uok && k < a.K) ? pa[k] : 0.0;
+  };
+
+  // ---- the rows' sorted thresholds into LDS, histogram zeroed
+  for (uint32_t e = tid; e < 64u * RQ_QCAP; e += 256) {
+    const uint32_t lr = e / RQ_QCAP, s = e % RQ_QCAP, row = rb0 + lr;
+    unsigned long long k = 0ull; uint32_t it = 0u;
+    if (row < a.nrows && s < a.row_nq[row]) { const uint32_t q = a.row_q0[row] + s; k = a.skey[q]; it = a.sitem[q]; }
+    tk[e] = k; ti[e] = it;
+  }
+  for (uint32_t e = tid; e < 64u * RQ_CNT_STRIDE; e += 256) cn[e] = 0u;
+  if (tid < 64) {
+    const uint32_t row = rb0 + tid;
+    const bool ok = row < a.nrows;
+    const uint32_t sel = ok ? a.row_sel[row] : 0u;
+    s_nq[tid] = ok ? a.row_nq[row] : 0u; s_sel[tid] = sel;
+    s_ub[tid] = (ok && a.ubias_col >= 0) ? a.Et[(size_t)a.users[sel] * a.ld + a.ubias_col] : 0.0;
+  }
+  __syncthreads();
+
+  // ---- item sweep
+  const uint32_t ntiles = (a.m + 63) / 64;
+  const uint32_t t0 = blockIdx.y * a.tiles_per_split, t1 = min(ntiles, t0 + a.tiles_per_split);
+  const uint32_t nchunks = (a.K + LOO_KC - 1) / LOO_KC;
+
+  // this thread's four 16-byte pieces of a 64 x 32 chunk: piece p = tid + 256 j -> row p / 16, columns 2 (p % 16), +1
+  double2 pre[4];
+  auto fetch = [&](uint32_t tile_i, uint32_t chunk) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const uint32_t p = (uint32_t)tid + 256u * j, row = p >> 4, c = chunk * LOO_KC + 2u * (p & 15u);
+      const uint32_t it = tile_i * 64 + row;
+      double2 v = make_double2(0.0, 0.0);
+      if (it < a.m && c < a.K) {                                 // c is even and ld is even: c + 1 < ld
+        v = *(const double2 *)(a.Eb + (size_t)it * a.ld + c);
+        if (c + 1 >= a.K) v.y = 0.0;
+      }
+      pre[j] = v;
+    }
+  };
+  if (t0 < t1) fetch(t0, 0);
+  for (uint32_t tl = t0; tl < t1; ++tl) {
+    double4_t acc[4];
+#pragma unroll
+    for (int t = 0; t < 4; ++t) acc[t] = (double4_t){0.0, 0.0, 0.0, 0.0};
+    auto stage = [&](uint32_t ch) {
+      __syncthreads();                                           // the previous chunk has been read
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const uint32_t p = (uint32_t)tid + 256u * j;
+        *(double2 *)&tile[(p >> 4) * LOO_LDS_STRIDE + 2u * (p & 15u)] = pre[j];
+      }
+      __syncthreads();
+      if (ch + 1 < nchunks) fetch(tl, ch + 1);
+      else if (tl + 1 < t1) fetch(tl + 1, 0);
+    };
+    if (NCH > 0) {
+#pragma unroll
+      for (int ch = 0; ch < NCH; ++ch)
+        if ((uint32_t)ch < nchunks) {
+          stage((uint32_t)ch);
+#pragma unroll
+          for (int s = 0; s < 8; ++s)
+            if ((uint32_t)(ch * 8 + s) < nsteps) {
+#pragma unroll
+              for (int t = 0; t < 4; ++t) {
+                const double bv = tile[(16 * t + r16) * LOO_LDS_STRIDE + 4 * s + kq];   // B[k = lane/16][j = lane%16]
+                acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(areg[ch * 8 + s], bv, acc[t], 0, 0, 0);
+              }
+            }
+        }
+    } else {
+      for (uint32_t ch = 0; ch < nchunks; ++ch) {
+        stage(ch);
+        for (uint32_t s = 0; s < 8 && ch * 8 + s < nsteps; ++s) {
+          const double av = a_of((int)(ch * 8 + s));
+#pragma unroll
+          for (int t = 0; t < 4; ++t) {
+            const double bv = tile[(16 * t + r16) * LOO_LDS_STRIDE + 4 * s + kq];
+            acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(av, bv, acc[t], 0, 0, 0);
+          }
+        }
+      }
+    }
+    // epilogue: register r of tile t holds local row wv 16 + kq + 4 r, item 64 tl + 16 t + r16.  What a row needs is
+    // read from LDS per tile (kept in registers it would cost the second wave per SIMD)
+    const uint32_t i0 = tl * 64;
+    double bi[4];
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      const uint32_t it = i0 + 16 * t + r16;
+      bi[t] = (it < a.m && a.ibias_col >= 0) ? a.Eb[(size_t)it * a.ld + a.ibias_col] : 0.0;
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const uint32_t lr = wv * 16 + kq + 4 * r, Q = s_nq[lr];
+      if (Q) {
+        const unsigned long long w = a.bits[(size_t)s_sel[lr] * a.words + tl];
+        const unsigned long long wk = tk[lr * RQ_QCAP + Q - 1];  // the row's worst threshold
+        const uint32_t wi = ti[lr * RQ_QCAP + Q - 1];
+        const double ub = s_ub[lr];
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+          const uint32_t it = i0 + 16 * t + r16;
+          double v = acc[t][r];
+          if (a.ubias_col >= 0) v += ub + bi[t];                 // s += Eb_u + Eb_i
+          if ((w >> (16 * t + r16)) & 1ull) v = 0.0;
+          const unsigned long long k = score_key(v);
+          if (it < a.m && (k > wk || (k == wk && it < wi))) {    // strictly before the worst threshold
+            uint32_t lo = 0, hi = Q - 1;                         // the first threshold this score is strictly before
+            while (lo < hi) {
+              const uint32_t mid = (lo + hi) >> 1;
+              const unsigned long long kt = tk[lr * RQ_QCAP + mid];
+              bool before = k > kt;
+              if (k == kt) before = it < ti[lr * RQ_QCAP + mid];
+              if (before) hi = mid; else lo = mid + 1;
+            }
+            atomicAdd(&cn[lr * RQ_CNT_STRIDE + lo], 1u);
+          }
+        }
+      }
+    }
+  }
+  __syncthreads();
+  if (tid < 64) {
+    const uint32_t row = rb0 + tid;
+    if (row < a.nrows) {
+      const uint32_t Q = a.row_nq[row], q0 = a.row_q0[row];
+      uint32_t run = 0;
+      for (uint32_t s = 0; s < Q; ++s) {
+        run += cn[tid * RQ_CNT_STRIDE + s];
+        if (run) atomicAdd(&a.rank[a.sperm[q0 + s]], run);
+      }
+    }
+  }
+}
+
 // materialise the per-element rate matrix for export (htheta_rate.tsv):
 // rate[row,k] = prior_used[row] + colsum[k]   (gpbase.hh:163-173,218-223)
 __global__ void build_rate_kernel(const double *prior_used, const double *colsum,

@@ -66,6 +66,9 @@ def lib():
     L.hg_partition_users.argtypes = [C.POINTER(C.c_int64), C.c_uint32, C.c_int, u32p]
     L.hg_partition_users.restype = None
     L.hg_stop_rule.argtypes = [u32p, dp, C.c_uint32, C.POINTER(C.c_int)]
+    u64p = C.POINTER(C.c_uint64)
+    L.hg_eval_from_ranks.argtypes = [u64p, u32p, u32p, C.c_uint64, u64p, dp]
+    L.hg_eval_from_ranks.restype = None
     _lib = L
     return L
 
@@ -263,3 +266,27 @@ def stop_rule(iters, series):
     at = lib().hg_stop_rule(it.ctypes.data_as(C.POINTER(C.c_uint32)), a.ctypes.data_as(C.POINTER(C.c_double)),
                             it.size, why)
     return at, list(why)
+
+
+EVAL_USER_FIELDS = ("ntest", "hits10", "hits100", "best_rank", "sum_rank", "nranked")
+EVAL_MEAN_FIELDS = ("users", "pairs", "precision10", "precision100", "recall100", "mrr", "meanrank")
+
+
+def eval_from_ranks(q_ptr, rank, nranked):
+    """-eval-all's arithmetic (eval_from_ranks, hgaprec_host.hpp): user b's ranks are rank[q_ptr[b]:q_ptr[b + 1]], nranked[b]
+    the items counted as ranked for it -> (per_user: (users, 6) uint64 in the order of EVAL_USER_FIELDS,
+    means: dict over EVAL_MEAN_FIELDS; users and pairs are ints)"""
+    qp = np.ascontiguousarray(q_ptr, np.uint64)
+    rk = np.ascontiguousarray(rank, np.uint32)
+    nr = np.ascontiguousarray(nranked, np.uint32)
+    nu = qp.size - 1
+    if nu < 0 or nr.size != nu or (nu and int(qp[-1]) > rk.size):
+        raise ValueError("q_ptr: len(nranked) + 1 entries, the last one at most len(rank)")
+    per = np.zeros((nu, 6), np.uint64)
+    means = np.zeros(7, np.float64)
+    lib().hg_eval_from_ranks(qp.ctypes.data_as(C.POINTER(C.c_uint64)), rk.ctypes.data_as(C.POINTER(C.c_uint32)),
+                             nr.ctypes.data_as(C.POINTER(C.c_uint32)), nu, per.ctypes.data_as(C.POINTER(C.c_uint64)),
+                             means.ctypes.data_as(C.POINTER(C.c_double)))
+    out = dict(zip(EVAL_MEAN_FIELDS, means.tolist()))
+    out["users"], out["pairs"] = int(out["users"]), int(out["pairs"])
+    return per, out

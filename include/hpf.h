@@ -351,6 +351,23 @@ int  hpf_loo_ranks(hpf_handle *h, const uint32_t *users, uint32_t n_sel,
                    const uint64_t *mask_ptr, const uint32_t *mask_items,
                    const uint32_t *q_item, uint32_t item_limit,
                    uint32_t *out_rank, double *out_score, uint32_t *out_masked);
+/* replaces: the position j of EVERY test item of a user in the fully sorted list of
+ * HGAPRec::compute_itemrank (hgaprec.cc:1628-1680), for any number of users, without a score
+ * matrix.  Queries are a CSR over the selected users: selected user b asks for items
+ * q_items[q_ptr[b] .. q_ptr[b+1]).  out_rank[q] / out_score[q] (q indexes q_items) equal, bit for
+ * bit, what hpf_item_ranks returns for the same users, masks and the expanded (q_sel, q_item)
+ * list.  A user may have no query; an item may be asked for twice.  The queried item itself is
+ * not counted, the user's other queried items are.  The user's row of scores is computed ONCE
+ * (hpf_loo_ranks with one entry per pair computes it once per pair); internally a user's queries
+ * go through in rows of at most 32 (RQ_QCAP in hpf_kernels.hpp).  q_ptr[0] != 0, a decreasing
+ * q_ptr, an item >= n_items or a user out of range is HPF_ERR_INVALID before anything is
+ * launched; n_sel = 0 or no query is HPF_OK.  At most 2^32 - 1 queries per call.  Device memory
+ * beyond inputs and outputs: the bit rows of a batch of users (<= 256 MB, HPF_LOO_BATCH as for
+ * hpf_loo_ranks) and 16 bytes per query + 12 per row. */
+int  hpf_rank_queries(hpf_handle *h, const uint32_t *users, uint32_t n_sel,
+                      const uint64_t *mask_ptr, const uint32_t *mask_items,
+                      const uint64_t *q_ptr, const uint32_t *q_items,
+                      uint32_t *out_rank, double *out_score);
 
 /* how the uploaded matrix was cut into work (diagnostics, tests, bench):
  * a "segment" is <= 512 consecutive nonzeros of one row; rows longer than that
