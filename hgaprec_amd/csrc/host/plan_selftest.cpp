@@ -132,6 +132,49 @@ int main()
           CHECK(same_plan(p, want), "sweep_cfg C=%u ws=%u %d,%d", C, ws, g, r);
         }
     }
+  // ---- the fused rank kernels (hpf_loo_ranks, hpf_rank_queries): users per batch, launch grid, chunks in registers
+  CHECK(rank_batch_users(100000, 1000000, 0) == 21440, "batch at m = 10^5: %u", rank_batch_users(100000, 1000000, 0));
+  {                                          // HPF_LOO_BATCH=16 as the batch-boundary tests set it: 37 users go as 16, 16, 5
+    const uint32_t b = rank_batch_users(70, 37, 16);
+    CHECK(b == 16 && 37 - 2 * b == 5, "batch of 37 users under the knob 16: %u", b);
+    CHECK(rank_batch_users(70, 37, 17) == 32 && rank_batch_users(70, 37, 1) == 16, "the knob is rounded up to 16 users");
+  }
+  for (long long knob : {0ll, -1ll, -16ll, (long long)INT64_MIN})
+    CHECK(rank_batch_users(100000, 1000000, knob) == 21440 && rank_batch_users(70, 37, knob) == 48, "knob %lld is ignored", knob);
+  CHECK(rank_batch_users(1, UINT32_MAX, 0) >= 64 && rank_batch_users(1, UINT32_MAX, 0) % 64 == 0, "m = 1: %u", rank_batch_users(1, UINT32_MAX, 0));
+  CHECK(rank_batch_users(UINT32_MAX, UINT32_MAX, 0) == 64, "the widest bit rows: a workgroup's 64 users, %u", rank_batch_users(UINT32_MAX, UINT32_MAX, 0));
+  CHECK(rank_batch_users(1, 5, 0) == 16 && rank_batch_users(1, 16, 0) == 16 && rank_batch_users(1, 17, 0) == 32, "n_sel rounded up to 16");
+  {
+    const struct { uint32_t rows, ntiles, blocks, tps, splits; } pins[] = {
+      {150, 391, 3, 2, 196},                 // test_a_workgroup_sweeps_several_tiles
+      {70000, 2, 1094, 2, 1},                // test_more_than_1024_blocks_of_rows_and_one_split
+      {1, 1, 1, 1, 1}};
+    for (const auto &p : pins) {
+      const RankGrid g = rank_grid(p.rows, p.ntiles);
+      CHECK(g.blocks == p.blocks && g.tiles_per_split == p.tps && g.splits == p.splits, "grid of %u rows x %u tiles: %u blocks, %u tiles per split, %u splits",
+            p.rows, p.ntiles, g.blocks, g.tiles_per_split, g.splits);
+    }
+    for (uint32_t rows = 1; rows <= 4200; rows += (rows < 200 ? 1 : 97))
+      for (uint32_t ntiles = 1; ntiles <= 3000; ntiles += (ntiles < 70 ? 1 : 53)) {
+        const RankGrid g = rank_grid(rows, ntiles);
+        CHECK(g.blocks == (rows + 63) / 64 && g.splits >= 1 && g.tiles_per_split >= 1, "grid %u x %u", rows, ntiles);
+        CHECK((uint64_t)g.splits * g.tiles_per_split >= ntiles, "grid %u x %u: tiles left out", rows, ntiles);            // every tile swept
+        CHECK((uint64_t)(g.splits - 1) * g.tiles_per_split < ntiles, "grid %u x %u: an empty split", rows, ntiles);       // no workgroup without one
+      }
+  }
+  {
+    const uint32_t Ks[] = {1, 32, 33, 64, 65, 128, 129, HPF_MAX_COLUMNS};
+    const int want[] = {1, 1, 2, 2, 4, 4, 0, 0};
+    for (int i = 0; i < 8; ++i) CHECK(rank_chunks(Ks[i]) == want[i], "K=%u: %d chunks", Ks[i], rank_chunks(Ks[i]));
+    bool returned[8] = {false, false, false, false, false, false, false, false};
+    for (uint32_t K = 1; K <= HPF_MAX_COLUMNS; ++K) {
+      const int nch = rank_chunks(K);
+      CHECK(nch >= 0 && nch < 8 && has_rank_chunks(nch), "K=%u: no instance for %d chunks", K, nch);
+      CHECK(nch == 0 || 32u * (uint32_t)nch >= K, "K=%u does not fit %d chunks of 32 columns", K, nch);
+      if (nch >= 0 && nch < 8) returned[nch] = true;
+    }
+    for (int nch = -1; nch <= 8; ++nch) CHECK(has_rank_chunks(nch) == (nch >= 0 && nch < 8 && returned[nch]), "has_rank_chunks(%d)", nch);
+  }
   if (g_fail) { fprintf(stderr, "plan_selftest: %d checks failed\n", g_fail); return 1; }
   printf("# plan_selftest ok: %u points, %u runs\n", points, runs);
   return 0;

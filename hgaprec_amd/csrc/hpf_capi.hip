@@ -349,6 +349,15 @@ bool launch_sweep(int mode, int G, int R, const SweepArgs &a, uint32_t blocks, h
       return false;
     }); }); });
 }
+// the fused rank kernels, by the chunks of A a column count keeps in registers (hpf_plan::rank_chunks); launch(nch) names
+// the kernel template: loo_rank_kernel<nch> or rank_queries_kernel<nch>
+template <typename F>
+bool launch_rank(uint32_t K, F &&launch)
+{
+  return pick(hpf_plan::rank_chunks(K), std::integer_sequence<int, 0, 1, 2, 4>(), [&](auto nch) {
+    if constexpr (hpf_plan::has_rank_chunks(PICKED(nch))) { launch(nch); return true; } else return false;
+  });
+}
 #undef PICKED
 
 int recover_flush(hpf_handle *h, uint32_t fl0, uint32_t begun);
@@ -530,6 +539,47 @@ int d2h(hpf_handle *h, void *dst, const void *src, size_t bytes)
   }
   return HPF_OK;
 }
+
+// Device side of a fused call (hpf_loo_ranks, hpf_rank_queries): the selected users, the mask list, the bit rows of one
+// batch of users (hpf_plan::rank_batch_users) and whatever else the call gets through alloc() -- all freed on the way
+// out, once the stream is idle (after an error something launched may still read them)
+struct FusedCtx {
+  hpf_handle *h;
+  std::vector<void *> owned;
+  uint32_t *d_users = nullptr, *d_mitems = nullptr; uint64_t *d_mptr = nullptr, *d_bits = nullptr;
+  uint32_t words = 0, batch = 0;       // 64-bit words of a bit row; users per batch
+  explicit FusedCtx(hpf_handle *h_) : h(h_) {}
+  FusedCtx(const FusedCtx &) = delete;
+  ~FusedCtx() { (void)hipStreamSynchronize(h->stream); for (void *p : owned) dfree(p); }
+
+  // n zeroed elements, or a copy of src[0 .. n)
+  template <typename T>
+  int alloc(T **p, size_t n, const T *src = nullptr)
+  {
+    const int rc = dalloc(h, p, n);
+    if (*p) owned.push_back(*p);                                 // also when only dalloc's memset failed
+    return rc || !src ? rc : h2d(h, *p, src, n * sizeof(T));
+  }
+  int upload(const uint32_t *users, uint32_t n_sel, const uint64_t *mask_ptr, const uint32_t *mask_items)
+  {
+    words = (h->it.rows + 63) / 64;
+    batch = hpf_plan::rank_batch_users(h->it.rows, n_sel, h->loo_batch);
+    int rc;
+    if ((rc = alloc(&d_users, n_sel, users)) || (rc = alloc(&d_bits, (size_t)batch * words))) return rc;
+    if (!mask_ptr) return HPF_OK;
+    if ((rc = alloc(&d_mptr, (size_t)n_sel + 1, mask_ptr))) return rc;
+    return alloc(&d_mitems, (size_t)mask_ptr[n_sel], mask_ptr[n_sel] ? mask_items : nullptr);
+  }
+  // the bit rows of the selected users [b0, b0 + rows): cleared (alloc left them zero for the first batch) and set
+  int mask_batch(uint32_t b0, uint32_t rows)
+  {
+    if (b0) HIPCHK(h, hipMemsetAsync(d_bits, 0, (size_t)rows * words * 8, h->stream));
+    hipLaunchKernelGGL(loo_mask_kernel, dim3(std::min<uint32_t>((rows + 3) / 4, 4096)), dim3(256), 0, h->stream,
+                       d_users + b0, rows, h->rowptr_dev, h->u.idx, h->u.val, d_mptr ? d_mptr + b0 : nullptr, d_mitems,
+                       (uint32_t *)d_bits, words);
+    return HPF_OK;
+  }
+};
 
 uint32_t grid_for(uint64_t n) { return (uint32_t)std::min<uint64_t>(std::max<uint64_t>((n + 255) / 256, 1), 16384); }
 
@@ -2479,22 +2529,30 @@ struct RankCtx {
   ~RankCtx() { dfree(d_users); dfree(d_mptr); dfree(d_mitems); dfree(d_scores); }
 };
 
-int rank_prepare(hpf_handle *h, const uint32_t *users, uint32_t n_sel, const uint64_t *mask_ptr,
-                 const uint32_t *mask_items, RankCtx &c)
+// what every ranking call asks of the handle, of the selected users and of the mask list
+int rank_check(hpf_handle *h, const uint32_t *users, uint32_t n_sel, const uint64_t *mask_ptr, const uint32_t *mask_items)
 {
   if (h->iterations == 0 && !(h->u.have_E && h->it.have_E)) { h->err = "E state not set"; return HPF_ERR_STATE; }
   if (!h->have_csr) { h->err = "hpf_upload_csr has not been called"; return HPF_ERR_STATE; }
-  const uint32_t m = h->it.rows;
   for (uint32_t b = 0; b < n_sel; ++b)
     if (users[b] >= h->u.rows) { h->err = "user index out of range"; return HPF_ERR_INVALID; }
-  const uint64_t nmask = mask_ptr ? mask_ptr[n_sel] : 0;
   if (mask_ptr) {
+    const uint64_t nmask = mask_ptr[n_sel];
     if (mask_ptr[0] != 0) { h->err = "mask_ptr[0] must be 0"; return HPF_ERR_INVALID; }
     for (uint32_t b = 0; b < n_sel; ++b) if (mask_ptr[b + 1] < mask_ptr[b]) { h->err = "mask_ptr not monotone"; return HPF_ERR_INVALID; }
     if (nmask && !mask_items) return HPF_ERR_INVALID;
-    for (uint64_t j = 0; j < nmask; ++j) if (mask_items[j] >= m) { h->err = "mask item out of range"; return HPF_ERR_INVALID; }
+    for (uint64_t j = 0; j < nmask; ++j) if (mask_items[j] >= h->it.rows) { h->err = "mask item out of range"; return HPF_ERR_INVALID; }
   }
+  return HPF_OK;
+}
+
+int rank_prepare(hpf_handle *h, const uint32_t *users, uint32_t n_sel, const uint64_t *mask_ptr,
+                 const uint32_t *mask_items, RankCtx &c)
+{
   int rc;
+  if ((rc = rank_check(h, users, n_sel, mask_ptr, mask_items))) return rc;
+  const uint32_t m = h->it.rows;
+  const uint64_t nmask = mask_ptr ? mask_ptr[n_sel] : 0;
   if ((rc = refresh_es(h, h->u)) || (rc = refresh_es(h, h->it))) return rc;
   c.n_sel = n_sel;
   // rows of scores kept at once: <= 1 GiB, a multiple of 16
@@ -2644,79 +2702,43 @@ int hpf_loo_ranks(hpf_handle *h, const uint32_t *users, uint32_t n_sel, const ui
 {
   if (!h || (n_sel && (!users || !q_item || !out_rank || !out_score))) return HPF_ERR_INVALID;
   if (!n_sel) return HPF_OK;
-  if (h->iterations == 0 && !(h->u.have_E && h->it.have_E)) { h->err = "E state not set"; return HPF_ERR_STATE; }
-  if (!h->have_csr) { h->err = "hpf_upload_csr has not been called"; return HPF_ERR_STATE; }
   const uint32_t m = h->it.rows;
   if (item_limit > m) { h->err = "item_limit beyond n_items"; return HPF_ERR_INVALID; }
   const uint32_t limit = item_limit ? item_limit : m;
   if (h->ld & 1u) { h->err = "hpf_loo_ranks: odd row stride"; return HPF_ERR_UNSUPPORTED; }
-  for (uint32_t b = 0; b < n_sel; ++b) {
-    if (users[b] >= h->u.rows) { h->err = "user index out of range"; return HPF_ERR_INVALID; }
-    if (q_item[b] >= m) { h->err = "query item out of range"; return HPF_ERR_INVALID; }
-  }
-  const uint64_t nmask = mask_ptr ? mask_ptr[n_sel] : 0;
-  if (mask_ptr) {
-    if (mask_ptr[0] != 0) { h->err = "mask_ptr[0] must be 0"; return HPF_ERR_INVALID; }
-    for (uint32_t b = 0; b < n_sel; ++b) if (mask_ptr[b + 1] < mask_ptr[b]) { h->err = "mask_ptr not monotone"; return HPF_ERR_INVALID; }
-    if (nmask && !mask_items) return HPF_ERR_INVALID;
-    for (uint64_t j = 0; j < nmask; ++j) if (mask_items[j] >= m) { h->err = "mask item out of range"; return HPF_ERR_INVALID; }
-  }
   int rc;
+  if ((rc = rank_check(h, users, n_sel, mask_ptr, mask_items))) return rc;
+  for (uint32_t b = 0; b < n_sel; ++b)
+    if (q_item[b] >= m) { h->err = "query item out of range"; return HPF_ERR_INVALID; }
   if ((rc = check_flags(h))) return rc;
   if ((rc = refresh_es(h, h->u)) || (rc = refresh_es(h, h->it))) return rc;
 
-  // users per batch: the bit rows of a batch stay under 256 MB; a multiple of the 64 users of a workgroup.
-  // HPF_LOO_BATCH (users, rounded up to the 16 users of a wave's block; a TEST knob, so that a handful of users
-  // crosses a batch boundary) makes it smaller.
-  const uint32_t words = (m + 63) / 64;
-  uint64_t batch = std::max<uint64_t>(64, (((uint64_t)256 << 20) / ((uint64_t)words * 8)) & ~63ull);
-  if (const char *e = getenv("HPF_LOO_BATCH")) { const long v = atol(e); if (v > 0) batch = std::min<uint64_t>(batch, ((uint64_t)v + 15) & ~15ull); }
-  batch = std::min<uint64_t>(batch, ((uint64_t)n_sel + 15) & ~15ull);
-
-  uint32_t *d_users = nullptr, *d_q = nullptr, *d_mitems = nullptr, *d_rank = nullptr, *d_masked = nullptr;
-  uint64_t *d_mptr = nullptr, *d_bits = nullptr; double *d_sc = nullptr;
-  do {
-    if ((rc = dalloc(h, &d_users, n_sel)) || (rc = dalloc(h, &d_q, n_sel)) || (rc = dalloc(h, &d_rank, n_sel)) ||
-        (rc = dalloc(h, &d_masked, n_sel)) || (rc = dalloc(h, &d_sc, n_sel)) || (rc = dalloc(h, &d_bits, (size_t)batch * words))) break;
-    if ((rc = h2d(h, d_users, users, (size_t)n_sel * 4)) || (rc = h2d(h, d_q, q_item, (size_t)n_sel * 4))) break;
-    if (mask_ptr) {
-      if ((rc = dalloc(h, &d_mptr, (size_t)n_sel + 1)) || (rc = dalloc(h, &d_mitems, (size_t)nmask))) break;
-      if ((rc = h2d(h, d_mptr, mask_ptr, ((size_t)n_sel + 1) * 8))) break;
-      if (nmask && (rc = h2d(h, d_mitems, mask_items, (size_t)nmask * 4))) break;
-    }
-    const uint32_t ntiles = (limit + 63) / 64;
-    for (uint32_t b0 = 0; b0 < n_sel && !rc; b0 += (uint32_t)batch) {
-      const uint32_t b1 = (uint32_t)std::min<uint64_t>(n_sel, (uint64_t)b0 + batch), rows = b1 - b0;
-      if (b0) { hipError_t e = hipMemsetAsync(d_bits, 0, (size_t)rows * words * 8, h->stream); if (e != hipSuccess) { h->err = hipGetErrorString(e); rc = HPF_ERR_HIP; break; } }
-      hipLaunchKernelGGL(loo_mask_kernel, dim3(std::min<uint32_t>((rows + 3) / 4, 4096)), dim3(256), 0, h->stream,
-                         d_users + b0, rows, h->rowptr_dev, h->u.idx, h->u.val, d_mptr ? d_mptr + b0 : nullptr, d_mitems,
-                         (uint32_t *)d_bits, words);
-      LooArgs a;
-      a.users = d_users + b0; a.q_item = d_q + b0; a.Et = h->u.E; a.Eb = h->it.E; a.bits = d_bits;
-      a.rank = d_rank + b0; a.masked = d_masked + b0; a.score = d_sc + b0;
-      a.n_sel = rows; a.limit = limit; a.ld = h->ld; a.K = h->K; a.words = words;
-      a.ubias_col = h->cfg.bias ? h->u.bias_col : -1; a.ibias_col = h->cfg.bias ? h->it.bias_col : -1;
-      // few user blocks: the item range is cut so that some 1024 workgroups exist; many: one sweep per block
-      const uint32_t blocks = (rows + 63) / 64;
-      uint32_t splits = std::max<uint32_t>(1, std::min<uint32_t>(ntiles, (1024 + blocks - 1) / blocks));
-      a.tiles_per_split = (ntiles + splits - 1) / splits;
-      splits = (ntiles + a.tiles_per_split - 1) / a.tiles_per_split;
-      if (h->K <= 32) hipLaunchKernelGGL(loo_rank_kernel<1>, dim3(blocks, splits), dim3(256), 0, h->stream, a);
-      else if (h->K <= 64) hipLaunchKernelGGL(loo_rank_kernel<2>, dim3(blocks, splits), dim3(256), 0, h->stream, a);
-      else if (h->K <= 128) hipLaunchKernelGGL(loo_rank_kernel<4>, dim3(blocks, splits), dim3(256), 0, h->stream, a);
-      else hipLaunchKernelGGL(loo_rank_kernel<0>, dim3(blocks, splits), dim3(256), 0, h->stream, a);
-      rc = check_launch(h, "loo_rank_kernel");
-    }
-    if (rc) break;
-    hipError_t e = hipMemcpyAsync(out_rank, d_rank, (size_t)n_sel * 4, hipMemcpyDeviceToHost, h->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(out_score, d_sc, (size_t)n_sel * 8, hipMemcpyDeviceToHost, h->stream);
-    if (e == hipSuccess && out_masked) e = hipMemcpyAsync(out_masked, d_masked, (size_t)n_sel * 4, hipMemcpyDeviceToHost, h->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    if (e != hipSuccess) { h->err = hipGetErrorString(e); rc = HPF_ERR_HIP; }
-  } while (0);
-  if (rc) (void)hipStreamSynchronize(h->stream);
-  dfree(d_users); dfree(d_q); dfree(d_mitems); dfree(d_rank); dfree(d_masked); dfree(d_mptr); dfree(d_bits); dfree(d_sc);
-  return rc;
+  FusedCtx c(h);
+  uint32_t *d_q = nullptr, *d_rank = nullptr, *d_masked = nullptr; double *d_sc = nullptr;
+  if ((rc = c.upload(users, n_sel, mask_ptr, mask_items)) || (rc = c.alloc(&d_q, n_sel, q_item)) || (rc = c.alloc(&d_rank, n_sel)) ||
+      (rc = c.alloc(&d_masked, n_sel)) || (rc = c.alloc(&d_sc, n_sel))) return rc;
+  for (uint32_t b0 = 0; b0 < n_sel; b0 += c.batch) {
+    const uint32_t rows = std::min(n_sel - b0, c.batch);
+    if ((rc = c.mask_batch(b0, rows))) return rc;
+    LooArgs a;
+    a.users = c.d_users + b0; a.q_item = d_q + b0; a.Et = h->u.E; a.Eb = h->it.E; a.bits = c.d_bits;
+    a.rank = d_rank + b0; a.masked = d_masked + b0; a.score = d_sc + b0;
+    a.n_sel = rows; a.limit = limit; a.ld = h->ld; a.K = h->K; a.words = c.words;
+    a.ubias_col = h->cfg.bias ? h->u.bias_col : -1; a.ibias_col = h->cfg.bias ? h->it.bias_col : -1;
+    const hpf_plan::RankGrid g = hpf_plan::rank_grid(rows, (limit + 63) / 64);
+    a.tiles_per_split = g.tiles_per_split;
+    const bool launched = launch_rank(h->K, [&](auto nch) {
+      hipLaunchKernelGGL(loo_rank_kernel<decltype(nch)::value>, dim3(g.blocks, g.splits), dim3(256), 0, h->stream, a);
+    });
+    if (!launched) { h->err = "loo_rank_kernel: no instance for this column count"; return HPF_ERR_UNSUPPORTED; }
+    if ((rc = check_launch(h, "loo_rank_kernel"))) return rc;
+  }
+  hipError_t e = hipMemcpyAsync(out_rank, d_rank, (size_t)n_sel * 4, hipMemcpyDeviceToHost, h->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(out_score, d_sc, (size_t)n_sel * 8, hipMemcpyDeviceToHost, h->stream);
+  if (e == hipSuccess && out_masked) e = hipMemcpyAsync(out_masked, d_masked, (size_t)n_sel * 4, hipMemcpyDeviceToHost, h->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+  if (e != hipSuccess) { h->err = hipGetErrorString(e); return HPF_ERR_HIP; }
+  return HPF_OK;
 }
 
 int hpf_rank_queries(hpf_handle *h, const uint32_t *users, uint32_t n_sel, const uint64_t *mask_ptr,
@@ -2725,104 +2747,66 @@ int hpf_rank_queries(hpf_handle *h, const uint32_t *users, uint32_t n_sel, const
 {
   if (!h || (n_sel && (!users || !q_ptr))) return HPF_ERR_INVALID;
   if (!n_sel) return HPF_OK;
-  if (h->iterations == 0 && !(h->u.have_E && h->it.have_E)) { h->err = "E state not set"; return HPF_ERR_STATE; }
-  if (!h->have_csr) { h->err = "hpf_upload_csr has not been called"; return HPF_ERR_STATE; }
   const uint32_t m = h->it.rows;
   if (h->ld & 1u) { h->err = "hpf_rank_queries: odd row stride"; return HPF_ERR_UNSUPPORTED; }
   if (q_ptr[0] != 0) { h->err = "q_ptr[0] must be 0"; return HPF_ERR_INVALID; }
-  for (uint32_t b = 0; b < n_sel; ++b) {
-    if (users[b] >= h->u.rows) { h->err = "user index out of range"; return HPF_ERR_INVALID; }
+  for (uint32_t b = 0; b < n_sel; ++b)
     if (q_ptr[b + 1] < q_ptr[b]) { h->err = "q_ptr not monotone"; return HPF_ERR_INVALID; }
-  }
   const uint64_t nq = q_ptr[n_sel];
   if (nq > 0xffffffffull) { h->err = "hpf_rank_queries: more than 2^32 - 1 queries in one call"; return HPF_ERR_INVALID; }
   if (nq && (!q_items || !out_rank || !out_score)) return HPF_ERR_INVALID;
-  for (uint64_t q = 0; q < nq; ++q) if (q_items[q] >= m) { h->err = "query item out of range"; return HPF_ERR_INVALID; }
-  const uint64_t nmask = mask_ptr ? mask_ptr[n_sel] : 0;
-  if (mask_ptr) {
-    if (mask_ptr[0] != 0) { h->err = "mask_ptr[0] must be 0"; return HPF_ERR_INVALID; }
-    for (uint32_t b = 0; b < n_sel; ++b) if (mask_ptr[b + 1] < mask_ptr[b]) { h->err = "mask_ptr not monotone"; return HPF_ERR_INVALID; }
-    if (nmask && !mask_items) return HPF_ERR_INVALID;
-    for (uint64_t j = 0; j < nmask; ++j) if (mask_items[j] >= m) { h->err = "mask item out of range"; return HPF_ERR_INVALID; }
-  }
-  if (!nq) return HPF_OK;
   int rc;
+  if ((rc = rank_check(h, users, n_sel, mask_ptr, mask_items))) return rc;
+  for (uint64_t q = 0; q < nq; ++q) if (q_items[q] >= m) { h->err = "query item out of range"; return HPF_ERR_INVALID; }
+  if (!nq) return HPF_OK;
   if ((rc = check_flags(h))) return rc;
   if ((rc = refresh_es(h, h->u)) || (rc = refresh_es(h, h->it))) return rc;
 
-  // users per batch as in hpf_loo_ranks (bit rows under 256 MB, HPF_LOO_BATCH)
-  const uint32_t words = (m + 63) / 64;
-  uint64_t batch = std::max<uint64_t>(64, (((uint64_t)256 << 20) / ((uint64_t)words * 8)) & ~63ull);
-  if (const char *e = getenv("HPF_LOO_BATCH")) { const long v = atol(e); if (v > 0) batch = std::min<uint64_t>(batch, ((uint64_t)v + 15) & ~15ull); }
-  batch = std::min<uint64_t>(batch, ((uint64_t)n_sel + 15) & ~15ull);
-
+  FusedCtx c(h);
+  if ((rc = c.upload(users, n_sel, mask_ptr, mask_items))) return rc;
   // rows: a selected user with at most RQ_QCAP of its queries (a query's rank does not depend on the user's other
   // queries, so cutting a user is exact); in the order of the selected users, so a batch owns a run of them
   std::vector<uint32_t> row_sel, row_q0, row_nq, first_row;   // first_row[batch index] -> its first row
   for (uint32_t b = 0; b < n_sel; ++b) {
-    if (b % batch == 0) first_row.push_back((uint32_t)row_sel.size());
+    if (b % c.batch == 0) first_row.push_back((uint32_t)row_sel.size());
     for (uint64_t q = q_ptr[b]; q < q_ptr[b + 1]; q += RQ_QCAP) {
-      row_sel.push_back((uint32_t)(b % batch)); row_q0.push_back((uint32_t)q);
+      row_sel.push_back(b % c.batch); row_q0.push_back((uint32_t)q);
       row_nq.push_back((uint32_t)std::min<uint64_t>(RQ_QCAP, q_ptr[b + 1] - q));
     }
   }
   first_row.push_back((uint32_t)row_sel.size());
   const size_t nrows = row_sel.size();
-
-  uint32_t *d_users = nullptr, *d_q = nullptr, *d_mitems = nullptr, *d_rank = nullptr, *d_rsel = nullptr, *d_rq0 = nullptr,
-           *d_rnq = nullptr, *d_sitem = nullptr, *d_sperm = nullptr;
-  uint64_t *d_mptr = nullptr, *d_bits = nullptr, *d_skey = nullptr; double *d_sc = nullptr;
-  do {
-    if ((rc = dalloc(h, &d_users, n_sel)) || (rc = dalloc(h, &d_q, (size_t)nq)) || (rc = dalloc(h, &d_rank, (size_t)nq)) ||
-        (rc = dalloc(h, &d_sc, (size_t)nq)) || (rc = dalloc(h, &d_skey, (size_t)nq)) || (rc = dalloc(h, &d_sitem, (size_t)nq)) ||
-        (rc = dalloc(h, &d_sperm, (size_t)nq)) || (rc = dalloc(h, &d_rsel, nrows)) || (rc = dalloc(h, &d_rq0, nrows)) ||
-        (rc = dalloc(h, &d_rnq, nrows)) || (rc = dalloc(h, &d_bits, (size_t)batch * words))) break;
-    if ((rc = h2d(h, d_users, users, (size_t)n_sel * 4)) || (rc = h2d(h, d_q, q_items, (size_t)nq * 4)) ||
-        (rc = h2d(h, d_rsel, row_sel.data(), nrows * 4)) || (rc = h2d(h, d_rq0, row_q0.data(), nrows * 4)) ||
-        (rc = h2d(h, d_rnq, row_nq.data(), nrows * 4))) break;
-    if (mask_ptr) {
-      if ((rc = dalloc(h, &d_mptr, (size_t)n_sel + 1)) || (rc = dalloc(h, &d_mitems, (size_t)nmask))) break;
-      if ((rc = h2d(h, d_mptr, mask_ptr, ((size_t)n_sel + 1) * 8))) break;
-      if (nmask && (rc = h2d(h, d_mitems, mask_items, (size_t)nmask * 4))) break;
-    }
-    const uint32_t ntiles = (m + 63) / 64;
-    size_t bi = 0;
-    for (uint32_t b0 = 0; b0 < n_sel && !rc; b0 += (uint32_t)batch, ++bi) {
-      const uint32_t b1 = (uint32_t)std::min<uint64_t>(n_sel, (uint64_t)b0 + batch), urows = b1 - b0;
-      const uint32_t r0 = first_row[bi], rows = first_row[bi + 1] - r0;
-      if (!rows) continue;
-      if (b0) { hipError_t e = hipMemsetAsync(d_bits, 0, (size_t)urows * words * 8, h->stream); if (e != hipSuccess) { h->err = hipGetErrorString(e); rc = HPF_ERR_HIP; break; } }   // (dalloc zeroes)
-      hipLaunchKernelGGL(loo_mask_kernel, dim3(std::min<uint32_t>((urows + 3) / 4, 4096)), dim3(256), 0, h->stream,
-                         d_users + b0, urows, h->rowptr_dev, h->u.idx, h->u.val, d_mptr ? d_mptr + b0 : nullptr, d_mitems,
-                         (uint32_t *)d_bits, words);
-      RqArgs a;
-      a.users = d_users + b0; a.row_sel = d_rsel + r0; a.row_q0 = d_rq0 + r0; a.row_nq = d_rnq + r0; a.q_item = d_q;
-      a.Et = h->u.E; a.Eb = h->it.E; a.bits = d_bits; a.skey = (unsigned long long *)d_skey; a.sitem = d_sitem;
-      a.sperm = d_sperm; a.rank = d_rank; a.score = d_sc;
-      a.nrows = rows; a.m = m; a.ld = h->ld; a.K = h->K; a.words = words;
-      a.ubias_col = h->cfg.bias ? h->u.bias_col : -1; a.ibias_col = h->cfg.bias ? h->it.bias_col : -1;
-      // hpf_loo_ranks' policy, over rows: few blocks of rows: the item range is cut so that some 1024 workgroups exist
-      const uint32_t blocks = (rows + 63) / 64;
-      uint32_t splits = std::max<uint32_t>(1, std::min<uint32_t>(ntiles, (1024 + blocks - 1) / blocks));
-      a.tiles_per_split = (ntiles + splits - 1) / splits;
-      splits = (ntiles + a.tiles_per_split - 1) / a.tiles_per_split;
-      hipLaunchKernelGGL(rq_threshold_kernel, dim3((rows + 3) / 4), dim3(256), 0, h->stream, a);
-      if (h->K <= 32) hipLaunchKernelGGL(rank_queries_kernel<1>, dim3(blocks, splits), dim3(256), 0, h->stream, a);
-      else if (h->K <= 64) hipLaunchKernelGGL(rank_queries_kernel<2>, dim3(blocks, splits), dim3(256), 0, h->stream, a);
-      else if (h->K <= 128) hipLaunchKernelGGL(rank_queries_kernel<4>, dim3(blocks, splits), dim3(256), 0, h->stream, a);
-      else hipLaunchKernelGGL(rank_queries_kernel<0>, dim3(blocks, splits), dim3(256), 0, h->stream, a);
-      rc = check_launch(h, "rank_queries_kernel");
-    }
-    if (rc) break;
-    hipError_t e = hipMemcpyAsync(out_rank, d_rank, (size_t)nq * 4, hipMemcpyDeviceToHost, h->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(out_score, d_sc, (size_t)nq * 8, hipMemcpyDeviceToHost, h->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    if (e != hipSuccess) { h->err = hipGetErrorString(e); rc = HPF_ERR_HIP; }
-  } while (0);
-  if (rc) (void)hipStreamSynchronize(h->stream);
-  dfree(d_users); dfree(d_q); dfree(d_mitems); dfree(d_rank); dfree(d_rsel); dfree(d_rq0); dfree(d_rnq); dfree(d_sitem);
-  dfree(d_sperm); dfree(d_mptr); dfree(d_bits); dfree(d_skey); dfree(d_sc);
-  return rc;
+  uint32_t *d_q = nullptr, *d_rank = nullptr, *d_rsel = nullptr, *d_rq0 = nullptr, *d_rnq = nullptr, *d_sitem = nullptr, *d_sperm = nullptr;
+  unsigned long long *d_skey = nullptr; double *d_sc = nullptr;
+  if ((rc = c.alloc(&d_q, (size_t)nq, q_items)) || (rc = c.alloc(&d_rank, (size_t)nq)) || (rc = c.alloc(&d_sc, (size_t)nq)) ||
+      (rc = c.alloc(&d_skey, (size_t)nq)) || (rc = c.alloc(&d_sitem, (size_t)nq)) || (rc = c.alloc(&d_sperm, (size_t)nq)) ||
+      (rc = c.alloc(&d_rsel, nrows, row_sel.data())) || (rc = c.alloc(&d_rq0, nrows, row_q0.data())) ||
+      (rc = c.alloc(&d_rnq, nrows, row_nq.data()))) return rc;
+  size_t bi = 0;
+  for (uint32_t b0 = 0; b0 < n_sel; b0 += c.batch, ++bi) {
+    const uint32_t r0 = first_row[bi], rows = first_row[bi + 1] - r0;
+    if (!rows) continue;
+    if ((rc = c.mask_batch(b0, std::min(n_sel - b0, c.batch)))) return rc;
+    RqArgs a;
+    a.users = c.d_users + b0; a.row_sel = d_rsel + r0; a.row_q0 = d_rq0 + r0; a.row_nq = d_rnq + r0; a.q_item = d_q;
+    a.Et = h->u.E; a.Eb = h->it.E; a.bits = c.d_bits; a.skey = d_skey; a.sitem = d_sitem;
+    a.sperm = d_sperm; a.rank = d_rank; a.score = d_sc;
+    a.nrows = rows; a.m = m; a.ld = h->ld; a.K = h->K; a.words = c.words;
+    a.ubias_col = h->cfg.bias ? h->u.bias_col : -1; a.ibias_col = h->cfg.bias ? h->it.bias_col : -1;
+    const hpf_plan::RankGrid g = hpf_plan::rank_grid(rows, (m + 63) / 64);
+    a.tiles_per_split = g.tiles_per_split;
+    hipLaunchKernelGGL(rq_threshold_kernel, dim3((rows + 3) / 4), dim3(256), 0, h->stream, a);
+    const bool launched = launch_rank(h->K, [&](auto nch) {
+      hipLaunchKernelGGL(rank_queries_kernel<decltype(nch)::value>, dim3(g.blocks, g.splits), dim3(256), 0, h->stream, a);
+    });
+    if (!launched) { h->err = "rank_queries_kernel: no instance for this column count"; return HPF_ERR_UNSUPPORTED; }
+    if ((rc = check_launch(h, "rank_queries_kernel"))) return rc;
+  }
+  hipError_t e = hipMemcpyAsync(out_rank, d_rank, (size_t)nq * 4, hipMemcpyDeviceToHost, h->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(out_score, d_sc, (size_t)nq * 8, hipMemcpyDeviceToHost, h->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+  if (e != hipSuccess) { h->err = hipGetErrorString(e); return HPF_ERR_HIP; }
+  return HPF_OK;
 }
 
 int hpf_get_work_info(hpf_handle *h, hpf_work_info *out)

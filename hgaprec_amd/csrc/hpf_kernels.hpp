@@ -1962,87 +1962,39 @@ struct LooArgs {
 constexpr int LOO_KC = 32;            // columns of an item tile staged at once
 constexpr int LOO_LDS_STRIDE = 34;    // doubles per staged row: the 16 rows x 2 k of a half wave fall into 32 different bank pairs
 
-// Workgroup = 4 waves = 64 users (16 per wave) x one split of the item range.  The 64 x 32 pieces of the
-// item rows go through LDS (16-byte loads, the next piece on its way while this one is multiplied) and are
-// shared by the four waves.  NCH > 0: the wave's A fragments (its 16 users, K <= 32 * NCH <= 128) stay in
-// registers; NCH == 0: they are read per step like score_tile_kernel does (K up to HPF_MAX_COLUMNS).
-// Per output ONE accumulator chain over k0 = 0, 4, 8, ... with the tail padded by zeros -- exactly the MFMAs
-// score_tile_kernel issues -- then + (E_ubias + E_ibias).  The threshold s(b, t) comes from the same
-// arithmetic: a 16 x 16 tile whose column j is the row of user j's query item, of which the diagonal is kept.
+// ---- the item sweep of the two fused rank kernels ---------------------------------------------------------------------
+// A wave's A fragments: the rows of E_theta of its 16 users, A[i = lane%16][k = 4 s + lane/16] for MFMA step s.  NCH > 0:
+// K <= 32 * NCH <= 128 and they stay in registers; NCH == 0: read per step like score_tile_kernel does (K up to
+// HPF_MAX_COLUMNS).
 template <int NCH>
-__global__ __launch_bounds__(256) void loo_rank_kernel(LooArgs a)
-{
-  __shared__ double tile[64 * LOO_LDS_STRIDE];
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  const int r16 = lane & 15, kq = lane >> 4;
-  const uint32_t ub0 = blockIdx.x * 64 + wv * 16;              // first user of this wave
-  const uint32_t usel = ub0 + r16;
-  const bool uok = usel < a.n_sel;
-  const uint32_t urow = uok ? a.users[usel] : 0u;
-  const double *pa = a.Et + (size_t)urow * a.ld;
-  const uint32_t nsteps = (a.K + 3) / 4;                       // MFMAs per output, as in score_tile_kernel
-
-  double areg[NCH > 0 ? NCH * 8 : 1];
-  if (NCH > 0) {
-#pragma unroll
-    for (int s = 0; s < NCH * 8; ++s) {
-      const uint32_t k = 4u * s + kq;
-      areg[s] = (uok && k < a.K) ? pa[k] : 0.0;
-    }
-  }
-  auto a_of = [&](int s) -> double {                           // A[i = lane%16][k = 4 s + lane/16]
-    if (NCH > 0) return areg[s];
-    const uint32_t k = 4u * (uint32_t)s + kq;
-    return (uok && k < a.K) ? pa[k] : 0.0;
-  };
-
-  // ---- thresholds: D[i][j] = E_theta[user i] . E_beta[query item of user j], diagonal kept
-  const uint32_t myq = uok ? a.q_item[usel] : 0u;
-  double thr[4]; uint32_t tq[4]; bool live[4];
+struct AFrag {
+  double reg[NCH > 0 ? NCH * 8 : 1];
+  const double *pa; uint32_t K, kq; bool ok;
+  __device__ __forceinline__ AFrag(const double *row, bool row_ok, uint32_t K_, uint32_t kq_) : pa(row), K(K_), kq(kq_), ok(row_ok)
   {
-    const double *pq = a.Eb + (size_t)myq * a.ld;
-    double4_t acc = (double4_t){0.0, 0.0, 0.0, 0.0};
     if (NCH > 0) {
 #pragma unroll
-      for (int s = 0; s < NCH * 8; ++s)
-        if ((uint32_t)s < nsteps) {
-          const uint32_t k = 4u * s + kq;
-          const double bv = (uok && k < a.K) ? pq[k] : 0.0;
-          acc = __builtin_amdgcn_mfma_f64_16x16x4f64(areg[s], bv, acc, 0, 0, 0);
-        }
-    } else {
-      for (uint32_t s = 0; s < nsteps; ++s) {
-        const uint32_t k = 4u * s + kq;
-        const double bv = (uok && k < a.K) ? pq[k] : 0.0;
-        acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a_of((int)s), bv, acc, 0, 0, 0);
-      }
-    }
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int src = (kq + 4 * r) + 16 * kq;                  // the lane that holds D[i][i] for i = kq + 4 r, in register r
-      double v = __shfl(acc[r], src);
-      const uint32_t us = ub0 + kq + 4 * r;
-      live[r] = us < a.n_sel;
-      tq[r] = live[r] ? a.q_item[us] : 0u;
-      if (live[r] && a.ubias_col >= 0)
-        v += a.Et[(size_t)a.users[us] * a.ld + a.ubias_col] + a.Eb[(size_t)tq[r] * a.ld + a.ibias_col];
-      if (live[r] && ((a.bits[(size_t)us * a.words + (tq[r] >> 6)] >> (tq[r] & 63u)) & 1ull)) v = 0.0;
-      if (tq[r] >= a.limit) live[r] = false;                   // outside the ranked range: rank 0, score 0.0
-      thr[r] = v;
+      for (int s = 0; s < NCH * 8; ++s) reg[s] = load((uint32_t)s);
     }
   }
+  __device__ __forceinline__ double load(uint32_t s) const { const uint32_t k = 4u * s + kq; return (ok && k < K) ? pa[k] : 0.0; }
+};
 
-  // ---- item sweep
-  const uint32_t ntiles = (a.limit + 63) / 64;
-  const uint32_t t0 = blockIdx.y * a.tiles_per_split, t1 = min(ntiles, t0 + a.tiles_per_split);
-  const uint32_t nchunks = (a.K + LOO_KC - 1) / LOO_KC;
-  uint32_t cnt[4] = {0, 0, 0, 0}, msk[4] = {0, 0, 0, 0};
-  double ubv[4];
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    const uint32_t us = ub0 + kq + 4 * r;
-    ubv[r] = (us < a.n_sel && a.ubias_col >= 0) ? a.Et[(size_t)a.users[us] * a.ld + a.ubias_col] : 0.0;
-  }
+// Workgroup = 4 waves = 64 users or rows (16 per wave) x one split of the item range: the 64-item tiles [t0, t1) of
+// blockIdx.y.  The 64 x 32 pieces of the item rows go through LDS (`tile`; 16-byte loads, the next piece on its way
+// while this one is multiplied) and are shared by the four waves.  Per output ONE accumulator chain over k0 = 0, 4, 8,
+// ... with the tail padded by zeros -- exactly the MFMAs score_tile_kernel issues.  epi(tl, acc) gets each tile's
+// scores before the biases: register r of acc[t] holds the wave's user kq + 4 r, item 64 tl + 16 t + r16.
+template <int NCH, typename Epi>
+__device__ __forceinline__ void rank_sweep(const AFrag<NCH> &A, const double *Eb, uint32_t limit, uint32_t ld, uint32_t K,
+                                           uint32_t tiles_per_split, double *tile, Epi &&epi)
+{
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int r16 = lane & 15, kq = lane >> 4;
+  const uint32_t nsteps = (K + 3) / 4;                           // MFMAs per output, as in score_tile_kernel
+  const uint32_t ntiles = (limit + 63) / 64;
+  const uint32_t t0 = blockIdx.y * tiles_per_split, t1 = min(ntiles, t0 + tiles_per_split);
+  const uint32_t nchunks = (K + LOO_KC - 1) / LOO_KC;
 
   // this thread's four 16-byte pieces of a 64 x 32 chunk: piece p = tid + 256 j -> row p / 16, columns 2 (p % 16), +1
   double2 pre[4];
@@ -2052,9 +2004,9 @@ __global__ __launch_bounds__(256) void loo_rank_kernel(LooArgs a)
       const uint32_t p = (uint32_t)tid + 256u * j, row = p >> 4, c = chunk * LOO_KC + 2u * (p & 15u);
       const uint32_t it = tile_i * 64 + row;
       double2 v = make_double2(0.0, 0.0);
-      if (it < a.limit && c < a.K) {                           // c is even and ld is even: c + 1 < ld
-        v = *(const double2 *)(a.Eb + (size_t)it * a.ld + c);
-        if (c + 1 >= a.K) v.y = 0.0;
+      if (it < limit && c < K) {                                 // c is even and ld is even: c + 1 < ld
+        v = *(const double2 *)(Eb + (size_t)it * ld + c);
+        if (c + 1 >= K) v.y = 0.0;
       }
       pre[j] = v;
     }
@@ -2086,7 +2038,7 @@ __global__ __launch_bounds__(256) void loo_rank_kernel(LooArgs a)
 #pragma unroll
               for (int t = 0; t < 4; ++t) {
                 const double bv = tile[(16 * t + r16) * LOO_LDS_STRIDE + 4 * s + kq];   // B[k = lane/16][j = lane%16]
-                acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(areg[ch * 8 + s], bv, acc[t], 0, 0, 0);
+                acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(A.reg[ch * 8 + s], bv, acc[t], 0, 0, 0);
               }
             }
         }
@@ -2094,7 +2046,7 @@ __global__ __launch_bounds__(256) void loo_rank_kernel(LooArgs a)
       for (uint32_t ch = 0; ch < nchunks; ++ch) {
         stage(ch);
         for (uint32_t s = 0; s < 8 && ch * 8 + s < nsteps; ++s) {
-          const double av = a_of((int)(ch * 8 + s));
+          const double av = A.load(ch * 8 + s);
 #pragma unroll
           for (int t = 0; t < 4; ++t) {
             const double bv = tile[(16 * t + r16) * LOO_LDS_STRIDE + 4 * s + kq];
@@ -2103,6 +2055,71 @@ __global__ __launch_bounds__(256) void loo_rank_kernel(LooArgs a)
         }
       }
     }
+    epi(tl, acc);
+  }
+}
+
+// The threshold s(b, t) comes from the sweep's arithmetic: a 16 x 16 tile whose column j is the row of user j's query
+// item, of which the diagonal is kept.  Every score and the threshold then get + (E_ubias + E_ibias).
+template <int NCH>
+__global__ __launch_bounds__(256) void loo_rank_kernel(LooArgs a)
+{
+  __shared__ double tile[64 * LOO_LDS_STRIDE];
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int r16 = lane & 15, kq = lane >> 4;
+  const uint32_t ub0 = blockIdx.x * 64 + wv * 16;              // first user of this wave
+  const uint32_t usel = ub0 + r16;
+  const bool uok = usel < a.n_sel;
+  const uint32_t urow = uok ? a.users[usel] : 0u;
+  const double *pa = a.Et + (size_t)urow * a.ld;
+  const uint32_t nsteps = (a.K + 3) / 4;
+  const AFrag<NCH> A(pa, uok, a.K, (uint32_t)kq);
+
+  // ---- thresholds: D[i][j] = E_theta[user i] . E_beta[query item of user j], diagonal kept
+  const uint32_t myq = uok ? a.q_item[usel] : 0u;
+  double thr[4]; uint32_t tq[4]; bool live[4];
+  {
+    const double *pq = a.Eb + (size_t)myq * a.ld;
+    double4_t acc = (double4_t){0.0, 0.0, 0.0, 0.0};
+    if (NCH > 0) {
+#pragma unroll
+      for (int s = 0; s < NCH * 8; ++s)
+        if ((uint32_t)s < nsteps) {
+          const uint32_t k = 4u * s + kq;
+          const double bv = (uok && k < a.K) ? pq[k] : 0.0;
+          acc = __builtin_amdgcn_mfma_f64_16x16x4f64(A.reg[s], bv, acc, 0, 0, 0);
+        }
+    } else {
+      for (uint32_t s = 0; s < nsteps; ++s) {
+        const uint32_t k = 4u * s + kq;
+        const double bv = (uok && k < a.K) ? pq[k] : 0.0;
+        acc = __builtin_amdgcn_mfma_f64_16x16x4f64(A.load(s), bv, acc, 0, 0, 0);
+      }
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int src = (kq + 4 * r) + 16 * kq;                  // the lane that holds D[i][i] for i = kq + 4 r, in register r
+      double v = __shfl(acc[r], src);
+      const uint32_t us = ub0 + kq + 4 * r;
+      live[r] = us < a.n_sel;
+      tq[r] = live[r] ? a.q_item[us] : 0u;
+      if (live[r] && a.ubias_col >= 0)
+        v += a.Et[(size_t)a.users[us] * a.ld + a.ubias_col] + a.Eb[(size_t)tq[r] * a.ld + a.ibias_col];
+      if (live[r] && ((a.bits[(size_t)us * a.words + (tq[r] >> 6)] >> (tq[r] & 63u)) & 1ull)) v = 0.0;
+      if (tq[r] >= a.limit) live[r] = false;                   // outside the ranked range: rank 0, score 0.0
+      thr[r] = v;
+    }
+  }
+
+  // ---- item sweep
+  uint32_t cnt[4] = {0, 0, 0, 0}, msk[4] = {0, 0, 0, 0};
+  double ubv[4];
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const uint32_t us = ub0 + kq + 4 * r;
+    ubv[r] = (us < a.n_sel && a.ubias_col >= 0) ? a.Et[(size_t)a.users[us] * a.ld + a.ubias_col] : 0.0;
+  }
+  rank_sweep<NCH>(A, a.Eb, a.limit, a.ld, a.K, a.tiles_per_split, tile, [&](uint32_t tl, const double4_t (&acc)[4]) {
     // epilogue: register r of tile t holds user kq + 4 r, item 64 tl + 16 t + r16
     const uint32_t i0 = tl * 64;
     unsigned long long w[4];
@@ -2129,7 +2146,7 @@ __global__ __launch_bounds__(256) void loo_rank_kernel(LooArgs a)
         cnt[r] += (iok && live[r] && it != tq[r] && (k > kt || (k == kt && it < tq[r]))) ? 1u : 0u;
       }
     }
-  }
+  });
   // one reduction per user block: over the 16 lanes that share kq
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
@@ -2149,7 +2166,7 @@ __global__ __launch_bounds__(256) void loo_rank_kernel(LooArgs a)
 //   rq_threshold_kernel  s(b, t) of every query of a ROW (one selected user with <= RQ_QCAP of its queries) from the
 //                        MFMA chain of score_tile_kernel, masked like loo_rank_kernel's threshold; the row's
 //                        thresholds sorted best first, with the permutation back to the caller's order
-//   rank_queries_kernel  loo_rank_kernel's sweep; each score finds by binary search how many of its row's sorted
+//   rank_queries_kernel  the same sweep (rank_sweep); each score finds by binary search how many of its row's sorted
 //                        thresholds come before or equal it and counts into an LDS histogram; prefix sums are the ranks
 // ---------------------------------------------------------------------
 constexpr int RQ_QCAP = 32;           // queries of one row (hgaprec_amd/capi.py mirrors it as RANK_QUERIES_QCAP)
@@ -2223,7 +2240,7 @@ __global__ __launch_bounds__(256) void rq_threshold_kernel(RqArgs a)
 constexpr int RQ_CNT_STRIDE = RQ_QCAP + 1;
 
 // Workgroup = 4 waves = 64 rows (16 per wave) x one split of the item range; staging, A fragments and MFMA order are
-// loo_rank_kernel's.  The 64 rows' sorted thresholds and a histogram [row][p] live in LDS.  A score (key, item) adds 1
+// rank_sweep's.  The 64 rows' sorted thresholds and a histogram [row][p] live in LDS.  A score (key, item) adds 1
 // at p = the number of its row's thresholds that come before or equal it; p = Q (it precedes none: one comparison
 // with the row's worst threshold, kept in registers) adds nothing.  "Before or equal" puts a queried item behind its
 // own threshold and behind every duplicate of it.  The rank of the threshold at sorted position s is the sum of the
@@ -2244,20 +2261,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void r
   const bool uok = rsel < a.nrows;
   const uint32_t urow = uok ? a.users[a.row_sel[rsel]] : 0u;
   const double *pa = a.Et + (size_t)urow * a.ld;
-  const uint32_t nsteps = (a.K + 3) / 4;                         // MFMAs per output, as in score_tile_kernel
-
-  double areg[NCH > 0 ? NCH * 8 : 1];
-  if (NCH > 0) {
-#pragma unroll
-    for (int s = 0; s < NCH * 8; ++s) {
-      const uint32_t k = 4u * s + kq;
-      areg[s] = (uok && k < a.K) ? pa[k] : 0.0;
-    }
-  }
-  auto a_of = [&](int s) -> double {                             // A[i = lane%16][k = 4 s + lane/16]
-    const uint32_t k = 4u * (uint32_t)s + kq;
-    return (uok && k < a.K) ? pa[k] : 0.0;
-  };
+  const AFrag<NCH> A(pa, uok, a.K, (uint32_t)kq);
 
   // ---- the rows' sorted thresholds into LDS, histogram zeroed
   for (uint32_t e = tid; e < 64u * RQ_QCAP; e += 256) {
@@ -2277,69 +2281,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void r
   __syncthreads();
 
   // ---- item sweep
-  const uint32_t ntiles = (a.m + 63) / 64;
-  const uint32_t t0 = blockIdx.y * a.tiles_per_split, t1 = min(ntiles, t0 + a.tiles_per_split);
-  const uint32_t nchunks = (a.K + LOO_KC - 1) / LOO_KC;
-
-  // this thread's four 16-byte pieces of a 64 x 32 chunk: piece p = tid + 256 j -> row p / 16, columns 2 (p % 16), +1
-  double2 pre[4];
-  auto fetch = [&](uint32_t tile_i, uint32_t chunk) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const uint32_t p = (uint32_t)tid + 256u * j, row = p >> 4, c = chunk * LOO_KC + 2u * (p & 15u);
-      const uint32_t it = tile_i * 64 + row;
-      double2 v = make_double2(0.0, 0.0);
-      if (it < a.m && c < a.K) {                                 // c is even and ld is even: c + 1 < ld
-        v = *(const double2 *)(a.Eb + (size_t)it * a.ld + c);
-        if (c + 1 >= a.K) v.y = 0.0;
-      }
-      pre[j] = v;
-    }
-  };
-  if (t0 < t1) fetch(t0, 0);
-  for (uint32_t tl = t0; tl < t1; ++tl) {
-    double4_t acc[4];
-#pragma unroll
-    for (int t = 0; t < 4; ++t) acc[t] = (double4_t){0.0, 0.0, 0.0, 0.0};
-    auto stage = [&](uint32_t ch) {
-      __syncthreads();                                           // the previous chunk has been read
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const uint32_t p = (uint32_t)tid + 256u * j;
-        *(double2 *)&tile[(p >> 4) * LOO_LDS_STRIDE + 2u * (p & 15u)] = pre[j];
-      }
-      __syncthreads();
-      if (ch + 1 < nchunks) fetch(tl, ch + 1);
-      else if (tl + 1 < t1) fetch(tl + 1, 0);
-    };
-    if (NCH > 0) {
-#pragma unroll
-      for (int ch = 0; ch < NCH; ++ch)
-        if ((uint32_t)ch < nchunks) {
-          stage((uint32_t)ch);
-#pragma unroll
-          for (int s = 0; s < 8; ++s)
-            if ((uint32_t)(ch * 8 + s) < nsteps) {
-#pragma unroll
-              for (int t = 0; t < 4; ++t) {
-                const double bv = tile[(16 * t + r16) * LOO_LDS_STRIDE + 4 * s + kq];   // B[k = lane/16][j = lane%16]
-                acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(areg[ch * 8 + s], bv, acc[t], 0, 0, 0);
-              }
-            }
-        }
-    } else {
-      for (uint32_t ch = 0; ch < nchunks; ++ch) {
-        stage(ch);
-        for (uint32_t s = 0; s < 8 && ch * 8 + s < nsteps; ++s) {
-          const double av = a_of((int)(ch * 8 + s));
-#pragma unroll
-          for (int t = 0; t < 4; ++t) {
-            const double bv = tile[(16 * t + r16) * LOO_LDS_STRIDE + 4 * s + kq];
-            acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(av, bv, acc[t], 0, 0, 0);
-          }
-        }
-      }
-    }
+  rank_sweep<NCH>(A, a.Eb, a.m, a.ld, a.K, a.tiles_per_split, tile, [&](uint32_t tl, const double4_t (&acc)[4]) {
     // epilogue: register r of tile t holds local row wv 16 + kq + 4 r, item 64 tl + 16 t + r16.  What a row needs is
     // read from LDS per tile (kept in registers it would cost the second wave per SIMD)
     const uint32_t i0 = tl * 64;
@@ -2378,7 +2320,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void r
         }
       }
     }
-  }
+  });
   __syncthreads();
   if (tid < 64) {
     const uint32_t row = rb0 + tid;

@@ -1,5 +1,6 @@
 // hpf_plan.hpp -- what the GPU will run, decided on the host: the experimental knobs, the shapes of the phi pass, of the rows
-// of W and of the row sweep for a column count (plan_shapes), and which kernel instances exist for them (has_*).
+// of W and of the row sweep for a column count (plan_shapes), which kernel instances exist for them (has_*), and the batches
+// and launch grid of the fused rank kernels (rank_batch_users, rank_grid, rank_chunks).
 // Plain C++17 without a HIP header: hpf_capi.hip builds its handle and its dispatcher from it, host/plan_selftest.cpp
 // walks every column count on a CPU.
 #pragma once
@@ -50,12 +51,14 @@ struct Knobs {
   // pays for (C4 18.65 -> 17.45 ms, a C5 shard 44.8 -> 41.5; experiments.md) and a pass bound by the fabric does not (C2's
   // user pass, a C3 shard: unchanged).  Same segments, same order inside each: the same bits.  HPF_PHI_WG forces 64 | 128 | 256.
   uint32_t phi_wg = 0;
+  long long loo_batch = 0;          // HPF_LOO_BATCH: at most so many users per batch of the fused rank calls (<= 0: no limit of its own)
 };
 
 // the one place that reads the knobs from the environment
 inline Knobs read_knobs()
 {
   Knobs k;
+  if (const char *e = getenv("HPF_LOO_BATCH")) k.loo_batch = atoll(e);      // outside the gate: the batch size cannot change a result
   const char *x = getenv("HPF_EXPERIMENTAL");
   if (!x || atoi(x) != 1) return k;
   if (const char *e = getenv("HPF_H2D")) k.xfer_mode = !strcmp(e, "plain") ? 0 : !strcmp(e, "register") ? 2 : 1;
@@ -103,6 +106,35 @@ constexpr bool has_sweep(int mode, int G, int R)
     case SW_PLAIN:   return R <= (G == 64 ? 16 : 8);        // G = 64 up to R = 16: 513..1024 columns
   }
   return false;
+}
+
+// loo_rank_kernel / rank_queries_kernel: NCH chunks of 32 columns of the A fragments in registers, 0 = re-read per step
+constexpr bool has_rank_chunks(int NCH) { return NCH == 0 || NCH == 1 || NCH == 2 || NCH == 4; }
+constexpr int rank_chunks(uint32_t K) { return K <= 32 ? 1 : K <= 64 ? 2 : K <= 128 ? 4 : 0; }
+
+// ---- the fused rank calls (hpf_loo_ranks, hpf_rank_queries) -----------------------------------------------------------
+// Users per batch: the bit rows of a batch (one bit per item, 64-bit words) stay under 256 MB, a multiple of the 64 users of
+// a workgroup; HPF_LOO_BATCH (rounded up to the 16 users of a wave's block; a TEST knob, so that a handful of users crosses
+// a batch boundary) makes it smaller; never more than the selected users need.
+inline uint32_t rank_batch_users(uint32_t m, uint32_t n_sel, long long knob)
+{
+  const uint64_t words = std::max<uint64_t>(((uint64_t)m + 63) / 64, 1);
+  uint64_t batch = std::max<uint64_t>(64, (((uint64_t)256 << 20) / (words * 8)) & ~63ull);
+  if (knob > 0) batch = std::min<uint64_t>(batch, ((uint64_t)knob + 15) & ~15ull);
+  return (uint32_t)std::min<uint64_t>(batch, ((uint64_t)n_sel + 15) & ~15ull);
+}
+
+// Launch grid over `rows` users or rows and `ntiles` 64-item tiles: a block per 64 rows.  Few blocks: the item range is
+// cut so that some 1024 workgroups exist; many: one sweep per block.  No split is empty.
+struct RankGrid { uint32_t blocks, splits, tiles_per_split; };
+inline RankGrid rank_grid(uint32_t rows, uint32_t ntiles)
+{
+  RankGrid g;
+  g.blocks = (rows + 63) / 64;
+  g.splits = std::max<uint32_t>(1, std::min<uint32_t>(ntiles, (1024 + g.blocks - 1) / g.blocks));
+  g.tiles_per_split = (ntiles + g.splits - 1) / g.splits;
+  g.splits = (ntiles + g.tiles_per_split - 1) / g.tiles_per_split;
+  return g;
 }
 
 // ---- the plan ---------------------------------------------------------------------------------------------------------

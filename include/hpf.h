@@ -346,7 +346,8 @@ int  hpf_predict(hpf_handle *h, const uint32_t *u, const uint32_t *i, size_t cnt
  * for q_sel = 0 .. n_sel - 1 on the same handle: the scores come out of the same MFMA chain.
  * No n_sel x n_items array exists anywhere: a tile of scores is compared and counted in
  * registers; the masked items are one BIT per (user, item) for a batch of users at a time
- * (<= 256 MB; HPF_LOO_BATCH=<users> makes the batches smaller -- a test knob). */
+ * (<= 256 MB; HPF_LOO_BATCH=<users> makes the batches smaller -- a test knob, read when the
+ * handle is created). */
 int  hpf_loo_ranks(hpf_handle *h, const uint32_t *users, uint32_t n_sel,
                    const uint64_t *mask_ptr, const uint32_t *mask_items,
                    const uint32_t *q_item, uint32_t item_limit,

@@ -195,3 +195,46 @@ def test_invalid_queries_and_empty_selections():
     r, s = D.rank_queries(users, np.zeros(users.size + 1, np.uint64), np.zeros(0, np.uint32), mptr, mitems)
     assert r.size == 0 and s.size == 0
     D.close()
+
+
+def test_several_workgroups_and_the_two_chunk_register_path():
+    """test_gpu_loo_ranks' shape of the same name, over rows: K = 40 (two staged chunks, A in registers:
+    rank_queries_kernel<2>), every user selected with 1-3 queries -- 150 users are three workgroups of 64 rows or more --
+    and m = 333 (five full tiles and one of 13 items)"""
+    from tests.test_gpu_ranking import _setup
+    from oracle import orc
+    n, m, K = 150, 333, 40
+    M, D, rowptr, col, val = _setup(orc, n, m, K, 5000, True, seed=3)
+    rng = np.random.default_rng(3)
+    users = np.arange(n, dtype=np.uint32)
+    counts = rng.integers(1, 4, n)
+    q_ptr = np.zeros(n + 1, np.uint64)
+    q_ptr[1:] = np.cumsum(counts)
+    q_items = rng.integers(0, m, int(q_ptr[-1])).astype(np.uint32)
+    q_items[0], q_items[1] = m - 1, 0
+    mptr = (np.arange(n + 1) * 3).astype(np.uint64)
+    mitems = rng.integers(0, m, 3 * n).astype(np.uint32)
+    want_r, want_s = D.item_ranks(users, np.repeat(users, counts), q_items, mptr, mitems)
+    rank, sc = D.rank_queries(users, q_ptr, q_items, mptr, mitems)
+    assert np.array_equal(rank, want_r) and np.array_equal(sc.view(np.uint64), want_s.view(np.uint64))
+    assert np.unique(rank).size > 50
+    D.close()
+
+
+@pytest.mark.parametrize("K", [32, 33, 64, 65, 128, 129])
+def test_chunk_count_boundaries_of_both_fused_kernels(K):
+    """The column counts at which the fused kernels change instance (NCH = 1 | 2 | 4 chunks of 32 columns in registers,
+    0 = A re-read per step): at K = 32, 64, 128 every unrolled step of the last chunk is live, at K = 33, 65, 129 one
+    step of a new chunk (or of the re-read path) is.  m = 70: one full tile and one of 6 items.  hpf_loo_ranks and
+    hpf_rank_queries each equal hpf_item_ranks bit for bit."""
+    D, rowptr, col, val, users, mask, mptr, mitems, q = _case(K, True, 70)
+    sel = np.arange(users.size, dtype=np.uint32)
+    want_r, want_s = D.item_ranks(users, sel, q, mptr, mitems)
+    rank, sc, _ = D.loo_ranks(users, q, mptr, mitems)
+    assert rank.dtype.kind == "u" and np.array_equal(rank, want_r)
+    assert np.array_equal(sc.view(np.uint64), want_s.view(np.uint64))
+    rank, sc = D.rank_queries(users, np.arange(users.size + 1, dtype=np.uint64), q, mptr, mitems)
+    assert rank.dtype.kind == "u" and np.array_equal(rank, want_r)
+    assert np.array_equal(sc.view(np.uint64), want_s.view(np.uint64))
+    assert np.count_nonzero(want_s) >= 10 and np.unique(want_r).size >= 10
+    D.close()

@@ -3,7 +3,8 @@
 `make -C hgaprec_amd/csrc plan` builds host/plan_selftest.cpp -- a stand-alone program, under ASan/UBSan -- which plans
 every column count 1..HPF_MAX_COLUMNS x w_storage 0..3 x HPF_W_PACK off/on, checks each plan (ld >= C, the packed and the
 plain row arithmetic, a kernel instance for the phi pass, the gather-only probe and the sweep, the fall-back to plain
-doubles equal to the w_storage = 3 plan) and the shapes the knobs HPF_PHI_CFG / HPF_SWEEP_CFG force, and prints the mapping
+doubles equal to the w_storage = 3 plan) and the shapes the knobs HPF_PHI_CFG / HPF_SWEEP_CFG force, pins the batches, the
+launch grid and the chunk counts of the fused rank kernels (rank_batch_users, rank_grid, rank_chunks), and prints the mapping
 as runs.  The runs must be tests/data/plan_table.txt, which was recorded from the library's hpf_get_work_info on a GPU
 before the planner became a header of its own.
 """
