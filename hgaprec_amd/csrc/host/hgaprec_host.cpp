@@ -1154,7 +1154,16 @@ bool load_row(const char *p, const char *e, double *dst, uint32_t cols, bool che
       char buf[96]; snprintf(buf, sizeof buf, "id %.0f where the ratings have %u (the model of another data set?)", d, want_id);
       *why = buf; return false;
     }
-    if (f >= 2) dst[f - 2] = d;
+    if (f >= 2) {
+      // every model file holds parameters or expectations of a Gamma: the ranking kernels order scores by their bit
+      // pattern, which is the order of the values only for finite E >= +0.0 (include/hpf.h).  -0.0 passes: it cannot
+      // change a sum that starts at +0.0
+      if (!(d >= 0.0) || !std::isfinite(d)) {
+        char buf[96]; snprintf(buf, sizeof buf, "value %g where a Gamma expectation (finite, >= 0) is expected", d);
+        *why = buf; return false;
+      }
+      dst[f - 2] = d;
+    }
   }
   if (f < cols + 2) {
     char buf[96]; snprintf(buf, sizeof buf, "%u values where %u are expected", f >= 2 ? f - 2 : 0u, cols);
@@ -1240,6 +1249,27 @@ int load_matrix(const std::string &path, double *out, uint32_t rows, uint32_t co
 int load_vector(const std::string &path, double *out, uint32_t rows, const uint32_t *ids, uint32_t nids, std::string *err)
 {
   return load_matrix(path, out, rows, 1, ids, nids, err);
+}
+
+int shape_over_rate(double *E, uint32_t rows, uint32_t cols, const double *rate, const std::string &rate_path, std::string *err)
+{
+  for (uint32_t c = 0; c < cols; ++c)
+    if (!(rate[c] > 0.0) || !std::isfinite(rate[c])) {
+      char buf[96]; snprintf(buf, sizeof buf, "line %u: rate %g where a Gamma rate (finite, > 0) is expected", c + 1, rate[c]);
+      if (err) *err = rate_path + ": " + buf;
+      return -1;
+    }
+  for (size_t r = 0; r < rows; ++r)
+    for (uint32_t c = 0; c < cols; ++c) {
+      const double e = E[r * cols + c] / rate[c];
+      if (!std::isfinite(e)) {                                  // a subnormal rate under an ordinary shape
+        char buf[128]; snprintf(buf, sizeof buf, "line %u: shape / rate %g of row %zu is not finite", c + 1, rate[c], r + 1);
+        if (err) *err = rate_path + ": " + buf;
+        return -1;
+      }
+      E[r * cols + c] = e;
+    }
+  return 0;
 }
 
 // ======================================================================

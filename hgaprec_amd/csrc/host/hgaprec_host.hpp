@@ -215,8 +215,13 @@ int save_vector(const std::string &path, const double *a, uint32_t rows,
 // *err = "<path>: ..." naming the line.  out: rows x cols doubles, row-major.
 int load_matrix(const std::string &path, double *out, uint32_t rows, uint32_t cols,
                 const uint32_t *ids, uint32_t nids, std::string *err);
+// A value field that is negative or not finite (strtod takes "-1", "nan", "inf") is an error of the same kind: the files
+// hold Gamma parameters and expectations, and the ranking calls are defined for finite E >= +0.0 only (include/hpf.h).
 int load_vector(const std::string &path, double *out, uint32_t rows,
                 const uint32_t *ids, uint32_t nids, std::string *err);
+// without -hier: E[r][c] = shape[r][c] / rate[c] in place (GPMatrixGR::compute_expectations, gpbase.hh:755-764).  A
+// rate that is not finite and > 0, or a quotient that is not finite, returns -1 with *err = "<rate_path>: line c+1: ..."
+int shape_over_rate(double *E, uint32_t rows, uint32_t cols, const double *rate, const std::string &rate_path, std::string *err);
 
 // ------------------------------------------- held-out series / stopping ---
 // HGAPRec::compute_likelihood bookkeeping (hgaprec.cc:1466-1500)

@@ -691,9 +691,9 @@ struct Driver {
       } else {
         std::vector<double> rate(k);
         if (load_matrix(model_path((base + "_shape.tsv").c_str()), E.data(), rows, k, ids.data(), (uint32_t)ids.size(), &err)) model_die(err);
-        if (load_vector(model_path((base + "_rate.tsv").c_str()), rate.data(), k, nullptr, 0, &err)) model_die(err);   // a K-vector: its id column is seq2id[k]
-        for (size_t r = 0; r < rows; ++r)
-          for (uint32_t c = 0; c < k; ++c) E[r * k + c] = E[r * k + c] / rate[c];
+        const std::string rate_path = model_path((base + "_rate.tsv").c_str());
+        if (load_vector(rate_path, rate.data(), k, nullptr, 0, &err)) model_die(err);   // a K-vector: its id column is seq2id[k]
+        if (shape_over_rate(E.data(), rows, k, rate.data(), rate_path, &err)) model_die(err);   // a zero rate would rank the item first
       }
       put(user_side ? HPF_THETA_E : HPF_BETA_E, E);
       if (env.hier) {

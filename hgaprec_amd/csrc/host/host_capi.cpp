@@ -131,6 +131,14 @@ int hg_load_vector(const char *path, double *out, uint32_t rows, const uint32_t 
   if (err && errcap) { strncpy(err, e.c_str(), errcap - 1); err[errcap - 1] = 0; }
   return rc;
 }
+// E = shape / rate[c] in place with load_model's check of the rates: 0, or -1 with the message in err
+int hg_shape_over_rate(double *E, uint32_t rows, uint32_t cols, const double *rate, const char *rate_path, char *err, size_t errcap)
+{
+  std::string e;
+  const int rc = shape_over_rate(E, rows, cols, rate, rate_path, &e);
+  if (err && errcap) { strncpy(err, e.c_str(), errcap - 1); err[errcap - 1] = 0; }
+  return rc;
+}
 
 // -eval-all's arithmetic from ranks to metrics.  per_user: n_users x 6 integers (ntest, hits10, hits100, best_rank,
 // sum_rank, nranked as given); means: users, pairs, precision@10, precision@100, recall@100, mrr, meanrank

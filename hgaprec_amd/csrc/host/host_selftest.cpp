@@ -393,6 +393,31 @@ static void test_loader()
   CHECK(load_vector(path("empty.tsv"), v, 1, nullptr, 0, &err) != 0 && load_vector(path("empty.tsv"), v, 0, nullptr, 0, &err) == 0);
   write_text(path("nl.tsv"), "\n\n");
   CHECK(load_vector(path("nl.tsv"), v, 2, nullptr, 0, &err) != 0 && err.find("line 1:") != std::string::npos);
+  // values outside a Gamma's domain, as the first row, a middle row and a last line without '\n'; one piece and several
+  const char *bad[] = {"-1", "nan", "inf", "-inf", "-1e-320", "NAN(7)", "-nan", "1e999"};
+  for (int threaded = 0; threaded < 2; ++threaded) {
+    if (threaded) { setenv("HGAPREC_READ_PARALLEL_MIN", "0", 1); setenv("HGAPREC_READ_THREADS", "3", 1); }
+    for (const char *b : bad)
+      for (int at : {0, 20, 39}) {                              // 40 lines of ~20 bytes: three pieces when threaded
+        std::string text;
+        for (int r = 0; r < 40; ++r)                            // the last line is bad too: the first in file order is reported
+          text += std::to_string(r) + "\t" + std::to_string(r + 5) + "\t0.50000000\t" + ((r == at || r == 39) ? b : "0.25") + (r == 39 ? "" : "\n");
+        write_text(path("domain.tsv"), text);
+        double w[80];
+        CHECK(load_matrix(path("domain.tsv"), w, 40, 2, nullptr, 0, &err) != 0 &&
+              err.find("line " + std::to_string(at + 1) + ":") != std::string::npos && err.find("(finite, >= 0)") != std::string::npos);
+        CHECK(load_matrix(path("domain.tsv"), w, 40, 1, nullptr, 0, &err) == 0);      // the bad column is beyond `cols`: ignored
+      }
+    write_text(path("edge.tsv"), "0\t5\t0\n1\t6\t-0.0\n2\t7\t1e-320");
+    CHECK(load_vector(path("edge.tsv"), v, 3, nullptr, 0, &err) == 0 && v[0] == 0.0 && v[1] == 0.0 && std::signbit(v[1]) && v[2] > 0.0 && v[2] < 1e-319);
+  }
+  unsetenv("HGAPREC_READ_PARALLEL_MIN"); unsetenv("HGAPREC_READ_THREADS");
+  double E[4] = {1.0, 2.0, 3.0, 0.0}, rate[2] = {2.0, 0.0};
+  CHECK(shape_over_rate(E, 2, 2, rate, "beta_rate.tsv", &err) != 0 && err.find("beta_rate.tsv: line 2:") != std::string::npos && E[0] == 1.0);
+  rate[1] = std::nan("");
+  CHECK(shape_over_rate(E, 2, 2, rate, "beta_rate.tsv", &err) != 0 && err.find("line 2:") != std::string::npos);
+  rate[1] = 4.0;
+  CHECK(shape_over_rate(E, 2, 2, rate, "beta_rate.tsv", &err) == 0 && E[0] == 0.5 && E[1] == 0.5 && E[2] == 1.5 && E[3] == 0.0);
 }
 
 int main(int argc, char **argv)

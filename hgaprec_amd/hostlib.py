@@ -61,6 +61,7 @@ def lib():
     L.hg_save_vector.argtypes = [C.c_char_p, dp, C.c_uint32, u32p, C.c_uint32]
     L.hg_load_matrix.argtypes = [C.c_char_p, dp, C.c_uint32, C.c_uint32, u32p, C.c_uint32, C.c_char_p, C.c_size_t]
     L.hg_load_vector.argtypes = [C.c_char_p, dp, C.c_uint32, u32p, C.c_uint32, C.c_char_p, C.c_size_t]
+    L.hg_shape_over_rate.argtypes = [dp, C.c_uint32, C.c_uint32, dp, C.c_char_p, C.c_char_p, C.c_size_t]
     L.hg_format_fixed8.argtypes = [dp, C.c_size_t, C.c_char_p]
     L.hg_format_fixed8.restype = C.c_size_t
     L.hg_partition_users.argtypes = [C.POINTER(C.c_int64), C.c_uint32, C.c_int, u32p]
@@ -240,6 +241,20 @@ def load_vector(path, rows, ids=None) -> np.ndarray:
     if rc:
         raise ValueError(err.value.decode())
     return out
+
+
+def shape_over_rate(shape, rate, rate_path="rate.tsv") -> np.ndarray:
+    """the expectations of a model saved without -hier, as the CLI forms them: shape / rate[None, :].  Raises ValueError
+    ("<rate_path>: line c+1: ...") for a rate that is not finite and > 0"""
+    E = np.array(shape, np.float64, order="C", ndmin=2)
+    r = np.ascontiguousarray(rate, np.float64)
+    if r.shape != (E.shape[1],):
+        raise ValueError("rate: one value per column of shape")
+    err = C.create_string_buffer(1024)
+    dp = C.POINTER(C.c_double)
+    if lib().hg_shape_over_rate(E.ctypes.data_as(dp), E.shape[0], E.shape[1], r.ctypes.data_as(dp), str(rate_path).encode(), err, 1024):
+        raise ValueError(err.value.decode())
+    return E
 
 
 def format_fixed8(values):

@@ -304,6 +304,13 @@ int  hpf_heldout_ll_bound(hpf_handle *h, int slot, double *sum_out, uint64_t *cn
 int  hpf_elbo(hpf_handle *h, double *out);
 
 /* ---- ranking evaluation (report steps) ------------------ */
+/* DOMAIN of every ranking call below (hpf_rank_topn, hpf_item_ranks, hpf_loo_ranks,
+ * hpf_rank_queries): "score descending" is defined for expectations E (theta, beta and both
+ * biases) that are finite and >= +0.0, as every Gamma expectation is.  The kernels order scores
+ * by their 64-bit pattern, which is the order of the values on that domain only: a negative
+ * score, a NaN or an infinity would sort in FRONT of every proper score.  hpf_set_state does not
+ * scan what it is handed; the model reader of the CLI refuses such a file (hgaprec_host.cpp,
+ * load_matrix).  A masked item counts as +0.0 and ties with every other zero score by item. */
 /* replaces: prediction_score_hier / prediction_score (hgaprec.cc:1966-1991,
  * 1850-1877; _use_rate_as_score) for every item: out[n_sel x n_items] =
  * E_theta[users] . E_beta^T (+ biases), on the fp64 matrix cores.  Host out. */

@@ -138,3 +138,93 @@ def test_non_hier_expectation_is_shape_over_rate(tmp_path):
     assert np.array_equal(r, np.array(_fields(tmp_path / "theta_rate.tsv"))[:, 0])
     E = s / r[None, :]
     assert np.max(np.abs(E - shape / rate[None, :]) / (shape / rate[None, :])) < 1e-6
+
+
+# ---- the domain: every model file holds parameters or expectations of a Gamma (finite, >= 0) ----
+BAD_VALUES = ["-1", "nan", "inf", "-inf"]
+ROWS, COLS = 40, 3                                                            # ~1.2 kB: several pieces when threaded
+
+
+def _domain_file(p, bad, at):
+    """ROWS x COLS proper values with `bad` in the middle column of 0-based line `at` AND of the last line, which
+    ends without a newline; the first bad line in file order is the one to be reported"""
+    lines = []
+    for r in range(ROWS):
+        mid = bad if r in (at, ROWS - 1) else "0.25000000"
+        lines.append(f"{r}\t{r + 100}\t0.50000000\t{mid}\t1.00000000")
+    p.write_text("\n".join(lines))
+
+
+@pytest.mark.parametrize("threaded", [False, True])
+@pytest.mark.parametrize("at", [0, ROWS // 2, ROWS - 1], ids=["first", "middle", "last-no-newline"])
+@pytest.mark.parametrize("bad", BAD_VALUES)
+def test_values_outside_the_gamma_domain_are_errors(tmp_path, monkeypatch, bad, at, threaded):
+    if threaded:
+        monkeypatch.setenv("HGAPREC_READ_PARALLEL_MIN", "0")
+        monkeypatch.setenv("HGAPREC_READ_THREADS", "5")
+    p = tmp_path / "hbeta.tsv"
+    _domain_file(p, bad, at)
+    ids = np.arange(ROWS, dtype=np.uint32) + 100
+    with pytest.raises(ValueError) as e:
+        hostlib.load_matrix(p, ROWS, COLS, ids)
+    msg = str(e.value)
+    assert f"hbeta.tsv: line {at + 1}:" in msg and "where a Gamma expectation (finite, >= 0) is expected" in msg
+    assert f"value {bad}" in msg
+    got = hostlib.load_matrix(p, ROWS, 1, ids)                                # the bad column is beyond `cols`: never a value
+    assert np.array_equal(got, np.full((ROWS, 1), 0.5))
+    if at < ROWS - 1:
+        got = hostlib.load_matrix(p, at, COLS, ids)                           # ... and so are the lines beyond `rows`
+        assert got.shape == (at, COLS)
+
+
+@pytest.mark.parametrize("threaded", [False, True])
+@pytest.mark.parametrize("at", [0, 3, 6], ids=["first", "middle", "last-no-newline"])
+@pytest.mark.parametrize("bad", BAD_VALUES)
+def test_bad_values_in_a_vector_file(tmp_path, monkeypatch, bad, at, threaded):
+    if threaded:
+        monkeypatch.setenv("HGAPREC_READ_PARALLEL_MIN", "0")
+        monkeypatch.setenv("HGAPREC_READ_THREADS", "5")
+    p = tmp_path / "betabias.tsv"
+    p.write_text("\n".join(f"{r}\t{r}\t{bad if r == at else '0.12500000'}" for r in range(7)))
+    with pytest.raises(ValueError) as e:
+        hostlib.load_vector(p, 7)
+    assert f"betabias.tsv: line {at + 1}:" in str(e.value) and "(finite, >= 0)" in str(e.value)
+
+
+@pytest.mark.parametrize("threaded", [False, True])
+def test_zero_negative_zero_and_subnormal_load(tmp_path, monkeypatch, threaded):
+    if threaded:
+        monkeypatch.setenv("HGAPREC_READ_PARALLEL_MIN", "0")
+        monkeypatch.setenv("HGAPREC_READ_THREADS", "5")
+    p = tmp_path / "hbeta.tsv"
+    p.write_text("0\t7\t0\t-0.0\t1e-320\n1\t8\t1e-320\t0\t-0.0\n2\t9\t-0.0\t1e-320\t0")
+    got = hostlib.load_matrix(p, 3, 3, np.array([7, 8, 9], np.uint32))
+    want = np.array([[0.0, -0.0, 1e-320], [1e-320, 0.0, -0.0], [-0.0, 1e-320, 0.0]])
+    assert np.array_equal(got.view(np.uint64), want.view(np.uint64))          # bit for bit: the sign of -0.0 is kept
+
+
+@pytest.mark.parametrize("bad", ["0", "nan", "-0.0", "-1", "inf"])
+@pytest.mark.parametrize("at", [0, 2, 5], ids=["first", "middle", "last-no-newline"])
+def test_non_hier_rate_must_be_positive_and_finite(tmp_path, bad, at):
+    """without -hier E = shape / rate[k]: a zero rate would make every such E infinite (or NaN) and rank the item
+    first for every user.  nan, inf and -1 never get past the reader; 0 and -0.0 do, and are refused before the
+    division.  Either way the message names the rate file and the line."""
+    n, K = 9, 6
+    shape = _values(n, K, seed=11) + 0.3
+    hostlib.save_matrix(tmp_path / "beta_shape.tsv", shape)
+    rp = tmp_path / "beta_rate.tsv"
+    rp.write_text("\n".join(f"{k}\t{k}\t{bad if k == at else '1.50000000'}" for k in range(K)))
+    s = hostlib.load_matrix(tmp_path / "beta_shape.tsv", n, K)
+    with pytest.raises(ValueError) as e:
+        hostlib.shape_over_rate(s, hostlib.load_vector(rp, K), rp)
+    assert f"beta_rate.tsv: line {at + 1}:" in str(e.value)
+    if bad in ("0", "-0.0"):
+        assert "where a Gamma rate (finite, > 0) is expected" in str(e.value)
+    else:
+        assert "where a Gamma expectation (finite, >= 0) is expected" in str(e.value)
+    rp.write_text("\n".join(f"{k}\t{k}\t1.50000000" for k in range(K)))
+    E = hostlib.shape_over_rate(s, hostlib.load_vector(rp, K), rp)
+    assert np.array_equal(E, s / 1.5)
+    with pytest.raises(ValueError) as e:                                      # a quotient beyond the largest double
+        hostlib.shape_over_rate(s, np.full(K, 1e-320), rp)
+    assert "beta_rate.tsv: line 1:" in str(e.value) and "not finite" in str(e.value)
