@@ -5,9 +5,16 @@
 // stdout: the mapping as runs of equal shapes, one line each --
 //   w_storage pack C_first C_last w_layout phi_G phi_R phi_V sweep_G sweep_R ld       (the fields hpf_get_work_info exports)
 // -- which tests/test_plan.py compares with tests/data/plan_table.txt, recorded from the library on a GPU.
+// Then the tiled pass: the policy's pins from DESIGN.md section 5, the invariants of plan_tile_queues over a seeded sweep,
+// and for a fixed list of cases a line
+//   tq case-id chunks chunk_segs fnv64-of-the-list
+// -- printed when the program is run as `plan_selftest_asan tile-queues` (then only the tiled pass is checked, and stdout
+// holds nothing else) -- which tests/test_plan.py compares with tests/data/tile_queue_table.txt, recorded from the queue arithmetic as it stood
+// inside hpf_capi.hip's build_tiled_side before it moved into the header.
 #include "../hpf_plan.hpp"
 
 #include <string>
+#include <vector>
 
 using namespace hpf_plan;
 
@@ -57,8 +64,155 @@ static std::string shape_of(int rc, const Plan &p)
   return b;
 }
 
-int main()
+// ---- the tiled pass ------------------------------------------------------------------------------------------------------
+struct Lcg { uint64_t s; uint32_t next() { s = s * 6364136223846793005ull + 1442695040888963407ull; return (uint32_t)(s >> 33); } };
+
+// A tiled side's first-segment table: key 0 (the row-major rest) holds rest_segs segments, tile k base + [0, spread) of them,
+// every absent_every-th tile none and every big_every-th one `big` more
+struct TqShape { uint64_t seed; uint32_t tiles, rest_segs, base, spread, absent_every, big_every, big; };
+static std::vector<uint32_t> make_fs(const TqShape &c, uint32_t *nseg)
 {
+  Lcg g = {c.seed};
+  std::vector<uint32_t> fs(c.tiles + 1, TILE_NO_SEG);
+  uint32_t at = 0;
+  if (c.rest_segs) { fs[0] = 0; at = c.rest_segs; }
+  for (uint32_t k = 1; k <= c.tiles; ++k) {
+    uint32_t n = c.base + (c.spread ? g.next() % c.spread : 0);
+    if (c.big_every && k % c.big_every == 1) n += c.big;
+    if (c.absent_every && k % c.absent_every == 0) n = 0;
+    if (n) { fs[k] = at; at += n; }
+  }
+  *nseg = at;
+  return fs;
+}
+
+// what must hold of any queue plan: every segment in exactly one chunk, no chunk across two keys, each queue's chunks in
+// front of its padding, and no more workgroups than a launch holds
+static void check_queues(const TileQueuePlan &qp, const std::vector<uint32_t> &fs, uint32_t nseg, size_t max_wgs, const char *what, unsigned id)
+{
+  CHECK(qp.ok == (nseg != 0), "%s %u: ok=%d with %u segments", what, id, (int)qp.ok, nseg);
+  if (!qp.ok) return;
+  CHECK(qp.chunks.size() % 8 == 0 && qp.chunks.size() <= 8 * max_wgs, "%s %u: %zu chunks, %zu workgroups fit", what, id, qp.chunks.size(), max_wgs);
+  std::vector<uint32_t> key_of(nseg, 0);
+  for (uint32_t k = 0; k < (uint32_t)fs.size(); ++k)
+    if (fs[k] != TILE_NO_SEG) for (uint32_t p = fs[k]; p < tile_key_end(fs, nseg, k); ++p) key_of[p] = k;
+  std::vector<uint8_t> seen(nseg, 0);
+  bool padded[8] = {false, false, false, false, false, false, false, false};
+  for (size_t j = 0; j < qp.chunks.size(); ++j) {
+    const TileChunk c = qp.chunks[j];
+    if (c.x == c.y) { CHECK(c.x == 0, "%s %u: padding {%u,%u}", what, id, c.x, c.y); padded[j % 8] = true; continue; }
+    CHECK(!padded[j % 8], "%s %u: a chunk behind the padding of queue %zu", what, id, j % 8);
+    CHECK(c.x < c.y && c.y <= nseg, "%s %u: chunk {%u,%u} of %u segments", what, id, c.x, c.y, nseg);
+    if (!(c.x < c.y && c.y <= nseg)) continue;
+    CHECK(key_of[c.x] == key_of[c.y - 1], "%s %u: chunk {%u,%u} spans keys %u and %u", what, id, c.x, c.y, key_of[c.x], key_of[c.y - 1]);
+    for (uint32_t p = c.x; p < c.y; ++p) { CHECK(!seen[p], "%s %u: segment %u twice", what, id, p); seen[p] = 1; }
+  }
+  for (uint32_t p = 0; p < nseg; ++p) CHECK(seen[p], "%s %u: segment %u in no chunk", what, id, p);
+}
+
+static uint64_t fnv64(const std::vector<TileChunk> &v)
+{
+  uint64_t hsh = 14695981039346656037ull;
+  for (const TileChunk &c : v)
+    for (uint32_t w : {c.x, c.y}) for (int b = 0; b < 4; ++b) { hsh ^= (w >> (8 * b)) & 0xffu; hsh *= 1099511628211ull; }
+  return hsh;
+}
+
+static void tile_checks(bool print_cases)
+{
+  // ---- policy, default knobs
+  const Knobs def;
+  {
+    const TilePolicy c2 = tile_policy(1000000, 768, 100000000, 100000, 8, true, def, 0);           // C2's item side gathers 10^6 users' rows
+    CHECK(c2.tile && c2.tiles == 184 && c2.T == 5461 && c2.min_run == 12 && c2.light_below == 184u * 12u, "C2 items: %u tiles of %u rows, bar %llu", c2.tiles, c2.T, (unsigned long long)c2.light_below);
+    const TilePolicy c4u = tile_policy(17770, 1536, 100480507, 480189, 4, false, def, 0), c4i = tile_policy(480189, 1536, 100480507, 17770, 4, true, def, 0);
+    CHECK(c4u.tile && c4u.tiles == 7 && c4u.light_below == 7u * 12u * 4u, "C4 users: %u tiles, bar %llu", c4u.tiles, (unsigned long long)c4u.light_below);   // x 4 below 8 tiles
+    CHECK(c4i.tile && c4i.tiles == 176 && c4i.light_below == 176u * 12u, "C4 items: %u tiles, bar %llu", c4i.tiles, (unsigned long long)c4i.light_below);
+    const TilePolicy k50 = tile_policy(1000000, 256, 100000000, 100000, 16, true, def, 0);         // a batch of sixteen nonzeros: runs of 32
+    CHECK(k50.tile && k50.min_run == 32 && k50.light_below == (uint64_t)k50.tiles * 32u, "16 per batch: run %u, bar %llu", k50.min_run, (unsigned long long)k50.light_below);
+    for (uint32_t tiles = 2; tiles <= 9; ++tiles) {                                                // x 4 below 8 tiles, x 1 from 8 on
+      Knobs kn; kn.tile_bytes = 4096; kn.tile_mode = 1;
+      const TilePolicy forced = tile_policy(tiles * 4, 1024, 1000, 100, 8, false, kn, 0);
+      CHECK(forced.tile && forced.tiles == tiles && forced.T == 4 && forced.light_below == 0, "forced, %u tiles", tiles);
+      kn.tile_mode = 2;
+      const TilePolicy autop = tile_policy(tiles * 4, 1024, 1000, 100, 8, false, kn, 0);
+      CHECK(autop.tile == (tiles >= 3) && (!autop.tile || autop.light_below == (uint64_t)tiles * 12u * (tiles < 8 ? 4u : 1u)), "auto, %u tiles: bar %llu", tiles, (unsigned long long)autop.light_below);
+    }
+    Knobs kn;
+    CHECK(!tile_policy(1000000, 768, 100000000, 100000, 8, true, def, 1).tile, "hpf_config.tiling = 1");
+    CHECK(!tile_policy(1000000, 768, 0, 100000, 8, true, def, 0).tile && !tile_policy(1000000, 768, 5, 0, 8, true, def, 0).tile, "nothing to tile");
+    CHECK(!tile_policy(5461, 768, 1000, 100, 8, true, def, 0).tile, "one tile");
+    CHECK(!tile_policy(13652, 768, 1000, 100, 8, true, def, 0).tile && tile_policy(13654, 768, 1000, 100, 8, true, def, 0).tile, "auto: 2.5 tiles");
+    kn.tile_bytes = 1024; CHECK(!tile_policy(65535, 1024, 1000, 100, 8, true, kn, 0).tile && tile_policy(65534, 1024, 1000, 100, 8, true, kn, 0).tiles == 65534, "at most 65 534 tiles");
+    kn = Knobs(); kn.tile_sides = 1; CHECK(!tile_policy(1000000, 768, 1000, 100, 8, true, kn, 0).tile && tile_policy(1000000, 768, 1000, 100, 8, false, kn, 0).tile, "HPF_TILE_SIDES");
+    kn = Knobs(); kn.tile_min_run = 2; CHECK(tile_policy(1000000, 768, 1000, 100, 16, true, kn, 0).min_run == 2, "HPF_TILE_RUN");
+    // the memory rule: a job of C4's size (some 23 GB with the temporaries) fits a device of 288 GB and not one of 8 GB
+    CHECK(tiling_fits(896, 480189, 17770, 100480507, true, (size_t)288 << 30) && !tiling_fits(896, 480189, 17770, 100480507, true, (size_t)8 << 30), "tiling_fits");
+  }
+  // ---- invariants of the queue plan over a seeded sweep
+  Lcg g = {20240521};
+  unsigned grown = 0;
+  for (unsigned t = 0; t < 4000; ++t) {
+    TqShape c;
+    c.seed = g.next(); c.tiles = 2 + g.next() % 199;
+    c.rest_segs = g.next() % 3 ? 1 + g.next() % 3000 : 0;
+    c.base = g.next() % 4 ? 1 + g.next() % 40 : 0; c.spread = 1 + g.next() % 60;          // base 0: tiles without a segment of their own accord
+    c.absent_every = g.next() % 3 ? 0 : 2 + g.next() % 9;
+    c.big_every = g.next() % 4 ? 0 : 1 + g.next() % 50; c.big = 1000 + g.next() % 9000;
+    uint32_t nseg = 0;
+    const std::vector<uint32_t> fs = make_fs(c, &nseg);
+    Knobs kn;
+    kn.tile_order = (int)(g.next() % 3); kn.tile_split_below = g.next() % 64; kn.tile_chunk = g.next() % 10;
+    const uint32_t wg = 64u << (g.next() % 3);
+    // a launch that holds few workgroups makes the chunks grow; never fewer than a chunk per range of a queue (each of
+    // the tiles and as many pieces of the rest), which is as far as growing goes
+    const size_t max_wgs = g.next() % 2 ? ((size_t)1 << 28) / wg : 8 * (size_t)(2 * (c.tiles + 8) + 2) + g.next() % 512;
+    const uint64_t rest_nnz = c.rest_segs ? (uint64_t)c.rest_segs * (1 + g.next() % 300) : 12345;
+    const TileQueuePlan qp = plan_tile_queues(fs, nseg, c.tiles, rest_nnz, wg, max_wgs, kn);
+    check_queues(qp, fs, nseg, max_wgs, "sweep case", t);
+    const uint32_t ch0 = kn.tile_chunk ? kn.tile_chunk : 2 * (wg / 64);
+    CHECK(qp.chunk_segs >= ch0 && qp.chunk_segs % ch0 == 0, "sweep case %u: chunks of %u segments from %u", t, qp.chunk_segs, ch0);
+    grown += qp.chunk_segs > ch0;
+  }
+  CHECK(grown >= 100, "the sweep reached the growing chunks %u times", grown);
+  // ---- the recorded cases: what the GPU tests force, one per tile_order, one where the chunks grow
+  const size_t W = (size_t)1 << 28;
+  const struct { const char *id; TqShape c; uint32_t wg, chunk; int order; uint32_t split_below; size_t max_wgs; uint32_t nnz_per_rest_seg; } cases[] = {
+    {"default",       {1, 12, 40, 3, 9, 0, 0, 0},        64,  0, 1, 8, W / 64,  37},
+    {"wg256_chunk8",  {1, 12, 40, 3, 9, 0, 0, 0},        256, 8, 1, 8, W / 256, 37},
+    {"wg128_chunk3",  {1, 12, 40, 3, 9, 0, 0, 0},        128, 3, 1, 8, W / 128, 37},
+    {"wg64_chunk1",   {1, 12, 40, 3, 9, 0, 0, 0},        64,  1, 1, 8, W / 64,  37},
+    {"tiles5",        {2, 5, 700, 20, 30, 0, 0, 0},      64,  0, 1, 8, W / 64,  12},
+    {"tiles7",        {3, 7, 2100, 150, 100, 0, 0, 0},   64,  0, 1, 8, W / 64,  60},
+    {"tiles8",        {4, 8, 300, 10, 25, 0, 0, 0},      64,  0, 1, 8, W / 64,  45},
+    {"tiles9",        {5, 9, 300, 10, 25, 0, 0, 0},      64,  0, 1, 8, W / 64,  45},
+    {"tiles12",       {6, 12, 300, 10, 25, 5, 0, 0},     64,  0, 1, 8, W / 64,  45},
+    {"tiles184",      {7, 184, 5000, 30, 90, 0, 23, 400}, 64, 0, 1, 8, W / 64,  500},
+    {"tiles184_norest", {8, 184, 0, 30, 90, 7, 0, 0},    64,  0, 1, 8, W / 64,  0},
+    {"order0",        {9, 22, 900, 15, 40, 0, 0, 0},     64,  0, 0, 8, W / 64,  30},
+    {"order1",        {9, 22, 900, 15, 40, 0, 0, 0},     64,  0, 1, 8, W / 64,  30},
+    {"order2",        {9, 22, 900, 15, 40, 0, 0, 0},     64,  0, 2, 8, W / 64,  30},
+    {"split_below32", {9, 22, 900, 15, 40, 0, 0, 0},     256, 8, 0, 32, W / 256, 30},
+    {"grow",          {10, 20, 4000, 50, 200, 0, 6, 5000}, 64, 0, 1, 8, 8 * 64, 20},
+  };
+  for (const auto &k : cases) {
+    uint32_t nseg = 0;
+    const std::vector<uint32_t> fs = make_fs(k.c, &nseg);
+    Knobs kn; kn.tile_order = k.order; kn.tile_split_below = k.split_below; kn.tile_chunk = k.chunk;
+    const uint64_t rest_nnz = k.c.rest_segs ? (uint64_t)k.c.rest_segs * k.nnz_per_rest_seg : 987654;
+    const TileQueuePlan qp = plan_tile_queues(fs, nseg, k.c.tiles, rest_nnz, k.wg, k.max_wgs, kn);
+    check_queues(qp, fs, nseg, k.max_wgs, k.id, 0);
+    if (print_cases) printf("tq %s %zu %u %016llx\n", k.id, qp.chunks.size(), qp.chunk_segs, (unsigned long long)fnv64(qp.chunks));
+  }
+}
+
+int main(int argc, char **argv)
+{
+  if (argc > 1 && !strcmp(argv[1], "tile-queues")) {
+    tile_checks(true);
+    if (g_fail) { fprintf(stderr, "plan_selftest: %d checks failed\n", g_fail); return 1; }
+    return 0;
+  }
   unsigned points = 0, runs = 0;
   for (uint32_t ws = 0; ws <= 3; ++ws)
     for (int pack = 0; pack <= 1; ++pack) {
@@ -175,6 +329,7 @@ int main()
     }
     for (int nch = -1; nch <= 8; ++nch) CHECK(has_rank_chunks(nch) == (nch >= 0 && nch < 8 && returned[nch]), "has_rank_chunks(%d)", nch);
   }
+  tile_checks(false);
   if (g_fail) { fprintf(stderr, "plan_selftest: %d checks failed\n", g_fail); return 1; }
   printf("# plan_selftest ok: %u points, %u runs\n", points, runs);
   return 0;

@@ -217,17 +217,6 @@ namespace {
 // per iteration, instead of as a hang in a later collective
 int check_comm_async(hpf_handle *h);
 
-// inside a do { ... } while (0) body that ends in the function's clean-up: sets rc and leaves the body
-#define HIPBRK(h, expr)                                                        \
-  {                                                                            \
-    hipError_t e_ = (expr);                                                    \
-    if (e_ != hipSuccess) {                                                    \
-      (h)->err = std::string(#expr) + ": " + hipGetErrorString(e_);            \
-      rc = (e_ == hipErrorOutOfMemory) ? HPF_ERR_OOM : HPF_ERR_HIP;            \
-      break;                                                                   \
-    }                                                                          \
-  }
-
 #define HIPCHK(h, expr)                                                        \
   do {                                                                         \
     hipError_t e_ = (expr);                                                    \
@@ -540,17 +529,15 @@ int d2h(hpf_handle *h, void *dst, const void *src, size_t bytes)
   return HPF_OK;
 }
 
-// Device side of a fused call (hpf_loo_ranks, hpf_rank_queries): the selected users, the mask list, the bit rows of one
-// batch of users (hpf_plan::rank_batch_users) and whatever else the call gets through alloc() -- all freed on the way
-// out, once the stream is idle (after an error something launched may still read them)
-struct FusedCtx {
+// Owner of the device temporaries of one call: what alloc() hands out is freed when the owner goes out of scope, once the
+// stream is idle (after an error something launched may still read it) -- unless it was released earlier or kept
+struct Scratch {
   hpf_handle *h;
   std::vector<void *> owned;
-  uint32_t *d_users = nullptr, *d_mitems = nullptr; uint64_t *d_mptr = nullptr, *d_bits = nullptr;
-  uint32_t words = 0, batch = 0;       // 64-bit words of a bit row; users per batch
-  explicit FusedCtx(hpf_handle *h_) : h(h_) {}
-  FusedCtx(const FusedCtx &) = delete;
-  ~FusedCtx() { (void)hipStreamSynchronize(h->stream); for (void *p : owned) dfree(p); }
+  explicit Scratch(hpf_handle *h_) : h(h_) {}
+  Scratch(const Scratch &) = delete;
+  Scratch &operator=(const Scratch &) = delete;
+  ~Scratch() { (void)hipStreamSynchronize(h->stream); for (void *p : owned) dfree(p); }
 
   // n zeroed elements, or a copy of src[0 .. n)
   template <typename T>
@@ -560,15 +547,38 @@ struct FusedCtx {
     if (*p) owned.push_back(*p);                                 // also when only dalloc's memset failed
     return rc || !src ? rc : h2d(h, *p, src, n * sizeof(T));
   }
+  // free this one now (a temporary of O(nnz) must not wait for the end of the call)
+  template <typename T>
+  void release(T *&p) { dfree(keep(p)); }
+  // give up ownership: the handle takes the pointer over
+  template <typename T>
+  T *keep(T *&p)
+  {
+    owned.erase(std::remove(owned.begin(), owned.end(), (void *)p), owned.end());
+    T *r = p; p = nullptr;
+    return r;
+  }
+};
+
+// Device side of a ranking call: the selected users and the mask list (upload) and, for the fused calls (hpf_loo_ranks,
+// hpf_rank_queries), the bit rows of one batch of users (bit_rows; hpf_plan::rank_batch_users)
+struct FusedCtx : Scratch {
+  uint32_t *d_users = nullptr, *d_mitems = nullptr; uint64_t *d_mptr = nullptr, *d_bits = nullptr;
+  uint32_t words = 0, batch = 0;       // 64-bit words of a bit row; users per batch
+  using Scratch::Scratch;
+
   int upload(const uint32_t *users, uint32_t n_sel, const uint64_t *mask_ptr, const uint32_t *mask_items)
+  {
+    int rc;
+    if ((rc = alloc(&d_users, n_sel, users)) || !mask_ptr) return rc;
+    if ((rc = alloc(&d_mptr, (size_t)n_sel + 1, mask_ptr))) return rc;
+    return alloc(&d_mitems, (size_t)mask_ptr[n_sel], mask_ptr[n_sel] ? mask_items : nullptr);
+  }
+  int bit_rows(uint32_t n_sel)
   {
     words = (h->it.rows + 63) / 64;
     batch = hpf_plan::rank_batch_users(h->it.rows, n_sel, h->loo_batch);
-    int rc;
-    if ((rc = alloc(&d_users, n_sel, users)) || (rc = alloc(&d_bits, (size_t)batch * words))) return rc;
-    if (!mask_ptr) return HPF_OK;
-    if ((rc = alloc(&d_mptr, (size_t)n_sel + 1, mask_ptr))) return rc;
-    return alloc(&d_mitems, (size_t)mask_ptr[n_sel], mask_ptr[n_sel] ? mask_items : nullptr);
+    return alloc(&d_bits, (size_t)batch * words);
   }
   // the bit rows of the selected users [b0, b0 + rows): cleared (alloc left them zero for the first batch) and set
   int mask_batch(uint32_t b0, uint32_t rows)
@@ -592,18 +602,18 @@ int copy_in(hpf_handle *h, double *dev, uint32_t ld, uint32_t col0, const double
   if (!rows || !cols) return HPF_OK;
   if (cols == ld && col0 == 0) return h2d(h, dev, host, (size_t)rows * cols * 8);
   const uint64_t rows_per = std::max<uint64_t>(1, (256u << 20) / ((uint64_t)cols * 8));
+  Scratch sc(h);
   double *tmp = nullptr; int rc;
-  if ((rc = dalloc(h, &tmp, (size_t)std::min<uint64_t>(rows, rows_per) * cols))) return rc;
-  for (uint64_t r0 = 0; r0 < rows && !rc; r0 += rows_per) {
+  if ((rc = sc.alloc(&tmp, (size_t)std::min<uint64_t>(rows, rows_per) * cols))) return rc;
+  for (uint64_t r0 = 0; r0 < rows; r0 += rows_per) {
     const uint64_t nr = std::min<uint64_t>(rows_per, rows - r0);
-    if ((rc = h2d(h, tmp, host + r0 * cols, (size_t)nr * cols * 8))) break;
+    if ((rc = h2d(h, tmp, host + r0 * cols, (size_t)nr * cols * 8))) return rc;
     hipLaunchKernelGGL(repack_in_kernel, dim3(grid_for(nr * cols)), dim3(256), 0, h->stream, tmp,
                        dev + r0 * ld, nr, cols, ld, col0);
-    rc = check_launch(h, "repack_in_kernel");
+    if ((rc = check_launch(h, "repack_in_kernel"))) return rc;
   }
-  if (!rc && hipStreamSynchronize(h->stream) != hipSuccess) { h->err = "copy_in: stream error"; rc = HPF_ERR_HIP; }
-  dfree(tmp);
-  return rc;
+  if (hipStreamSynchronize(h->stream) != hipSuccess) { h->err = "copy_in: stream error"; return HPF_ERR_HIP; }
+  return HPF_OK;
 }
 int copy_out(hpf_handle *h, const double *dev, uint32_t ld, uint32_t col0, double *host,
              uint32_t rows, uint32_t cols)
@@ -611,17 +621,17 @@ int copy_out(hpf_handle *h, const double *dev, uint32_t ld, uint32_t col0, doubl
   if (!rows || !cols) return HPF_OK;
   if (cols == ld && col0 == 0) return d2h(h, host, dev, (size_t)rows * cols * 8);
   const uint64_t rows_per = std::max<uint64_t>(1, (256u << 20) / ((uint64_t)cols * 8));
+  Scratch sc(h);
   double *tmp = nullptr; int rc;
-  if ((rc = dalloc(h, &tmp, (size_t)std::min<uint64_t>(rows, rows_per) * cols))) return rc;
-  for (uint64_t r0 = 0; r0 < rows && !rc; r0 += rows_per) {
+  if ((rc = sc.alloc(&tmp, (size_t)std::min<uint64_t>(rows, rows_per) * cols))) return rc;
+  for (uint64_t r0 = 0; r0 < rows; r0 += rows_per) {
     const uint64_t nr = std::min<uint64_t>(rows_per, rows - r0);
     hipLaunchKernelGGL(repack_out_kernel, dim3(grid_for(nr * cols)), dim3(256), 0, h->stream,
                        dev + r0 * ld, tmp, nr, cols, ld, col0);
-    if ((rc = check_launch(h, "repack_out_kernel"))) break;
-    rc = d2h(h, host + r0 * cols, tmp, (size_t)nr * cols * 8);
+    if ((rc = check_launch(h, "repack_out_kernel"))) return rc;
+    if ((rc = d2h(h, host + r0 * cols, tmp, (size_t)nr * cols * 8))) return rc;
   }
-  dfree(tmp);
-  return rc;
+  return HPF_OK;
 }
 // the same for a caller's DEVICE buffer (hpf_set_state_device / hpf_get_state_device)
 int copy_in_dev(hpf_handle *h, double *dev, uint32_t ld, uint32_t col0, const double *src,
@@ -664,15 +674,15 @@ int device_scan(hpf_handle *h, const IN *in, uint64_t n, uint64_t *out, bool wri
     return HPF_OK;
   }
   const uint64_t nb = (n + SCAN_CHUNK - 1) / SCAN_CHUNK;
+  Scratch sc(h);
   uint64_t *bsum = nullptr; int rc;
-  if ((rc = dalloc(h, &bsum, (size_t)nb))) return rc;
+  if ((rc = sc.alloc(&bsum, (size_t)nb))) return rc;
   hipLaunchKernelGGL((scan_reduce_kernel<IN>), dim3((uint32_t)nb), dim3(256), 0, h->stream, in, n, bsum);
   hipLaunchKernelGGL(scan_spine_kernel, dim3(1), dim3(256), 0, h->stream, bsum, nb);
   hipLaunchKernelGGL((scan_apply_kernel<IN>), dim3((uint32_t)nb), dim3(256), 0, h->stream, in, n, bsum, out,
                      write_total ? 1 : 0);
   rc = check_launch(h, "device_scan");
-  hipError_t e = hipStreamSynchronize(h->stream);
-  dfree(bsum);
+  const hipError_t e = hipStreamSynchronize(h->stream);
   if (!rc && e != hipSuccess) { h->err = std::string("device_scan: ") + hipGetErrorString(e); rc = HPF_ERR_HIP; }
   return rc;
 }
@@ -691,41 +701,37 @@ int device_side_work(hpf_handle *h, Side &s, const int64_t *dptr, uint32_t rows)
   s.p_idx = nullptr; s.p_val = nullptr; s.chunks = nullptr;
   s.nchunk_blocks = 0; s.tiles = 0; s.tile_rows = 0; s.chunk_segs = 0; s.tiled_nnz = 0; s.light_below = 0;
   if (rows == 0) return HPF_OK;
-  int rc = HPF_OK;
+  int rc;
+  Scratch sc(h);
   uint64_t *cnt[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
   uint32_t *bad = nullptr;
-  do {
-    for (int k = 0; k < 5 && !rc; ++k) rc = dalloc(h, &cnt[k], (size_t)rows + 1);
-    if (rc || (rc = dalloc(h, &bad, 1))) break;
-    SegPlan pl = {cnt[0], cnt[1], cnt[2], cnt[3], cnt[4]};
-    hipLaunchKernelGGL(seg_plan_kernel, dim3(grid_for(rows)), dim3(256), 0, h->stream, dptr, rows, h->seg_max,
-                       h->huge_slots, h->group_slots, pl, bad);
-    if ((rc = check_launch(h, "seg_plan_kernel"))) break;
-    for (int k = 0; k < 5 && !rc; ++k) rc = device_scan<uint64_t>(h, cnt[k], rows, cnt[k], true);
-    if (rc) break;
-    uint64_t tot[5]; uint32_t hb = 0;
-    hipError_t e = hipSuccess;
-    for (int k = 0; k < 5 && e == hipSuccess; ++k)
-      e = hipMemcpyAsync(&tot[k], cnt[k] + rows, 8, hipMemcpyDeviceToHost, h->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(&hb, bad, 4, hipMemcpyDeviceToHost, h->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    if (e != hipSuccess) { h->err = std::string("seg_plan_kernel: ") + hipGetErrorString(e); rc = HPF_ERR_HIP; break; }
-    if (hb) { h->err = "row pointers must start at 0 and be monotone"; rc = HPF_ERR_INVALID; break; }
-    if (tot[0] > 0xffffffffull || tot[1] > 0x7fffffffull) { h->err = "too many segments for 32-bit work lists"; rc = HPF_ERR_UNSUPPORTED; break; }
-    s.nseg = (uint32_t)tot[0]; s.npartial = (uint32_t)tot[1]; s.nlong = s.nlong_wave = (uint32_t)tot[2];
-    s.nhuge = (uint32_t)tot[3]; s.ngroup = s.npartial2 = (uint32_t)tot[4];
-    if ((rc = dalloc(h, &s.segs, s.nseg)) || (rc = dalloc(h, &s.longrows, s.nlong))) break;
-    if (s.ngroup && ((rc = dalloc(h, &s.grouprows, s.ngroup)) || (rc = dalloc(h, &s.hugerows, s.nhuge)))) break;
-    hipLaunchKernelGGL(seg_fill_kernel, dim3(grid_for(rows)), dim3(256), 0, h->stream, dptr, rows, h->seg_max,
-                       h->huge_slots, h->group_slots, pl, s.segs, s.longrows, s.hugerows, s.grouprows);
-    if ((rc = check_launch(h, "seg_fill_kernel"))) break;
-    if ((rc = dalloc(h, &s.partial, (size_t)s.npartial * h->ld))) break;
-    if (s.npartial2 && (rc = dalloc(h, &s.partial2, (size_t)s.npartial2 * h->ld))) break;
-    if (hipStreamSynchronize(h->stream) != hipSuccess) { h->err = "work-list build failed on the device"; rc = HPF_ERR_HIP; }
-  } while (0);
-  for (int k = 0; k < 5; ++k) dfree(cnt[k]);
-  dfree(bad);
-  return rc;
+  for (int k = 0; k < 5; ++k) if ((rc = sc.alloc(&cnt[k], (size_t)rows + 1))) return rc;
+  if ((rc = sc.alloc(&bad, 1))) return rc;
+  SegPlan pl = {cnt[0], cnt[1], cnt[2], cnt[3], cnt[4]};
+  hipLaunchKernelGGL(seg_plan_kernel, dim3(grid_for(rows)), dim3(256), 0, h->stream, dptr, rows, h->seg_max,
+                     h->huge_slots, h->group_slots, pl, bad);
+  if ((rc = check_launch(h, "seg_plan_kernel"))) return rc;
+  for (int k = 0; k < 5; ++k) if ((rc = device_scan<uint64_t>(h, cnt[k], rows, cnt[k], true))) return rc;
+  uint64_t tot[5]; uint32_t hb = 0;
+  hipError_t e = hipSuccess;
+  for (int k = 0; k < 5 && e == hipSuccess; ++k)
+    e = hipMemcpyAsync(&tot[k], cnt[k] + rows, 8, hipMemcpyDeviceToHost, h->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(&hb, bad, 4, hipMemcpyDeviceToHost, h->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+  if (e != hipSuccess) { h->err = std::string("seg_plan_kernel: ") + hipGetErrorString(e); return HPF_ERR_HIP; }
+  if (hb) { h->err = "row pointers must start at 0 and be monotone"; return HPF_ERR_INVALID; }
+  if (tot[0] > 0xffffffffull || tot[1] > 0x7fffffffull) { h->err = "too many segments for 32-bit work lists"; return HPF_ERR_UNSUPPORTED; }
+  s.nseg = (uint32_t)tot[0]; s.npartial = (uint32_t)tot[1]; s.nlong = s.nlong_wave = (uint32_t)tot[2];
+  s.nhuge = (uint32_t)tot[3]; s.ngroup = s.npartial2 = (uint32_t)tot[4];
+  if ((rc = dalloc(h, &s.segs, s.nseg)) || (rc = dalloc(h, &s.longrows, s.nlong))) return rc;
+  if (s.ngroup && ((rc = dalloc(h, &s.grouprows, s.ngroup)) || (rc = dalloc(h, &s.hugerows, s.nhuge)))) return rc;
+  hipLaunchKernelGGL(seg_fill_kernel, dim3(grid_for(rows)), dim3(256), 0, h->stream, dptr, rows, h->seg_max,
+                     h->huge_slots, h->group_slots, pl, s.segs, s.longrows, s.hugerows, s.grouprows);
+  if ((rc = check_launch(h, "seg_fill_kernel"))) return rc;
+  if ((rc = dalloc(h, &s.partial, (size_t)s.npartial * h->ld))) return rc;
+  if (s.npartial2 && (rc = dalloc(h, &s.partial2, (size_t)s.npartial2 * h->ld))) return rc;
+  if (hipStreamSynchronize(h->stream) != hipSuccess) { h->err = "work-list build failed on the device"; return HPF_ERR_HIP; }
+  return HPF_OK;
 }
 
 // ---- stable LSD radix sort of n records on the low `bits` bits of a 32-bit key, carrying a 32-bit
@@ -740,9 +746,11 @@ int radix_sort_records(hpf_handle *h, uint64_t n, uint32_t bits, const uint32_t 
   const uint32_t P = std::max<uint32_t>(1, (bits + RADIX_BITS - 1) / RADIX_BITS);
   const uint64_t ntiles = (n + RADIX_TILE - 1) / RADIX_TILE;
   const uint32_t nblk = (uint32_t)((ntiles + 3) / 4);
+  Scratch sc(h);
   uint64_t *counts = nullptr; uint32_t *bad = nullptr; int rc;
-  if ((rc = dalloc(h, &counts, (size_t)ntiles * RADIX_DIGITS)) || (rc = dalloc(h, &bad, 1))) { dfree(counts); dfree(bad); return rc; }
-  for (uint32_t p = 0; p < P && !rc; ++p) {
+  *res = (int)((P - 1) & 1);
+  if ((rc = sc.alloc(&counts, (size_t)ntiles * RADIX_DIGITS)) || (rc = sc.alloc(&bad, 1))) return rc;
+  for (uint32_t p = 0; p < P; ++p) {
     const int o = (int)(p & 1), i = o ^ 1;
     RadixArgs a;
     a.keys_in = p == 0 ? in_k : b.K[i];
@@ -756,322 +764,224 @@ int radix_sort_records(hpf_handle *h, uint64_t n, uint32_t bits, const uint32_t 
     a.offsets = counts; a.nnz = n; a.ntiles = ntiles; a.shift = p * RADIX_BITS;
     hipLaunchKernelGGL(radix_count_kernel, dim3(nblk), dim3(256), 0, h->stream, a.keys_in, n, a.shift, ntiles, counts,
                        0xffffffffu, bad);
-    if ((rc = check_launch(h, "radix_count_kernel"))) break;
-    if ((rc = device_scan<uint64_t>(h, counts, ntiles * RADIX_DIGITS, counts, false))) break;
+    if ((rc = check_launch(h, "radix_count_kernel"))) return rc;
+    if ((rc = device_scan<uint64_t>(h, counts, ntiles * RADIX_DIGITS, counts, false))) return rc;
     hipLaunchKernelGGL(radix_scatter_kernel, dim3(nblk), dim3(256), 0, h->stream, a);
-    rc = check_launch(h, "radix_scatter_kernel");
+    if ((rc = check_launch(h, "radix_scatter_kernel"))) return rc;
   }
-  if (!rc && hipStreamSynchronize(h->stream) != hipSuccess) { h->err = "record sort failed on the device"; rc = HPF_ERR_HIP; }
-  dfree(counts); dfree(bad);
-  *res = (int)((P - 1) & 1);
-  return rc;
+  if (hipStreamSynchronize(h->stream) != hipSuccess) { h->err = "record sort failed on the device"; return HPF_ERR_HIP; }
+  return HPF_OK;
 }
 
 uint32_t bits_for(uint64_t count) { uint32_t b = 0; while (b < 32 && ((uint64_t)1 << b) < count) ++b; return std::max<uint32_t>(b, 1); }
 
-// Tiled work list of one side (hpf_build.hpp "Tiled phi pass").  Called after
-// device_side_work: when the policy finds the side worth tiling, the plain work list is replaced.
-//   ptr       the side's own row pointers (rows + 1), idx / val its nonzeros in row order
-//   ptr_oth   row pointers of the gathered side (rows_oth + 1): degrees for the hot-set policy
-// Policy (auto):  the gathered matrix must be larger than twice a tile.
-//   "ranges"  tiles of T consecutive gathered rows; owner rows with at least tiles * min_run nonzeros are
-//             heavy (their nonzeros are regrouped), taken when those hold >= 15 % of the nonzeros
-// Forced by HPF_TILE (experimental knob): 0 never, 1 ranges whenever there are two tiles.
+// ---- Tiled work list of one side (hpf_build.hpp "Tiled phi pass"), stage by stage.  What a stage
+// allocates belongs to the caller's Scratch; what the next stage no longer reads is released at once (the temporaries are
+// 26 bytes per nonzero).
+
+// the side's nonzeros sorted by (tile of the gathered row | 0 for a light owner row), stable: key, owner row, index, rating
+struct TiledRecords { uint32_t *key = nullptr, *row = nullptr, *idx = nullptr; uint8_t *val = nullptr; };
+int tile_sort_records(hpf_handle *h, Scratch &sc, const Side &s, const int64_t *ptr, uint32_t rows_oth, uint64_t nnz,
+                      const hpf_plan::TilePolicy &tp, TiledRecords *out)
+{
+  int rc;
+  uint32_t *tilemap = nullptr, *key0 = nullptr, *row0 = nullptr;
+  if ((rc = sc.alloc(&tilemap, rows_oth)) || (rc = sc.alloc(&key0, (size_t)nnz)) || (rc = sc.alloc(&row0, (size_t)nnz))) return rc;
+  hipLaunchKernelGGL(tile_map_kernel, dim3(grid_for(rows_oth)), dim3(256), 0, h->stream, tilemap, rows_oth, tp.T);
+  const uint32_t wblk = (uint32_t)(((nnz + RADIX_TILE - 1) / RADIX_TILE + 3) / 4);
+  hipLaunchKernelGGL(tile_key_kernel, dim3(wblk), dim3(256), 0, h->stream, ptr, s.rows, s.idx, nnz, tilemap, tp.light_below,
+                     key0, row0);
+  if ((rc = check_launch(h, "tile_key_kernel"))) return rc;
+  const uint32_t kbits = bits_for(tp.tiles + 1), KP = (kbits + RADIX_BITS - 1) / RADIX_BITS;
+  SortSets b = {{nullptr, nullptr}, {nullptr, nullptr}, {nullptr, nullptr}, {nullptr, nullptr}};
+  for (int k = 0; k < (KP > 1 ? 2 : 1); ++k) {
+    if ((rc = sc.alloc(&b.K[k], (size_t)nnz)) || (rc = sc.alloc(&b.U[k], (size_t)nnz)) || (rc = sc.alloc(&b.X[k], (size_t)nnz))) return rc;
+    if (s.val && (rc = sc.alloc(&b.V[k], (size_t)nnz))) return rc;
+  }
+  int r = 0;
+  if ((rc = radix_sort_records(h, nnz, kbits, key0, row0, s.idx, s.val, nullptr, 0, b, &r))) return rc;
+  sc.release(key0); sc.release(row0); sc.release(tilemap);
+  sc.release(b.K[r ^ 1]); sc.release(b.U[r ^ 1]); sc.release(b.X[r ^ 1]); sc.release(b.V[r ^ 1]);      // the set that lost
+  *out = {b.K[r], b.U[r], b.X[r], b.V[r]};
+  return HPF_OK;
+}
+
+// the segments of the sorted records (<= seg_max nonzeros of one owner row and one key), each one's owner row, and the
+// first segment of every key on the host; rec.key and rec.row are released.  nseg == 0: no list the pass can index
+struct TiledSegs { Seg *segs = nullptr; uint32_t *seg_row = nullptr; uint32_t nseg = 0; std::vector<uint32_t> fs; };
+int tile_segments(hpf_handle *h, Scratch &sc, uint64_t nnz, uint32_t nkeys, TiledRecords &rec, TiledSegs *out)
+{
+  int rc;
+  const uint64_t nwt = (nnz + RADIX_TILE - 1) / RADIX_TILE;
+  const uint32_t wblk = (uint32_t)((nwt + 3) / 4);
+  uint64_t *cnt = nullptr; uint32_t *seg_key = nullptr, *first_seg = nullptr;
+  if ((rc = sc.alloc(&cnt, (size_t)nwt + 1))) return rc;
+  hipLaunchKernelGGL(seg_count_kernel, dim3(wblk), dim3(256), 0, h->stream, rec.key, rec.row, nnz, h->seg_max, cnt);
+  if ((rc = check_launch(h, "seg_count_kernel"))) return rc;
+  if ((rc = device_scan<uint64_t>(h, cnt, nwt, cnt, true))) return rc;
+  uint64_t nseg64 = 0;
+  HIPCHK(h, hipMemcpyAsync(&nseg64, cnt + nwt, 8, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  if (nseg64 == 0 || nseg64 > 0x7fffffffull) return HPF_OK;
+  const uint32_t nseg = (uint32_t)nseg64;
+  if ((rc = sc.alloc(&out->segs, nseg)) || (rc = sc.alloc(&out->seg_row, nseg)) || (rc = sc.alloc(&seg_key, nseg)) ||
+      (rc = sc.alloc(&first_seg, nkeys))) return rc;
+  HIPCHK(h, hipMemsetAsync(first_seg, 0xff, (size_t)nkeys * 4, h->stream));
+  hipLaunchKernelGGL(seg_emit_kernel, dim3(wblk), dim3(256), 0, h->stream, rec.key, rec.row, nnz, h->seg_max, cnt, out->segs, out->seg_row, seg_key);
+  hipLaunchKernelGGL(seg_len_kernel, dim3(grid_for(nseg)), dim3(256), 0, h->stream, out->segs, nseg, nnz, seg_key, first_seg);
+  if ((rc = check_launch(h, "seg_emit_kernel"))) return rc;
+  out->fs.resize(nkeys);
+  HIPCHK(h, hipMemcpyAsync(out->fs.data(), first_seg, (size_t)nkeys * 4, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  sc.release(rec.key); sc.release(rec.row);
+  sc.release(cnt); sc.release(seg_key); sc.release(first_seg);
+  out->nseg = nseg;
+  return HPF_OK;
+}
+
+// per owner row: its segments in key order -> partial slots and combine lists (the segments get their slots).
+// fits == false: more partial slots than the work lists index
+struct TiledSlots {
+  LongRow *longs = nullptr, *huges = nullptr, *groups = nullptr; double *partial = nullptr, *partial2 = nullptr;
+  uint32_t npartial = 0, nlong = 0, nlong_wave = 0, nhuge = 0, ngroup = 0; bool fits = false;
+};
+int tile_slots(hpf_handle *h, Scratch &sc, uint32_t rows, const TiledSegs &sg, TiledSlots *out)
+{
+  int rc;
+  const uint32_t nseg = sg.nseg;
+  uint32_t *iota = nullptr; int64_t *segptr = nullptr; uint64_t *pl[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+  SortSets sb = {{nullptr, nullptr}, {nullptr, nullptr}, {nullptr, nullptr}, {nullptr, nullptr}};
+  if ((rc = sc.alloc(&iota, nseg))) return rc;
+  hipLaunchKernelGGL(iota_kernel, dim3(grid_for(nseg)), dim3(256), 0, h->stream, iota, nseg);
+  for (int k = 0; k < 2; ++k) if ((rc = sc.alloc(&sb.K[k], nseg)) || (rc = sc.alloc(&sb.U[k], nseg))) return rc;
+  int sr = 0;
+  if ((rc = radix_sort_records(h, nseg, bits_for(rows), sg.seg_row, iota, nullptr, nullptr, nullptr, 0, sb, &sr))) return rc;
+  if ((rc = sc.alloc(&segptr, (size_t)rows + 1))) return rc;
+  hipLaunchKernelGGL(colptr_from_sorted_kernel, dim3(grid_for(nseg)), dim3(256), 0, h->stream, sb.K[sr], (uint64_t)nseg, rows, segptr);
+  for (int k = 0; k < 5; ++k) if ((rc = sc.alloc(&pl[k], (size_t)rows + 1))) return rc;
+  SegPlan plan = {pl[0], pl[1], pl[2], pl[3], pl[4]};
+  hipLaunchKernelGGL(slot_plan_kernel, dim3(grid_for(rows)), dim3(256), 0, h->stream, segptr, rows, h->huge_slots,
+                     h->group_slots, plan);
+  if ((rc = check_launch(h, "slot_plan_kernel"))) return rc;
+  for (int k = 0; k < 5; ++k) if ((rc = device_scan<uint64_t>(h, pl[k], rows, pl[k], true))) return rc;
+  uint64_t tot[5];
+  for (int k = 0; k < 5; ++k) HIPCHK(h, hipMemcpyAsync(&tot[k], pl[k] + rows, 8, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  if (tot[1] > 0x7fffffffull) return HPF_OK;
+  TiledSlots &o = *out;
+  o.npartial = (uint32_t)tot[1]; o.nlong = (uint32_t)tot[2]; o.nhuge = (uint32_t)tot[3]; o.ngroup = (uint32_t)tot[4];
+  if ((rc = sc.alloc(&o.longs, o.nlong))) return rc;
+  if (o.ngroup && ((rc = sc.alloc(&o.groups, o.ngroup)) || (rc = sc.alloc(&o.huges, o.nhuge)))) return rc;
+  hipLaunchKernelGGL(slot_fill_kernel, dim3(grid_for(rows)), dim3(256), 0, h->stream, segptr, rows, h->huge_slots,
+                     h->group_slots, plan, sb.U[sr], sg.segs, o.longs, o.huges, o.groups);
+  if ((rc = check_launch(h, "slot_fill_kernel"))) return rc;
+  if ((rc = sc.alloc(&o.partial, (size_t)o.npartial * h->ld))) return rc;
+  if (o.ngroup && (rc = sc.alloc(&o.partial2, (size_t)o.ngroup * h->ld))) return rc;
+  // the combine gives the rows with more than COMBINE_SPLIT partials a workgroup each: they go behind the others (a stable
+  // partition of the row-ordered list: a function of the matrix alone)
+  // (the rows WITHOUT any nonzero stay in the wave kernel's part: taking them out -- cleared once, and again only after
+  // an export or a hand-over had written S -- was built in round 5 and bought nothing measurable: C2's 48 000 of them
+  // are 40 MB of zeros, ~10 us of a 45 us launch that the multi-segment light rows' chains set; experiments.md)
+  o.nlong_wave = o.nlong;
+  if (o.nlong) {
+    std::vector<LongRow> lr(o.nlong), big;
+    HIPCHK(h, hipMemcpyAsync(lr.data(), o.longs, (size_t)o.nlong * sizeof(LongRow), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    size_t w = 0;
+    for (const LongRow &x : lr) { if (x.nslots > COMBINE_SPLIT) big.push_back(x); else lr[w++] = x; }
+    if (!big.empty()) {
+      std::copy(big.begin(), big.end(), lr.begin() + (ptrdiff_t)w);
+      o.nlong_wave = (uint32_t)w;
+      HIPCHK(h, hipMemcpyAsync(o.longs, lr.data(), (size_t)o.nlong * sizeof(LongRow), hipMemcpyHostToDevice, h->stream));
+      HIPCHK(h, hipStreamSynchronize(h->stream));
+    }
+  }
+  o.fits = true;
+  return HPF_OK;
+}
+
+// the queues and chunks of the segments (hpf_plan::plan_tile_queues) on the device; *chunks stays null where there is no list
+int tile_chunks(hpf_handle *h, Scratch &sc, const TiledSegs &sg, uint32_t tiles, uint64_t nnz, uint2 **chunks, uint32_t *nchunks, uint32_t *chunk_segs)
+{
+  uint64_t rest_nnz = nnz;
+  const uint32_t rest_end = hpf_plan::tile_rest_end(sg.fs, sg.nseg);
+  if (rest_end && rest_end < sg.nseg) {
+    Seg first_tiled;
+    HIPCHK(h, hipMemcpy(&first_tiled, sg.segs + rest_end, sizeof(Seg), hipMemcpyDeviceToHost));
+    rest_nnz = (uint64_t)first_tiled.start;
+  }
+  const uint32_t wg = h->wg_of(true);
+  const hpf_plan::TileQueuePlan qp = hpf_plan::plan_tile_queues(sg.fs, sg.nseg, tiles, rest_nnz, wg, ((size_t)1 << 28) / wg, *h);
+  if (!qp.ok) return HPF_OK;
+  static_assert(sizeof(hpf_plan::TileChunk) == sizeof(uint2) && offsetof(hpf_plan::TileChunk, x) == offsetof(uint2, x) &&
+                offsetof(hpf_plan::TileChunk, y) == offsetof(uint2, y), "chunk");
+  int rc;
+  if ((rc = sc.alloc(chunks, qp.chunks.size()))) return rc;
+  HIPCHK(h, hipMemcpyAsync(*chunks, qp.chunks.data(), qp.chunks.size() * sizeof(uint2), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  *nchunks = (uint32_t)qp.chunks.size(); *chunk_segs = qp.chunk_segs;
+  return HPF_OK;
+}
+
+// Replaces the side's plain work list by the tiled one -- once the new one is complete; until then the side is not touched
+int tile_side(hpf_handle *h, Side &s, const int64_t *ptr, uint32_t rows_oth, uint64_t nnz, const hpf_plan::TilePolicy &tp, uint64_t heavy_nnz)
+{
+  int rc;
+  Scratch sc(h);
+  TiledRecords rec; TiledSegs sg; TiledSlots sl;
+  uint2 *chunks = nullptr; uint32_t nchunks = 0, chunk_segs = 0;
+  if ((rc = tile_sort_records(h, sc, s, ptr, rows_oth, nnz, tp, &rec))) return rc;
+  if ((rc = tile_segments(h, sc, nnz, tp.tiles + 1, rec, &sg)) || !sg.nseg) return rc;
+  if ((rc = tile_slots(h, sc, s.rows, sg, &sl)) || !sl.fits) return rc;
+  if ((rc = tile_chunks(h, sc, sg, tp.tiles, nnz, &chunks, &nchunks, &chunk_segs)) || !chunks) return rc;
+  dfree(s.segs); dfree(s.longrows); dfree(s.grouprows); dfree(s.hugerows); dfree(s.partial); dfree(s.partial2);
+  s.segs = sc.keep(sg.segs); s.nseg = sg.nseg;
+  s.longrows = sc.keep(sl.longs); s.nlong = sl.nlong; s.nlong_wave = sl.nlong_wave;
+  s.grouprows = sc.keep(sl.groups); s.ngroup = sl.ngroup;
+  s.hugerows = sc.keep(sl.huges); s.nhuge = sl.nhuge;
+  s.partial = sc.keep(sl.partial); s.npartial = sl.npartial;
+  s.partial2 = sc.keep(sl.partial2); s.npartial2 = sl.ngroup;
+  s.p_idx = sc.keep(rec.idx); s.p_val = sc.keep(rec.val);
+  s.chunks = sc.keep(chunks); s.nchunk_blocks = nchunks;
+  s.tiles = tp.tiles; s.tile_rows = tp.T; s.tiled_nnz = heavy_nnz; s.light_below = tp.light_below; s.chunk_segs = chunk_segs;
+  return HPF_OK;
+}
+
+// Called after device_side_work: when the policy (hpf_plan::tile_policy) finds the side worth tiling, the plain work list
+// is replaced.
+//   ptr       the side's own row pointers (rows + 1), s.idx / s.val its nonzeros in row order
+//   rows_oth  rows of the gathered side, row_bytes bytes each
+// Auto mode takes the "ranges" policy when the heavy rows hold >= 15 % (tile_min_share) of the nonzeros.
 int build_tiled_side(hpf_handle *h, Side &s, const int64_t *ptr, uint32_t rows_oth, uint64_t nnz, size_t row_bytes)
 {
-  if (!((h->tile_sides >> (&s == &h->it ? 1 : 0)) & 1)) return HPF_OK;
-  if (h->tile_mode == 0 || h->cfg.tiling == 1 || nnz == 0 || s.rows == 0) return HPF_OK;      // (>= 2^32 nonzeros: positions are 64-bit throughout;
-                                                                                              //  segments and partial slots must number < 2^31, checked below)
-  const uint32_t T = (uint32_t)std::max<uint64_t>(h->tile_bytes / row_bytes, 1);
-  const uint32_t tiles = (rows_oth + T - 1) / T;
-  if (tiles < 2 || tiles > 65534) return HPF_OK;
-  if (h->tile_mode == 2 && (uint64_t)rows_oth * row_bytes < 2 * h->tile_bytes + h->tile_bytes / 2) return HPF_OK;
-  int rc = HPF_OK;
-  // a gathered matrix of a few tiles is already served largely from L2 when the ratings are skewed (the popular
-  // rows stay resident): regrouping then pays only for rows that meet a tile many times (size sweep, m = 20 000:
-  // four tiles, user pass 3.19 ms row-major, 3.64 ms with runs of 16)
-  // ... and a run is worth its fixed work from two batches on: a batch is 64 / G nonzeros (K = 50: G = 4, sixteen
-  // per batch -- with runs of 16 its ten-tile user side went 2.31 -> 2.68 ms)
-  // Round 5: with one wave per workgroup on a tiled side (hpf_handle::phi_wg) a run costs less, and the bar of 16 came down
-  // to 12 where a batch holds eight nonzeros or fewer (C2 8.42 -> 8.34 ms, a C3 shard 24.3 -> 23.9; 10 is better still at C2
-  // and worse on the shard; C4 is flat from 10 to 16; K = 50's two batches of sixteen stay: 24 loses 1 %; experiments.md)
-  const uint32_t per_batch = h->nz_per_batch();
-  const uint32_t min_run = h->tile_min_run ? h->tile_min_run                    // HPF_TILE_RUN: as given
-                                           : (per_batch >= 16u ? 2u * per_batch : 12u);
-  uint64_t light_below = (uint64_t)tiles * min_run * (tiles < 8 ? 4u : 1u);
-  if (h->tile_mode == 1) light_below = 0;                         // forced: every row is regrouped
-  unsigned long long *stat = nullptr;
-  uint64_t heavy_rows = 0, heavy_nnz = nnz;
-  if (light_below) {
-    if ((rc = dalloc(h, &stat, 2))) return rc;
-    hipLaunchKernelGGL(deg_ge_kernel, dim3(grid_for(s.rows)), dim3(256), 0, h->stream, ptr, s.rows, light_below, stat);
-    unsigned long long hv[2] = {0, 0};
+  const bool item_side = &s == &h->it;
+  const hpf_plan::TilePolicy tp = hpf_plan::tile_policy(rows_oth, row_bytes, nnz, s.rows, h->nz_per_batch(), item_side, *h, h->cfg.tiling);
+  if (!tp.tile) return HPF_OK;
+  int rc;
+  uint64_t heavy_nnz = nnz;
+  if (tp.light_below) {
+    Scratch sc(h);
+    unsigned long long *stat = nullptr;
+    if ((rc = sc.alloc(&stat, 2))) return rc;
+    hipLaunchKernelGGL(deg_ge_kernel, dim3(grid_for(s.rows)), dim3(256), 0, h->stream, ptr, s.rows, tp.light_below, stat);
+    unsigned long long hv[2] = {0, 0};       // heavy rows, their nonzeros
     hipError_t e = hipMemcpyAsync(hv, stat, 16, hipMemcpyDeviceToHost, h->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    dfree(stat);
     if (e != hipSuccess) { h->err = std::string("deg_ge_kernel: ") + hipGetErrorString(e); return HPF_ERR_HIP; }
-    heavy_rows = hv[0]; heavy_nnz = hv[1];
+    heavy_nnz = hv[1];
     if ((double)heavy_nnz < h->tile_min_share * (double)nnz) return HPF_OK;
   }
-  (void)heavy_rows;
-  {
-    // Room for the temporaries (26 bytes per nonzero)?  Decided from what this handle holds and the size of the device, not
-    // from the free memory of the moment: tiling changes the order of a row's sum, and whether a side is tiled
-    // must be a function of the job, not of what else happens to be allocated.  If the allocations fail all the same the
-    // side stays row-major and hpf_work_info.notes says so.
-    size_t fr = 0, tot = 0;
-    const double by = h->u.val ? 1.0 : 0.0;
-    const double resident = 5.0 * 8.0 * (double)h->ld * ((double)h->u.rows + (double)h->it.rows)        // S, E, L, W + vectors of both sides
-                          + (double)nnz * (3.0 * (4.0 + by));                                          // CSR, CSC and the other side's tiled copy
-    if (hipMemGetInfo(&fr, &tot) == hipSuccess && resident + (double)nnz * (26.0 + 4.0 + by) + (double)(1ull << 30) > 0.9 * (double)tot) {
-      h->notes |= (&s == &h->it ? 2u : 1u);
-      return HPF_OK;
-    }
+  // if the allocations fail although the rule finds room, the side stays row-major and hpf_work_info.notes says so
+  size_t fr = 0, tot = 0;
+  if (hipMemGetInfo(&fr, &tot) == hipSuccess && !hpf_plan::tiling_fits(h->ld, h->u.rows, h->it.rows, nnz, h->u.val != nullptr, tot)) {
+    h->notes |= (item_side ? 2u : 1u);
+    return HPF_OK;
   }
-
-  const uint32_t nkeys = tiles + 1;
-  uint32_t *tilemap = nullptr, *first_seg = nullptr, *seg_row = nullptr, *seg_key = nullptr, *iota = nullptr;
-  uint64_t *cnt = nullptr, *pl[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-  int64_t *segptr = nullptr;
-  SortSets b = {{nullptr, nullptr}, {nullptr, nullptr}, {nullptr, nullptr}, {nullptr, nullptr}};
-  SortSets sb = {{nullptr, nullptr}, {nullptr, nullptr}, {nullptr, nullptr}, {nullptr, nullptr}};
-  uint32_t *key0 = nullptr, *row0 = nullptr;
-  Seg *segs = nullptr; LongRow *longs = nullptr, *huges = nullptr, *groups = nullptr;
-  double *partial = nullptr, *partial2 = nullptr; uint2 *chunks_dev = nullptr;
-  uint32_t *keep_idx = nullptr; uint8_t *keep_val = nullptr;
-  bool done = false;
-  do {
-    // ---- keys and the sort
-    if ((rc = dalloc(h, &tilemap, rows_oth)) || (rc = dalloc(h, &key0, (size_t)nnz)) || (rc = dalloc(h, &row0, (size_t)nnz))) break;
-    hipLaunchKernelGGL(tile_map_kernel, dim3(grid_for(rows_oth)), dim3(256), 0, h->stream, tilemap, rows_oth, T);
-    const uint64_t nwt = (nnz + RADIX_TILE - 1) / RADIX_TILE;
-    const uint32_t wblk = (uint32_t)((nwt + 3) / 4);
-    hipLaunchKernelGGL(tile_key_kernel, dim3(wblk), dim3(256), 0, h->stream, ptr, s.rows, s.idx, nnz, tilemap, light_below,
-                       key0, row0);
-    if ((rc = check_launch(h, "tile_key_kernel"))) break;
-    const uint32_t kbits = bits_for(nkeys), KP = (kbits + RADIX_BITS - 1) / RADIX_BITS;
-    for (int k = 0; k < (KP > 1 ? 2 : 1) && !rc; ++k) {
-      if ((rc = dalloc(h, &b.K[k], (size_t)nnz)) || (rc = dalloc(h, &b.U[k], (size_t)nnz)) || (rc = dalloc(h, &b.X[k], (size_t)nnz))) break;
-      if (s.val) rc = dalloc(h, &b.V[k], (size_t)nnz);
-    }
-    if (rc) break;
-    int r = 0;
-    if ((rc = radix_sort_records(h, nnz, kbits, key0, row0, s.idx, s.val, nullptr, 0, b, &r))) break;
-    dfree(key0); key0 = nullptr; dfree(row0); row0 = nullptr; dfree(tilemap); tilemap = nullptr;
-    const uint32_t *skey = b.K[r], *srow = b.U[r];
-    keep_idx = b.X[r]; keep_val = b.V[r]; b.X[r] = nullptr; b.V[r] = nullptr;
-    for (int k = 0; k < 2; ++k) if (k != r) { dfree(b.K[k]); dfree(b.U[k]); dfree(b.X[k]); dfree(b.V[k]); b.K[k] = b.U[k] = b.X[k] = nullptr; b.V[k] = nullptr; }
-
-    // ---- segments
-    if ((rc = dalloc(h, &cnt, (size_t)nwt + 1))) break;
-    hipLaunchKernelGGL(seg_count_kernel, dim3(wblk), dim3(256), 0, h->stream, skey, srow, nnz, h->seg_max, cnt);
-    if ((rc = check_launch(h, "seg_count_kernel"))) break;
-    if ((rc = device_scan<uint64_t>(h, cnt, nwt, cnt, true))) break;
-    uint64_t nseg64 = 0;
-    HIPBRK(h, hipMemcpyAsync(&nseg64, cnt + nwt, 8, hipMemcpyDeviceToHost, h->stream));
-    HIPBRK(h, hipStreamSynchronize(h->stream));
-    if (nseg64 == 0 || nseg64 > 0x7fffffffull) break;              // leaves the plain list in place
-    const uint32_t nseg = (uint32_t)nseg64;
-    if ((rc = dalloc(h, &segs, nseg)) || (rc = dalloc(h, &seg_row, nseg)) || (rc = dalloc(h, &seg_key, nseg)) ||
-        (rc = dalloc(h, &first_seg, nkeys))) break;
-    HIPBRK(h, hipMemsetAsync(first_seg, 0xff, (size_t)nkeys * 4, h->stream));
-    hipLaunchKernelGGL(seg_emit_kernel, dim3(wblk), dim3(256), 0, h->stream, skey, srow, nnz, h->seg_max, cnt, segs, seg_row, seg_key);
-    hipLaunchKernelGGL(seg_len_kernel, dim3(grid_for(nseg)), dim3(256), 0, h->stream, segs, nseg, nnz, seg_key, first_seg);
-    if ((rc = check_launch(h, "seg_emit_kernel"))) break;
-    std::vector<uint32_t> fs(nkeys);
-    HIPBRK(h, hipMemcpyAsync(fs.data(), first_seg, (size_t)nkeys * 4, hipMemcpyDeviceToHost, h->stream));
-    HIPBRK(h, hipStreamSynchronize(h->stream));
-    dfree(b.K[r]); dfree(b.U[r]); b.K[r] = b.U[r] = nullptr;
-    dfree(cnt); cnt = nullptr; dfree(seg_key); seg_key = nullptr; dfree(first_seg); first_seg = nullptr;
-
-    // ---- per owner row: its segments in key order -> partial slots and combine lists
-    if ((rc = dalloc(h, &iota, nseg))) break;
-    hipLaunchKernelGGL(iota_kernel, dim3(grid_for(nseg)), dim3(256), 0, h->stream, iota, nseg);
-    for (int k = 0; k < 2 && !rc; ++k) { if ((rc = dalloc(h, &sb.K[k], nseg))) break; rc = dalloc(h, &sb.U[k], nseg); }
-    if (rc) break;
-    int sr = 0;
-    if ((rc = radix_sort_records(h, nseg, bits_for(s.rows), seg_row, iota, nullptr, nullptr, nullptr, 0, sb, &sr))) break;
-    if ((rc = dalloc(h, &segptr, (size_t)s.rows + 1))) break;
-    hipLaunchKernelGGL(colptr_from_sorted_kernel, dim3(grid_for(nseg)), dim3(256), 0, h->stream, sb.K[sr], (uint64_t)nseg, s.rows, segptr);
-    for (int k = 0; k < 5 && !rc; ++k) rc = dalloc(h, &pl[k], (size_t)s.rows + 1);
-    if (rc) break;
-    SegPlan plan = {pl[0], pl[1], pl[2], pl[3], pl[4]};
-    hipLaunchKernelGGL(slot_plan_kernel, dim3(grid_for(s.rows)), dim3(256), 0, h->stream, segptr, s.rows, h->huge_slots,
-                       h->group_slots, plan);
-    if ((rc = check_launch(h, "slot_plan_kernel"))) break;
-    for (int k = 0; k < 5 && !rc; ++k) rc = device_scan<uint64_t>(h, pl[k], s.rows, pl[k], true);
-    if (rc) break;
-    uint64_t tot[5];
-    {
-      hipError_t e = hipSuccess;
-      for (int k = 0; k < 5 && e == hipSuccess; ++k) e = hipMemcpyAsync(&tot[k], pl[k] + s.rows, 8, hipMemcpyDeviceToHost, h->stream);
-      HIPBRK(h, e);
-    }
-    HIPBRK(h, hipStreamSynchronize(h->stream));
-    if (tot[1] > 0x7fffffffull) break;
-    const uint32_t npartial = (uint32_t)tot[1], nlong = (uint32_t)tot[2], nhuge = (uint32_t)tot[3], ngroup = (uint32_t)tot[4];
-    if ((rc = dalloc(h, &longs, nlong))) break;
-    if (ngroup && ((rc = dalloc(h, &groups, ngroup)) || (rc = dalloc(h, &huges, nhuge)))) break;
-    hipLaunchKernelGGL(slot_fill_kernel, dim3(grid_for(s.rows)), dim3(256), 0, h->stream, segptr, s.rows, h->huge_slots,
-                       h->group_slots, plan, sb.U[sr], segs, longs, huges, groups);
-    if ((rc = check_launch(h, "slot_fill_kernel"))) break;
-    if ((rc = dalloc(h, &partial, (size_t)npartial * h->ld))) break;
-    if (ngroup && (rc = dalloc(h, &partial2, (size_t)ngroup * h->ld))) break;
-    // the combine gives the rows with more than COMBINE_SPLIT partials a workgroup each: they go behind the others (a stable
-    // partition of the row-ordered list: a function of the matrix alone)
-    // (the rows WITHOUT any nonzero stay in the wave kernel's part: taking them out -- cleared once, and again only after
-    // an export or a hand-over had written S -- was built in round 5 and bought nothing measurable: C2's 48 000 of them
-    // are 40 MB of zeros, ~10 us of a 45 us launch that the multi-segment light rows' chains set; experiments.md)
-    uint32_t nlong_wave = nlong;
-    if (nlong) {
-      std::vector<LongRow> lr(nlong), big;
-      HIPBRK(h, hipMemcpyAsync(lr.data(), longs, (size_t)nlong * sizeof(LongRow), hipMemcpyDeviceToHost, h->stream));
-      HIPBRK(h, hipStreamSynchronize(h->stream));
-      size_t w = 0;
-      for (const LongRow &x : lr) { if (x.nslots > COMBINE_SPLIT) big.push_back(x); else lr[w++] = x; }
-      if (!big.empty()) {
-        std::copy(big.begin(), big.end(), lr.begin() + (ptrdiff_t)w);
-        nlong_wave = (uint32_t)w;
-        HIPBRK(h, hipMemcpyAsync(longs, lr.data(), (size_t)nlong * sizeof(LongRow), hipMemcpyHostToDevice, h->stream));
-        HIPBRK(h, hipStreamSynchronize(h->stream));
-      }
-    }
-
-    // ---- chunks: eight queues, one per XCD (workgroup b runs on XCD b % 8).  The first 8 * floor(t / 8) of the t tiles
-    // that hold segments go WHOLE to the queue with the least work so far (a tile's segments stay together and in order:
-    // its rows are fetched into one L2, once); the remaining t mod 8 tiles level the queues: their segments are poured, in
-    // order, into the queues up to the common fill mark, so that a levelling tile is shared by two or three XCDs instead of
-    // all eight and every queue ends at the same count (round 5; until round 4 EVERY tile was cut eight ways below 32
-    // tiles, so that each XCD fetched every tile: an eighth of C4 -- 22 tiles of users -- ran its item pass in 1.36 ms,
-    // now 1.10; 9 and 12 tiles: -4 %; from 32 tiles on nothing changes).  Below tile_split_below = 8 tiles the old rule
-    // stays (HPF_TILE_SPLIT_BELOW=N: for fewer than N tiles).  The row-major rest (key 0) is cut eight ways.
-    std::vector<std::pair<uint32_t, uint32_t>> q[8], qt[8];
-    uint64_t load[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    auto key_end = [&](uint32_t k) { for (uint32_t j = k + 1; j < nkeys; ++j) if (fs[j] != 0xffffffffu) return fs[j]; return nseg; };
-    uint64_t tiled_segs = 0;
-    uint32_t tiles_present = 0;
-    for (uint32_t k = 1; k < nkeys; ++k) if (fs[k] != 0xffffffffu) { tiles_present++; tiled_segs += key_end(k) - fs[k]; }
-    const bool old_rule = tiles < h->tile_split_below;
-    const uint32_t whole_tiles = old_rule ? 0u : (tiles_present / 8u) * 8u;
-    uint32_t seen = 0;
-    int fill = 0;                                                  // the queue the levelling tiles are being poured into
-    const uint64_t mark = (tiled_segs + 7) / 8;                    // the common fill mark
-    for (uint32_t k = 1; k < nkeys; ++k) {
-      if (fs[k] == 0xffffffffu) continue;
-      const uint32_t a0 = fs[k], a1 = key_end(k);
-      if (seen++ < whole_tiles) {
-        int best = 0;
-        for (int x = 1; x < 8; ++x) if (load[x] < load[best]) best = x;
-        qt[best].push_back({a0, a1}); load[best] += a1 - a0;
-        continue;
-      }
-      if (old_rule) {
-        const uint64_t n = a1 - a0;
-        for (int x = 0; x < 8; ++x) {
-          const uint32_t lo = a0 + (uint32_t)(n * x / 8), hi = a0 + (uint32_t)(n * (x + 1) / 8);
-          if (hi > lo) { qt[x].push_back({lo, hi}); load[x] += hi - lo; }
-        }
-        continue;
-      }
-      for (uint32_t p0 = a0; p0 < a1;) {
-        while (fill < 7 && load[fill] >= mark) ++fill;
-        const uint64_t room = fill < 7 ? mark - load[fill] : (uint64_t)(a1 - p0);
-        const uint32_t take = (uint32_t)std::min<uint64_t>(room, a1 - p0);
-        qt[fill].push_back({p0, p0 + take}); load[fill] += take;
-        p0 += take;
-      }
-    }
-    // the row-major rest: an eighth per queue.  tile_order 0: in front of the tiles; 1: in front on the even
-    // XCDs, behind on the odd ones (half the chip pulls over the fabric while the other half runs from L2);
-    // 2: dealt between the tiles in equal pieces
-    const uint32_t c0 = fs[0] != 0xffffffffu ? fs[0] : 0u, c1 = fs[0] != 0xffffffffu ? key_end(0) : 0u;
-    for (int x = 0; x < 8; ++x) {
-      const uint64_t n = c1 - c0;
-      const uint32_t lo = c0 + (uint32_t)(n * x / 8), hi = c0 + (uint32_t)(n * (x + 1) / 8);
-      const bool front = h->tile_order == 0 || (h->tile_order == 1 && (x & 1) == 0);
-      if (h->tile_order == 2 && !qt[x].empty()) {
-        const uint64_t nt = qt[x].size(), nc = hi - lo;
-        for (uint64_t t = 0; t < nt; ++t) {
-          const uint32_t l2 = lo + (uint32_t)(nc * t / nt), h2 = lo + (uint32_t)(nc * (t + 1) / nt);
-          if (h2 > l2) q[x].push_back({l2, h2});
-          q[x].push_back(qt[x][t]);
-        }
-        continue;
-      }
-      if (front && hi > lo) q[x].push_back({lo, hi});
-      for (auto &rg : qt[x]) q[x].push_back(rg);
-      if (!front && hi > lo) q[x].push_back({lo, hi});
-    }
-    // a launch holds fewer than 2^32 work-items (the AQL packet counts them in 32 bits): at most 2^28 / wg workgroups
-    // (2^20 of four waves, 2^22 of one -- round 5 kept 2^20 for the one-wave groups as well, and the longest lists, whole
-    // C3 or C5 on one GPU, got chunks of 8-16 segments instead of two), so a list too long for chunks of
-    // tile_chunk segments gets longer chunks; hpf_work_info.tile_chunk_user / _item say what was used
-    const uint32_t wg = h->wg_of(true);
-    const size_t max_wgs = ((size_t)1 << 28) / wg;
-    uint32_t CH = h->tile_chunk ? h->tile_chunk : 2 * (wg / 64);      // two segments per wave
-    // the row-major segments of a side with short rows (users: a few batches each) come in chunks of ~4096 nonzeros:
-    // a workgroup that lives for two 40-nonzero rows costs more to dispatch than to run (K = 50, 10^6 light users
-    // in chunks of 8: user pass 2.27 -> 2.54 ms)
-    uint32_t CHc = CH;
-    if (c1 > c0) {
-      int64_t cold_nnz = (int64_t)nnz;
-      if (c1 < nseg) {
-        Seg first_tiled;
-        HIPBRK(h, hipMemcpy(&first_tiled, segs + c1, sizeof(Seg), hipMemcpyDeviceToHost));
-        cold_nnz = first_tiled.start;
-      }
-      const uint64_t avg = std::max<uint64_t>((uint64_t)cold_nnz / (c1 - c0), 1);
-      CHc = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(4096ull * wg / 256 / avg, CH), 512);
-    }
-    auto chunk_of = [&](const std::pair<uint32_t, uint32_t> &rg, uint32_t ch, uint32_t chc) { return (rg.first >= c0 && rg.second <= c1) ? chc : ch; };
-    for (;; CH *= 2, CHc *= 2) {
-      size_t worst = 0;
-      for (int x = 0; x < 8; ++x) {
-        size_t c = 0;
-        for (auto &rg : q[x]) { const uint32_t ch = chunk_of(rg, CH, CHc); c += (rg.second - rg.first + ch - 1) / ch; }
-        worst = std::max(worst, c);
-      }
-      if (worst * 8 <= max_wgs || CH >= (1u << 30)) break;
-    }
-    std::vector<uint2> qc[8];
-    size_t longest = 0;
-    for (int x = 0; x < 8; ++x) {
-      for (auto &rg : q[x]) {
-        const uint32_t ch = chunk_of(rg, CH, CHc);
-        for (uint32_t p0 = rg.first; p0 < rg.second; p0 += std::min(ch, rg.second - p0)) qc[x].push_back(make_uint2(p0, p0 + std::min(ch, rg.second - p0)));
-      }
-      longest = std::max(longest, qc[x].size());
-    }
-    if (longest == 0 || longest * 8 > max_wgs) break;
-    std::vector<uint2> chunks(longest * 8, make_uint2(0u, 0u));
-    for (int x = 0; x < 8; ++x) for (size_t j = 0; j < qc[x].size(); ++j) chunks[j * 8 + x] = qc[x][j];
-    if ((rc = dalloc(h, &chunks_dev, chunks.size()))) break;
-    HIPBRK(h, hipMemcpyAsync(chunks_dev, chunks.data(), chunks.size() * sizeof(uint2), hipMemcpyHostToDevice, h->stream));
-    HIPBRK(h, hipStreamSynchronize(h->stream));
-
-    // ---- swap the side's work list
-    dfree(s.segs); dfree(s.longrows); dfree(s.grouprows); dfree(s.hugerows); dfree(s.partial); dfree(s.partial2);
-    s.segs = segs; s.nseg = nseg; segs = nullptr;
-    s.longrows = longs; s.nlong = nlong; s.nlong_wave = nlong_wave; longs = nullptr;
-    s.grouprows = groups; s.ngroup = ngroup; groups = nullptr;
-    s.hugerows = huges; s.nhuge = nhuge; huges = nullptr;
-    s.partial = partial; s.npartial = npartial; partial = nullptr;
-    s.partial2 = partial2; s.npartial2 = ngroup; partial2 = nullptr;
-    s.p_idx = keep_idx; s.p_val = keep_val; keep_idx = nullptr; keep_val = nullptr;
-    s.chunks = chunks_dev; s.nchunk_blocks = (uint32_t)chunks.size(); chunks_dev = nullptr;
-    s.tiles = tiles; s.tile_rows = T; s.tiled_nnz = heavy_nnz; s.light_below = light_below; s.chunk_segs = CH;
-    (void)tiled_segs;
-    done = true;
-  } while (0);
-  dfree(tilemap); dfree(first_seg); dfree(seg_row); dfree(seg_key); dfree(iota); dfree(cnt); dfree(segptr);
-  for (int k = 0; k < 5; ++k) dfree(pl[k]);
-  for (int k = 0; k < 2; ++k) { dfree(b.K[k]); dfree(b.U[k]); dfree(b.X[k]); dfree(b.V[k]); dfree(sb.K[k]); dfree(sb.U[k]); }
-  dfree(key0); dfree(row0); dfree(segs); dfree(longs); dfree(huges); dfree(groups); dfree(partial); dfree(partial2);
-  dfree(chunks_dev); dfree(keep_idx); dfree(keep_val);
-  if (rc == HPF_ERR_OOM && !done) {       // tiling is optional: without the room for it the side stays row-major -- and says so
+  rc = tile_side(h, s, ptr, rows_oth, nnz, tp, heavy_nnz);
+  if (rc == HPF_ERR_OOM) {       // tiling is optional: without the room for it the side stays row-major -- and says so
     (void)hipGetLastError();
     h->err.clear();
-    h->notes |= (&s == &h->it ? 8u : 4u);
+    h->notes |= (item_side ? 8u : 4u);
     rc = HPF_OK;
   }
   return rc;
@@ -1094,70 +1004,67 @@ int build_work_lists_tiled(hpf_handle *h, uint64_t nnz)
 int build_csc_device(hpf_handle *h, uint32_t n, uint32_t m, uint64_t nnz)
 {
   int rc;
+  Scratch sc(h);
   uint32_t *bad = nullptr;
   uint32_t *kbuf[2] = {nullptr, nullptr}, *ut = nullptr; uint8_t *vt = nullptr; uint64_t *counts = nullptr;
   unsigned char *pool = nullptr;
   dfree(h->colptr_dev); h->colptr_dev = nullptr;
   dfree(h->it.idx); dfree(h->it.val); h->it.idx = nullptr; h->it.val = nullptr;
-  do {
-    if ((rc = dalloc(h, &h->colptr_dev, (size_t)m + 1))) break;          // zeroed: the answer for nnz == 0
-    if ((rc = dalloc(h, &h->it.idx, (size_t)nnz))) break;
-    if (h->u.val && (rc = dalloc(h, &h->it.val, (size_t)nnz))) break;
-    if (nnz == 0) break;
-    if ((rc = dalloc(h, &bad, 1))) break;
-    uint32_t bits = 0;
-    while (bits < 32 && ((uint64_t)1 << bits) < (uint64_t)m) ++bits;
-    const uint32_t P = std::max<uint32_t>(1, (bits + RADIX_BITS - 1) / RADIX_BITS);
-    const uint64_t ntiles = (nnz + RADIX_TILE - 1) / RADIX_TILE;
-    const uint32_t nblk = (uint32_t)((ntiles + 3) / 4);
-    // one allocation for every temporary of the sort (mapping ~100 GB piecewise was most of
-    // whole C5's upload time): [counts | keys A | keys B | users | ratings], 256-byte aligned parts
-    {
-      auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-      const size_t b_counts = up((size_t)ntiles * RADIX_DIGITS * 8), b_k = up((size_t)nnz * 4);
-      const size_t b_k1 = P >= 2 ? b_k : 0, b_ut = P >= 2 ? b_k : 0, b_vt = (P >= 2 && h->u.val) ? up((size_t)nnz) : 0;
-      if ((rc = dalloc(h, &pool, b_counts + b_k + b_k1 + b_ut + b_vt))) break;
-      char *q = (char *)pool;
-      counts = (uint64_t *)q; q += b_counts;
-      kbuf[0] = (uint32_t *)q; q += b_k;
-      if (b_k1) { kbuf[1] = (uint32_t *)q; q += b_k1; }
-      if (b_ut) { ut = (uint32_t *)q; q += b_ut; }
-      if (b_vt) { vt = (uint8_t *)q; q += b_vt; }
+  if ((rc = dalloc(h, &h->colptr_dev, (size_t)m + 1))) return rc;          // zeroed: the answer for nnz == 0
+  if ((rc = dalloc(h, &h->it.idx, (size_t)nnz))) return rc;
+  if (h->u.val && (rc = dalloc(h, &h->it.val, (size_t)nnz))) return rc;
+  if (nnz == 0) return HPF_OK;
+  if ((rc = sc.alloc(&bad, 1))) return rc;
+  uint32_t bits = 0;
+  while (bits < 32 && ((uint64_t)1 << bits) < (uint64_t)m) ++bits;
+  const uint32_t P = std::max<uint32_t>(1, (bits + RADIX_BITS - 1) / RADIX_BITS);
+  const uint64_t ntiles = (nnz + RADIX_TILE - 1) / RADIX_TILE;
+  const uint32_t nblk = (uint32_t)((ntiles + 3) / 4);
+  // one allocation for every temporary of the sort (mapping ~100 GB piecewise was most of
+  // whole C5's upload time): [counts | keys A | keys B | users | ratings], 256-byte aligned parts
+  {
+    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t b_counts = up((size_t)ntiles * RADIX_DIGITS * 8), b_k = up((size_t)nnz * 4);
+    const size_t b_k1 = P >= 2 ? b_k : 0, b_ut = P >= 2 ? b_k : 0, b_vt = (P >= 2 && h->u.val) ? up((size_t)nnz) : 0;
+    if ((rc = sc.alloc(&pool, b_counts + b_k + b_k1 + b_ut + b_vt))) return rc;
+    char *q = (char *)pool;
+    counts = (uint64_t *)q; q += b_counts;
+    kbuf[0] = (uint32_t *)q; q += b_k;
+    if (b_k1) { kbuf[1] = (uint32_t *)q; q += b_k1; }
+    if (b_ut) { ut = (uint32_t *)q; q += b_ut; }
+    if (b_vt) { vt = (uint8_t *)q; q += b_vt; }
+  }
+  for (uint32_t p = 0; p < P; ++p) {
+    RadixArgs a;
+    a.keys_in = p == 0 ? h->u.idx : kbuf[(p - 1) & 1];
+    const bool out_final = ((P - 1 - p) & 1u) == 0;      // the last pass lands in it.idx / it.val
+    a.users_in = p == 0 ? nullptr : (out_final ? ut : h->it.idx);
+    a.vals_in = !h->u.val ? nullptr : p == 0 ? h->u.val : (out_final ? vt : h->it.val);
+    a.rowptr = h->rowptr_dev; a.n_rows = n;
+    a.extra_in = nullptr; a.extra_out = nullptr;
+    a.keys_out = kbuf[p & 1];
+    a.users_out = out_final ? h->it.idx : ut;
+    a.vals_out = !h->u.val ? nullptr : (out_final ? h->it.val : vt);
+    a.offsets = counts; a.nnz = nnz; a.ntiles = ntiles; a.shift = p * RADIX_BITS;
+    hipLaunchKernelGGL(radix_count_kernel, dim3(nblk), dim3(256), 0, h->stream, a.keys_in, nnz, a.shift, ntiles, counts,
+                       m, bad);
+    if ((rc = check_launch(h, "radix_count_kernel"))) return rc;
+    if (p == 0) {                                        // every item id was range-checked on the way
+      uint32_t hb = 0;
+      hipError_t e = hipMemcpyAsync(&hb, bad, 4, hipMemcpyDeviceToHost, h->stream);
+      if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+      if (e != hipSuccess) { h->err = std::string("radix_count_kernel: ") + hipGetErrorString(e); return HPF_ERR_HIP; }
+      if (hb) { h->err = "item index out of range"; return HPF_ERR_INVALID; }
     }
-    for (uint32_t p = 0; p < P && !rc; ++p) {
-      RadixArgs a;
-      a.keys_in = p == 0 ? h->u.idx : kbuf[(p - 1) & 1];
-      const bool out_final = ((P - 1 - p) & 1u) == 0;      // the last pass lands in it.idx / it.val
-      a.users_in = p == 0 ? nullptr : (out_final ? ut : h->it.idx);
-      a.vals_in = !h->u.val ? nullptr : p == 0 ? h->u.val : (out_final ? vt : h->it.val);
-      a.rowptr = h->rowptr_dev; a.n_rows = n;
-      a.extra_in = nullptr; a.extra_out = nullptr;
-      a.keys_out = kbuf[p & 1];
-      a.users_out = out_final ? h->it.idx : ut;
-      a.vals_out = !h->u.val ? nullptr : (out_final ? h->it.val : vt);
-      a.offsets = counts; a.nnz = nnz; a.ntiles = ntiles; a.shift = p * RADIX_BITS;
-      hipLaunchKernelGGL(radix_count_kernel, dim3(nblk), dim3(256), 0, h->stream, a.keys_in, nnz, a.shift, ntiles, counts,
-                         m, bad);
-      if ((rc = check_launch(h, "radix_count_kernel"))) break;
-      if (p == 0) {                                        // every item id was range-checked on the way
-        uint32_t hb = 0;
-        hipError_t e = hipMemcpyAsync(&hb, bad, 4, hipMemcpyDeviceToHost, h->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-        if (e != hipSuccess) { h->err = std::string("radix_count_kernel: ") + hipGetErrorString(e); rc = HPF_ERR_HIP; break; }
-        if (hb) { h->err = "item index out of range"; rc = HPF_ERR_INVALID; break; }
-      }
-      if ((rc = device_scan<uint64_t>(h, counts, ntiles * RADIX_DIGITS, counts, false))) break;
-      hipLaunchKernelGGL(radix_scatter_kernel, dim3(nblk), dim3(256), 0, h->stream, a);
-      rc = check_launch(h, "radix_scatter_kernel");
-    }
-    if (rc) break;
-    hipLaunchKernelGGL(colptr_from_sorted_kernel, dim3(grid_for(nnz)), dim3(256), 0, h->stream, kbuf[(P - 1) & 1], nnz, m,
-                       h->colptr_dev);
-    if ((rc = check_launch(h, "colptr_from_sorted_kernel"))) break;
-    if (hipStreamSynchronize(h->stream) != hipSuccess) { h->err = "CSC build failed on the device"; rc = HPF_ERR_HIP; }
-  } while (0);
-  dfree(bad); dfree(pool);
-  return rc;
+    if ((rc = device_scan<uint64_t>(h, counts, ntiles * RADIX_DIGITS, counts, false))) return rc;
+    hipLaunchKernelGGL(radix_scatter_kernel, dim3(nblk), dim3(256), 0, h->stream, a);
+    if ((rc = check_launch(h, "radix_scatter_kernel"))) return rc;
+  }
+  hipLaunchKernelGGL(colptr_from_sorted_kernel, dim3(grid_for(nnz)), dim3(256), 0, h->stream, kbuf[(P - 1) & 1], nnz, m,
+                     h->colptr_dev);
+  if ((rc = check_launch(h, "colptr_from_sorted_kernel"))) return rc;
+  if (hipStreamSynchronize(h->stream) != hipSuccess) { h->err = "CSC build failed on the device"; return HPF_ERR_HIP; }
+  return HPF_OK;
 }
 
 // host digamma for the xi/eta Elog export (same series as the device one)
@@ -1200,6 +1107,41 @@ int refresh_elog(hpf_handle *h, Side &s)
   int rc = check_launch(h, "elog_kernel");
   if (!rc) s.l_stale = false;
   return rc;
+}
+
+// ---- what the report-step endpoints share -------------------------------------------------------------------------------
+// E of both sides must have been set, or an iteration must have run
+int need_e(hpf_handle *h)
+{
+  if (!(h->u.have_E && h->it.have_E) && h->iterations == 0) { h->err = "E state not set"; return HPF_ERR_STATE; }
+  return HPF_OK;
+}
+int refresh_e(hpf_handle *h) { const int rc = refresh_es(h, h->u); return rc ? rc : refresh_es(h, h->it); }
+// before a kernel scores pairs from E: E exists, no breakdown is flagged, and E is that of the last sweep.  (A call that
+// validates its arguments in between asks need_e first: which error a bad call gets does not depend on the device.)
+int scoring_ready(hpf_handle *h)
+{
+  int rc;
+  if ((rc = need_e(h)) || (rc = check_flags(h))) return rc;
+  return refresh_e(h);
+}
+// the fields every scoring kernel's argument struct has
+template <class Args>
+void factor_args(const hpf_handle *h, Args &a)
+{
+  a.Et = h->u.E; a.Eb = h->it.E; a.ld = h->ld; a.K = h->K;
+  a.ubias_col = h->cfg.bias ? h->u.bias_col : -1;
+  a.ibias_col = h->cfg.bias ? h->it.bias_col : -1;
+}
+// the tail of a call: its outputs back to the host (a null dst is one the caller did not ask for), the stream idle
+struct HostOut { void *dst; const void *src; size_t bytes; };
+int copy_back(hpf_handle *h, std::initializer_list<HostOut> outs)
+{
+  hipError_t e = hipSuccess;
+  for (const HostOut &o : outs) if (e == hipSuccess && o.dst) e = hipMemcpyAsync(o.dst, o.src, o.bytes, hipMemcpyDeviceToHost, h->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+  if (e != hipSuccess) { h->err = hipGetErrorString(e); return HPF_ERR_HIP; }
+  return HPF_OK;
 }
 
 int prepare_derived(hpf_handle *h)
@@ -1513,6 +1455,35 @@ int set_rows_f64(hpf_handle *h)
   return HPF_OK;
 }
 
+// recover_flush between setting and clearing hpf_handle::in_recovery; redo: the iterations the passes skipped
+int redo_in_plain_rows(hpf_handle *h, uint32_t fl0, uint64_t redo)
+{
+  int rc;
+  if ((rc = set_rows_f64(h))) return rc;
+  const uint32_t clear[2] = {fl0 & 1u, 0u};
+  if (hipMemcpyAsync(h->flags, clear, 8, hipMemcpyHostToDevice, h->stream) != hipSuccess) { h->err = "recover_flush: cannot reset the flags"; return HPF_ERR_HIP; }
+  h->iters_counted = 0;
+  Side *sides[2] = {&h->u, &h->it};
+  for (Side *s : sides) {
+    if (!s->rows) continue;
+    if (!s->w_from_sweep || s->w_dirty) { s->w_dirty = true; h->derived_dirty = true; continue; }     // from Elog: prepare_derived
+    SweepArgs a;
+    sweep_args(h, *s, a);
+    a.prior_E = s->prior_used; a.colsum_oth = s->colsum_used; a.colsum_used = nullptr;             // what that sweep read
+    if (!s->es_stale) a.s_prior = 0.0;      // an export has turned S into the shape (prior added, in place) since: the same sum, not taken twice
+    if (!launch_sweep(h->sw_mode, h->swG, h->swR, a, s->sweep_blocks, h->stream)) { h->err = "no sweep kernel for this configuration"; return HPF_ERR_UNSUPPORTED; }
+  }
+  if ((rc = check_launch(h, "repeat of the sweeps in plain rows"))) return rc;
+  h->fallbacks++;
+  if (redo) {
+    if (h->cfg.n_ranks != 1) { h->err = "internal: iterations were skipped on a rank of several"; return HPF_ERR_STATE; }
+    h->iterations -= (uint32_t)std::min<uint64_t>(redo, h->iterations);
+    for (uint64_t t = 0; t < redo; ++t) if ((rc = iterate_local(h)) || (rc = iterate_global(h))) return rc;
+  }
+  if (hipStreamSynchronize(h->stream) != hipSuccess) { h->err = "recover_flush: stream error"; return HPF_ERR_HIP; }
+  return HPF_OK;
+}
+
 // Flag bit 1: an element of W fell below 2^-126 of its row maximum (an Elog spread above 88 inside a row) and the p59
 // rows cannot hold it.  The layout is lossless by contract, and the library holds everything it takes to go on without
 // it: the rows become plain doubles, W is written again -- by a W-ONLY repeat of the side's last sweep (same S, the prior
@@ -1522,33 +1493,9 @@ int set_rows_f64(hpf_handle *h)
 int recover_flush(hpf_handle *h, uint32_t fl0, uint32_t begun)
 {
   if (h->wl != WL_P59) { h->err = "internal: an entry of W was reported flushed, but the rows are not packed"; return HPF_ERR_STATE; }
-  int rc;
-  h->in_recovery = true;
   const uint64_t redo = h->iters_counted > (uint64_t)begun ? h->iters_counted - (uint64_t)begun : 0;   // several ranks: none (the host looks every iteration)
-  do {
-    if ((rc = set_rows_f64(h))) break;
-    const uint32_t clear[2] = {fl0 & 1u, 0u};
-    if (hipMemcpyAsync(h->flags, clear, 8, hipMemcpyHostToDevice, h->stream) != hipSuccess) { h->err = "recover_flush: cannot reset the flags"; rc = HPF_ERR_HIP; break; }
-    h->iters_counted = 0;
-    Side *sides[2] = {&h->u, &h->it};
-    for (Side *s : sides) {
-      if (!s->rows) continue;
-      if (!s->w_from_sweep || s->w_dirty) { s->w_dirty = true; h->derived_dirty = true; continue; }     // from Elog: prepare_derived
-      SweepArgs a;
-      sweep_args(h, *s, a);
-      a.prior_E = s->prior_used; a.colsum_oth = s->colsum_used; a.colsum_used = nullptr;             // what that sweep read
-      if (!s->es_stale) a.s_prior = 0.0;      // an export has turned S into the shape (prior added, in place) since: the same sum, not taken twice
-      if (!launch_sweep(h->sw_mode, h->swG, h->swR, a, s->sweep_blocks, h->stream)) { h->err = "no sweep kernel for this configuration"; rc = HPF_ERR_UNSUPPORTED; break; }
-    }
-    if (rc || (rc = check_launch(h, "repeat of the sweeps in plain rows"))) break;
-    h->fallbacks++;
-    if (redo) {
-      if (h->cfg.n_ranks != 1) { h->err = "internal: iterations were skipped on a rank of several"; rc = HPF_ERR_STATE; break; }
-      h->iterations -= (uint32_t)std::min<uint64_t>(redo, h->iterations);
-      for (uint64_t t = 0; t < redo && !rc; ++t) { if (!(rc = iterate_local(h))) rc = iterate_global(h); }
-    }
-    if (!rc && hipStreamSynchronize(h->stream) != hipSuccess) { h->err = "recover_flush: stream error"; rc = HPF_ERR_HIP; }
-  } while (0);
+  h->in_recovery = true;
+  const int rc = redo_in_plain_rows(h, fl0, redo);
   h->in_recovery = false;
   return rc;
 }
@@ -1943,12 +1890,12 @@ int hpf_upload_csr_device(hpf_handle *h, const int64_t *d_rowptr, const uint32_t
   HIPCHK(h, hipMemcpyAsync(h->rowptr_dev, d_rowptr, ((size_t)n + 1) * 8, hipMemcpyDeviceToDevice, h->stream));
   // the sort's first pass bisects the row pointers: they must be monotone BEFORE it runs
   {
+    Scratch sc(h);
     uint32_t *bad = nullptr; uint32_t hb = 0;
-    if ((rc = dalloc(h, &bad, 1))) return rc;
+    if ((rc = sc.alloc(&bad, 1))) return rc;
     hipLaunchKernelGGL(rowptr_check_kernel, dim3(grid_for(n)), dim3(256), 0, h->stream, h->rowptr_dev, n, bad);
     hipError_t e = hipMemcpyAsync(&hb, bad, 4, hipMemcpyDeviceToHost, h->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    dfree(bad);
     if (e != hipSuccess) { h->err = std::string("rowptr check: ") + hipGetErrorString(e); return HPF_ERR_HIP; }
     if (hb) { h->err = "rowptr not monotone"; return HPF_ERR_INVALID; }
   }
@@ -2108,17 +2055,15 @@ static int get_state_impl(hpf_handle *h, hpf_state which, double *host, size_t c
       HIPCHK(h, hipStreamSynchronize(h->stream));
       return HPF_OK;
     }
-    double *tmp = on_device ? host : nullptr; int rc = HPF_OK;
-    if (!on_device && (rc = dalloc(h, &tmp, want))) return rc;
+    Scratch sc(h);
+    double *tmp = on_device ? host : nullptr; int rc;
+    if (!on_device && (rc = sc.alloc(&tmp, want))) return rc;
     hipLaunchKernelGGL(build_rate_kernel, dim3(1024), dim3(256), 0, h->stream, s->prior_used,
                        s->colsum_used, rows, h->K, tmp);
-    rc = check_launch(h, "build_rate");
-    if (!rc) {
-      if (on_device) { if (hipStreamSynchronize(h->stream) != hipSuccess) { h->err = "build_rate failed"; rc = HPF_ERR_HIP; } }
-      else rc = d2h(h, host, tmp, want * 8);
-    }
-    if (!on_device) dfree(tmp);
-    return rc;
+    if ((rc = check_launch(h, "build_rate"))) return rc;
+    if (!on_device) return d2h(h, host, tmp, want * 8);
+    if (hipStreamSynchronize(h->stream) != hipSuccess) { h->err = "build_rate failed"; return HPF_ERR_HIP; }
+    return HPF_OK;
   }
   if (count != (size_t)rows * cols) return HPF_ERR_INVALID;
   { int rc = check_flags(h); if (rc) return rc; }
@@ -2268,18 +2213,17 @@ int hpf_snapshot_load(hpf_handle *h, const void *host, size_t bytes)
     if (tot != bytes) { h->err = "damaged snapshot header"; return HPF_ERR_INVALID; }
   }
   int rc;
+  Scratch sc(h);
   double *new_rate[2] = {nullptr, nullptr}, *new_pss[2] = {nullptr, nullptr};
   for (int k = 0; k < 2; ++k) {                           // optional arrays the snapshot carries
     Side &s = *sides[k];
-    rc = HPF_OK;
-    if ((hd.side_flags[k] & 64u)) rc = dalloc(h, &new_rate[k], (size_t)hd.rate_set_count[k]);
-    if (!rc && (hd.side_flags[k] & 128u) && !s.prior_shape_set) rc = dalloc(h, &new_pss[k], s.rows);
-    if (rc) { for (int j = 0; j < 2; ++j) { dfree(new_rate[j]); dfree(new_pss[j]); } return rc; }
+    if ((hd.side_flags[k] & 64u) && (rc = sc.alloc(&new_rate[k], (size_t)hd.rate_set_count[k]))) return rc;
+    if ((hd.side_flags[k] & 128u) && !s.prior_shape_set && (rc = sc.alloc(&new_pss[k], s.rows))) return rc;
   }
   for (int k = 0; k < 2; ++k) {
     Side &s = *sides[k];
-    dfree(s.rate_set); s.rate_set = new_rate[k]; s.rate_set_count = (size_t)hd.rate_set_count[k];
-    if (new_pss[k]) s.prior_shape_set = new_pss[k];
+    dfree(s.rate_set); s.rate_set = sc.keep(new_rate[k]); s.rate_set_count = (size_t)hd.rate_set_count[k];
+    if (new_pss[k]) s.prior_shape_set = sc.keep(new_pss[k]);
   }
   std::vector<SnapSection> sec;
   snapshot_sections(h, hd.rate_set_count, hd.side_flags, &sec);
@@ -2345,14 +2289,10 @@ int heldout_run(hpf_handle *h, const uint32_t *du, const uint32_t *di, const int
                 double *sum_out, bool pinned)
 {
   int rc;
-  if ((rc = check_flags(h))) return rc;
-  if ((rc = refresh_es(h, h->u)) || (rc = refresh_es(h, h->it))) return rc;
+  if ((rc = scoring_ready(h))) return rc;
   LLArgs a;
-  a.u = du; a.i = di; a.y = dy; a.cnt = cnt; a.Et = h->u.E; a.Eb = h->it.E;
-  a.logfact = h->logfact; a.out = dout; a.ld = h->ld; a.K = h->K;
-  a.ubias_col = h->cfg.bias ? h->u.bias_col : -1;
-  a.ibias_col = h->cfg.bias ? h->it.bias_col : -1;
-  a.binary = h->cfg.binary;
+  factor_args(h, a);
+  a.u = du; a.i = di; a.y = dy; a.cnt = cnt; a.logfact = h->logfact; a.out = dout; a.binary = h->cfg.binary;
   const uint32_t blocks = (uint32_t)std::min<size_t>((cnt + 15) / 16, 4096);
   hipLaunchKernelGGL(heldout_ll_kernel, dim3(blocks), dim3(256), 0, h->stream, a);
   if ((rc = check_launch(h, "heldout_ll"))) return rc;
@@ -2381,9 +2321,7 @@ int heldout_run(hpf_handle *h, const uint32_t *du, const uint32_t *di, const int
     *sum_out = s;
     return HPF_OK;
   }
-  e = hipMemcpyAsync(hout, dout, cnt * 8, hipMemcpyDeviceToHost, h->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-  if (e != hipSuccess) { h->err = hipGetErrorString(e); return HPF_ERR_HIP; }
+  if ((rc = copy_back(h, {{hout, dout, cnt * 8}}))) return rc;
   double s = .0;
   for (size_t p = 0; p < cnt; ++p) s += hout[p];
   *sum_out = s;
@@ -2398,23 +2336,18 @@ int hpf_heldout_ll(hpf_handle *h, const uint32_t *u, const uint32_t *i, const in
   *sum_out = 0.0; if (cnt_out) *cnt_out = cnt;
   if (cnt == 0) return HPF_OK;
   if (!u || !i || !y) return HPF_ERR_INVALID;
-  if (!(h->u.have_E && h->it.have_E) && h->iterations == 0) { h->err = "E state not set"; return HPF_ERR_STATE; }
+  int rc;
+  if ((rc = need_e(h))) return rc;
   for (size_t p = 0; p < cnt; ++p)
     if (u[p] >= h->u.rows || i[p] >= h->it.rows) { h->err = "held-out index out of range"; return HPF_ERR_INVALID; }
+  Scratch sc(h);
   uint32_t *du = nullptr, *di = nullptr; int32_t *dy = nullptr; double *dout = nullptr;
-  int rc = HPF_OK;
   std::vector<double> out(cnt);
-  do {
-    if ((rc = dalloc(h, &du, cnt)) || (rc = dalloc(h, &di, cnt)) || (rc = dalloc(h, &dy, cnt)) ||
-        (rc = dalloc(h, &dout, cnt))) break;
-    hipError_t e = hipMemcpyAsync(du, u, cnt * 4, hipMemcpyHostToDevice, h->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(di, i, cnt * 4, hipMemcpyHostToDevice, h->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(dy, y, cnt * 4, hipMemcpyHostToDevice, h->stream);
-    if (e != hipSuccess) { h->err = hipGetErrorString(e); rc = HPF_ERR_HIP; break; }
-    rc = heldout_run(h, du, di, dy, dout, out.data(), cnt, sum_out, false);
-  } while (0);
-  dfree(du); dfree(di); dfree(dy); dfree(dout);
-  return rc;
+  if ((rc = sc.alloc(&du, cnt)) || (rc = sc.alloc(&di, cnt)) || (rc = sc.alloc(&dy, cnt)) || (rc = sc.alloc(&dout, cnt))) return rc;
+  HIPCHK(h, hipMemcpyAsync(du, u, cnt * 4, hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, hipMemcpyAsync(di, i, cnt * 4, hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, hipMemcpyAsync(dy, y, cnt * 4, hipMemcpyHostToDevice, h->stream));
+  return heldout_run(h, du, di, dy, dout, out.data(), cnt, sum_out, false);
 }
 
 // A report step evaluates the SAME validation and test pairs every time (hgaprec.cc:1439-1470 walks the same two maps):
@@ -2445,7 +2378,6 @@ int hpf_heldout_ll_bound(hpf_handle *h, int slot, double *sum_out, uint64_t *cnt
   if (!hs.bound) { h->err = "hpf_heldout_ll_bound: nothing bound to this slot"; return HPF_ERR_STATE; }
   *sum_out = 0.0; if (cnt_out) *cnt_out = hs.cnt;
   if (hs.cnt == 0) return HPF_OK;
-  if (!(h->u.have_E && h->it.have_E) && h->iterations == 0) { h->err = "E state not set"; return HPF_ERR_STATE; }
   return heldout_run(h, hs.du, hs.di, hs.dy, hs.dout, hs.hout, hs.cnt, sum_out, true);
 }
 
@@ -2460,79 +2392,64 @@ int hpf_elbo(hpf_handle *h, double *out)
   // per-nonzero term: the user-major work list(s) of the phi pass, one wave per segment
   const uint32_t nb_nnz = (uint32_t)std::min<uint64_t>(((uint64_t)h->u.nseg + 3) / 4 + 1, 16384);
   const uint32_t nb_g = 1024;
+  Scratch sc(h);
   double *part = nullptr, *Mt = nullptr, *Mb = nullptr;
   const size_t npart = (size_t)2 * nb_nnz + 2 * nb_g;
-  if ((rc = dalloc(h, &part, npart))) return rc;
+  if ((rc = sc.alloc(&part, npart))) return rc;
   std::vector<double> hp(npart, 0.0);
-  do {
-    // fp64 W: logsumexp from the hot loop's W and the row maxima of Elog (no exp per
-    // element); the f32-stored W is not precise enough for that, it takes the Elog form
-    const bool from_w = !h->w32 && h->wl == WL_PLAIN && h->nnz;
-    if (from_w) {
-      if ((rc = prepare_derived(h))) break;                  // W follows a set_state(ELOG), if any
-      if ((rc = dalloc(h, &Mt, h->u.rows)) || (rc = dalloc(h, &Mb, h->it.rows))) break;
-      hipLaunchKernelGGL(rowmax_elog_kernel, dim3((h->u.rows + 255) / 256), dim3(256), 0, h->stream,
-                         h->u.L, Mt, h->u.rows, h->ld, h->K, h->u.bias_col, h->u.junk_col);
-      hipLaunchKernelGGL(rowmax_elog_kernel, dim3((h->it.rows + 255) / 256), dim3(256), 0, h->stream,
-                         h->it.L, Mb, h->it.rows, h->ld, h->K, h->it.bias_col, h->it.junk_col);
-    }
-    if (from_w && h->u.nseg) {
-      const uint32_t ph = 0;
-      ElboNnzWArgs a;
-      a.segs = h->u.segs; a.nseg = h->u.nseg; a.col = h->u.pass_idx(); a.val = h->u.pass_val();
-      a.Wt = (const double *)h->u.W; a.Wb = (const double *)h->it.W; a.Et = h->u.E; a.Eb = h->it.E;
-      a.Mt = Mt; a.Mb = Mb;
-      a.partial = part + (size_t)ph * nb_nnz; a.ld = h->ld; a.K = h->K;
-      a.ubias_col = h->cfg.bias ? h->u.bias_col : -1; a.ibias_col = h->cfg.bias ? h->it.bias_col : -1;
-      hipLaunchKernelGGL(elbo_nnz_w_kernel, dim3(nb_nnz), dim3(256), 0, h->stream, a);
-    }
-    if (h->nnz && !from_w && h->u.nseg) {
-      const uint32_t ph = 0;
-      ElboNnzArgs a;
-      a.segs = h->u.segs; a.nseg = h->u.nseg; a.col = h->u.pass_idx(); a.val = h->u.pass_val();
-      a.Lt = h->u.L; a.Lb = h->it.L; a.Et = h->u.E; a.Eb = h->it.E;
-      a.partial = part + (size_t)ph * nb_nnz; a.ld = h->ld; a.K = h->K; a.C = h->C;
-      a.ubias_col = h->cfg.bias ? h->u.bias_col : -1; a.ibias_col = h->cfg.bias ? h->it.bias_col : -1;
-      hipLaunchKernelGGL(elbo_nnz_kernel, dim3(nb_nnz), dim3(256), 0, h->stream, a);
-    }
-    const double s0 = h->cfg.s_prior, ps = s0 + (double)h->K * s0;
-    Side *sides[2] = {&h->u, &h->it};
-    for (int k = 0; k < 2; ++k) {
-      Side &s = *sides[k];
-      if (k == 1 && h->cfg.rank != 0) continue;      // replicated item side: counted once
-      if (!s.rows) continue;
-      ElboGammaArgs g;
-      g.S = s.S; g.E = s.E; g.L = s.L; g.prior_used = s.prior_used; g.prior_elog_used = s.prior_elog_used;
-      g.colsum_used = s.colsum_used; g.prior_E = s.prior_E; g.prior_elog = s.prior_elog; g.prior_rate = s.prior_rate;
-      g.partial = part + (size_t)2 * nb_nnz + (size_t)k * nb_g; g.rows = s.rows; g.ld = h->ld; g.K = h->K;
-      g.bias_col = s.bias_col; g.bias_rate_add = s.bias_rate_add; g.s_prior = s0; g.r_prior = h->cfg.r_prior;
-      g.lg_s_prior = std::lgamma(s0); g.prior_shape = ps; g.lg_prior_shape = std::lgamma(ps); g.hier = h->cfg.hier;
-      hipLaunchKernelGGL(elbo_gamma_kernel, dim3(nb_g), dim3(256), 0, h->stream, g);
-    }
-    if ((rc = check_launch(h, "elbo"))) break;
-    hipError_t e = hipMemcpyAsync(hp.data(), part, npart * 8, hipMemcpyDeviceToHost, h->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    if (e != hipSuccess) { h->err = hipGetErrorString(e); rc = HPF_ERR_HIP; break; }
-    double s = 0.0;
-    for (size_t k = 0; k < npart; ++k) s += hp[k];
-    *out = s;
-  } while (0);
-  dfree(part); dfree(Mt); dfree(Mb);
-  return rc;
+  // fp64 W: logsumexp from the hot loop's W and the row maxima of Elog (no exp per
+  // element); the f32-stored W is not precise enough for that, it takes the Elog form
+  const bool from_w = !h->w32 && h->wl == WL_PLAIN && h->nnz;
+  if (from_w) {
+    if ((rc = prepare_derived(h))) return rc;                  // W follows a set_state(ELOG), if any
+    if ((rc = sc.alloc(&Mt, h->u.rows)) || (rc = sc.alloc(&Mb, h->it.rows))) return rc;
+    hipLaunchKernelGGL(rowmax_elog_kernel, dim3((h->u.rows + 255) / 256), dim3(256), 0, h->stream,
+                       h->u.L, Mt, h->u.rows, h->ld, h->K, h->u.bias_col, h->u.junk_col);
+    hipLaunchKernelGGL(rowmax_elog_kernel, dim3((h->it.rows + 255) / 256), dim3(256), 0, h->stream,
+                       h->it.L, Mb, h->it.rows, h->ld, h->K, h->it.bias_col, h->it.junk_col);
+  }
+  if (from_w && h->u.nseg) {
+    ElboNnzWArgs a;
+    factor_args(h, a);
+    a.segs = h->u.segs; a.nseg = h->u.nseg; a.col = h->u.pass_idx(); a.val = h->u.pass_val();
+    a.Wt = (const double *)h->u.W; a.Wb = (const double *)h->it.W; a.Mt = Mt; a.Mb = Mb; a.partial = part;
+    hipLaunchKernelGGL(elbo_nnz_w_kernel, dim3(nb_nnz), dim3(256), 0, h->stream, a);
+  }
+  if (h->nnz && !from_w && h->u.nseg) {
+    ElboNnzArgs a;
+    factor_args(h, a);
+    a.segs = h->u.segs; a.nseg = h->u.nseg; a.col = h->u.pass_idx(); a.val = h->u.pass_val();
+    a.Lt = h->u.L; a.Lb = h->it.L; a.partial = part; a.C = h->C;
+    hipLaunchKernelGGL(elbo_nnz_kernel, dim3(nb_nnz), dim3(256), 0, h->stream, a);
+  }
+  const double s0 = h->cfg.s_prior, ps = s0 + (double)h->K * s0;
+  Side *sides[2] = {&h->u, &h->it};
+  for (int k = 0; k < 2; ++k) {
+    Side &s = *sides[k];
+    if (k == 1 && h->cfg.rank != 0) continue;      // replicated item side: counted once
+    if (!s.rows) continue;
+    ElboGammaArgs g;
+    g.S = s.S; g.E = s.E; g.L = s.L; g.prior_used = s.prior_used; g.prior_elog_used = s.prior_elog_used;
+    g.colsum_used = s.colsum_used; g.prior_E = s.prior_E; g.prior_elog = s.prior_elog; g.prior_rate = s.prior_rate;
+    g.partial = part + (size_t)2 * nb_nnz + (size_t)k * nb_g; g.rows = s.rows; g.ld = h->ld; g.K = h->K;
+    g.bias_col = s.bias_col; g.bias_rate_add = s.bias_rate_add; g.s_prior = s0; g.r_prior = h->cfg.r_prior;
+    g.lg_s_prior = std::lgamma(s0); g.prior_shape = ps; g.lg_prior_shape = std::lgamma(ps); g.hier = h->cfg.hier;
+    hipLaunchKernelGGL(elbo_gamma_kernel, dim3(nb_g), dim3(256), 0, h->stream, g);
+  }
+  if ((rc = check_launch(h, "elbo"))) return rc;
+  if ((rc = copy_back(h, {{hp.data(), part, npart * 8}}))) return rc;
+  double s = 0.0;
+  for (size_t k = 0; k < npart; ++k) s += hp[k];
+  *out = s;
+  return HPF_OK;
 }
 
 // ---- ranking evaluation ----------------------------------------------------
 namespace {
-struct RankCtx {
-  uint32_t *d_users = nullptr; uint64_t *d_mptr = nullptr; uint32_t *d_mitems = nullptr;
-  double *d_scores = nullptr; uint32_t batch = 0, n_sel = 0;
-  ~RankCtx() { dfree(d_users); dfree(d_mptr); dfree(d_mitems); dfree(d_scores); }
-};
-
 // what every ranking call asks of the handle, of the selected users and of the mask list
 int rank_check(hpf_handle *h, const uint32_t *users, uint32_t n_sel, const uint64_t *mask_ptr, const uint32_t *mask_items)
 {
-  if (h->iterations == 0 && !(h->u.have_E && h->it.have_E)) { h->err = "E state not set"; return HPF_ERR_STATE; }
+  if (int rc = need_e(h)) return rc;
   if (!h->have_csr) { h->err = "hpf_upload_csr has not been called"; return HPF_ERR_STATE; }
   for (uint32_t b = 0; b < n_sel; ++b)
     if (users[b] >= h->u.rows) { h->err = "user index out of range"; return HPF_ERR_INVALID; }
@@ -2546,59 +2463,47 @@ int rank_check(hpf_handle *h, const uint32_t *users, uint32_t n_sel, const uint6
   return HPF_OK;
 }
 
-int rank_prepare(hpf_handle *h, const uint32_t *users, uint32_t n_sel, const uint64_t *mask_ptr,
-                 const uint32_t *mask_items, RankCtx &c)
-{
-  int rc;
-  if ((rc = rank_check(h, users, n_sel, mask_ptr, mask_items))) return rc;
-  const uint32_t m = h->it.rows;
-  const uint64_t nmask = mask_ptr ? mask_ptr[n_sel] : 0;
-  if ((rc = refresh_es(h, h->u)) || (rc = refresh_es(h, h->it))) return rc;
-  c.n_sel = n_sel;
-  // rows of scores kept at once: <= 1 GiB, a multiple of 16
-  uint64_t bmax = ((1ull << 30) / (8ull * std::max<uint32_t>(m, 1))) & ~15ull;
-  bmax = std::max<uint64_t>(bmax, 16);
-  c.batch = (uint32_t)std::min<uint64_t>(bmax, ((uint64_t)n_sel + 15) & ~15ull);
-  if ((rc = dalloc(h, &c.d_users, n_sel))) return rc;
-  if ((rc = dalloc(h, &c.d_scores, (size_t)c.batch * m))) return rc;
-  HIPCHK(h, hipMemcpyAsync(c.d_users, users, (size_t)n_sel * 4, hipMemcpyHostToDevice, h->stream));
-  if (mask_ptr) {
-    if ((rc = dalloc(h, &c.d_mptr, (size_t)n_sel + 1))) return rc;
-    if ((rc = dalloc(h, &c.d_mitems, (size_t)nmask))) return rc;
-    HIPCHK(h, hipMemcpyAsync(c.d_mptr, mask_ptr, ((size_t)n_sel + 1) * 8, hipMemcpyHostToDevice, h->stream));
-    if (nmask) HIPCHK(h, hipMemcpyAsync(c.d_mitems, mask_items, (size_t)nmask * 4, hipMemcpyHostToDevice, h->stream));
-  }
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  return HPF_OK;
-}
+// The unfused ranking calls (hpf_scores, hpf_rank_topn, hpf_item_ranks) keep the scores of a batch of users
+// (hpf_plan::score_batch_rows) and run their own kernel over them
+struct ScoreCtx : FusedCtx {
+  double *d_scores = nullptr;
+  using FusedCtx::FusedCtx;
 
-// scores (+ mask) of selected rows [b0, b1) into c.d_scores
-int rank_scores(hpf_handle *h, RankCtx &c, uint32_t b0, uint32_t b1, bool mask)
-{
-  const uint32_t m = h->it.rows, rows = b1 - b0;
-  ScoreArgs a;
-  a.users = c.d_users + b0; a.Et = h->u.E; a.Eb = h->it.E; a.scores = c.d_scores;
-  a.n_sel = rows; a.m = m; a.ld = h->ld; a.K = h->K;
-  a.ubias_col = h->cfg.bias ? h->u.bias_col : -1; a.ibias_col = h->cfg.bias ? h->it.bias_col : -1;
-  hipLaunchKernelGGL(score_tile_kernel, dim3((m + 255) / 256, (rows + 15) / 16), dim3(256), 0, h->stream, a);
-  if (mask)
-    hipLaunchKernelGGL(mask_scores_kernel, dim3(std::min<uint32_t>((rows + 3) / 4, 4096)), dim3(256), 0,
-                       h->stream, c.d_users + b0, rows, h->rowptr_dev, h->u.idx, h->u.val,
-                       c.d_mptr ? c.d_mptr + b0 : nullptr, c.d_mitems, c.d_scores, m);
-  return check_launch(h, "score/mask");
-}
+  int prepare(const uint32_t *users, uint32_t n_sel, const uint64_t *mask_ptr, const uint32_t *mask_items)
+  {
+    int rc;
+    if ((rc = rank_check(h, users, n_sel, mask_ptr, mask_items)) || (rc = refresh_e(h))) return rc;
+    batch = hpf_plan::score_batch_rows(h->it.rows, n_sel);
+    if ((rc = upload(users, n_sel, mask_ptr, mask_items))) return rc;
+    return alloc(&d_scores, (size_t)batch * h->it.rows);
+  }
+  // scores (+ mask) of selected rows [b0, b1) into d_scores
+  int scores(uint32_t b0, uint32_t b1, bool mask)
+  {
+    const uint32_t m = h->it.rows, rows = b1 - b0;
+    ScoreArgs a;
+    factor_args(h, a);
+    a.users = d_users + b0; a.scores = d_scores; a.n_sel = rows; a.m = m;
+    hipLaunchKernelGGL(score_tile_kernel, dim3((m + 255) / 256, (rows + 15) / 16), dim3(256), 0, h->stream, a);
+    if (mask)
+      hipLaunchKernelGGL(mask_scores_kernel, dim3(std::min<uint32_t>((rows + 3) / 4, 4096)), dim3(256), 0,
+                         h->stream, d_users + b0, rows, h->rowptr_dev, h->u.idx, h->u.val,
+                         d_mptr ? d_mptr + b0 : nullptr, d_mitems, d_scores, m);
+    return check_launch(h, "score/mask");
+  }
+};
 }  // namespace
 
 int hpf_scores(hpf_handle *h, const uint32_t *users, uint32_t n_sel, double *out)
 {
   if (!h || (n_sel && (!users || !out))) return HPF_ERR_INVALID;
   if (!n_sel) return HPF_OK;
-  RankCtx c; int rc;
-  if ((rc = rank_prepare(h, users, n_sel, nullptr, nullptr, c))) return rc;
+  ScoreCtx c(h); int rc;
+  if ((rc = c.prepare(users, n_sel, nullptr, nullptr))) return rc;
   const uint32_t m = h->it.rows;
   for (uint32_t b0 = 0; b0 < n_sel; b0 += c.batch) {
     const uint32_t b1 = std::min(n_sel, b0 + c.batch);
-    if ((rc = rank_scores(h, c, b0, b1, false))) return rc;
+    if ((rc = c.scores(b0, b1, false))) return rc;
     HIPCHK(h, hipMemcpyAsync(out + (size_t)b0 * m, c.d_scores, (size_t)(b1 - b0) * m * 8, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
   }
@@ -2610,26 +2515,19 @@ int hpf_rank_topn(hpf_handle *h, const uint32_t *users, uint32_t n_sel, const ui
 {
   if (!h || topn == 0 || topn > 1024 || (n_sel && (!users || !out_items || !out_scores))) return HPF_ERR_INVALID;
   if (!n_sel) return HPF_OK;
-  RankCtx c; int rc;
-  if ((rc = rank_prepare(h, users, n_sel, mask_ptr, mask_items, c))) return rc;
+  ScoreCtx c(h); int rc;
+  if ((rc = c.prepare(users, n_sel, mask_ptr, mask_items))) return rc;
   uint32_t NP = 1; while (NP < topn) NP <<= 1;
   uint32_t *d_items = nullptr; double *d_sc = nullptr;
-  if ((rc = dalloc(h, &d_items, (size_t)n_sel * topn)) || (rc = dalloc(h, &d_sc, (size_t)n_sel * topn))) { dfree(d_items); return rc; }
-  for (uint32_t b0 = 0; b0 < n_sel && !rc; b0 += c.batch) {
+  if ((rc = c.alloc(&d_items, (size_t)n_sel * topn)) || (rc = c.alloc(&d_sc, (size_t)n_sel * topn))) return rc;
+  for (uint32_t b0 = 0; b0 < n_sel; b0 += c.batch) {
     const uint32_t b1 = std::min(n_sel, b0 + c.batch);
-    if ((rc = rank_scores(h, c, b0, b1, true))) break;
+    if ((rc = c.scores(b0, b1, true))) return rc;
     hipLaunchKernelGGL(topn_kernel, dim3(b1 - b0), dim3(256), (size_t)NP * 12, h->stream, c.d_scores, b1 - b0,
                        h->it.rows, topn, NP, d_items + (size_t)b0 * topn, d_sc + (size_t)b0 * topn);
-    rc = check_launch(h, "topn_kernel");
+    if ((rc = check_launch(h, "topn_kernel"))) return rc;
   }
-  if (!rc) {
-    hipError_t e = hipMemcpyAsync(out_items, d_items, (size_t)n_sel * topn * 4, hipMemcpyDeviceToHost, h->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(out_scores, d_sc, (size_t)n_sel * topn * 8, hipMemcpyDeviceToHost, h->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    if (e != hipSuccess) { h->err = hipGetErrorString(e); rc = HPF_ERR_HIP; }
-  }
-  dfree(d_items); dfree(d_sc);
-  return rc;
+  return copy_back(h, {{out_items, d_items, (size_t)n_sel * topn * 4}, {out_scores, d_sc, (size_t)n_sel * topn * 8}});
 }
 
 int hpf_item_ranks(hpf_handle *h, const uint32_t *users, uint32_t n_sel, const uint64_t *mask_ptr,
@@ -2640,29 +2538,18 @@ int hpf_item_ranks(hpf_handle *h, const uint32_t *users, uint32_t n_sel, const u
   if (!nq) return HPF_OK;
   for (uint32_t q = 0; q < nq; ++q)
     if (q_sel[q] >= n_sel || q_item[q] >= h->it.rows) { h->err = "query out of range"; return HPF_ERR_INVALID; }
-  RankCtx c; int rc;
-  if ((rc = rank_prepare(h, users, n_sel, mask_ptr, mask_items, c))) return rc;
+  ScoreCtx c(h); int rc;
+  if ((rc = c.prepare(users, n_sel, mask_ptr, mask_items))) return rc;
   uint32_t *d_qs = nullptr, *d_qi = nullptr, *d_rank = nullptr; double *d_sc = nullptr;
-  do {
-    if ((rc = dalloc(h, &d_qs, nq)) || (rc = dalloc(h, &d_qi, nq)) || (rc = dalloc(h, &d_rank, nq)) || (rc = dalloc(h, &d_sc, nq))) break;
-    hipError_t e = hipMemcpyAsync(d_qs, q_sel, (size_t)nq * 4, hipMemcpyHostToDevice, h->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_qi, q_item, (size_t)nq * 4, hipMemcpyHostToDevice, h->stream);
-    if (e != hipSuccess) { h->err = hipGetErrorString(e); rc = HPF_ERR_HIP; break; }
-    for (uint32_t b0 = 0; b0 < n_sel && !rc; b0 += c.batch) {
-      const uint32_t b1 = std::min(n_sel, b0 + c.batch);
-      if ((rc = rank_scores(h, c, b0, b1, true))) break;
-      hipLaunchKernelGGL(rank_query_kernel, dim3(std::min<uint32_t>(nq, 16384)), dim3(256), 0, h->stream, c.d_scores,
-                         h->it.rows, d_qs, d_qi, nq, b0, b1, d_rank, d_sc);
-      rc = check_launch(h, "rank_query_kernel");
-    }
-    if (rc) break;
-    e = hipMemcpyAsync(out_rank, d_rank, (size_t)nq * 4, hipMemcpyDeviceToHost, h->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(out_score, d_sc, (size_t)nq * 8, hipMemcpyDeviceToHost, h->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    if (e != hipSuccess) { h->err = hipGetErrorString(e); rc = HPF_ERR_HIP; }
-  } while (0);
-  dfree(d_qs); dfree(d_qi); dfree(d_rank); dfree(d_sc);
-  return rc;
+  if ((rc = c.alloc(&d_qs, nq, q_sel)) || (rc = c.alloc(&d_qi, nq, q_item)) || (rc = c.alloc(&d_rank, nq)) || (rc = c.alloc(&d_sc, nq))) return rc;
+  for (uint32_t b0 = 0; b0 < n_sel; b0 += c.batch) {
+    const uint32_t b1 = std::min(n_sel, b0 + c.batch);
+    if ((rc = c.scores(b0, b1, true))) return rc;
+    hipLaunchKernelGGL(rank_query_kernel, dim3(std::min<uint32_t>(nq, 16384)), dim3(256), 0, h->stream, c.d_scores,
+                       h->it.rows, d_qs, d_qi, nq, b0, b1, d_rank, d_sc);
+    if ((rc = check_launch(h, "rank_query_kernel"))) return rc;
+  }
+  return copy_back(h, {{out_rank, d_rank, (size_t)nq * 4}, {out_score, d_sc, (size_t)nq * 8}});
 }
 
 // ---- scoring a saved model: per-pair predictions, fused leave-one-out ranks ----
@@ -2671,29 +2558,21 @@ int hpf_predict(hpf_handle *h, const uint32_t *u, const uint32_t *i, size_t cnt,
   if (!h) return HPF_ERR_INVALID;
   if (cnt == 0) return HPF_OK;
   if (!u || !i || !out) return HPF_ERR_INVALID;
-  if (!(h->u.have_E && h->it.have_E) && h->iterations == 0) { h->err = "E state not set"; return HPF_ERR_STATE; }
+  int rc;
+  if ((rc = need_e(h))) return rc;
   for (size_t p = 0; p < cnt; ++p)
     if (u[p] >= h->u.rows || i[p] >= h->it.rows) { h->err = "hpf_predict: index out of range"; return HPF_ERR_INVALID; }
+  if ((rc = scoring_ready(h))) return rc;
+  Scratch sc(h);
   uint32_t *du = nullptr, *di = nullptr; double *dout = nullptr;
-  int rc = HPF_OK;
-  do {
-    if ((rc = check_flags(h))) break;
-    if ((rc = refresh_es(h, h->u)) || (rc = refresh_es(h, h->it))) break;
-    if ((rc = dalloc(h, &du, cnt)) || (rc = dalloc(h, &di, cnt)) || (rc = dalloc(h, &dout, cnt))) break;
-    if ((rc = h2d(h, du, u, cnt * 4)) || (rc = h2d(h, di, i, cnt * 4))) break;
-    PredictArgs a;
-    a.u = du; a.i = di; a.cnt = cnt; a.Et = h->u.E; a.Eb = h->it.E; a.out = dout; a.ld = h->ld; a.K = h->K;
-    a.ubias_col = h->cfg.bias ? h->u.bias_col : -1;
-    a.ibias_col = h->cfg.bias ? h->it.bias_col : -1;
-    const uint32_t blocks = (uint32_t)std::min<size_t>((cnt + 15) / 16, 4096);
-    hipLaunchKernelGGL(predict_kernel, dim3(blocks), dim3(256), 0, h->stream, a);
-    if ((rc = check_launch(h, "predict_kernel"))) break;
-    hipError_t e = hipMemcpyAsync(out, dout, cnt * 8, hipMemcpyDeviceToHost, h->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    if (e != hipSuccess) { h->err = hipGetErrorString(e); rc = HPF_ERR_HIP; }
-  } while (0);
-  dfree(du); dfree(di); dfree(dout);
-  return rc;
+  if ((rc = sc.alloc(&du, cnt, u)) || (rc = sc.alloc(&di, cnt, i)) || (rc = sc.alloc(&dout, cnt))) return rc;
+  PredictArgs a;
+  factor_args(h, a);
+  a.u = du; a.i = di; a.cnt = cnt; a.out = dout;
+  const uint32_t blocks = (uint32_t)std::min<size_t>((cnt + 15) / 16, 4096);
+  hipLaunchKernelGGL(predict_kernel, dim3(blocks), dim3(256), 0, h->stream, a);
+  if ((rc = check_launch(h, "predict_kernel"))) return rc;
+  return copy_back(h, {{out, dout, cnt * 8}});
 }
 
 int hpf_loo_ranks(hpf_handle *h, const uint32_t *users, uint32_t n_sel, const uint64_t *mask_ptr,
@@ -2710,21 +2589,20 @@ int hpf_loo_ranks(hpf_handle *h, const uint32_t *users, uint32_t n_sel, const ui
   if ((rc = rank_check(h, users, n_sel, mask_ptr, mask_items))) return rc;
   for (uint32_t b = 0; b < n_sel; ++b)
     if (q_item[b] >= m) { h->err = "query item out of range"; return HPF_ERR_INVALID; }
-  if ((rc = check_flags(h))) return rc;
-  if ((rc = refresh_es(h, h->u)) || (rc = refresh_es(h, h->it))) return rc;
+  if ((rc = scoring_ready(h))) return rc;
 
   FusedCtx c(h);
   uint32_t *d_q = nullptr, *d_rank = nullptr, *d_masked = nullptr; double *d_sc = nullptr;
-  if ((rc = c.upload(users, n_sel, mask_ptr, mask_items)) || (rc = c.alloc(&d_q, n_sel, q_item)) || (rc = c.alloc(&d_rank, n_sel)) ||
+  if ((rc = c.upload(users, n_sel, mask_ptr, mask_items)) || (rc = c.bit_rows(n_sel)) || (rc = c.alloc(&d_q, n_sel, q_item)) || (rc = c.alloc(&d_rank, n_sel)) ||
       (rc = c.alloc(&d_masked, n_sel)) || (rc = c.alloc(&d_sc, n_sel))) return rc;
   for (uint32_t b0 = 0; b0 < n_sel; b0 += c.batch) {
     const uint32_t rows = std::min(n_sel - b0, c.batch);
     if ((rc = c.mask_batch(b0, rows))) return rc;
     LooArgs a;
-    a.users = c.d_users + b0; a.q_item = d_q + b0; a.Et = h->u.E; a.Eb = h->it.E; a.bits = c.d_bits;
+    factor_args(h, a);
+    a.users = c.d_users + b0; a.q_item = d_q + b0; a.bits = c.d_bits;
     a.rank = d_rank + b0; a.masked = d_masked + b0; a.score = d_sc + b0;
-    a.n_sel = rows; a.limit = limit; a.ld = h->ld; a.K = h->K; a.words = c.words;
-    a.ubias_col = h->cfg.bias ? h->u.bias_col : -1; a.ibias_col = h->cfg.bias ? h->it.bias_col : -1;
+    a.n_sel = rows; a.limit = limit; a.words = c.words;
     const hpf_plan::RankGrid g = hpf_plan::rank_grid(rows, (limit + 63) / 64);
     a.tiles_per_split = g.tiles_per_split;
     const bool launched = launch_rank(h->K, [&](auto nch) {
@@ -2733,12 +2611,7 @@ int hpf_loo_ranks(hpf_handle *h, const uint32_t *users, uint32_t n_sel, const ui
     if (!launched) { h->err = "loo_rank_kernel: no instance for this column count"; return HPF_ERR_UNSUPPORTED; }
     if ((rc = check_launch(h, "loo_rank_kernel"))) return rc;
   }
-  hipError_t e = hipMemcpyAsync(out_rank, d_rank, (size_t)n_sel * 4, hipMemcpyDeviceToHost, h->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(out_score, d_sc, (size_t)n_sel * 8, hipMemcpyDeviceToHost, h->stream);
-  if (e == hipSuccess && out_masked) e = hipMemcpyAsync(out_masked, d_masked, (size_t)n_sel * 4, hipMemcpyDeviceToHost, h->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-  if (e != hipSuccess) { h->err = hipGetErrorString(e); return HPF_ERR_HIP; }
-  return HPF_OK;
+  return copy_back(h, {{out_rank, d_rank, (size_t)n_sel * 4}, {out_score, d_sc, (size_t)n_sel * 8}, {out_masked, d_masked, (size_t)n_sel * 4}});
 }
 
 int hpf_rank_queries(hpf_handle *h, const uint32_t *users, uint32_t n_sel, const uint64_t *mask_ptr,
@@ -2759,11 +2632,10 @@ int hpf_rank_queries(hpf_handle *h, const uint32_t *users, uint32_t n_sel, const
   if ((rc = rank_check(h, users, n_sel, mask_ptr, mask_items))) return rc;
   for (uint64_t q = 0; q < nq; ++q) if (q_items[q] >= m) { h->err = "query item out of range"; return HPF_ERR_INVALID; }
   if (!nq) return HPF_OK;
-  if ((rc = check_flags(h))) return rc;
-  if ((rc = refresh_es(h, h->u)) || (rc = refresh_es(h, h->it))) return rc;
+  if ((rc = scoring_ready(h))) return rc;
 
   FusedCtx c(h);
-  if ((rc = c.upload(users, n_sel, mask_ptr, mask_items))) return rc;
+  if ((rc = c.upload(users, n_sel, mask_ptr, mask_items)) || (rc = c.bit_rows(n_sel))) return rc;
   // rows: a selected user with at most RQ_QCAP of its queries (a query's rank does not depend on the user's other
   // queries, so cutting a user is exact); in the order of the selected users, so a batch owns a run of them
   std::vector<uint32_t> row_sel, row_q0, row_nq, first_row;   // first_row[batch index] -> its first row
@@ -2788,11 +2660,11 @@ int hpf_rank_queries(hpf_handle *h, const uint32_t *users, uint32_t n_sel, const
     if (!rows) continue;
     if ((rc = c.mask_batch(b0, std::min(n_sel - b0, c.batch)))) return rc;
     RqArgs a;
+    factor_args(h, a);
     a.users = c.d_users + b0; a.row_sel = d_rsel + r0; a.row_q0 = d_rq0 + r0; a.row_nq = d_rnq + r0; a.q_item = d_q;
-    a.Et = h->u.E; a.Eb = h->it.E; a.bits = c.d_bits; a.skey = d_skey; a.sitem = d_sitem;
+    a.bits = c.d_bits; a.skey = d_skey; a.sitem = d_sitem;
     a.sperm = d_sperm; a.rank = d_rank; a.score = d_sc;
-    a.nrows = rows; a.m = m; a.ld = h->ld; a.K = h->K; a.words = c.words;
-    a.ubias_col = h->cfg.bias ? h->u.bias_col : -1; a.ibias_col = h->cfg.bias ? h->it.bias_col : -1;
+    a.nrows = rows; a.m = m; a.words = c.words;
     const hpf_plan::RankGrid g = hpf_plan::rank_grid(rows, (m + 63) / 64);
     a.tiles_per_split = g.tiles_per_split;
     hipLaunchKernelGGL(rq_threshold_kernel, dim3((rows + 3) / 4), dim3(256), 0, h->stream, a);
@@ -2802,11 +2674,7 @@ int hpf_rank_queries(hpf_handle *h, const uint32_t *users, uint32_t n_sel, const
     if (!launched) { h->err = "rank_queries_kernel: no instance for this column count"; return HPF_ERR_UNSUPPORTED; }
     if ((rc = check_launch(h, "rank_queries_kernel"))) return rc;
   }
-  hipError_t e = hipMemcpyAsync(out_rank, d_rank, (size_t)nq * 4, hipMemcpyDeviceToHost, h->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(out_score, d_sc, (size_t)nq * 8, hipMemcpyDeviceToHost, h->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-  if (e != hipSuccess) { h->err = hipGetErrorString(e); return HPF_ERR_HIP; }
-  return HPF_OK;
+  return copy_back(h, {{out_rank, d_rank, (size_t)nq * 4}, {out_score, d_sc, (size_t)nq * 8}});
 }
 
 int hpf_get_work_info(hpf_handle *h, hpf_work_info *out)
@@ -2848,8 +2716,9 @@ int hpf_gather_only(hpf_handle *h, int side, int reps, float *ms_out)
   const PhiLaunch pl = phi_setup(h, own, oth, false, a);         // the pass's own workgroups
   *ms_out = 0.0f;
   if (!a.nseg) return HPF_OK;
+  Scratch sc(h);
   uint32_t *sink = nullptr;
-  if ((rc = dalloc(h, &sink, 1))) return rc;
+  if ((rc = sc.alloc(&sink, 1))) return rc;
   hipEvent_t e0 = nullptr, e1 = nullptr;
   hipError_t e = hipEventCreate(&e0);
   if (e == hipSuccess) e = hipEventCreate(&e1);
@@ -2865,7 +2734,6 @@ int hpf_gather_only(hpf_handle *h, int side, int reps, float *ms_out)
   }
   if (e0) (void)hipEventDestroy(e0);
   if (e1) (void)hipEventDestroy(e1);
-  dfree(sink);
   if (!ok) { h->err = "no gather-only kernel for this shape"; return HPF_ERR_UNSUPPORTED; }
   if (e != hipSuccess) { h->err = std::string("gather-only probe: ") + hipGetErrorString(e); return HPF_ERR_HIP; }
   return check_launch(h, "gather-only probe");

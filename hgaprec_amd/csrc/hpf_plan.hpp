@@ -1,8 +1,11 @@
 // hpf_plan.hpp -- what the GPU will run, decided on the host: the experimental knobs, the shapes of the phi pass, of the rows
 // of W and of the row sweep for a column count (plan_shapes), which kernel instances exist for them (has_*), and the batches
-// and launch grid of the fused rank kernels (rank_batch_users, rank_grid, rank_chunks).
+// and launch grid of the fused rank kernels (rank_batch_users, rank_grid, rank_chunks), the score batch of the unfused ones
+// (score_batch_rows), and the tiled pass: whether a side is tiled and with which tiles (tile_policy, tiling_fits) and which
+// XCD queue and chunk every segment runs in (plan_tile_queues).
 // Plain C++17 without a HIP header: hpf_capi.hip builds its handle and its dispatcher from it, host/plan_selftest.cpp
-// walks every column count on a CPU.
+// walks every column count on a CPU, pins the tile policy, checks the invariants of the queue plan over a seeded sweep and
+// prints the plan of a fixed list of cases (tests/data/tile_queue_table.txt, recorded before the arithmetic moved here).
 #pragma once
 #include "../../include/hpf.h"
 
@@ -11,6 +14,8 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <utility>
+#include <vector>
 
 namespace hpf_plan {
 
@@ -40,7 +45,7 @@ struct Knobs {
   int tile_order = 1;
   uint32_t tile_split_below = 8;       // with fewer tiles than this EVERY tile is cut eight ways, a piece per XCD queue (round 4: below 32 tiles; C4's seven tiles of
                                        // items are 2 % faster that way than levelled); from here on whole tiles are dealt eight at a time and the remainder levels
-                                       // the queues (build_tiled_side)
+                                       // the queues (plan_tile_queues)
   int tile_sides = 3;                   // HPF_TILE_SIDES: bit 0 the user pass, bit 1 the item pass (experiments)
   int tile_mode = 2; uint64_t tile_bytes = 4u << 20; uint32_t tile_chunk = 0 /* 0: two segments per wave of the workgroup */, tile_min_run = 0; double tile_min_share = 0.15;
   uint32_t phi_blocks = 65536;      // ~one wave per few segments; the dispatcher balances (HPF_PHI_BLOCKS)
@@ -135,6 +140,191 @@ inline RankGrid rank_grid(uint32_t rows, uint32_t ntiles)
   g.tiles_per_split = (ntiles + g.splits - 1) / g.splits;
   g.splits = (ntiles + g.tiles_per_split - 1) / g.tiles_per_split;
   return g;
+}
+
+// Rows of scores the unfused ranking calls (hpf_scores, hpf_rank_topn, hpf_item_ranks) keep at once: <= 1 GiB of rows of
+// m doubles, a multiple of 16, at least 16; never more than the selected users need
+inline uint32_t score_batch_rows(uint32_t m, uint32_t n_sel)
+{
+  uint64_t bmax = ((1ull << 30) / (8ull * std::max<uint32_t>(m, 1))) & ~15ull;
+  bmax = std::max<uint64_t>(bmax, 16);
+  return (uint32_t)std::min<uint64_t>(bmax, ((uint64_t)n_sel + 15) & ~15ull);
+}
+
+// ---- the tiled phi pass: what is tiled, and where its segments run --------------------------------
+// Policy of one side, decided before anything is allocated.  The gathered matrix (rows_oth rows of row_bytes) is cut into
+// tiles of T consecutive rows; owner rows with at least light_below nonzeros are heavy (their nonzeros are regrouped by
+// tile), the rest stay row-major.  Auto mode (tile_mode 2): the gathered matrix must be larger than 2.5 tiles.  Forced
+// (tile_mode 1, an experimental knob): every row is regrouped whenever there are two tiles.  tile == false: not worth tiling.
+struct TilePolicy { bool tile = false; uint32_t T = 0, tiles = 0, min_run = 0; uint64_t light_below = 0; };
+inline TilePolicy tile_policy(uint32_t rows_oth, size_t row_bytes, uint64_t nnz, uint32_t rows, uint32_t nz_per_batch, bool item_side,
+                              const Knobs &kn, uint32_t cfg_tiling)
+{
+  TilePolicy p;
+  if (!((kn.tile_sides >> (item_side ? 1 : 0)) & 1)) return p;
+  if (kn.tile_mode == 0 || cfg_tiling == 1 || nnz == 0 || rows == 0) return p;      // (>= 2^32 nonzeros: positions are 64-bit throughout;
+                                                                                    //  segments and partial slots must number < 2^31, checked by the builder)
+  p.T = (uint32_t)std::max<uint64_t>(kn.tile_bytes / row_bytes, 1);
+  p.tiles = (rows_oth + p.T - 1) / p.T;
+  if (p.tiles < 2 || p.tiles > 65534) return p;
+  if (kn.tile_mode == 2 && (uint64_t)rows_oth * row_bytes < 2 * kn.tile_bytes + kn.tile_bytes / 2) return p;
+  // a gathered matrix of a few tiles is already served largely from L2 when the ratings are skewed (the popular
+  // rows stay resident): regrouping then pays only for rows that meet a tile many times (size sweep, m = 20 000:
+  // four tiles, user pass 3.19 ms row-major, 3.64 ms with runs of 16)
+  // ... and a run is worth its fixed work from two batches on: a batch is 64 / G nonzeros (K = 50: G = 4, sixteen
+  // per batch -- with runs of 16 its ten-tile user side went 2.31 -> 2.68 ms)
+  // Round 5: with one wave per workgroup on a tiled side (Knobs::phi_wg) a run costs less, and the bar of 16 came down
+  // to 12 where a batch holds eight nonzeros or fewer (C2 8.42 -> 8.34 ms, a C3 shard 24.3 -> 23.9; 10 is better still at C2
+  // and worse on the shard; C4 is flat from 10 to 16; K = 50's two batches of sixteen stay: 24 loses 1 %; experiments.md)
+  p.min_run = kn.tile_min_run ? kn.tile_min_run                    // HPF_TILE_RUN: as given
+                              : (nz_per_batch >= 16u ? 2u * nz_per_batch : 12u);
+  p.light_below = (uint64_t)p.tiles * p.min_run * (p.tiles < 8 ? 4u : 1u);
+  if (kn.tile_mode == 1) p.light_below = 0;                         // forced: every row is regrouped
+  p.tile = true;
+  return p;
+}
+
+// Room for the temporaries of the tiling (26 bytes per nonzero)?  Decided from what the handle holds and the size of the
+// device (tot: its TOTAL bytes), not from the free memory of the moment: tiling changes the order of a row's
+// sum, and whether a side is tiled must be a function of the job, not of what else happens to be allocated.
+inline bool tiling_fits(uint32_t ld, uint32_t n_users, uint32_t n_items, uint64_t nnz, bool with_val, size_t tot)
+{
+  const double by = with_val ? 1.0 : 0.0;
+  const double resident = 5.0 * 8.0 * (double)ld * ((double)n_users + (double)n_items)        // S, E, L, W + vectors of both sides
+                        + (double)nnz * (3.0 * (4.0 + by));                                  // CSR, CSC and the other side's tiled copy
+  return !(resident + (double)nnz * (26.0 + 4.0 + by) + (double)(1ull << 30) > 0.9 * (double)tot);
+}
+
+// A tiled side's segments are sorted by key: key 0 the row-major rest, key t the tile t - 1.  fs[k] = the first segment of
+// key k, TILE_NO_SEG where it has none; a key ends where the next one that is present begins
+constexpr uint32_t TILE_NO_SEG = 0xffffffffu;
+inline uint32_t tile_key_end(const std::vector<uint32_t> &fs, uint32_t nseg, uint32_t k)
+{
+  for (uint32_t j = k + 1; j < (uint32_t)fs.size(); ++j) if (fs[j] != TILE_NO_SEG) return fs[j];
+  return nseg;
+}
+// end of the row-major rest: the first tiled segment (nseg where there is none); 0 without a rest
+inline uint32_t tile_rest_end(const std::vector<uint32_t> &fs, uint32_t nseg) { return fs[0] != TILE_NO_SEG ? tile_key_end(fs, nseg, 0) : 0u; }
+
+struct TileChunk { uint32_t x, y; };          // segments [x, y) of one workgroup: the uint2 the pass reads; {0, 0} = none
+struct TileQueuePlan {
+  std::vector<TileChunk> chunks;              // chunks[j * 8 + x]: the j-th workgroup of XCD x's queue
+  uint32_t chunk_segs = 0;                    // segments per chunk of a tile (hpf_work_info.tile_chunk_*)
+  bool ok = false;                            // false: no list (no segment at all, or too long for a launch even so)
+};
+
+// Where every segment of a tiled pass runs.
+//   fs, nseg   the first segment per key (tiles + 1 keys) and the number of segments
+//   rest_nnz   nonzeros in front of the first tiled segment (its Seg::start; all of them where nothing is tiled)
+//   wg         threads per workgroup of the pass; max_wgs the workgroups a launch holds (2^28 / wg)
+// Chunks: eight queues, one per XCD (workgroup b runs on XCD b % 8).  The first 8 * floor(t / 8) of the t tiles
+// that hold segments go WHOLE to the queue with the least work so far (a tile's segments stay together and in order:
+// its rows are fetched into one L2, once); the remaining t mod 8 tiles level the queues: their segments are poured, in
+// order, into the queues up to the common fill mark, so that a levelling tile is shared by two or three XCDs instead of
+// all eight and every queue ends at the same count (round 5; until round 4 EVERY tile was cut eight ways below 32
+// tiles, so that each XCD fetched every tile: an eighth of C4 -- 22 tiles of users -- ran its item pass in 1.36 ms,
+// now 1.10; 9 and 12 tiles: -4 %; from 32 tiles on nothing changes).  Below tile_split_below = 8 tiles the old rule
+// stays (HPF_TILE_SPLIT_BELOW=N: for fewer than N tiles).  The row-major rest (key 0) is cut eight ways.
+inline TileQueuePlan plan_tile_queues(const std::vector<uint32_t> &fs, uint32_t nseg, uint32_t tiles, uint64_t rest_nnz, uint32_t wg,
+                                      size_t max_wgs, const Knobs &kn)
+{
+  TileQueuePlan out;
+  const uint32_t nkeys = tiles + 1;
+  std::vector<std::pair<uint32_t, uint32_t>> q[8], qt[8];
+  uint64_t load[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  auto key_end = [&](uint32_t k) { return tile_key_end(fs, nseg, k); };
+  uint64_t tiled_segs = 0;
+  uint32_t tiles_present = 0;
+  for (uint32_t k = 1; k < nkeys; ++k) if (fs[k] != TILE_NO_SEG) { tiles_present++; tiled_segs += key_end(k) - fs[k]; }
+  const bool old_rule = tiles < kn.tile_split_below;
+  const uint32_t whole_tiles = old_rule ? 0u : (tiles_present / 8u) * 8u;
+  uint32_t seen = 0;
+  int fill = 0;                                                  // the queue the levelling tiles are being poured into
+  const uint64_t mark = (tiled_segs + 7) / 8;                    // the common fill mark
+  for (uint32_t k = 1; k < nkeys; ++k) {
+    if (fs[k] == TILE_NO_SEG) continue;
+    const uint32_t a0 = fs[k], a1 = key_end(k);
+    if (seen++ < whole_tiles) {
+      int best = 0;
+      for (int x = 1; x < 8; ++x) if (load[x] < load[best]) best = x;
+      qt[best].push_back({a0, a1}); load[best] += a1 - a0;
+      continue;
+    }
+    if (old_rule) {
+      const uint64_t n = a1 - a0;
+      for (int x = 0; x < 8; ++x) {
+        const uint32_t lo = a0 + (uint32_t)(n * x / 8), hi = a0 + (uint32_t)(n * (x + 1) / 8);
+        if (hi > lo) { qt[x].push_back({lo, hi}); load[x] += hi - lo; }
+      }
+      continue;
+    }
+    for (uint32_t p0 = a0; p0 < a1;) {
+      while (fill < 7 && load[fill] >= mark) ++fill;
+      const uint64_t room = fill < 7 ? mark - load[fill] : (uint64_t)(a1 - p0);
+      const uint32_t take = (uint32_t)std::min<uint64_t>(room, a1 - p0);
+      qt[fill].push_back({p0, p0 + take}); load[fill] += take;
+      p0 += take;
+    }
+  }
+  // the row-major rest: an eighth per queue.  tile_order 0: in front of the tiles; 1: in front on the even
+  // XCDs, behind on the odd ones (half the chip pulls over the fabric while the other half runs from L2);
+  // 2: dealt between the tiles in equal pieces
+  const uint32_t c0 = fs[0] != TILE_NO_SEG ? fs[0] : 0u, c1 = fs[0] != TILE_NO_SEG ? key_end(0) : 0u;
+  for (int x = 0; x < 8; ++x) {
+    const uint64_t n = c1 - c0;
+    const uint32_t lo = c0 + (uint32_t)(n * x / 8), hi = c0 + (uint32_t)(n * (x + 1) / 8);
+    const bool front = kn.tile_order == 0 || (kn.tile_order == 1 && (x & 1) == 0);
+    if (kn.tile_order == 2 && !qt[x].empty()) {
+      const uint64_t nt = qt[x].size(), nc = hi - lo;
+      for (uint64_t t = 0; t < nt; ++t) {
+        const uint32_t l2 = lo + (uint32_t)(nc * t / nt), h2 = lo + (uint32_t)(nc * (t + 1) / nt);
+        if (h2 > l2) q[x].push_back({l2, h2});
+        q[x].push_back(qt[x][t]);
+      }
+      continue;
+    }
+    if (front && hi > lo) q[x].push_back({lo, hi});
+    for (auto &rg : qt[x]) q[x].push_back(rg);
+    if (!front && hi > lo) q[x].push_back({lo, hi});
+  }
+  // a launch holds fewer than 2^32 work-items (the AQL packet counts them in 32 bits): at most 2^28 / wg workgroups
+  // (2^20 of four waves, 2^22 of one -- round 5 kept 2^20 for the one-wave groups as well, and the longest lists, whole
+  // C3 or C5 on one GPU, got chunks of 8-16 segments instead of two), so a list too long for chunks of
+  // tile_chunk segments gets longer chunks; hpf_work_info.tile_chunk_user / _item say what was used
+  uint32_t CH = kn.tile_chunk ? kn.tile_chunk : 2 * (wg / 64);      // two segments per wave
+  // the row-major segments of a side with short rows (users: a few batches each) come in chunks of ~4096 nonzeros:
+  // a workgroup that lives for two 40-nonzero rows costs more to dispatch than to run (K = 50, 10^6 light users
+  // in chunks of 8: user pass 2.27 -> 2.54 ms)
+  uint32_t CHc = CH;
+  if (c1 > c0) {
+    const uint64_t avg = std::max<uint64_t>(rest_nnz / (c1 - c0), 1);
+    CHc = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(4096ull * wg / 256 / avg, CH), 512);
+  }
+  auto chunk_of = [&](const std::pair<uint32_t, uint32_t> &rg, uint32_t ch, uint32_t chc) { return (rg.first >= c0 && rg.second <= c1) ? chc : ch; };
+  for (;; CH *= 2, CHc *= 2) {
+    size_t worst = 0;
+    for (int x = 0; x < 8; ++x) {
+      size_t c = 0;
+      for (auto &rg : q[x]) { const uint32_t ch = chunk_of(rg, CH, CHc); c += (rg.second - rg.first + ch - 1) / ch; }
+      worst = std::max(worst, c);
+    }
+    if (worst * 8 <= max_wgs || CH >= (1u << 30)) break;
+  }
+  std::vector<TileChunk> qc[8];
+  size_t longest = 0;
+  for (int x = 0; x < 8; ++x) {
+    for (auto &rg : q[x]) {
+      const uint32_t ch = chunk_of(rg, CH, CHc);
+      for (uint32_t p0 = rg.first; p0 < rg.second; p0 += std::min(ch, rg.second - p0)) qc[x].push_back({p0, p0 + std::min(ch, rg.second - p0)});
+    }
+    longest = std::max(longest, qc[x].size());
+  }
+  out.chunk_segs = CH;
+  if (longest == 0 || longest * 8 > max_wgs) return out;
+  out.chunks.assign(longest * 8, TileChunk{0u, 0u});
+  for (int x = 0; x < 8; ++x) for (size_t j = 0; j < qc[x].size(); ++j) out.chunks[j * 8 + x] = qc[x][j];
+  out.ok = true;
+  return out;
 }
 
 // ---- the plan ---------------------------------------------------------------------------------------------------------

@@ -7,6 +7,11 @@ doubles equal to the w_storage = 3 plan) and the shapes the knobs HPF_PHI_CFG / 
 launch grid and the chunk counts of the fused rank kernels (rank_batch_users, rank_grid, rank_chunks), and prints the mapping
 as runs.  The runs must be tests/data/plan_table.txt, which was recorded from the library's hpf_get_work_info on a GPU
 before the planner became a header of its own.
+
+The same program pins the tile policy (tile_policy, tiling_fits) to DESIGN.md section 5, checks the invariants of the queue
+plan of a tiled pass (plan_tile_queues) over a seeded sweep and, run as `plan_selftest_asan tile-queues`, prints
+`tq case-id chunks chunk_segs fnv64` for a fixed list of cases.  Those lines must be tests/data/tile_queue_table.txt, recorded from the queue arithmetic as it stood inside
+hpf_capi.hip before it moved into the header.
 """
 import subprocess
 from pathlib import Path
@@ -30,3 +35,9 @@ def test_planner_selftest_and_recorded_table():
     got, want = table_rows(r.stdout), table_rows((ROOT / "tests" / "data" / "plan_table.txt").read_text())
     assert len(want) > 100 and all(len(row) in (5, 11) for row in want)
     assert got == want, [(g, w) for g, w in zip(got, want) if g != w][:5]
+    r = subprocess.run([str(ROOT / "hgaprec_amd" / "plan_selftest_asan"), "tile-queues"], capture_output=True, text=True, env=env, timeout=300)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-6000:]
+    assert "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr
+    got_tq, want_tq = table_rows(r.stdout), table_rows((ROOT / "tests" / "data" / "tile_queue_table.txt").read_text())
+    assert len(want_tq) >= 16 and all(len(row) == 5 and row[0] == "tq" for row in want_tq)
+    assert got_tq == want_tq, [(g, w) for g, w in zip(got_tq, want_tq) if g != w][:5]
