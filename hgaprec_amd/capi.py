@@ -41,12 +41,38 @@ EXPORTS = [
     "hpf_get_work_info", "hpf_upload_csr_device", "hpf_get_csc", "hpf_set_state_device", "hpf_get_state_device",
     "hpf_iteration_times", "hpf_debug_poke_index", "hpf_start_sums", "hpf_host_alloc", "hpf_host_free",
     "hpf_heldout_bind", "hpf_heldout_ll_bound",
-    "hpf_predict", "hpf_loo_ranks", "hpf_rank_queries",
+    "hpf_predict", "hpf_loo_ranks", "hpf_rank_queries", "hpf_recommend",
 ]
 
 # queries of one row of rank_queries_kernel (RQ_QCAP in csrc/hpf_kernels.hpp): hpf_rank_queries cuts a user with more
 # into several rows; tests put their query counts around it
 RANK_QUERIES_QCAP = 32
+
+# largest topn hpf_recommend runs fused (TOPN_FUSED_MAX in csrc/hpf_plan.hpp); above it, up to 1024, hpf_rank_topn's route
+RECOMMEND_FUSED_MAX = 256
+
+
+def recommend_cap(topn):
+    """entries of the candidate buffer of one (user, split) of hpf_recommend (hpf_plan::topn_cap)"""
+    np2 = 64
+    while np2 < topn:
+        np2 *= 2
+    return 2 * np2
+
+
+def recommend_grid(rows, n_items, topn):
+    """(blocks, splits, tiles_per_split) of hpf_recommend's sweep over `rows` users (hpf_plan::topn_grid): rank_grid's policy,
+    and a split of at least cap / 16 tiles unless the item range is shorter"""
+    ntiles = (n_items + 63) // 64
+    blocks = (rows + 63) // 64
+    splits = max(1, min(ntiles, (1024 + blocks - 1) // blocks))
+    tps = (ntiles + splits - 1) // splits
+    splits = (ntiles + tps - 1) // tps
+    least = max(1, min(ntiles, recommend_cap(topn) // 16))
+    if tps < least:
+        tps = least
+        splits = max(1, (ntiles + least - 1) // least)
+    return blocks, splits, tps
 
 
 
@@ -190,6 +216,8 @@ def load_library(path: os.PathLike | None = None) -> C.CDLL:
         lib.hpf_loo_ranks.argtypes = [vp, u32p, C.c_uint32, u64p, u32p, u32p, C.c_uint32, u32p, dp, u32p]
     if hasattr(lib, "hpf_rank_queries"):
         lib.hpf_rank_queries.argtypes = [vp, u32p, C.c_uint32, u64p, u32p, u64p, u32p, u32p, dp]
+    if hasattr(lib, "hpf_recommend"):
+        lib.hpf_recommend.argtypes = [vp, u32p, C.c_uint32, u64p, u32p, C.c_uint32, u32p, dp]
     lib.hpf_comm_unique_id.argtypes = [vp]
     lib.hpf_comm_init.argtypes = [vp, vp]
     lib.hpf_allreduce_exchange.argtypes = [vp]
@@ -510,6 +538,23 @@ class Hpf:
         items = np.empty((users.size, topn), dtype=np.uint32)
         sc = np.empty((users.size, topn), dtype=np.float64)
         self._check(self.lib.hpf_rank_topn(self._h, _ptr(users, C.c_uint32), users.size, pmp, pmi, topn,
+                                           _ptr(items, C.c_uint32), _ptr(sc, C.c_double)))
+        return items, sc
+
+    def recommend(self, users, topn=100, mask_ptr=None, mask_items=None):
+        """the topn best items of every selected user (hpf_recommend): what rank_topn returns, bit for bit, without a
+        score matrix up to RECOMMEND_FUSED_MAX -> (items, scores), each [len(users), topn]"""
+        users = np.ascontiguousarray(users, dtype=np.uint32)
+        if users.ndim != 1:
+            raise ValueError("users: a one-dimensional array")
+        mp, mi, pmp, pmi = self._mask(mask_ptr, mask_items)
+        if mp is not None and mp.size != users.size + 1:
+            raise ValueError("mask_ptr must have len(users) + 1 entries")
+        topn = int(topn)
+        shape = (users.size, topn if 0 < topn <= 1024 else 0)
+        items = np.empty(shape, dtype=np.uint32)
+        sc = np.empty(shape, dtype=np.float64)
+        self._check(self.lib.hpf_recommend(self._h, _ptr(users, C.c_uint32), users.size, pmp, pmi, topn & 0xffffffff,
                                            _ptr(items, C.c_uint32), _ptr(sc, C.c_double)))
         return items, sc
 

@@ -70,6 +70,16 @@ int Env::parse(int argc, char **argv, bool echo, std::string *bad)
     else if (!strcmp(s, "-rmse")) { rmse = true; }
     else if (!strcmp(s, "-msr")) { msr = true; }
     else if (!strcmp(s, "-eval-all")) { eval_all = true; }       // extension: every user's every test item, from a saved model
+    else if (!strcmp(s, "-recommend")) {                          // extension: the N best items of every user, from a saved model
+      const char *v = next(); char *end = nullptr;
+      const long nrec = strtol(v, &end, 10);
+      if (!*v || *end || nrec < 1 || nrec > 1024) {
+        usage_error = "-recommend needs the number of items per user, 1 .. 1024";
+        if (bad) *bad = s;
+        return 2;
+      }
+      recommend = (uint32_t)nrec;
+    }
     else if (!strcmp(s, "-model-dir")) { model_dir = next(); }   // extension: where a score mode finds the factor files
     else if (!strcmp(s, "-novb")) { vb = false; }
     else if (!strcmp(s, "-wals_l") || !strcmp(s, "-wals_C")) { next(); }

@@ -57,7 +57,12 @@ struct Env {
   // extension: -eval-all ranks EVERY hit test item of EVERY user of a saved model (compute_itemrank judges a sample of at
   // most 1000 users) and writes itemrank_all.tsv, eval_users.tsv and eval_all.txt; a score mode like the three above
   bool eval_all = false;
-  bool score_mode() const { return gen_ranking || rmse || msr || eval_all; }
+  // extension: -recommend N writes the N best items of EVERY user of a saved model (recommend.tsv: the first three columns
+  // of ranking.tsv, which lists a sample of at most 1000 users; recommend.txt) through hpf_recommend; a score mode too.
+  // N outside 1 .. 1024 or no N: parse() returns 2 and says why in usage_error
+  uint32_t recommend = 0;
+  std::string usage_error;
+  bool score_mode() const { return gen_ranking || rmse || msr || eval_all || recommend > 0; }
 
   std::string prefix;          // output directory (Env::prefix)
   FILE *plogf = nullptr;       // param.txt

@@ -13,7 +13,7 @@
 // stand-in (`-comm host`, for tests on a single GPU).  The output files are
 // the same as in a single-GPU run.
 //
-// Scoring a saved model: -gen-ranking / -rmse / -msr / -eval-all read the data like a training run, load
+// Scoring a saved model: -gen-ranking / -rmse / -msr / -eval-all / -recommend read the data like a training run, load
 // the factor files a run has written (from the current directory like the reference, or from
 // -model-dir DIR) into the handle's expectations, write ONE report and exit (Driver::score).
 //
@@ -848,12 +848,51 @@ struct Driver {
     env.lerr("-eval-all: %llu users, %llu test items ranked", (unsigned long long)mean.users, (unsigned long long)mean.pairs);
   }
 
+  // -recommend N (extension): what a recommender is for -- the N best items of EVERY user, training items with a
+  // rating > 0 and the user's validation items zeroed exactly as compute_precision zeroes them for its sample -- through
+  // hpf_recommend (no score reaches memory up to N = 256).  recommend.tsv has the first three columns of ranking.tsv under
+  // ranking.tsv's rule (train_r(u, it) == 0; the padding beyond m items is never printed), users in seq order;
+  // recommend.txt users, lines and N.  A chunk of users is written before the next is ranked: host memory is O(chunk x N).
+  void recommend_report() {
+    const uint32_t N = env.recommend, CH = 1u << 16;
+    const std::string rpath = env.file_str("/recommend.tsv"), cpath = env.file_str("/recommend.txt");
+    FILE *f = open_or_die(rpath, "w");
+    std::vector<uint32_t> us, mitems, items; std::vector<uint64_t> mptr; std::vector<double> scores;
+    unsigned long long lines = 0;
+    for (uint32_t u0 = 0; u0 < n; u0 += CH) {
+      const uint32_t u1 = std::min(n, u0 + CH);
+      us.clear(); mitems.clear(); mptr.assign(1, 0);
+      for (uint32_t u = u0; u < u1; ++u) {
+        us.push_back(u);
+        for (size_t a = lower(rt.validation, u, 0); a < rt.validation.u.size() && rt.validation.u[a] == u; ++a)
+          mitems.push_back(rt.validation.i[a]);
+        mptr.push_back(mitems.size());
+      }
+      items.resize(us.size() * (size_t)N); scores.resize(us.size() * (size_t)N);
+      int rc = hpf_recommend(h, us.data(), (uint32_t)us.size(), mptr.data(), mitems.data(), N, items.data(), scores.data());
+      if (rc) die("hpf_recommend", rc);
+      for (size_t b = 0; b < us.size(); ++b) {
+        const uint32_t u = us[b];
+        for (uint32_t j = 0; j < m && j < N; ++j) {
+          const uint32_t it = items[b * N + j];
+          if (train_r(u, it) == 0) { fprintf(f, "%d\t%d\t%.5f\n", rt.seq2user[u], rt.seq2item[it], scores[b * N + j]); ++lines; }
+        }
+      }
+    }
+    close_or_die(f, rpath);
+    FILE *cf = open_or_die(cpath, "w");
+    fprintf(cf, "%u\t%llu\t%u\n", n, lines, N);
+    close_or_die(cf, cpath);
+    env.lerr("-recommend: %u users, %llu lines in recommend.tsv", n, lines);
+  }
+
   // one report on the loaded state, in the reference's order of tests (main.cc:254-285, then -gen-ranking)
   void score() {
     load_model();
     if (env.rmse) compute_rmse();
     else if (env.msr) gen_msr_csv();
     else if (env.eval_all) eval_all_report();
+    else if (env.recommend) recommend_report();
     else gen_ranking_for_users();
     finish(0);
   }
@@ -1080,7 +1119,12 @@ int main(int argc, char **argv)
   int rank = 0, world = 1;
   if (spawned) { rank = atoi(getenv("HGAPREC_RANK")); world = atoi(getenv("HGAPREC_WORLD")); }
   else if (getenv("RANK") && getenv("WORLD_SIZE")) { rank = atoi(getenv("RANK")); world = atoi(getenv("WORLD_SIZE")); }
-  if (env.parse(argc, argv, rank == 0, &bad)) {
+  const int parsed = env.parse(argc, argv, rank == 0, &bad);
+  if (parsed && !env.usage_error.empty()) {
+    fprintf(stderr, "error: %s\n", env.usage_error.c_str());
+    return 2;
+  }
+  if (parsed) {
     fprintf(stdout, "error: unknown option %s\n", bad.c_str());
     fflush(stdout);
     abort();                                    // the reference asserts (main.cc:227-230)
@@ -1093,13 +1137,13 @@ int main(int argc, char **argv)
   if (!env.unsupported.empty()) {
     fprintf(stderr, "error: option %s selects a mode outside the MI355X hot-path build "
                     "(supported: -dir -n -m -k -hier -bias -binary-data -rfreq -max-iterations "
-                    "-seed -label -rating-threshold -logl -novb -a -b -c -d, -gen-ranking -rmse -msr -eval-all -model-dir, "
+                    "-seed -label -rating-threshold -logl -novb -a -b -c -d, -gen-ranking -rmse -msr -eval-all -recommend -model-dir, "
                     "-ngpus -comm -single-allreduce -device)\n", env.unsupported.c_str());
     return 2;
   }
   if (env.score_mode()) {
     if (env.ngpus > 1 || world > 1) {
-      fprintf(stderr, "error: -gen-ranking / -rmse / -msr / -eval-all score a saved model on ONE GPU: run them without -ngpus\n");
+      fprintf(stderr, "error: -gen-ranking / -rmse / -msr / -eval-all / -recommend score a saved model on ONE GPU: run them without -ngpus\n");
       return 1;
     }
     // the start of a run truncates validation.txt, precision.txt and friends in its output directory: that directory

@@ -11,6 +11,10 @@
 // -- printed when the program is run as `plan_selftest_asan tile-queues` (then only the tiled pass is checked, and stdout
 // holds nothing else) -- which tests/test_plan.py compares with tests/data/tile_queue_table.txt, recorded from the queue arithmetic as it stood
 // inside hpf_capi.hip's build_tiled_side before it moved into the header.
+// Then top-N for every user (hpf_recommend): the invariants of topn_cap, topn_grid and topn_batch_users over a seeded sweep and,
+// run as `plan_selftest_asan topn-grid`, for a fixed list of cases a line
+//   tg case-id m n_sel topn fused cap batch blocks splits tiles_per_split candidate-bytes
+// which tests/test_plan_topn.py compares with tests/data/topn_grid_table.txt.
 #include "../hpf_plan.hpp"
 
 #include <string>
@@ -206,8 +210,76 @@ static void tile_checks(bool print_cases)
   }
 }
 
+// ---- top-N for every user (hpf_recommend) ----------------------------------------------------------------------------------
+static void topn_checks(bool print_cases)
+{
+  CHECK(TOPN_MAX == 1024 && TOPN_FUSED_MAX == 256 && !topn_fused(0) && topn_fused(1) && topn_fused(256) && !topn_fused(257), "the fused range");
+  for (uint32_t topn = 1; topn <= TOPN_MAX; ++topn) {
+    const uint32_t np = topn_np(topn), cap = topn_cap(topn);
+    CHECK(np >= 64 && np >= topn && (np & (np - 1)) == 0 && (np == 64 || np / 2 < topn) && cap == 2 * np, "topn=%u: np=%u cap=%u", topn, np, cap);
+    CHECK(cap >= topn + 64, "topn=%u: a compacted buffer of %u has no room for a tile", topn, cap);
+    CHECK(!topn_fused(topn) || cap * TOPN_ENTRY_BYTES <= 6144, "topn=%u: %u entries do not fit a wave's 6 KB of LDS", topn, cap);
+  }
+  // C2 at topn = 100: 21 440 users x 4 splits x 256 entries x 12 B = 263 MB
+  {
+    const uint32_t cap = topn_cap(100), batch = topn_batch_users(100000, 1000000, cap, 0);
+    const RankGrid g = topn_grid(batch, 1563, cap);
+    CHECK(cap == 256 && batch == 21440 && g.blocks == 335 && g.splits == 4 && g.tiles_per_split == 391, "C2: cap %u, %u users, %u x %u of %u tiles", cap, batch, g.blocks, g.splits, g.tiles_per_split);
+    CHECK(topn_batch_bytes(batch, 1563, cap) == 21440ull * 4 * 256 * 12 && topn_batch_bytes(batch, 1563, cap) / 1000000 == 263, "C2: %llu bytes", (unsigned long long)topn_batch_bytes(batch, 1563, cap));
+  }
+  // test_gpu_recommend's compaction case: 150 users x 391 tiles are 3 blocks with splits of 8, 16 and 32 tiles
+  for (uint32_t topn : {1u, 100u, 256u}) {
+    const RankGrid g = topn_grid(150, 391, topn_cap(topn));
+    CHECK(g.blocks == 3 && g.tiles_per_split == topn_cap(topn) / 16 && g.tiles_per_split > topn_cap(topn) / 64, "topn=%u: %u blocks, %u tiles per split", topn, g.blocks, g.tiles_per_split);
+  }
+  Lcg r = {20260107};
+  unsigned reduced = 0, ruled = 0;
+  for (unsigned t = 0; t < 6000; ++t) {
+    const uint32_t topn = 1 + r.next() % TOPN_FUSED_MAX, cap = topn_cap(topn);
+    const uint32_t m = t % 5 == 0 ? 1 + r.next() % 300 : t % 5 == 1 ? 1 + r.next() % 4000000 : 1 + r.next() % 200000;
+    const uint32_t n_sel = t % 3 == 0 ? 1 + r.next() % 200 : 1 + r.next() % 3000000;
+    const long long knob = t % 4 == 0 ? 1 + (long long)(r.next() % 5000) : 0;
+    const uint32_t ntiles = (m + 63) / 64;
+    const uint32_t batch = topn_batch_users(m, n_sel, cap, knob), base = rank_batch_users(m, n_sel, knob);
+    CHECK(batch >= 16 && batch <= base && batch % 16 == 0, "case %u: batch %u of %u", t, batch, base);
+    CHECK(batch == base || batch % 64 == 0, "case %u: a reduced batch of %u users", t, batch);
+    if (!knob) CHECK(batch % 64 == 0 || batch == ((n_sel + 15) & ~15u), "case %u: batch %u, n_sel %u", t, batch, n_sel);
+    CHECK(topn_batch_bytes(batch, ntiles, cap) <= TOPN_BATCH_BYTES, "case %u: %llu bytes of candidates", t, (unsigned long long)topn_batch_bytes(batch, ntiles, cap));
+    reduced += batch < base;
+    for (uint32_t rows : {batch, 1u + r.next() % batch}) {
+      const RankGrid g = topn_grid(rows, ntiles, cap), g0 = rank_grid(rows, ntiles);
+      CHECK(g.blocks == (rows + 63) / 64 && g.splits >= 1 && g.splits <= g0.splits && g.tiles_per_split >= g0.tiles_per_split, "case %u: grid %u x %u", t, rows, ntiles);
+      CHECK((uint64_t)g.splits * g.tiles_per_split >= ntiles, "case %u: tiles left out", t);
+      CHECK((uint64_t)(g.splits - 1) * g.tiles_per_split < ntiles, "case %u: an empty split", t);
+      CHECK(g.tiles_per_split >= cap / 16 || g.splits == 1, "case %u: %u splits of %u tiles, cap %u", t, g.splits, g.tiles_per_split, cap);
+      ruled += g.splits < g0.splits;
+    }
+  }
+  CHECK(reduced >= 50 && ruled >= 500, "the sweep reduced %u batches and regrouped %u grids", reduced, ruled);
+  const struct { const char *id; uint32_t m, n_sel, topn; long long knob; } cases[] = {
+    {"c2_top10", 100000, 1000000, 10, 0},     {"c2_top100", 100000, 1000000, 100, 0},   {"c2_top256", 100000, 1000000, 256, 0},
+    {"c2_16k_top100", 100000, 16384, 100, 0}, {"c2_top257", 100000, 1000000, 257, 0},   {"c2_top1024", 100000, 1000000, 1024, 0},
+    {"edges_top1", 25000, 150, 1, 0},         {"edges_top100", 25000, 150, 100, 0},     {"edges_top256", 25000, 150, 256, 0},
+    {"m200_top100", 200, 37, 100, 0},         {"m64_top256", 64, 37, 256, 0},           {"m1000_knob16", 1000, 37, 64, 16},
+    {"one_user", 100000, 1, 100, 0},          {"m4e6_top256", 4000000, 3000000, 256, 0}, {"m1e4_many", 10000, 3000000, 256, 0},
+    {"m64_many", 64, 3000000, 256, 0},
+  };
+  for (const auto &k : cases) {
+    const uint32_t cap = topn_cap(k.topn), ntiles = (k.m + 63) / 64, batch = topn_batch_users(k.m, k.n_sel, cap, k.knob);
+    const RankGrid g = topn_grid(batch, ntiles, cap);
+    if (print_cases)
+      printf("tg %s %u %u %u %d %u %u %u %u %u %llu\n", k.id, k.m, k.n_sel, k.topn, (int)topn_fused(k.topn), cap, batch, g.blocks, g.splits, g.tiles_per_split,
+             (unsigned long long)topn_batch_bytes(batch, ntiles, cap));
+  }
+}
+
 int main(int argc, char **argv)
 {
+  if (argc > 1 && !strcmp(argv[1], "topn-grid")) {
+    topn_checks(true);
+    if (g_fail) { fprintf(stderr, "plan_selftest: %d checks failed\n", g_fail); return 1; }
+    return 0;
+  }
   if (argc > 1 && !strcmp(argv[1], "tile-queues")) {
     tile_checks(true);
     if (g_fail) { fprintf(stderr, "plan_selftest: %d checks failed\n", g_fail); return 1; }
@@ -330,6 +402,7 @@ int main(int argc, char **argv)
     for (int nch = -1; nch <= 8; ++nch) CHECK(has_rank_chunks(nch) == (nch >= 0 && nch < 8 && returned[nch]), "has_rank_chunks(%d)", nch);
   }
   tile_checks(false);
+  topn_checks(false);
   if (g_fail) { fprintf(stderr, "plan_selftest: %d checks failed\n", g_fail); return 1; }
   printf("# plan_selftest ok: %u points, %u runs\n", points, runs);
   return 0;

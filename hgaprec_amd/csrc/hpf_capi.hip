@@ -2677,6 +2677,53 @@ int hpf_rank_queries(hpf_handle *h, const uint32_t *users, uint32_t n_sel, const
   return copy_back(h, {{out_rank, d_rank, (size_t)nq * 4}, {out_score, d_sc, (size_t)nq * 8}});
 }
 
+// Top-N for every selected user.  Up to hpf_plan::TOPN_FUSED_MAX: the sweep of the other two fused calls with a streaming
+// selection behind it (topn_sweep_kernel) and a merge of each user's splits (topn_merge_kernel) -- per batch the bit rows
+// and the candidate buffers (hpf_plan::topn_batch_users), nothing of n_sel x n_items.  Above it: hpf_rank_topn's route.
+int hpf_recommend(hpf_handle *h, const uint32_t *users, uint32_t n_sel, const uint64_t *mask_ptr,
+                  const uint32_t *mask_items, uint32_t topn, uint32_t *out_items, double *out_scores)
+{
+  if (!h || topn == 0 || topn > hpf_plan::TOPN_MAX || (n_sel && (!users || !out_items || !out_scores))) return HPF_ERR_INVALID;
+  if (!n_sel) return HPF_OK;
+  if (!hpf_plan::topn_fused(topn)) return hpf_rank_topn(h, users, n_sel, mask_ptr, mask_items, topn, out_items, out_scores);
+  const uint32_t m = h->it.rows, ntiles = (m + 63) / 64;
+  if (h->ld & 1u) { h->err = "hpf_recommend: odd row stride"; return HPF_ERR_UNSUPPORTED; }
+  int rc;
+  if ((rc = rank_check(h, users, n_sel, mask_ptr, mask_items)) || (rc = scoring_ready(h))) return rc;
+
+  FusedCtx c(h);
+  if ((rc = c.upload(users, n_sel, mask_ptr, mask_items)) || (rc = c.bit_rows(n_sel))) return rc;
+  const uint32_t cap = hpf_plan::topn_cap(topn);
+  static_assert(hpf_plan::topn_cap(hpf_plan::TOPN_FUSED_MAX) == TOPN_CAP_MAX, "a wave's LDS scratch holds the largest candidate buffer");
+  c.batch = hpf_plan::topn_batch_users(m, n_sel, cap, h->loo_batch);      // <= the users the bit rows were sized for
+  // segments (user, split) of a batch: a full batch's; a shorter last batch takes its own grid where that needs no more
+  const hpf_plan::RankGrid gfull = hpf_plan::topn_grid(std::min(c.batch, n_sel), ntiles, cap);
+  const size_t nseg = (size_t)c.batch * gfull.splits;
+  unsigned long long *d_ckey = nullptr; uint32_t *d_citem = nullptr, *d_ccount = nullptr, *d_items = nullptr; double *d_sc = nullptr;
+  if ((rc = c.alloc(&d_ckey, nseg * cap)) || (rc = c.alloc(&d_citem, nseg * cap)) || (rc = c.alloc(&d_ccount, nseg)) ||
+      (rc = c.alloc(&d_items, (size_t)n_sel * topn)) || (rc = c.alloc(&d_sc, (size_t)n_sel * topn))) return rc;
+  uint32_t NP = 1; while (NP < topn) NP <<= 1;
+  for (uint32_t b0 = 0; b0 < n_sel; b0 += c.batch) {
+    const uint32_t rows = std::min(n_sel - b0, c.batch);
+    if ((rc = c.mask_batch(b0, rows))) return rc;
+    hpf_plan::RankGrid g = hpf_plan::topn_grid(rows, ntiles, cap);
+    if ((size_t)rows * g.splits > nseg) { g.splits = gfull.splits; g.tiles_per_split = gfull.tiles_per_split; }
+    TopnArgs a;
+    factor_args(h, a);
+    a.users = c.d_users + b0; a.bits = c.d_bits; a.ckey = d_ckey; a.citem = d_citem; a.ccount = d_ccount;
+    a.out_items = d_items + (size_t)b0 * topn; a.out_scores = d_sc + (size_t)b0 * topn;
+    a.n_sel = rows; a.m = m; a.words = c.words; a.tiles_per_split = g.tiles_per_split;
+    a.splits = g.splits; a.topn = topn; a.cap = cap; a.lg_cap = 0; while ((1u << a.lg_cap) < cap) ++a.lg_cap;
+    const bool launched = launch_rank(h->K, [&](auto nch) {
+      hipLaunchKernelGGL(topn_sweep_kernel<decltype(nch)::value>, dim3(g.blocks, g.splits), dim3(256), 0, h->stream, a);
+    });
+    if (!launched) { h->err = "topn_sweep_kernel: no instance for this column count"; return HPF_ERR_UNSUPPORTED; }
+    hipLaunchKernelGGL(topn_merge_kernel, dim3(rows), dim3(256), (size_t)NP * 12, h->stream, a, NP);
+    if ((rc = check_launch(h, "topn_sweep_kernel/topn_merge_kernel"))) return rc;
+  }
+  return copy_back(h, {{out_items, d_items, (size_t)n_sel * topn * 4}, {out_scores, d_sc, (size_t)n_sel * topn * 8}});
+}
+
 int hpf_get_work_info(hpf_handle *h, hpf_work_info *out)
 {
   if (!h || !out) return HPF_ERR_INVALID;

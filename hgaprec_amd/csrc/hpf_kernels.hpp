@@ -2335,6 +2335,257 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void r
   }
 }
 
+// ---------------------------------------------------------------------
+// Top-N for every user without a score matrix (hpf_recommend, -recommend).
+//   topn_sweep_kernel  the same sweep (rank_sweep); a score that can still be among the best `topn` of its (user, split)
+//                      is appended to that pair's candidate buffer in global memory, which the owning wave sorts and cuts
+//                      back to `topn` (compaction) whenever a further tile might not fit, raising the bar for what follows
+//   topn_merge_kernel  the exact top-N of a user's segments: topn_kernel's radix select, tie walk and bitonic sort over
+//                      the (key, item) lists the sweep left instead of a row of scores
+// Masked items score +0.0 and stay candidates; order and padding are topn_kernel's.
+// ---------------------------------------------------------------------
+constexpr int TOPN_CAP_MAX = 512;     // entries of a candidate buffer at the largest fused topn (hpf_plan::topn_cap(TOPN_FUSED_MAX))
+
+struct TopnArgs {
+  const uint32_t *users;    // [n_sel] user rows of this batch
+  const double   *Et, *Eb;  // [n x ld], [m x ld]
+  const uint64_t *bits;     // [n_sel x words] masked items
+  unsigned long long *ckey; // [n_sel x splits x cap] candidate keys of segment (user, split) ...
+  uint32_t       *citem;    // ... and items
+  uint32_t       *ccount;   // [n_sel x splits] entries a segment holds after the sweep: <= topn, sorted best first
+  uint32_t       *out_items;   // [n_sel x topn]
+  double         *out_scores;  // [n_sel x topn]
+  uint32_t        n_sel, m, ld, K, words;
+  uint32_t        tiles_per_split;   // 64-item tiles per blockIdx.y
+  uint32_t        splits, topn, cap, lg_cap;   // cap = 1 << lg_cap <= TOPN_CAP_MAX, cap >= topn + 64
+  int32_t         ubias_col, ibias_col;
+};
+
+// The lanes of ONE wave hand each other data through LDS and through the buffers they own: what was written is complete
+// and visible to the wave's other lanes behind this (no other wave is waited for)
+__device__ __forceinline__ void wave_sync()
+{
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+  __builtin_amdgcn_wave_barrier();
+}
+
+// One wave sorts the c <= cap entries of a segment by (key descending, item ascending) in its LDS scratch and writes the
+// best min(c, topn) back; *worst = the last key kept.  c, topn are the same in every lane.
+__device__ __forceinline__ uint32_t topn_compact(unsigned long long *gk, uint32_t *gi, uint32_t c, uint32_t topn,
+                                                 unsigned long long *sk, uint32_t *si, uint32_t lane, unsigned long long *worst)
+{
+  uint32_t P = 64; while (P < c) P <<= 1;                        // c <= cap, a power of two >= 128: P <= cap
+  for (uint32_t e = lane; e < P; e += 64) { const bool ok = e < c; sk[e] = ok ? gk[e] : 0ull; si[e] = ok ? gi[e] : 0xffffffffu; }
+  wave_sync();
+  for (uint32_t k = 2; k <= P; k <<= 1)
+    for (uint32_t j = k >> 1; j > 0; j >>= 1) {
+      for (uint32_t t = lane; t < P; t += 64) {
+        const uint32_t x = t ^ j;
+        if (x > t) {
+          const bool up = (t & k) == 0;                          // "up" block: best entries first
+          const unsigned long long ka = sk[t], kb = sk[x]; const uint32_t ia = si[t], ib = si[x];
+          const bool a_first = ka > kb || (ka == kb && ia < ib);
+          if (a_first != up) { sk[t] = kb; sk[x] = ka; si[t] = ib; si[x] = ia; }
+        }
+      }
+      wave_sync();
+    }
+  const uint32_t keep = c < topn ? c : topn;
+  for (uint32_t e = lane; e < keep; e += 64) { gk[e] = sk[e]; gi[e] = si[e]; }
+  *worst = keep ? sk[keep - 1] : 0ull;
+  wave_sync();                                                   // the scratch is free again, the segment rewritten
+  return keep;
+}
+
+// Workgroup = 4 waves = 64 users (16 per wave) x one split of the item range, as loo_rank_kernel.  A wave owns its 16
+// users' segments: no other wave reads or writes them.  Per user in LDS: the entries its segment holds and the least key
+// still accepted, `lo`.  lo = 0 until the first compaction (every item is a candidate), then the worst kept key + 1: items
+// ascend through a split, so a later item that ties the worst kept key comes behind it and cannot be among the best.
+template <int NCH>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void topn_sweep_kernel(TopnArgs a)
+{
+  __shared__ double tile[64 * LOO_LDS_STRIDE];
+  __shared__ unsigned long long scr_k[4 * TOPN_CAP_MAX];          // per wave: the entries being sorted
+  __shared__ uint32_t scr_i[4 * TOPN_CAP_MAX];
+  __shared__ unsigned long long s_lo[64];
+  __shared__ uint32_t s_cnt[64];
+  __shared__ double s_ub[64];                                       // E_ubias of the user
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int r16 = lane & 15, kq = lane >> 4;
+  const uint32_t ub0 = blockIdx.x * 64;                          // first user of this workgroup
+  const uint32_t usel = ub0 + wv * 16 + r16;
+  const bool uok = usel < a.n_sel;
+  const uint32_t urow = uok ? a.users[usel] : 0u;
+  const double *pa = a.Et + (size_t)urow * a.ld;
+  const AFrag<NCH> A(pa, uok, a.K, (uint32_t)kq);
+  unsigned long long *sk = scr_k + wv * TOPN_CAP_MAX;
+  uint32_t *si = scr_i + wv * TOPN_CAP_MAX;
+
+  if (tid < 64) {
+    const uint32_t us = ub0 + tid;
+    s_cnt[tid] = 0u; s_lo[tid] = 0ull;
+    s_ub[tid] = (us < a.n_sel && a.ubias_col >= 0) ? a.Et[(size_t)a.users[us] * a.ld + a.ubias_col] : 0.0;
+  }
+  __syncthreads();
+
+  rank_sweep<NCH>(A, a.Eb, a.m, a.ld, a.K, a.tiles_per_split, tile, [&](uint32_t tl, const double4_t (&acc)[4]) {
+    // epilogue: register r of tile t holds local user wv 16 + kq + 4 r, item 64 tl + 16 t + r16
+    const uint32_t i0 = tl * 64;
+    double bi[4];
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      const uint32_t it = i0 + 16 * t + r16;
+      bi[t] = (it < a.m && a.ibias_col >= 0) ? a.Eb[(size_t)it * a.ld + a.ibias_col] : 0.0;
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const uint32_t lr = wv * 16 + kq + 4 * r, us = ub0 + lr;
+      const bool live = us < a.n_sel;
+      const unsigned long long w = live ? a.bits[(size_t)us * a.words + tl] : 0ull;
+      const unsigned long long lo = s_lo[lr];
+      const double ub = s_ub[lr];
+      uint32_t cnt = s_cnt[lr];                                  // <= cap - 64: the 64 items of a tile fit
+      // first entry of the segment (a batch's buffers hold < 2^26 entries: hpf_plan::topn_batch_users)
+      const uint32_t e0 = live ? (us * a.splits + blockIdx.y) << a.lg_cap : 0u;
+#pragma unroll
+      for (int t = 0; t < 4; ++t) {
+        const uint32_t it = i0 + 16 * t + r16;
+        double v = acc[t][r];
+        if (a.ubias_col >= 0) v += ub + bi[t];                   // s += Eb_u + Eb_i
+        if ((w >> (16 * t + r16)) & 1ull) v = 0.0;
+        const unsigned long long k = score_key(v);
+        const bool take = live && it < a.m && k >= lo;
+        const uint32_t grp = (uint32_t)(__ballot(take) >> (16 * kq)) & 0xffffu;   // the 16 lanes that share this user
+        if (take) {
+          const uint32_t slot = cnt + (uint32_t)__popc(grp & ((1u << r16) - 1u));
+          a.ckey[e0 + slot] = k; a.citem[e0 + slot] = it;
+        }
+        cnt += (uint32_t)__popc(grp);
+      }
+      if (r16 == 0) s_cnt[lr] = cnt;
+      __builtin_amdgcn_sched_barrier(0);                         // one user's state at a time: the K = 100 instance has no register to spare
+    }
+    wave_sync();
+    // users of this wave whose buffer might not hold another tile: the whole wave compacts them, one after the other
+    const uint32_t c16 = lane < 16 ? s_cnt[wv * 16 + lane] : 0u;
+    unsigned long long full = __ballot(c16 > a.cap - 64u);
+    while (full) {
+      const uint32_t lr = wv * 16 + (uint32_t)__ffsll((long long)full) - 1u;
+      full &= full - 1ull;
+      const size_t seg = (size_t)(ub0 + lr) * a.splits + blockIdx.y;
+      const uint32_t c = (uint32_t)__builtin_amdgcn_readfirstlane((int)s_cnt[lr]);
+      unsigned long long worst;
+      const uint32_t keep = topn_compact(a.ckey + (seg << a.lg_cap), a.citem + (seg << a.lg_cap), c, a.topn, sk, si, (uint32_t)lane, &worst);
+      if (lane == 0) { s_cnt[lr] = keep; s_lo[lr] = worst + 1ull; }    // c > cap - 64 >= topn: keep == topn
+      wave_sync();
+    }
+  });
+
+  // the end of the split: every segment sorted and cut to its best topn
+  wave_sync();
+  for (uint32_t uu = 0; uu < 16; ++uu) {
+    const uint32_t lr = wv * 16 + uu, us = ub0 + lr;
+    if (us >= a.n_sel) break;
+    const size_t seg = (size_t)us * a.splits + blockIdx.y;
+    const uint32_t c = (uint32_t)__builtin_amdgcn_readfirstlane((int)s_cnt[lr]);
+    unsigned long long worst;
+    const uint32_t keep = topn_compact(a.ckey + (seg << a.lg_cap), a.citem + (seg << a.lg_cap), c, a.topn, sk, si, (uint32_t)lane, &worst);
+    if (lane == 0) a.ccount[seg] = keep;
+  }
+}
+
+// One workgroup per user.  Entry i of the user's list is slot i % cap of segment i / cap, present when the slot is below
+// the segment's count.  Segments are sorted and cover ascending item ranges, so walking i upwards meets equal keys in
+// ascending item order -- which is all topn_kernel's scheme asks of a row of scores.  NP = pow2 >= topn.
+__global__ __launch_bounds__(256) void topn_merge_kernel(TopnArgs a, uint32_t NP)
+{
+  extern __shared__ unsigned char smem[];
+  unsigned long long *ck = (unsigned long long *)smem;            // [NP] candidate keys
+  uint32_t *ci = (uint32_t *)(ck + NP);                          // [NP] candidate items
+  __shared__ uint32_t hist[256];
+  __shared__ unsigned long long s_prefix;
+  __shared__ uint32_t s_remaining, s_cnt, s_wtot[4], s_eq_taken;
+  const uint32_t tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const uint32_t b = blockIdx.x;
+  if (b >= a.n_sel) return;
+  const uint32_t N = a.topn, Ne = N < a.m ? N : a.m;
+  const uint32_t L = a.splits << a.lg_cap;                       // <= 1025 x 512
+  const unsigned long long *gk = a.ckey + (((size_t)b * a.splits) << a.lg_cap);
+  const uint32_t *gi = a.citem + (((size_t)b * a.splits) << a.lg_cap);
+  const uint32_t *gc = a.ccount + (size_t)b * a.splits;
+  auto present = [&](uint32_t i) { return i < L && (i & (a.cap - 1u)) < gc[i >> a.lg_cap]; };
+
+  for (uint32_t k = tid; k < NP; k += 256) { ck[k] = 0ull; ci[k] = 0xffffffffu; }
+  if (tid == 0) { s_prefix = 0ull; s_remaining = Ne; s_cnt = 0; s_eq_taken = 0; }
+  __syncthreads();
+  if (Ne > 0) {
+    for (int pass = 0; pass < 8; ++pass) {
+      const int shift = 56 - 8 * pass;
+      hist[tid] = 0;
+      __syncthreads();
+      const unsigned long long prefix = s_prefix;
+      for (uint32_t i = tid; i < L; i += 256) {
+        if (!present(i)) continue;
+        const unsigned long long key = gk[i];
+        if (pass == 0 || (key >> (shift + 8)) == prefix) atomicAdd(&hist[(key >> shift) & 255ull], 1u);
+      }
+      __syncthreads();
+      if (tid == 0) {
+        uint32_t cum = 0, rem = s_remaining; int d = 255;
+        for (; d > 0; --d) { if (cum + hist[d] >= rem) break; cum += hist[d]; }
+        s_remaining = rem - cum;
+        s_prefix = (prefix << 8) | (unsigned long long)d;
+      }
+      __syncthreads();
+    }
+    const unsigned long long T = s_prefix;       // key of the Ne-th best entry
+    const uint32_t need_eq = s_remaining;         // how many of the == T to take (lowest items)
+    for (uint32_t i = tid; i < L; i += 256) {
+      if (!present(i)) continue;
+      const unsigned long long key = gk[i];
+      if (key > T) { const uint32_t p = atomicAdd(&s_cnt, 1u); if (p < NP) { ck[p] = key; ci[p] = gi[i]; } }
+    }
+    __syncthreads();
+    const uint32_t base = s_cnt;                  // = Ne - need_eq
+    for (uint32_t c0 = 0; c0 < L; c0 += 256) {    // ties in ascending item order
+      const uint32_t i = c0 + tid;
+      const bool eq = present(i) && gk[i] == T;
+      const unsigned long long bal = __ballot(eq);
+      const uint32_t before = __popcll(bal & ((1ull << lane) - 1ull));
+      if (lane == 0) s_wtot[wv] = (uint32_t)__popcll(bal);
+      __syncthreads();
+      uint32_t woff = 0, tot = 0;
+      for (uint32_t w = 0; w < 4; ++w) { if (w < wv) woff += s_wtot[w]; tot += s_wtot[w]; }
+      const uint32_t taken = s_eq_taken;
+      const uint32_t pos = taken + woff + before;
+      if (eq && pos < need_eq && base + pos < NP) { ck[base + pos] = T; ci[base + pos] = gi[i]; }
+      __syncthreads();
+      if (tid == 0) s_eq_taken = taken + tot;
+      __syncthreads();
+      if (s_eq_taken >= need_eq) break;
+    }
+    __syncthreads();
+    // bitonic sort of NP entries: key descending, item ascending
+    for (uint32_t k = 2; k <= NP; k <<= 1)
+      for (uint32_t j = k >> 1; j > 0; j >>= 1) {
+        for (uint32_t t = tid; t < NP; t += 256) {
+          const uint32_t x = t ^ j;
+          if (x > t) {
+            const bool up = (t & k) == 0;         // "up" block: best entries first
+            const unsigned long long ka = ck[t], kb = ck[x]; const uint32_t ia = ci[t], ib = ci[x];
+            const bool a_first = ka > kb || (ka == kb && ia < ib);
+            if (a_first != up) { ck[t] = kb; ck[x] = ka; ci[t] = ib; ci[x] = ia; }
+          }
+        }
+        __syncthreads();
+      }
+  }
+  for (uint32_t k = tid; k < N; k += 256) {
+    a.out_items[(size_t)b * N + k] = k < Ne ? ci[k] : 0xffffffffu;
+    a.out_scores[(size_t)b * N + k] = k < Ne ? __longlong_as_double((long long)ck[k]) : 0.0;
+  }
+}
+
 // materialise the per-element rate matrix for export (htheta_rate.tsv):
 // rate[row,k] = prior_used[row] + colsum[k]   (gpbase.hh:163-173,218-223)
 __global__ void build_rate_kernel(const double *prior_used, const double *colsum,

@@ -1,7 +1,8 @@
 // hpf_plan.hpp -- what the GPU will run, decided on the host: the experimental knobs, the shapes of the phi pass, of the rows
 // of W and of the row sweep for a column count (plan_shapes), which kernel instances exist for them (has_*), and the batches
 // and launch grid of the fused rank kernels (rank_batch_users, rank_grid, rank_chunks), the score batch of the unfused ones
-// (score_batch_rows), and the tiled pass: whether a side is tiled and with which tiles (tile_policy, tiling_fits) and which
+// (score_batch_rows), the fused range, candidate buffers, grid and batches of hpf_recommend (topn_fused, topn_cap, topn_grid,
+// topn_batch_users), and the tiled pass: whether a side is tiled and with which tiles (tile_policy, tiling_fits) and which
 // XCD queue and chunk every segment runs in (plan_tile_queues).
 // Plain C++17 without a HIP header: hpf_capi.hip builds its handle and its dispatcher from it, host/plan_selftest.cpp
 // walks every column count on a CPU, pins the tile policy, checks the invariants of the queue plan over a seeded sweep and
@@ -149,6 +150,45 @@ inline uint32_t score_batch_rows(uint32_t m, uint32_t n_sel)
   uint64_t bmax = ((1ull << 30) / (8ull * std::max<uint32_t>(m, 1))) & ~15ull;
   bmax = std::max<uint64_t>(bmax, 16);
   return (uint32_t)std::min<uint64_t>(bmax, ((uint64_t)n_sel + 15) & ~15ull);
+}
+
+// ---- top-N for every user (hpf_recommend) ---------------------------------------------------------
+// Up to TOPN_FUSED_MAX the call is fused (topn_sweep_kernel + topn_merge_kernel); above it, up to TOPN_MAX, it runs the
+// materialising route of hpf_rank_topn.  hgaprec_amd/capi.py mirrors the cut as RECOMMEND_FUSED_MAX.
+constexpr uint32_t TOPN_MAX = 1024, TOPN_FUSED_MAX = 256;
+constexpr bool topn_fused(uint32_t topn) { return topn >= 1 && topn <= TOPN_FUSED_MAX; }
+// Entries of the candidate buffer of one (user, split): twice the power of two >= max(topn, 64).  A tile adds at most 64
+// and a compacted buffer holds topn, so cap >= topn + 64 leaves room for a tile after every compaction.
+constexpr uint32_t topn_np(uint32_t topn) { uint32_t np = 64; while (np < topn) np <<= 1; return np; }
+constexpr uint32_t topn_cap(uint32_t topn) { return 2 * topn_np(topn); }
+constexpr uint64_t TOPN_ENTRY_BYTES = 12, TOPN_BATCH_BYTES = (uint64_t)512 << 20;    // a key and an item; candidate memory of a batch
+
+// rank_grid's policy with one more rule: a split covers at least four buffers' worth of items (cap / 16 tiles) unless the
+// whole range is shorter -- with the one or two tiles per split that rank_grid gives a handful of users nothing would be
+// filtered and the merge would do all the work.  No split is empty.
+inline RankGrid topn_grid(uint32_t rows, uint32_t ntiles, uint32_t cap)
+{
+  RankGrid g = rank_grid(rows, ntiles);
+  const uint32_t least = std::max<uint32_t>(1, std::min<uint32_t>(ntiles, cap / 16));
+  if (g.tiles_per_split < least) {
+    g.tiles_per_split = least;
+    g.splits = std::max<uint32_t>(1, (ntiles + least - 1) / least);
+  }
+  return g;
+}
+// candidate memory of a batch of `rows` users
+inline uint64_t topn_batch_bytes(uint32_t rows, uint32_t ntiles, uint32_t cap)
+{
+  return (uint64_t)((rows + 15) & ~15u) * topn_grid(rows, ntiles, cap).splits * cap * TOPN_ENTRY_BYTES;
+}
+// Users per batch: rank_batch_users (the bit rows; HPF_LOO_BATCH), reduced -- staying a multiple of 64 -- until the
+// candidate buffers of a batch are <= 512 MB.  64 users always fit: 1024 + 1 splits at most, 64 x 1025 x 512 x 12 B = 403 MB.
+inline uint32_t topn_batch_users(uint32_t m, uint32_t n_sel, uint32_t cap, long long knob)
+{
+  const uint32_t ntiles = (uint32_t)(((uint64_t)m + 63) / 64);
+  uint32_t batch = rank_batch_users(m, n_sel, knob);
+  while (batch > 64 && topn_batch_bytes(batch, ntiles, cap) > TOPN_BATCH_BYTES) batch = (batch - 1) & ~63u;
+  return batch;
 }
 
 // ---- the tiled phi pass: what is tiled, and where its segments run --------------------------------

@@ -376,6 +376,26 @@ int  hpf_rank_queries(hpf_handle *h, const uint32_t *users, uint32_t n_sel,
                       const uint64_t *mask_ptr, const uint32_t *mask_items,
                       const uint64_t *q_ptr, const uint32_t *q_items,
                       uint32_t *out_rank, double *out_score);
+/* replaces: the scoring loop, qsort and top-N walk input of HGAPRec::compute_precision
+ * (hgaprec.cc:1722-1765) for ANY number of users -- the list of recommended items of each --
+ * without a score matrix.  Arguments, domain, masking, order, padding and error cases are
+ * hpf_rank_topn's: topn = 0 or > 1024, a user or a mask item out of range, mask_ptr[0] != 0 or a
+ * decreasing mask_ptr is HPF_ERR_INVALID before anything is launched; n_sel = 0 is HPF_OK.
+ * out_items and out_scores equal, bit for bit, what hpf_rank_topn returns for the same arguments:
+ * the scores come out of the same MFMA chain, and the top-N of a total order (score descending,
+ * item ascending) does not depend on how it is found.
+ * topn <= 256: one sweep over the items per batch of users; a score that can still be among a
+ * user's best topn is appended to a candidate buffer, which is sorted and cut back to topn whenever
+ * it fills up; a second kernel merges the buffers of a user.  Device memory beyond inputs and
+ * outputs: the bit rows of a batch of users (<= 256 MB, HPF_LOO_BATCH as for hpf_loo_ranks) and its
+ * candidate buffers, 12 bytes x 2 pow2(max(topn, 64)) per user and split of the item range
+ * (<= 512 MB: the batch shrinks until they fit; 10^5 items, topn = 100: 21 440 users x 4 splits x
+ * 256 entries = 263 MB).  Nothing of size n_sel x n_items exists.  An odd row stride is
+ * HPF_ERR_UNSUPPORTED, as for the other fused calls.
+ * 256 < topn <= 1024: the call runs hpf_rank_topn's route (scores of a batch of users in memory). */
+int  hpf_recommend(hpf_handle *h, const uint32_t *users, uint32_t n_sel,
+                   const uint64_t *mask_ptr, const uint32_t *mask_items, uint32_t topn,
+                   uint32_t *out_items, double *out_scores);
 
 /* how the uploaded matrix was cut into work (diagnostics, tests, bench):
  * a "segment" is <= 512 consecutive nonzeros of one row; rows longer than that
