@@ -338,14 +338,18 @@ bool launch_sweep(int mode, int G, int R, const SweepArgs &a, uint32_t blocks, h
       return false;
     }); }); });
 }
+int check_launch(hpf_handle *h, const char *what);
 // the fused rank kernels, by the chunks of A a column count keeps in registers (hpf_plan::rank_chunks); launch(nch) names
-// the kernel template: loo_rank_kernel<nch> or rank_queries_kernel<nch>
+// the kernel template: loo_rank_kernel<nch>, rank_queries_kernel<nch> or topn_sweep_kernel<nch>.  Fails where the column
+// count has no instance of `kernel`; what was launched is checked under `what` (the kernel's name unless given).
 template <typename F>
-bool launch_rank(uint32_t K, F &&launch)
+int launch_rank(hpf_handle *h, const char *kernel, F &&launch, const char *what = nullptr)
 {
-  return pick(hpf_plan::rank_chunks(K), std::integer_sequence<int, 0, 1, 2, 4>(), [&](auto nch) {
+  const bool launched = pick(hpf_plan::rank_chunks(h->K), std::integer_sequence<int, 0, 1, 2, 4>(), [&](auto nch) {
     if constexpr (hpf_plan::has_rank_chunks(PICKED(nch))) { launch(nch); return true; } else return false;
   });
+  if (!launched) { h->err = std::string(kernel) + ": no instance for this column count"; return HPF_ERR_UNSUPPORTED; }
+  return check_launch(h, what ? what : kernel);
 }
 #undef PICKED
 
@@ -561,7 +565,7 @@ struct Scratch {
 };
 
 // Device side of a ranking call: the selected users and the mask list (upload) and, for the fused calls (hpf_loo_ranks,
-// hpf_rank_queries), the bit rows of one batch of users (bit_rows; hpf_plan::rank_batch_users)
+// hpf_rank_queries, hpf_recommend), the bit rows of one batch of users (bit_rows; hpf_plan::rank_batch_users)
 struct FusedCtx : Scratch {
   uint32_t *d_users = nullptr, *d_mitems = nullptr; uint64_t *d_mptr = nullptr, *d_bits = nullptr;
   uint32_t words = 0, batch = 0;       // 64-bit words of a bit row; users per batch
@@ -2463,6 +2467,16 @@ int rank_check(hpf_handle *h, const uint32_t *users, uint32_t n_sel, const uint6
   return HPF_OK;
 }
 
+// What a fused call (hpf_loo_ranks, hpf_rank_queries, hpf_recommend) settles before it allocates, in the order that decides
+// which error a bad call gets: rank_check, the items q[0 .. nq) it asks about (none for hpf_recommend), scoring_ready
+int fused_ready(hpf_handle *h, const uint32_t *users, uint32_t n_sel, const uint64_t *mask_ptr, const uint32_t *mask_items,
+                const uint32_t *q = nullptr, uint64_t nq = 0)
+{
+  if (int rc = rank_check(h, users, n_sel, mask_ptr, mask_items)) return rc;
+  for (uint64_t k = 0; k < nq; ++k) if (q[k] >= h->it.rows) { h->err = "query item out of range"; return HPF_ERR_INVALID; }
+  return scoring_ready(h);
+}
+
 // The unfused ranking calls (hpf_scores, hpf_rank_topn, hpf_item_ranks) keep the scores of a batch of users
 // (hpf_plan::score_batch_rows) and run their own kernel over them
 struct ScoreCtx : FusedCtx {
@@ -2517,7 +2531,7 @@ int hpf_rank_topn(hpf_handle *h, const uint32_t *users, uint32_t n_sel, const ui
   if (!n_sel) return HPF_OK;
   ScoreCtx c(h); int rc;
   if ((rc = c.prepare(users, n_sel, mask_ptr, mask_items))) return rc;
-  uint32_t NP = 1; while (NP < topn) NP <<= 1;
+  const uint32_t NP = hpf_plan::pow2_ceil(topn);
   uint32_t *d_items = nullptr; double *d_sc = nullptr;
   if ((rc = c.alloc(&d_items, (size_t)n_sel * topn)) || (rc = c.alloc(&d_sc, (size_t)n_sel * topn))) return rc;
   for (uint32_t b0 = 0; b0 < n_sel; b0 += c.batch) {
@@ -2585,13 +2599,8 @@ int hpf_loo_ranks(hpf_handle *h, const uint32_t *users, uint32_t n_sel, const ui
   if (item_limit > m) { h->err = "item_limit beyond n_items"; return HPF_ERR_INVALID; }
   const uint32_t limit = item_limit ? item_limit : m;
   if (h->ld & 1u) { h->err = "hpf_loo_ranks: odd row stride"; return HPF_ERR_UNSUPPORTED; }
-  int rc;
-  if ((rc = rank_check(h, users, n_sel, mask_ptr, mask_items))) return rc;
-  for (uint32_t b = 0; b < n_sel; ++b)
-    if (q_item[b] >= m) { h->err = "query item out of range"; return HPF_ERR_INVALID; }
-  if ((rc = scoring_ready(h))) return rc;
-
-  FusedCtx c(h);
+  if (int rc = fused_ready(h, users, n_sel, mask_ptr, mask_items, q_item, n_sel)) return rc;
+  FusedCtx c(h); int rc;
   uint32_t *d_q = nullptr, *d_rank = nullptr, *d_masked = nullptr; double *d_sc = nullptr;
   if ((rc = c.upload(users, n_sel, mask_ptr, mask_items)) || (rc = c.bit_rows(n_sel)) || (rc = c.alloc(&d_q, n_sel, q_item)) || (rc = c.alloc(&d_rank, n_sel)) ||
       (rc = c.alloc(&d_masked, n_sel)) || (rc = c.alloc(&d_sc, n_sel))) return rc;
@@ -2605,11 +2614,9 @@ int hpf_loo_ranks(hpf_handle *h, const uint32_t *users, uint32_t n_sel, const ui
     a.n_sel = rows; a.limit = limit; a.words = c.words;
     const hpf_plan::RankGrid g = hpf_plan::rank_grid(rows, (limit + 63) / 64);
     a.tiles_per_split = g.tiles_per_split;
-    const bool launched = launch_rank(h->K, [&](auto nch) {
-      hipLaunchKernelGGL(loo_rank_kernel<decltype(nch)::value>, dim3(g.blocks, g.splits), dim3(256), 0, h->stream, a);
-    });
-    if (!launched) { h->err = "loo_rank_kernel: no instance for this column count"; return HPF_ERR_UNSUPPORTED; }
-    if ((rc = check_launch(h, "loo_rank_kernel"))) return rc;
+    if ((rc = launch_rank(h, "loo_rank_kernel", [&](auto nch) {
+          hipLaunchKernelGGL(loo_rank_kernel<decltype(nch)::value>, dim3(g.blocks, g.splits), dim3(256), 0, h->stream, a);
+        }))) return rc;
   }
   return copy_back(h, {{out_rank, d_rank, (size_t)n_sel * 4}, {out_score, d_sc, (size_t)n_sel * 8}, {out_masked, d_masked, (size_t)n_sel * 4}});
 }
@@ -2628,13 +2635,9 @@ int hpf_rank_queries(hpf_handle *h, const uint32_t *users, uint32_t n_sel, const
   const uint64_t nq = q_ptr[n_sel];
   if (nq > 0xffffffffull) { h->err = "hpf_rank_queries: more than 2^32 - 1 queries in one call"; return HPF_ERR_INVALID; }
   if (nq && (!q_items || !out_rank || !out_score)) return HPF_ERR_INVALID;
-  int rc;
-  if ((rc = rank_check(h, users, n_sel, mask_ptr, mask_items))) return rc;
-  for (uint64_t q = 0; q < nq; ++q) if (q_items[q] >= m) { h->err = "query item out of range"; return HPF_ERR_INVALID; }
-  if (!nq) return HPF_OK;
-  if ((rc = scoring_ready(h))) return rc;
-
-  FusedCtx c(h);
+  if (!nq) return rank_check(h, users, n_sel, mask_ptr, mask_items);      // nothing asked: only the checks
+  if (int rc = fused_ready(h, users, n_sel, mask_ptr, mask_items, q_items, nq)) return rc;
+  FusedCtx c(h); int rc;
   if ((rc = c.upload(users, n_sel, mask_ptr, mask_items)) || (rc = c.bit_rows(n_sel))) return rc;
   // rows: a selected user with at most RQ_QCAP of its queries (a query's rank does not depend on the user's other
   // queries, so cutting a user is exact); in the order of the selected users, so a batch owns a run of them
@@ -2668,11 +2671,9 @@ int hpf_rank_queries(hpf_handle *h, const uint32_t *users, uint32_t n_sel, const
     const hpf_plan::RankGrid g = hpf_plan::rank_grid(rows, (m + 63) / 64);
     a.tiles_per_split = g.tiles_per_split;
     hipLaunchKernelGGL(rq_threshold_kernel, dim3((rows + 3) / 4), dim3(256), 0, h->stream, a);
-    const bool launched = launch_rank(h->K, [&](auto nch) {
-      hipLaunchKernelGGL(rank_queries_kernel<decltype(nch)::value>, dim3(g.blocks, g.splits), dim3(256), 0, h->stream, a);
-    });
-    if (!launched) { h->err = "rank_queries_kernel: no instance for this column count"; return HPF_ERR_UNSUPPORTED; }
-    if ((rc = check_launch(h, "rank_queries_kernel"))) return rc;
+    if ((rc = launch_rank(h, "rank_queries_kernel", [&](auto nch) {
+          hipLaunchKernelGGL(rank_queries_kernel<decltype(nch)::value>, dim3(g.blocks, g.splits), dim3(256), 0, h->stream, a);
+        }))) return rc;
   }
   return copy_back(h, {{out_rank, d_rank, (size_t)nq * 4}, {out_score, d_sc, (size_t)nq * 8}});
 }
@@ -2688,10 +2689,8 @@ int hpf_recommend(hpf_handle *h, const uint32_t *users, uint32_t n_sel, const ui
   if (!hpf_plan::topn_fused(topn)) return hpf_rank_topn(h, users, n_sel, mask_ptr, mask_items, topn, out_items, out_scores);
   const uint32_t m = h->it.rows, ntiles = (m + 63) / 64;
   if (h->ld & 1u) { h->err = "hpf_recommend: odd row stride"; return HPF_ERR_UNSUPPORTED; }
-  int rc;
-  if ((rc = rank_check(h, users, n_sel, mask_ptr, mask_items)) || (rc = scoring_ready(h))) return rc;
-
-  FusedCtx c(h);
+  if (int rc = fused_ready(h, users, n_sel, mask_ptr, mask_items)) return rc;
+  FusedCtx c(h); int rc;
   if ((rc = c.upload(users, n_sel, mask_ptr, mask_items)) || (rc = c.bit_rows(n_sel))) return rc;
   const uint32_t cap = hpf_plan::topn_cap(topn);
   static_assert(hpf_plan::topn_cap(hpf_plan::TOPN_FUSED_MAX) == TOPN_CAP_MAX, "a wave's LDS scratch holds the largest candidate buffer");
@@ -2702,7 +2701,7 @@ int hpf_recommend(hpf_handle *h, const uint32_t *users, uint32_t n_sel, const ui
   unsigned long long *d_ckey = nullptr; uint32_t *d_citem = nullptr, *d_ccount = nullptr, *d_items = nullptr; double *d_sc = nullptr;
   if ((rc = c.alloc(&d_ckey, nseg * cap)) || (rc = c.alloc(&d_citem, nseg * cap)) || (rc = c.alloc(&d_ccount, nseg)) ||
       (rc = c.alloc(&d_items, (size_t)n_sel * topn)) || (rc = c.alloc(&d_sc, (size_t)n_sel * topn))) return rc;
-  uint32_t NP = 1; while (NP < topn) NP <<= 1;
+  const uint32_t NP = hpf_plan::pow2_ceil(topn);
   for (uint32_t b0 = 0; b0 < n_sel; b0 += c.batch) {
     const uint32_t rows = std::min(n_sel - b0, c.batch);
     if ((rc = c.mask_batch(b0, rows))) return rc;
@@ -2713,13 +2712,11 @@ int hpf_recommend(hpf_handle *h, const uint32_t *users, uint32_t n_sel, const ui
     a.users = c.d_users + b0; a.bits = c.d_bits; a.ckey = d_ckey; a.citem = d_citem; a.ccount = d_ccount;
     a.out_items = d_items + (size_t)b0 * topn; a.out_scores = d_sc + (size_t)b0 * topn;
     a.n_sel = rows; a.m = m; a.words = c.words; a.tiles_per_split = g.tiles_per_split;
-    a.splits = g.splits; a.topn = topn; a.cap = cap; a.lg_cap = 0; while ((1u << a.lg_cap) < cap) ++a.lg_cap;
-    const bool launched = launch_rank(h->K, [&](auto nch) {
-      hipLaunchKernelGGL(topn_sweep_kernel<decltype(nch)::value>, dim3(g.blocks, g.splits), dim3(256), 0, h->stream, a);
-    });
-    if (!launched) { h->err = "topn_sweep_kernel: no instance for this column count"; return HPF_ERR_UNSUPPORTED; }
-    hipLaunchKernelGGL(topn_merge_kernel, dim3(rows), dim3(256), (size_t)NP * 12, h->stream, a, NP);
-    if ((rc = check_launch(h, "topn_sweep_kernel/topn_merge_kernel"))) return rc;
+    a.splits = g.splits; a.topn = topn; a.cap = cap; a.lg_cap = hpf_plan::log2_of(cap);
+    if ((rc = launch_rank(h, "topn_sweep_kernel", [&](auto nch) {
+          hipLaunchKernelGGL(topn_sweep_kernel<decltype(nch)::value>, dim3(g.blocks, g.splits), dim3(256), 0, h->stream, a);
+          hipLaunchKernelGGL(topn_merge_kernel, dim3(rows), dim3(256), (size_t)NP * 12, h->stream, a, NP);
+        }, "topn_sweep_kernel/topn_merge_kernel"))) return rc;
   }
   return copy_back(h, {{out_items, d_items, (size_t)n_sel * topn * 4}, {out_scores, d_sc, (size_t)n_sel * topn * 8}});
 }

@@ -1680,10 +1680,12 @@ __global__ __launch_bounds__(256) void elbo_gamma_kernel(ElboGammaArgs a)
 //   score_tile_kernel   dense E_theta[sel] x E_beta^T on the fp64 matrix cores
 //                       (v_mfma_f64_16x16x4_f64) -- the one GEMM-shaped piece
 //   mask_scores_kernel  training (rating > 0) and validation items -> 0.0
-//   topn_kernel         exact top-N per user: 8-pass radix select on the
-//                       64-bit score pattern, ties by ascending item index
+//   topn_kernel         exact top-N per user (block_topn): 8-pass radix select
+//                       on the 64-bit score pattern, ties by ascending item index
 //                       (= glibc's stable merge-sort qsort), bitonic sort of N
 //   rank_query_kernel   position of one item in the full order (itemrank)
+// One order (ranks_before), one sort (bitonic_sort) and one selection (block_topn)
+// serve every ranking kernel of this file.
 // ---------------------------------------------------------------------
 typedef double double4_t __attribute__((ext_vector_type(4)));
 
@@ -1743,9 +1745,21 @@ __global__ __launch_bounds__(256) void score_tile_kernel(ScoreArgs a)
   }
 }
 
-// one wave per selected user: zero the scores of training items with a stored
-// rating > 0 (a uint8-wrapped 0 is NOT skipped: "_ratings.r(n,m) > 0") and of
-// the caller's mask list (validation items)
+// What is masked for selected user b (row u of the training matrix): its training items with a stored rating > 0 (a
+// uint8-wrapped 0 is NOT skipped: "_ratings.r(n,m) > 0") and the caller's mask list (validation items).  The 64 lanes of
+// one wave share the walk; f(item) may meet an item twice.
+template <typename F>
+__device__ __forceinline__ void masked_items(uint32_t u, uint32_t b, int lane, const int64_t *rowptr, const uint32_t *col,
+                                             const uint8_t *val, const uint64_t *mask_ptr, const uint32_t *mask_items, F &&f)
+{
+  if (rowptr)
+    for (int64_t j = rowptr[u] + lane; j < rowptr[u + 1]; j += 64)
+      if (!val || val[j] > 0) f(col[j]);
+  if (mask_ptr)
+    for (uint64_t j = mask_ptr[b] + lane; j < mask_ptr[b + 1]; j += 64) f(mask_items[j]);
+}
+
+// one wave per selected user: zero the scores of its masked items
 __global__ void mask_scores_kernel(const uint32_t *users, uint32_t n_sel, const int64_t *rowptr,
                                    const uint32_t *col, const uint8_t *val, const uint64_t *mask_ptr,
                                    const uint32_t *mask_items, double *scores, uint32_t m)
@@ -1754,12 +1768,8 @@ __global__ void mask_scores_kernel(const uint32_t *users, uint32_t n_sel, const 
   const uint32_t wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
   const uint32_t nwaves = (gridDim.x * blockDim.x) >> 6;
   for (uint32_t b = wave; b < n_sel; b += nwaves) {
-    const uint32_t u = users[b];
     double *row = scores + (size_t)b * m;
-    for (int64_t j = rowptr[u] + lane; j < rowptr[u + 1]; j += 64)
-      if (!val || val[j] > 0) row[col[j]] = 0.0;
-    if (mask_ptr)
-      for (uint64_t j = mask_ptr[b] + lane; j < mask_ptr[b + 1]; j += 64) row[mask_items[j]] = 0.0;
+    masked_items(users[b], b, lane, rowptr, col, val, mask_ptr, mask_items, [&](uint32_t it) { row[it] = 0.0; });
   }
 }
 
@@ -1768,10 +1778,38 @@ __device__ __forceinline__ unsigned long long score_key(double v)
   return (unsigned long long)__double_as_longlong(v);     // scores are >= +0.0: bit order = value order
 }
 
-// exact top-N of one row of scores per block (256 threads); NP = pow2 >= N
-__global__ __launch_bounds__(256) void topn_kernel(const double *scores, uint32_t n_sel, uint32_t m,
-                                                   uint32_t N, uint32_t NP, uint32_t *out_items,
-                                                   double *out_scores)
+// THE order of every ranking result: the larger key first, of equal keys the smaller item
+__device__ __forceinline__ bool ranks_before(unsigned long long ka, uint32_t ia, unsigned long long kb, uint32_t ib)
+{
+  return ka > kb || (ka == kb && ia < ib);
+}
+
+// Bitonic sort of the P (a power of two) entries (sk[e], si[e]) in LDS into that order, by NT threads of which this is
+// thread `tid`; barrier() stands between one step's exchanges and the next step's reads (and behind the last)
+template <uint32_t NT, typename Barrier>
+__device__ __forceinline__ void bitonic_sort(unsigned long long *sk, uint32_t *si, uint32_t P, uint32_t tid, Barrier &&barrier)
+{
+  for (uint32_t k = 2; k <= P; k <<= 1)
+    for (uint32_t j = k >> 1; j > 0; j >>= 1) {
+      for (uint32_t t = tid; t < P; t += NT) {
+        const uint32_t x = t ^ j;
+        if (x > t) {
+          const bool up = (t & k) == 0;           // "up" block: best entries first
+          const unsigned long long ka = sk[t], kb = sk[x]; const uint32_t ia = si[t], ib = si[x];
+          if (ranks_before(ka, ia, kb, ib) != up) { sk[t] = kb; sk[x] = ka; si[t] = ib; si[x] = ia; }
+        }
+      }
+      barrier();
+    }
+}
+
+// Exact top-N of a list of entries by one workgroup of 256 threads: 8-pass radix select on the 64-bit key, the entries
+// above the N-th key gathered, its ties taken in ascending i, bitonic sort; NP = pow2 >= N in dynamic LDS (NP * 12 bytes).
+// The list is src: entries i < n(), of which those with present(i) count, each a key(i) and an item(i).  All it asks of
+// the list is that equal keys come in ascending item order as i ascends.  Ne = the entries wanted (<= N, <= the present
+// ones); the N - Ne places behind them are padded (item 0xffffffff, score 0.0).
+template <typename Src>
+__device__ __forceinline__ void block_topn(const Src &src, uint32_t N, uint32_t Ne, uint32_t NP, uint32_t *out_items, double *out_scores)
 {
   extern __shared__ unsigned char smem[];
   unsigned long long *ck = (unsigned long long *)smem;            // [NP] candidate keys
@@ -1780,10 +1818,7 @@ __global__ __launch_bounds__(256) void topn_kernel(const double *scores, uint32_
   __shared__ unsigned long long s_prefix;
   __shared__ uint32_t s_remaining, s_cnt, s_wtot[4], s_eq_taken;
   const uint32_t tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  const uint32_t b = blockIdx.x;
-  if (b >= n_sel) return;
-  const double *row = scores + (size_t)b * m;
-  const uint32_t Ne = N < m ? N : m;
+  const uint32_t L = src.n();
 
   for (uint32_t k = tid; k < NP; k += 256) { ck[k] = 0ull; ci[k] = 0xffffffffu; }
   if (tid == 0) { s_prefix = 0ull; s_remaining = Ne; s_cnt = 0; s_eq_taken = 0; }
@@ -1794,8 +1829,9 @@ __global__ __launch_bounds__(256) void topn_kernel(const double *scores, uint32_
       hist[tid] = 0;
       __syncthreads();
       const unsigned long long prefix = s_prefix;
-      for (uint32_t i = tid; i < m; i += 256) {
-        const unsigned long long key = score_key(row[i]);
+      for (uint32_t i = tid; i < L; i += 256) {
+        if (!src.present(i)) continue;
+        const unsigned long long key = src.key(i);
         if (pass == 0 || (key >> (shift + 8)) == prefix) atomicAdd(&hist[(key >> shift) & 255ull], 1u);
       }
       __syncthreads();
@@ -1807,17 +1843,18 @@ __global__ __launch_bounds__(256) void topn_kernel(const double *scores, uint32_
       }
       __syncthreads();
     }
-    const unsigned long long T = s_prefix;       // key of the Ne-th largest score
-    const uint32_t need_eq = s_remaining;         // how many of the == T to take (lowest indices)
-    for (uint32_t i = tid; i < m; i += 256) {
-      const unsigned long long key = score_key(row[i]);
-      if (key > T) { const uint32_t p = atomicAdd(&s_cnt, 1u); ck[p] = key; ci[p] = i; }
+    const unsigned long long T = s_prefix;       // key of the Ne-th best entry
+    const uint32_t need_eq = s_remaining;         // how many of the == T to take (lowest items)
+    for (uint32_t i = tid; i < L; i += 256) {
+      if (!src.present(i)) continue;
+      const unsigned long long key = src.key(i);
+      if (key > T) { const uint32_t p = atomicAdd(&s_cnt, 1u); if (p < NP) { ck[p] = key; ci[p] = src.item(i); } }
     }
     __syncthreads();
     const uint32_t base = s_cnt;                  // = Ne - need_eq
-    for (uint32_t c0 = 0; c0 < m; c0 += 256) {    // ties in ascending item order
+    for (uint32_t c0 = 0; c0 < L; c0 += 256) {    // ties in ascending item order
       const uint32_t i = c0 + tid;
-      const bool eq = i < m && score_key(row[i]) == T;
+      const bool eq = src.present(i) && src.key(i) == T;
       const unsigned long long bal = __ballot(eq);
       const uint32_t before = __popcll(bal & ((1ull << lane) - 1ull));
       if (lane == 0) s_wtot[wv] = (uint32_t)__popcll(bal);
@@ -1826,32 +1863,38 @@ __global__ __launch_bounds__(256) void topn_kernel(const double *scores, uint32_
       for (uint32_t w = 0; w < 4; ++w) { if (w < wv) woff += s_wtot[w]; tot += s_wtot[w]; }
       const uint32_t taken = s_eq_taken;
       const uint32_t pos = taken + woff + before;
-      if (eq && pos < need_eq) { ck[base + pos] = T; ci[base + pos] = i; }
+      if (eq && pos < need_eq && base + pos < NP) { ck[base + pos] = T; ci[base + pos] = src.item(i); }
       __syncthreads();
       if (tid == 0) s_eq_taken = taken + tot;
       __syncthreads();
       if (s_eq_taken >= need_eq) break;
     }
     __syncthreads();
-    // bitonic sort of NP entries: key descending, item ascending
-    for (uint32_t k = 2; k <= NP; k <<= 1)
-      for (uint32_t j = k >> 1; j > 0; j >>= 1) {
-        for (uint32_t t = tid; t < NP; t += 256) {
-          const uint32_t x = t ^ j;
-          if (x > t) {
-            const bool up = (t & k) == 0;         // "up" block: best entries first
-            const unsigned long long ka = ck[t], kb = ck[x]; const uint32_t ia = ci[t], ib = ci[x];
-            const bool a_first = ka > kb || (ka == kb && ia < ib);
-            if (a_first != up) { ck[t] = kb; ck[x] = ka; ci[t] = ib; ci[x] = ia; }
-          }
-        }
-        __syncthreads();
-      }
+    bitonic_sort<256>(ck, ci, NP, tid, [] { __syncthreads(); });
   }
   for (uint32_t k = tid; k < N; k += 256) {
-    out_items[(size_t)b * N + k] = k < Ne ? ci[k] : 0xffffffffu;
-    out_scores[(size_t)b * N + k] = k < Ne ? __longlong_as_double((long long)ck[k]) : 0.0;
+    out_items[k] = k < Ne ? ci[k] : 0xffffffffu;
+    out_scores[k] = k < Ne ? __longlong_as_double((long long)ck[k]) : 0.0;
   }
+}
+
+// a row of m scores as such a list: entry i is item i
+struct RowEntries {
+  const double *row; uint32_t m;
+  __device__ __forceinline__ uint32_t n() const { return m; }
+  __device__ __forceinline__ bool present(uint32_t i) const { return i < m; }
+  __device__ __forceinline__ unsigned long long key(uint32_t i) const { return score_key(row[i]); }
+  __device__ __forceinline__ uint32_t item(uint32_t i) const { return i; }
+};
+
+// exact top-N of one row of scores per block (256 threads); NP = pow2 >= N
+__global__ __launch_bounds__(256) void topn_kernel(const double *scores, uint32_t n_sel, uint32_t m,
+                                                   uint32_t N, uint32_t NP, uint32_t *out_items,
+                                                   double *out_scores)
+{
+  const uint32_t b = blockIdx.x;
+  if (b >= n_sel) return;
+  block_topn(RowEntries{scores + (size_t)b * m, m}, N, N < m ? N : m, NP, out_items + (size_t)b * N, out_scores + (size_t)b * N);
 }
 
 // rank position (0-based) of item q_item[q] in the full descending order of
@@ -1871,7 +1914,7 @@ __global__ __launch_bounds__(256) void rank_query_kernel(const double *scores, u
     uint32_t c = 0;
     for (uint32_t i = threadIdx.x; i < m; i += 256) {
       const unsigned long long k = score_key(row[i]);
-      c += (k > kq || (k == kq && i < it)) ? 1u : 0u;
+      c += ranks_before(k, i, kq, it) ? 1u : 0u;
     }
     red[threadIdx.x] = c;
     __syncthreads();
@@ -1925,8 +1968,8 @@ __global__ __launch_bounds__(256) void predict_kernel(PredictArgs a)
   }
 }
 
-// one wave per user of the batch: bit i of row b is set when item i is zeroed for that user
-// (mask_scores_kernel's rules).  Rows are `words` 64-bit words, written as dwords.
+// one wave per user of the batch: bit i of row b is set when item i is masked for that user (masked_items).  Rows are
+// `words` 64-bit words, written as dwords.
 __global__ void loo_mask_kernel(const uint32_t *users, uint32_t n_sel, const int64_t *rowptr,
                                 const uint32_t *col, const uint8_t *val, const uint64_t *mask_ptr,
                                 const uint32_t *mask_items, uint32_t *bits, uint32_t words)
@@ -1935,14 +1978,9 @@ __global__ void loo_mask_kernel(const uint32_t *users, uint32_t n_sel, const int
   const uint32_t wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
   const uint32_t nwaves = (gridDim.x * blockDim.x) >> 6;
   for (uint32_t b = wave; b < n_sel; b += nwaves) {
-    const uint32_t u = users[b];
     uint32_t *row = bits + (size_t)b * words * 2;
-    if (rowptr)
-      for (int64_t j = rowptr[u] + lane; j < rowptr[u + 1]; j += 64)
-        if (!val || val[j] > 0) atomicOr(&row[col[j] >> 5], 1u << (col[j] & 31u));
-    if (mask_ptr)
-      for (uint64_t j = mask_ptr[b] + lane; j < mask_ptr[b + 1]; j += 64)
-        atomicOr(&row[mask_items[j] >> 5], 1u << (mask_items[j] & 31u));
+    masked_items(users[b], b, lane, rowptr, col, val, mask_ptr, mask_items,
+                 [&](uint32_t it) { atomicOr(&row[it >> 5], 1u << (it & 31u)); });
   }
 }
 
@@ -2059,6 +2097,33 @@ __device__ __forceinline__ void rank_sweep(const AFrag<NCH> &A, const double *Eb
   }
 }
 
+// ---- what the epilogues of the fused kernels share (a: LooArgs, RqArgs or TopnArgs) --------------------------------------
+// E_ubias of selected user `sel` and E_ibias of item `it`; 0.0 without -bias or where there is no such user or item
+template <typename Args>
+__device__ __forceinline__ double user_bias(const Args &a, uint32_t sel, bool ok)
+{
+  return (ok && a.ubias_col >= 0) ? a.Et[(size_t)a.users[sel] * a.ld + a.ubias_col] : 0.0;
+}
+template <typename Args>
+__device__ __forceinline__ double item_bias(const Args &a, uint32_t it, bool ok)
+{
+  return (ok && a.ibias_col >= 0) ? a.Eb[(size_t)it * a.ld + a.ibias_col] : 0.0;
+}
+// is item `it` masked for selected user `sel`?
+template <typename Args>
+__device__ __forceinline__ bool item_masked(const Args &a, uint32_t sel, uint32_t it)
+{
+  return (a.bits[(size_t)sel * a.words + (it >> 6)] >> (it & 63u)) & 1ull;
+}
+// Key of an epilogue register: the sweep's dot product v, + (E_ubias + E_ibias) with -bias, +0.0 where bit `bit` of the
+// user's mask word w of this tile is set
+__device__ __forceinline__ unsigned long long epilogue_key(double v, bool bias, double ub, double bi, unsigned long long w, int bit)
+{
+  if (bias) v += ub + bi;                                        // s += Eb_u + Eb_i
+  if ((w >> bit) & 1ull) v = 0.0;
+  return score_key(v);
+}
+
 // The threshold s(b, t) comes from the sweep's arithmetic: a 16 x 16 tile whose column j is the row of user j's query
 // item, of which the diagonal is kept.  Every score and the threshold then get + (E_ubias + E_ibias).
 template <int NCH>
@@ -2105,7 +2170,7 @@ __global__ __launch_bounds__(256) void loo_rank_kernel(LooArgs a)
       tq[r] = live[r] ? a.q_item[us] : 0u;
       if (live[r] && a.ubias_col >= 0)
         v += a.Et[(size_t)a.users[us] * a.ld + a.ubias_col] + a.Eb[(size_t)tq[r] * a.ld + a.ibias_col];
-      if (live[r] && ((a.bits[(size_t)us * a.words + (tq[r] >> 6)] >> (tq[r] & 63u)) & 1ull)) v = 0.0;
+      if (live[r] && item_masked(a, us, tq[r])) v = 0.0;
       if (tq[r] >= a.limit) live[r] = false;                   // outside the ranked range: rank 0, score 0.0
       thr[r] = v;
     }
@@ -2117,7 +2182,7 @@ __global__ __launch_bounds__(256) void loo_rank_kernel(LooArgs a)
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
     const uint32_t us = ub0 + kq + 4 * r;
-    ubv[r] = (us < a.n_sel && a.ubias_col >= 0) ? a.Et[(size_t)a.users[us] * a.ld + a.ubias_col] : 0.0;
+    ubv[r] = user_bias(a, us, us < a.n_sel);
   }
   rank_sweep<NCH>(A, a.Eb, a.limit, a.ld, a.K, a.tiles_per_split, tile, [&](uint32_t tl, const double4_t (&acc)[4]) {
     // epilogue: register r of tile t holds user kq + 4 r, item 64 tl + 16 t + r16
@@ -2136,14 +2201,15 @@ __global__ __launch_bounds__(256) void loo_rank_kernel(LooArgs a)
     for (int t = 0; t < 4; ++t) {
       const uint32_t it = i0 + 16 * t + r16;
       const bool iok = it < a.limit;
-      const double bi = (iok && a.ibias_col >= 0) ? a.Eb[(size_t)it * a.ld + a.ibias_col] : 0.0;
+      const double bi = item_bias(a, it, iok);
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        double v = acc[t][r];
+        double v = acc[t][r];                                  // epilogue_key spelled out, as the bias loads of the threshold
+                                                               // above are: these two sites keep the code this kernel had (profiles/r10)
         if (a.ubias_col >= 0) v += ubv[r] + bi;                // s += Eb_u + Eb_i
         if ((w[r] >> (16 * t + r16)) & 1ull) v = 0.0;
         const unsigned long long k = score_key(v), kt = score_key(thr[r]);
-        cnt[r] += (iok && live[r] && it != tq[r] && (k > kt || (k == kt && it < tq[r]))) ? 1u : 0u;
+        cnt[r] += (iok && live[r] && it != tq[r] && ranks_before(k, it, kt, tq[r])) ? 1u : 0u;
       }
     }
   });
@@ -2220,7 +2286,7 @@ __global__ __launch_bounds__(256) void rq_threshold_kernel(RqArgs a)
     if (kq == 0 && ok) {                                         // register 0 of lane j: D[0][j]
       double v = acc[0];
       if (a.ubias_col >= 0) v += pa[a.ubias_col] + pq[a.ibias_col];
-      if ((a.bits[(size_t)sel * a.words + (it >> 6)] >> (it & 63u)) & 1ull) v = 0.0;
+      if (item_masked(a, sel, it)) v = 0.0;
       sk[wv][j] = score_key(v); si[wv][j] = it;
       a.score[q0 + j] = v;
     }
@@ -2231,7 +2297,7 @@ __global__ __launch_bounds__(256) void rq_threshold_kernel(RqArgs a)
     uint32_t pos = 0;
     for (uint32_t f = 0; f < Q; ++f) {
       const unsigned long long kf = sk[wv][f]; const uint32_t jf = si[wv][f];
-      pos += (kf > ke || (kf == ke && (jf < ie || (jf == ie && f < (uint32_t)lane)))) ? 1u : 0u;
+      pos += (ranks_before(kf, jf, ke, ie) || (kf == ke && jf == ie && f < (uint32_t)lane)) ? 1u : 0u;
     }
     a.skey[q0 + pos] = ke; a.sitem[q0 + pos] = ie; a.sperm[q0 + pos] = q0 + (uint32_t)lane;
   }
@@ -2276,7 +2342,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void r
     const bool ok = row < a.nrows;
     const uint32_t sel = ok ? a.row_sel[row] : 0u;
     s_nq[tid] = ok ? a.row_nq[row] : 0u; s_sel[tid] = sel;
-    s_ub[tid] = (ok && a.ubias_col >= 0) ? a.Et[(size_t)a.users[sel] * a.ld + a.ubias_col] : 0.0;
+    s_ub[tid] = user_bias(a, sel, ok);
   }
   __syncthreads();
 
@@ -2289,7 +2355,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void r
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
       const uint32_t it = i0 + 16 * t + r16;
-      bi[t] = (it < a.m && a.ibias_col >= 0) ? a.Eb[(size_t)it * a.ld + a.ibias_col] : 0.0;
+      bi[t] = item_bias(a, it, it < a.m);
     }
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
@@ -2302,16 +2368,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void r
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
           const uint32_t it = i0 + 16 * t + r16;
-          double v = acc[t][r];
-          if (a.ubias_col >= 0) v += ub + bi[t];                 // s += Eb_u + Eb_i
-          if ((w >> (16 * t + r16)) & 1ull) v = 0.0;
-          const unsigned long long k = score_key(v);
-          if (it < a.m && (k > wk || (k == wk && it < wi))) {    // strictly before the worst threshold
+          const unsigned long long k = epilogue_key(acc[t][r], a.ubias_col >= 0, ub, bi[t], w, 16 * t + r16);
+          if (it < a.m && ranks_before(k, it, wk, wi)) {         // strictly before the worst threshold
             uint32_t lo = 0, hi = Q - 1;                         // the first threshold this score is strictly before
             while (lo < hi) {
               const uint32_t mid = (lo + hi) >> 1;
               const unsigned long long kt = tk[lr * RQ_QCAP + mid];
-              bool before = k > kt;
+              bool before = k > kt;                              // ranks_before, the threshold's item read only at a tie
               if (k == kt) before = it < ti[lr * RQ_QCAP + mid];
               if (before) hi = mid; else lo = mid + 1;
             }
@@ -2340,8 +2403,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void r
 //   topn_sweep_kernel  the same sweep (rank_sweep); a score that can still be among the best `topn` of its (user, split)
 //                      is appended to that pair's candidate buffer in global memory, which the owning wave sorts and cuts
 //                      back to `topn` (compaction) whenever a further tile might not fit, raising the bar for what follows
-//   topn_merge_kernel  the exact top-N of a user's segments: topn_kernel's radix select, tie walk and bitonic sort over
-//                      the (key, item) lists the sweep left instead of a row of scores
+//   topn_merge_kernel  the exact top-N of a user's segments: block_topn, the selection topn_kernel runs over a row of
+//                      scores, over the (key, item) lists the sweep left
 // Masked items score +0.0 and stay candidates; order and padding are topn_kernel's.
 // ---------------------------------------------------------------------
 constexpr int TOPN_CAP_MAX = 512;     // entries of a candidate buffer at the largest fused topn (hpf_plan::topn_cap(TOPN_FUSED_MAX))
@@ -2377,19 +2440,7 @@ __device__ __forceinline__ uint32_t topn_compact(unsigned long long *gk, uint32_
   uint32_t P = 64; while (P < c) P <<= 1;                        // c <= cap, a power of two >= 128: P <= cap
   for (uint32_t e = lane; e < P; e += 64) { const bool ok = e < c; sk[e] = ok ? gk[e] : 0ull; si[e] = ok ? gi[e] : 0xffffffffu; }
   wave_sync();
-  for (uint32_t k = 2; k <= P; k <<= 1)
-    for (uint32_t j = k >> 1; j > 0; j >>= 1) {
-      for (uint32_t t = lane; t < P; t += 64) {
-        const uint32_t x = t ^ j;
-        if (x > t) {
-          const bool up = (t & k) == 0;                          // "up" block: best entries first
-          const unsigned long long ka = sk[t], kb = sk[x]; const uint32_t ia = si[t], ib = si[x];
-          const bool a_first = ka > kb || (ka == kb && ia < ib);
-          if (a_first != up) { sk[t] = kb; sk[x] = ka; si[t] = ib; si[x] = ia; }
-        }
-      }
-      wave_sync();
-    }
+  bitonic_sort<64>(sk, si, P, lane, [] { wave_sync(); });
   const uint32_t keep = c < topn ? c : topn;
   for (uint32_t e = lane; e < keep; e += 64) { gk[e] = sk[e]; gi[e] = si[e]; }
   *worst = keep ? sk[keep - 1] : 0ull;
@@ -2424,7 +2475,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void t
   if (tid < 64) {
     const uint32_t us = ub0 + tid;
     s_cnt[tid] = 0u; s_lo[tid] = 0ull;
-    s_ub[tid] = (us < a.n_sel && a.ubias_col >= 0) ? a.Et[(size_t)a.users[us] * a.ld + a.ubias_col] : 0.0;
+    s_ub[tid] = user_bias(a, us, us < a.n_sel);
   }
   __syncthreads();
 
@@ -2435,7 +2486,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void t
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
       const uint32_t it = i0 + 16 * t + r16;
-      bi[t] = (it < a.m && a.ibias_col >= 0) ? a.Eb[(size_t)it * a.ld + a.ibias_col] : 0.0;
+      bi[t] = item_bias(a, it, it < a.m);
     }
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
@@ -2450,10 +2501,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void t
 #pragma unroll
       for (int t = 0; t < 4; ++t) {
         const uint32_t it = i0 + 16 * t + r16;
-        double v = acc[t][r];
-        if (a.ubias_col >= 0) v += ub + bi[t];                   // s += Eb_u + Eb_i
-        if ((w >> (16 * t + r16)) & 1ull) v = 0.0;
-        const unsigned long long k = score_key(v);
+        const unsigned long long k = epilogue_key(acc[t][r], a.ubias_col >= 0, ub, bi[t], w, 16 * t + r16);
         const bool take = live && it < a.m && k >= lo;
         const uint32_t grp = (uint32_t)(__ballot(take) >> (16 * kq)) & 0xffffu;   // the 16 lanes that share this user
         if (take) {
@@ -2494,96 +2542,26 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void t
   }
 }
 
-// One workgroup per user.  Entry i of the user's list is slot i % cap of segment i / cap, present when the slot is below
+// The segments of one user as block_topn's list: entry i is slot i % cap of segment i / cap, present when the slot is below
 // the segment's count.  Segments are sorted and cover ascending item ranges, so walking i upwards meets equal keys in
-// ascending item order -- which is all topn_kernel's scheme asks of a row of scores.  NP = pow2 >= topn.
+// ascending item order -- which is all block_topn asks of a list.
+struct SegmentEntries {
+  const unsigned long long *gk; const uint32_t *gi, *gc;          // the user's keys, items and counts per segment
+  uint32_t L, cap, lg_cap;                                       // L = splits x cap <= 1025 x 512
+  __device__ __forceinline__ uint32_t n() const { return L; }
+  __device__ __forceinline__ bool present(uint32_t i) const { return i < L && (i & (cap - 1u)) < gc[i >> lg_cap]; }
+  __device__ __forceinline__ unsigned long long key(uint32_t i) const { return gk[i]; }
+  __device__ __forceinline__ uint32_t item(uint32_t i) const { return gi[i]; }
+};
+
+// One workgroup per user: block_topn over what the sweep left of it.  NP = pow2 >= topn.
 __global__ __launch_bounds__(256) void topn_merge_kernel(TopnArgs a, uint32_t NP)
 {
-  extern __shared__ unsigned char smem[];
-  unsigned long long *ck = (unsigned long long *)smem;            // [NP] candidate keys
-  uint32_t *ci = (uint32_t *)(ck + NP);                          // [NP] candidate items
-  __shared__ uint32_t hist[256];
-  __shared__ unsigned long long s_prefix;
-  __shared__ uint32_t s_remaining, s_cnt, s_wtot[4], s_eq_taken;
-  const uint32_t tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const uint32_t b = blockIdx.x;
   if (b >= a.n_sel) return;
-  const uint32_t N = a.topn, Ne = N < a.m ? N : a.m;
-  const uint32_t L = a.splits << a.lg_cap;                       // <= 1025 x 512
-  const unsigned long long *gk = a.ckey + (((size_t)b * a.splits) << a.lg_cap);
-  const uint32_t *gi = a.citem + (((size_t)b * a.splits) << a.lg_cap);
-  const uint32_t *gc = a.ccount + (size_t)b * a.splits;
-  auto present = [&](uint32_t i) { return i < L && (i & (a.cap - 1u)) < gc[i >> a.lg_cap]; };
-
-  for (uint32_t k = tid; k < NP; k += 256) { ck[k] = 0ull; ci[k] = 0xffffffffu; }
-  if (tid == 0) { s_prefix = 0ull; s_remaining = Ne; s_cnt = 0; s_eq_taken = 0; }
-  __syncthreads();
-  if (Ne > 0) {
-    for (int pass = 0; pass < 8; ++pass) {
-      const int shift = 56 - 8 * pass;
-      hist[tid] = 0;
-      __syncthreads();
-      const unsigned long long prefix = s_prefix;
-      for (uint32_t i = tid; i < L; i += 256) {
-        if (!present(i)) continue;
-        const unsigned long long key = gk[i];
-        if (pass == 0 || (key >> (shift + 8)) == prefix) atomicAdd(&hist[(key >> shift) & 255ull], 1u);
-      }
-      __syncthreads();
-      if (tid == 0) {
-        uint32_t cum = 0, rem = s_remaining; int d = 255;
-        for (; d > 0; --d) { if (cum + hist[d] >= rem) break; cum += hist[d]; }
-        s_remaining = rem - cum;
-        s_prefix = (prefix << 8) | (unsigned long long)d;
-      }
-      __syncthreads();
-    }
-    const unsigned long long T = s_prefix;       // key of the Ne-th best entry
-    const uint32_t need_eq = s_remaining;         // how many of the == T to take (lowest items)
-    for (uint32_t i = tid; i < L; i += 256) {
-      if (!present(i)) continue;
-      const unsigned long long key = gk[i];
-      if (key > T) { const uint32_t p = atomicAdd(&s_cnt, 1u); if (p < NP) { ck[p] = key; ci[p] = gi[i]; } }
-    }
-    __syncthreads();
-    const uint32_t base = s_cnt;                  // = Ne - need_eq
-    for (uint32_t c0 = 0; c0 < L; c0 += 256) {    // ties in ascending item order
-      const uint32_t i = c0 + tid;
-      const bool eq = present(i) && gk[i] == T;
-      const unsigned long long bal = __ballot(eq);
-      const uint32_t before = __popcll(bal & ((1ull << lane) - 1ull));
-      if (lane == 0) s_wtot[wv] = (uint32_t)__popcll(bal);
-      __syncthreads();
-      uint32_t woff = 0, tot = 0;
-      for (uint32_t w = 0; w < 4; ++w) { if (w < wv) woff += s_wtot[w]; tot += s_wtot[w]; }
-      const uint32_t taken = s_eq_taken;
-      const uint32_t pos = taken + woff + before;
-      if (eq && pos < need_eq && base + pos < NP) { ck[base + pos] = T; ci[base + pos] = gi[i]; }
-      __syncthreads();
-      if (tid == 0) s_eq_taken = taken + tot;
-      __syncthreads();
-      if (s_eq_taken >= need_eq) break;
-    }
-    __syncthreads();
-    // bitonic sort of NP entries: key descending, item ascending
-    for (uint32_t k = 2; k <= NP; k <<= 1)
-      for (uint32_t j = k >> 1; j > 0; j >>= 1) {
-        for (uint32_t t = tid; t < NP; t += 256) {
-          const uint32_t x = t ^ j;
-          if (x > t) {
-            const bool up = (t & k) == 0;         // "up" block: best entries first
-            const unsigned long long ka = ck[t], kb = ck[x]; const uint32_t ia = ci[t], ib = ci[x];
-            const bool a_first = ka > kb || (ka == kb && ia < ib);
-            if (a_first != up) { ck[t] = kb; ck[x] = ka; ci[t] = ib; ci[x] = ia; }
-          }
-        }
-        __syncthreads();
-      }
-  }
-  for (uint32_t k = tid; k < N; k += 256) {
-    a.out_items[(size_t)b * N + k] = k < Ne ? ci[k] : 0xffffffffu;
-    a.out_scores[(size_t)b * N + k] = k < Ne ? __longlong_as_double((long long)ck[k]) : 0.0;
-  }
+  const size_t e0 = ((size_t)b * a.splits) << a.lg_cap;
+  block_topn(SegmentEntries{a.ckey + e0, a.citem + e0, a.ccount + (size_t)b * a.splits, a.splits << a.lg_cap, a.cap, a.lg_cap},
+             a.topn, a.topn < a.m ? a.topn : a.m, NP, a.out_items + (size_t)b * a.topn, a.out_scores + (size_t)b * a.topn);
 }
 
 // materialise the per-element rate matrix for export (htheta_rate.tsv):

@@ -159,7 +159,9 @@ constexpr uint32_t TOPN_MAX = 1024, TOPN_FUSED_MAX = 256;
 constexpr bool topn_fused(uint32_t topn) { return topn >= 1 && topn <= TOPN_FUSED_MAX; }
 // Entries of the candidate buffer of one (user, split): twice the power of two >= max(topn, 64).  A tile adds at most 64
 // and a compacted buffer holds topn, so cap >= topn + 64 leaves room for a tile after every compaction.
-constexpr uint32_t topn_np(uint32_t topn) { uint32_t np = 64; while (np < topn) np <<= 1; return np; }
+constexpr uint32_t pow2_ceil(uint32_t x, uint32_t least = 1) { while (least < x) least <<= 1; return least; }   // `least` a power of two
+constexpr uint32_t log2_of(uint32_t pow2) { uint32_t lg = 0; while ((1u << lg) < pow2) ++lg; return lg; }
+constexpr uint32_t topn_np(uint32_t topn) { return pow2_ceil(topn, 64); }
 constexpr uint32_t topn_cap(uint32_t topn) { return 2 * topn_np(topn); }
 constexpr uint64_t TOPN_ENTRY_BYTES = 12, TOPN_BATCH_BYTES = (uint64_t)512 << 20;    // a key and an item; candidate memory of a batch
 

@@ -155,17 +155,20 @@ def _masks_small(S, users):
 # the four routes against the reference
 # ---------------------------------------------------------------------------------------------------------------------
 def check_topn(sel, N):
+    """rank_topn and recommend (the same selection over a row of scores and over the sweep's lists), each against the reference"""
     S = sel.S
-    items, sc = S.D.rank_topn(sel.users, N, sel.mptr, sel.mitems)
-    assert items.shape == sc.shape == (len(sel.users), N)
     Ne = min(N, S.m)
-    for b, u in enumerate(sel.users):
-        if int(u) in S.loose:
-            continue
-        _, f64, order, _ = sel.expect(b)
-        assert np.array_equal(items[b, :Ne], order[:Ne].astype(np.uint32)), f"top-{N} items of user {u} (m = {S.m})"
-        assert np.array_equal(_bits(sc[b, :Ne]), _bits(f64[order[:Ne]])), f"top-{N} scores of user {u}"
-        assert np.all(items[b, Ne:] == NONE) and np.all(_bits(sc[b, Ne:]) == 0), f"entries beyond m of user {u}"
+    for route in (S.D.rank_topn, S.D.recommend):
+        name = route.__name__
+        items, sc = route(sel.users, N, sel.mptr, sel.mitems)
+        assert items.shape == sc.shape == (len(sel.users), N)
+        for b, u in enumerate(sel.users):
+            if int(u) in S.loose:
+                continue
+            _, f64, order, _ = sel.expect(b)
+            assert np.array_equal(items[b, :Ne], order[:Ne].astype(np.uint32)), f"{name}: top-{N} items of user {u} (m = {S.m})"
+            assert np.array_equal(_bits(sc[b, :Ne]), _bits(f64[order[:Ne]])), f"{name}: top-{N} scores of user {u}"
+            assert np.all(items[b, Ne:] == NONE) and np.all(_bits(sc[b, Ne:]) == 0), f"{name}: entries beyond m of user {u}"
 
 
 def check_item_ranks(sel, three):
