@@ -41,7 +41,7 @@ EXPORTS = [
     "hpf_get_work_info", "hpf_upload_csr_device", "hpf_get_csc", "hpf_set_state_device", "hpf_get_state_device",
     "hpf_iteration_times", "hpf_debug_poke_index", "hpf_start_sums", "hpf_host_alloc", "hpf_host_free",
     "hpf_heldout_bind", "hpf_heldout_ll_bound",
-    "hpf_predict", "hpf_loo_ranks", "hpf_rank_queries", "hpf_recommend",
+    "hpf_predict", "hpf_loo_ranks", "hpf_rank_queries", "hpf_recommend", "hpf_fold_in",
 ]
 
 # queries of one row of rank_queries_kernel (RQ_QCAP in csrc/hpf_kernels.hpp): hpf_rank_queries cuts a user with more
@@ -74,6 +74,25 @@ def recommend_grid(rows, n_items, topn):
         splits = max(1, (ntiles + least - 1) // least)
     return blocks, splits, tps
 
+
+# hpf_fold_in (hpf_plan::fold_plan in csrc/hpf_plan.hpp): workgroups of FOLD_WAVES waves, a slice of LDS per wave
+FOLD_WAVES, FOLD_SLICE_BYTES, FOLD_BLOCKS_MAX = 4, 12288, 65536
+
+
+def fold_plan(K, bias=False):
+    """shape of fold_in_kernel for K factors: row stride of the gathered item rows (columns), columns per lane R, LDS bytes
+    per wave and the gathered rows a wave holds there between iterations (a user with more re-gathers them)"""
+    C_ = K + (2 if bias else 0)
+    if K < 1 or C_ > 1024:
+        raise ValueError("no fold-in kernel for this column count")
+    ld = (C_ + 15) & ~15
+    return {"ld": ld, "R": (ld + 63) // 64, "lds_wave_bytes": FOLD_SLICE_BYTES,
+            "rows_held": min(64, FOLD_SLICE_BYTES // (ld * 8))}
+
+
+def fold_grid(n):
+    """workgroups hpf_fold_in launches for n users"""
+    return max(1, min((n + FOLD_WAVES - 1) // FOLD_WAVES, FOLD_BLOCKS_MAX))
 
 
 class _PinnedBlock:
@@ -218,6 +237,8 @@ def load_library(path: os.PathLike | None = None) -> C.CDLL:
         lib.hpf_rank_queries.argtypes = [vp, u32p, C.c_uint32, u64p, u32p, u64p, u32p, u32p, dp]
     if hasattr(lib, "hpf_recommend"):
         lib.hpf_recommend.argtypes = [vp, u32p, C.c_uint32, u64p, u32p, C.c_uint32, u32p, dp]
+    if hasattr(lib, "hpf_fold_in"):
+        lib.hpf_fold_in.argtypes = [vp, C.c_uint32, C.c_double, u32p]
     lib.hpf_comm_unique_id.argtypes = [vp]
     lib.hpf_comm_init.argtypes = [vp, vp]
     lib.hpf_allreduce_exchange.argtypes = [vp]
@@ -557,6 +578,15 @@ class Hpf:
         self._check(self.lib.hpf_recommend(self._h, _ptr(users, C.c_uint32), users.size, pmp, pmi, topn & 0xffffffff,
                                            _ptr(items, C.c_uint32), _ptr(sc, C.c_double)))
         return items, sc
+
+    def fold_in(self, n_iters=10, tol=0.0, want_iters=True):
+        """fold this handle's users in against the item side handed in (hpf_fold_in): from the prior, n_iters user-side
+        iterations (tol > 0: a user stops once its E[theta] moves by no more than tol of its largest entry)
+        -> the iterations every user ran (None with want_iters=False: iters_out = NULL)"""
+        iters = np.zeros(self.n_users, dtype=np.uint32) if want_iters else None
+        self._check(self.lib.hpf_fold_in(self._h, int(n_iters) & 0xffffffff, float(tol),
+                                         _ptr(iters, C.c_uint32) if want_iters else None))
+        return iters
 
     def item_ranks(self, users, q_sel, q_item, mask_ptr=None, mask_items=None):
         users = np.ascontiguousarray(users, dtype=np.uint32)

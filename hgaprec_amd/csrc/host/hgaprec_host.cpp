@@ -80,6 +80,35 @@ int Env::parse(int argc, char **argv, bool echo, std::string *bad)
       }
       recommend = (uint32_t)nrec;
     }
+    else if (!strcmp(s, "-fold-in")) {                            // extension: fold the users of FILE into a saved model
+      const char *v = next();
+      if (!*v || *v == '-') {
+        usage_error = "-fold-in needs the file with the new users' ratings (user id, item id, rating)";
+        if (bad) *bad = s;
+        return 2;
+      }
+      fold_in = v;
+    }
+    else if (!strcmp(s, "-fold-iters")) {
+      const char *v = next(); char *end = nullptr;
+      const long t = strtol(v, &end, 10);
+      if (!*v || *end || t < 1 || t > 1000000) {
+        usage_error = "-fold-iters needs the number of iterations, 1 .. 1000000";
+        if (bad) *bad = s;
+        return 2;
+      }
+      fold_iters = (uint32_t)t;
+    }
+    else if (!strcmp(s, "-fold-tol")) {
+      const char *v = next(); char *end = nullptr;
+      const double x = strtod(v, &end);
+      if (!*v || *end || !(x >= 0.0) || x > 1.0) {
+        usage_error = "-fold-tol needs the relative change at which a user stops, 0 .. 1 (0: every user runs -fold-iters iterations)";
+        if (bad) *bad = s;
+        return 2;
+      }
+      fold_tol = x;
+    }
     else if (!strcmp(s, "-model-dir")) { model_dir = next(); }   // extension: where a score mode finds the factor files
     else if (!strcmp(s, "-novb")) { vb = false; }
     else if (!strcmp(s, "-wals_l") || !strcmp(s, "-wals_C")) { next(); }
@@ -500,6 +529,53 @@ int Ratings::read_train(const std::string &path)
   int rc = read_generic(f, nullptr);
   fclose(f);
   if (rc) return rc;
+  build_csr();
+  return 0;
+}
+
+// -fold-in FILE: ratings of users who need not be in the data set this object holds, against ITS items.  The token rules
+// are read_generic's (any white space separates fields, a non-numeric token is -2, a last record cut short goes on with
+// the stale values); an empty file is zero users and no error.  Per record, in this order: an item the data set does not
+// know -> skipped and counted; a rating of class 0 (-binary-data below the threshold) -> dropped, as by the train reader;
+// otherwise the user gets the next sequence number at its first accepted record -- a user all of whose lines were skipped
+// or dropped does not exist, as for the train reader.  Rows in file order, every copy of a duplicated pair with the LAST
+// rating (build_csr).  out: n, seq2user and the CSR of the new users; m and seq2item are this object's.
+int Ratings::read_fold_in(const std::string &path, Ratings *out, uint64_t *skipped_unknown) const
+{
+  FILE *f = fopen(path.c_str(), "r");
+  if (!f) return -1;
+  *out = Ratings();
+  out->binary = binary; out->rating_threshold = rating_threshold;
+  out->cap_n = 0xffffffffu; out->cap_m = m; out->m = m; out->seq2item = seq2item;
+  *skipped_unknown = 0;
+  Tok tk(f);
+  uint32_t uid = 0, mid = 0, rating = 0;
+  while (!tk.at_eof()) {
+    const int r1 = tk.next_u32(&uid);
+    const int r2 = r1 == 1 ? tk.next_u32(&mid) : 0;
+    const int r3 = r2 == 1 ? tk.next_u32(&rating) : (r2 < 0 ? -1 : 0);
+    if (r1 == 0 || r2 == 0 || r3 == 0) {
+      fprintf(stderr, "error: malformed line in ratings file\n");
+      fclose(f);
+      return -2;
+    }
+    uint32_t us = 0, ms = 0;
+    if (!item2seq.find(mid, &ms)) { ++*skipped_unknown; continue; }
+    if (input_rating_class(rating) == 0) continue;
+    if (!out->user2seq.find(uid, &us)) {
+      if (out->n == 0xffffffffu) break;
+      us = out->n; out->user2seq.put(uid, us); out->seq2user.push_back(uid); out->n++;
+    }
+    out->nratings++;
+    out->tr_u_.push_back(us); out->tr_i_.push_back(ms); out->tr_y_.push_back(rating);
+  }
+  fclose(f);
+  out->build_csr();
+  return 0;
+}
+
+void Ratings::build_csr()
+{
   // CSR: rows by user seq, inside a row the file order (ratings.cc:105
   // push_back); the rating used for every copy of a duplicated (u,i) is the
   // LAST one written to the per-user std::map<item,uint8_t> (ratings.cc:96-103)
@@ -560,7 +636,6 @@ int Ratings::read_train(const std::string &path)
     }
   });
   std::vector<uint32_t>().swap(tr_u_); std::vector<uint32_t>().swap(tr_i_); std::vector<uint32_t>().swap(tr_y_);
-  return 0;
 }
 
 int Ratings::read_heldout(const std::string &path, HeldOut *out)

@@ -61,8 +61,16 @@ struct Env {
   // of ranking.tsv, which lists a sample of at most 1000 users; recommend.txt) through hpf_recommend; a score mode too.
   // N outside 1 .. 1024 or no N: parse() returns 2 and says why in usage_error
   uint32_t recommend = 0;
+  // extension: -fold-in FILE [-fold-iters T] [-fold-tol X] folds the users of FILE -- who need not be in -dir -- into a
+  // saved model through hpf_fold_in (HGAPRec::test(), hgaprec.cc:2257-2346: T = 10 iterations from the prior against the
+  // frozen item side; X > 0 stops a user once its E[theta] moves by no more than X of its largest entry) and writes the
+  // user-side files of save_model under the prefix foldin_, foldin.txt and, with -recommend N, foldin_recommend.tsv / .txt.
+  // A score mode too.  No FILE, T outside 1 .. 10^6 or X outside 0 .. 1: parse() returns 2 and says why in usage_error
+  std::string fold_in;
+  uint32_t fold_iters = 10;
+  double fold_tol = 0.0;
   std::string usage_error;
-  bool score_mode() const { return gen_ranking || rmse || msr || eval_all || recommend > 0; }
+  bool score_mode() const { return gen_ranking || rmse || msr || eval_all || recommend > 0 || !fold_in.empty(); }
 
   std::string prefix;          // output directory (Env::prefix)
   FILE *plogf = nullptr;       // param.txt
@@ -109,6 +117,12 @@ struct Ratings {
   // "unexpected lines" exit(-1))
   int read_train(const std::string &path);
   int read_heldout(const std::string &path, HeldOut *out);
+  // -fold-in FILE (extension): "user id, item id, rating" lines of users who need not be in this data set, read by the
+  // token rules of train.tsv against THIS data set's items.  out: the new users -- n, seq2user in order of first
+  // appearance, CSR (every copy of a duplicated pair with the last rating); m and seq2item are this object's.  Lines whose
+  // item is unknown are skipped and counted; ratings the train reader drops are dropped; a user none of whose lines is
+  // accepted does not exist; an empty file is zero users.  0 / -1 (cannot open) / -2 (malformed)
+  int read_fold_in(const std::string &path, Ratings *out, uint64_t *skipped_unknown) const;
   // ratings.cc:273-292: seq ids (sorted, unique) of the listed users that
   // appear in the training set.  -1 if the file cannot be opened
   int read_test_users(const std::string &path, std::vector<uint32_t> *out) const;
@@ -143,6 +157,7 @@ struct Ratings {
   int read_generic_parallel(FILE *f, HeldOut *out);   // 0 done, 1 not for this file (small, not well-formed, one thread)
   struct Consumer;
   uint32_t input_rating_class(uint32_t v) const;
+  void build_csr();                            // tr_u_ / tr_i_ / tr_y_ -> rowptr, col, val (and frees the triples)
   std::vector<uint32_t> tr_u_, tr_i_, tr_y_;   // training triples in file order
 };
 

@@ -15,7 +15,8 @@
 //
 // Scoring a saved model: -gen-ranking / -rmse / -msr / -eval-all / -recommend read the data like a training run, load
 // the factor files a run has written (from the current directory like the reference, or from
-// -model-dir DIR) into the handle's expectations, write ONE report and exit (Driver::score).
+// -model-dir DIR) into the handle's expectations, write ONE report and exit (Driver::score).  -fold-in FILE reads the
+// item side of those files as shape and rate and folds the users of FILE in on a second handle (Driver::fold_in_report).
 //
 // Out of scope: competitor bridges, MLE/Canny ablations, -test; their
 // flags are recognised and refused.
@@ -886,8 +887,135 @@ struct Driver {
     env.lerr("-recommend: %u users, %llu lines in recommend.tsv", n, lines);
   }
 
+  // -fold-in FILE (extension; HGAPRec::test(), hgaprec.cc:2257-2346): the users of FILE, who need not be in -dir, folded
+  // into the saved model.  The item side comes from -model-dir as SHAPE and RATE (E alone does not give Elog) through the
+  // strict readers; the host forms E = shape / rate and Elog = psi(shape) - log(rate) and hands them to a second handle
+  // that holds the new users; hpf_fold_in runs -fold-iters iterations from the prior (-fold-tol: a stopping time per
+  // user).  Output: the user-side files of save_model under the prefix foldin_, through the same writers; foldin.txt
+  // (users, nonzeros, lines skipped for an unknown item, T, X, iterations min / mean / max); with -recommend N also
+  // foldin_recommend.tsv / .txt, recommend_report's lines for the new users with their given ratings masked.
+  void fold_in_report() {
+    Ratings nu; uint64_t skipped = 0;
+    const int frc = rt.read_fold_in(env.fold_in, &nu, &skipped);
+    if (frc) { fprintf(stderr, "error: -fold-in: cannot %s %s\n", frc == -1 ? "open" : "parse", env.fold_in.c_str()); exit(1); }
+    std::string err;
+    const std::vector<uint32_t> &iid = rt.seq2item;
+    std::vector<double> E((size_t)m * k), L((size_t)m * k), rate(env.hier ? (size_t)m * k : (size_t)k);
+    const std::string base = env.hier ? "hbeta" : "beta";
+    const std::string rate_path = model_path((base + "_rate.tsv").c_str());
+    if (load_matrix(model_path((base + "_shape.tsv").c_str()), E.data(), m, k, iid.data(), (uint32_t)iid.size(), &err)) model_die(err);
+    if (env.hier ? load_matrix(rate_path, rate.data(), m, k, iid.data(), (uint32_t)iid.size(), &err)
+                 : load_vector(rate_path, rate.data(), k, nullptr, 0, &err)) model_die(err);
+    auto expectations = [&](double *e, double *l, const double *r, size_t rows, size_t cols, bool vec, const std::string &what) {
+      for (size_t i = 0; i < rows; ++i)
+        for (size_t c = 0; c < cols; ++c) {
+          const double sh = e[i * cols + c], rv = r[vec ? c : i * cols + c];
+          if (!(sh > 0.0) || !(rv > 0.0)) model_die(what + ": a shape or a rate that is not > 0 (row " + std::to_string(i) + ")");
+          e[i * cols + c] = sh / rv;
+          l[i * cols + c] = digamma(sh) - std::log(rv);
+        }
+    };
+    expectations(E.data(), L.data(), rate.data(), m, k, !env.hier, rate_path);
+    std::vector<double> bE, bL;
+    if (env.bias) {
+      bE.resize(m); bL.resize(m);
+      std::vector<double> br(m);
+      const std::string bp = model_path("betabias_rate.tsv");
+      if (load_matrix(model_path("betabias_shape.tsv"), bE.data(), m, 1, iid.data(), (uint32_t)iid.size(), &err)) model_die(err);
+      if (load_matrix(bp, br.data(), m, 1, iid.data(), (uint32_t)iid.size(), &err)) model_die(err);
+      expectations(bE.data(), bL.data(), br.data(), m, 1, false, bp);
+    }
+    env.lerr("-fold-in: item side loaded from %s", env.model_dir.empty() ? "." : env.model_dir.c_str());
+
+    hpf_handle *train = h;                       // die() reports the handle in h
+    hpf_config cfg; memset(&cfg, 0, sizeof cfg);
+    cfg.struct_size = sizeof cfg;
+    cfg.n_users = nu.n; cfg.n_items = m; cfg.K = k;
+    cfg.hier = env.hier; cfg.bias = env.bias; cfg.binary = env.binary_data;
+    cfg.n_users_total = nu.n; cfg.device = env.device; cfg.n_ranks = 1; cfg.rank = 0;
+    cfg.tiling = env.no_tiles ? 1u : 0u;
+    cfg.w_storage = env.w48 ? 2u : env.plain_rows ? 3u : 0u;
+    cfg.s_prior = 0.3; cfg.r_prior = 0.3;
+    h = nullptr;
+    int rc = hpf_create(&cfg, &h);
+    if (rc) die("hpf_create (-fold-in)", rc);
+    rc = hpf_upload_csr(h, nu.rowptr.data(), nu.col.data(), env.binary_data ? nullptr : nu.val.data());
+    if (rc) die("hpf_upload_csr (-fold-in)", rc);
+    auto put = [&](hpf_state w, const std::vector<double> &v) {
+      const int r2 = hpf_set_state(h, w, v.data(), v.size());
+      if (r2) die("hpf_set_state", r2);
+    };
+    put(HPF_BETA_E, E); put(HPF_BETA_ELOG, L);
+    if (env.bias) { put(HPF_IBIAS_E, bE); put(HPF_IBIAS_ELOG, bL); }
+    std::vector<uint32_t> iters(nu.n);
+    rc = hpf_fold_in(h, env.fold_iters, env.fold_tol, iters.data());
+    if (rc) die("hpf_fold_in", rc);
+
+    // the user-side files of save_model, prefix foldin_
+    const std::vector<uint32_t> &uid = nu.seq2user;
+    std::vector<double> buf;
+    auto write = [&](const std::string &name, hpf_state w, uint32_t rows, uint32_t cols, bool as_vector) {
+      buf.resize((size_t)rows * cols);
+      const int r2 = hpf_get_state(h, w, buf.data(), buf.size());
+      if (r2) die("hpf_get_state", r2);
+      const std::string path = env.file_str("/foldin_" + name);
+      if (as_vector ? save_vector(path, buf.data(), rows, uid.data(), (uint32_t)uid.size())
+                    : save_matrix(path, buf.data(), rows, cols, uid.data(), (uint32_t)uid.size())) io_die("cannot write", path);
+    };
+    const char *suf[3] = {"_shape.tsv", "_rate.tsv", ".tsv"};
+    const std::string tb = env.hier ? "htheta" : "theta";
+    for (int j = 0; j < 3; ++j) {
+      if (j == 1 && !env.hier) write(tb + suf[j], HPF_THETA_RATE, k, 1, true);      // GPMatrixGR rate: the K-vector
+      else write(tb + suf[j], (hpf_state)(HPF_THETA_SHAPE + j), nu.n, k, false);
+      if (env.hier) write(std::string("thetarate") + suf[j], (hpf_state)(HPF_XI_SHAPE + j), nu.n, 1, true);
+      if (env.bias) write(std::string("thetabias") + suf[j], (hpf_state)(HPF_UBIAS_SHAPE + j), nu.n, 1, false);
+    }
+    uint32_t imin = 0, imax = 0; double isum = 0;
+    for (uint32_t u = 0; u < nu.n; ++u) { imin = u ? std::min(imin, iters[u]) : iters[u]; imax = std::max(imax, iters[u]); isum += iters[u]; }
+    const std::string cpath = env.file_str("/foldin.txt");
+    FILE *cf = open_or_die(cpath, "w");
+    fprintf(cf, "%u\t%llu\t%llu\t%u\t%g\t%u\t%.5f\t%u\n", nu.n, (unsigned long long)nu.col.size(), (unsigned long long)skipped,
+            env.fold_iters, env.fold_tol, imin, nu.n ? isum / nu.n : 0.0, imax);
+    close_or_die(cf, cpath);
+    env.lerr("-fold-in: %u users, %llu ratings, %llu lines skipped (unknown item), iterations %u .. %u", nu.n,
+             (unsigned long long)nu.col.size(), (unsigned long long)skipped, imin, imax);
+
+    if (env.recommend) {
+      const uint32_t N = env.recommend, CH = 1u << 16;
+      const std::string rpath = env.file_str("/foldin_recommend.tsv"), tpath = env.file_str("/foldin_recommend.txt");
+      FILE *f = open_or_die(rpath, "w");
+      std::vector<uint32_t> us, items; std::vector<uint64_t> mptr; std::vector<double> scores;
+      unsigned long long lines = 0;
+      for (uint32_t u0 = 0; u0 < nu.n; u0 += CH) {
+        const uint32_t u1 = std::min(nu.n, u0 + CH);
+        us.clear();
+        for (uint32_t u = u0; u < u1; ++u) us.push_back(u);
+        mptr.assign(us.size() + 1, 0);               // no list beyond the given ratings, which the call masks itself
+        items.resize(us.size() * (size_t)N); scores.resize(us.size() * (size_t)N);
+        rc = hpf_recommend(h, us.data(), (uint32_t)us.size(), mptr.data(), nullptr, N, items.data(), scores.data());
+        if (rc) die("hpf_recommend", rc);
+        for (size_t b = 0; b < us.size(); ++b) {
+          const uint32_t u = us[b];
+          for (uint32_t j = 0; j < m && j < N; ++j) {
+            const uint32_t it = items[b * N + j];
+            uint32_t given = 0;
+            for (int64_t q = nu.rowptr[u]; q < nu.rowptr[u + 1]; ++q) if (nu.col[(size_t)q] == it) given = nu.val[(size_t)q];
+            if (given == 0) { fprintf(f, "%d\t%d\t%.5f\n", uid[u], rt.seq2item[it], scores[b * N + j]); ++lines; }
+          }
+        }
+      }
+      close_or_die(f, rpath);
+      FILE *tf2 = open_or_die(tpath, "w");
+      fprintf(tf2, "%u\t%llu\t%u\n", nu.n, lines, N);
+      close_or_die(tf2, tpath);
+    }
+    hpf_destroy(h);
+    h = train;
+  }
+
   // one report on the loaded state, in the reference's order of tests (main.cc:254-285, then -gen-ranking)
   void score() {
+    if (!env.fold_in.empty()) { fold_in_report(); finish(0); return; }      // needs the item side only, as shape and rate
     load_model();
     if (env.rmse) compute_rmse();
     else if (env.msr) gen_msr_csv();
@@ -1137,13 +1265,13 @@ int main(int argc, char **argv)
   if (!env.unsupported.empty()) {
     fprintf(stderr, "error: option %s selects a mode outside the MI355X hot-path build "
                     "(supported: -dir -n -m -k -hier -bias -binary-data -rfreq -max-iterations "
-                    "-seed -label -rating-threshold -logl -novb -a -b -c -d, -gen-ranking -rmse -msr -eval-all -recommend -model-dir, "
+                    "-seed -label -rating-threshold -logl -novb -a -b -c -d, -gen-ranking -rmse -msr -eval-all -recommend -fold-in -fold-iters -fold-tol -model-dir, "
                     "-ngpus -comm -single-allreduce -device)\n", env.unsupported.c_str());
     return 2;
   }
   if (env.score_mode()) {
     if (env.ngpus > 1 || world > 1) {
-      fprintf(stderr, "error: -gen-ranking / -rmse / -msr / -eval-all / -recommend score a saved model on ONE GPU: run them without -ngpus\n");
+      fprintf(stderr, "error: -gen-ranking / -rmse / -msr / -eval-all / -recommend / -fold-in score a saved model on ONE GPU: run them without -ngpus\n");
       return 1;
     }
     // the start of a run truncates validation.txt, precision.txt and friends in its output directory: that directory

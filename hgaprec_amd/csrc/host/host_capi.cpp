@@ -44,6 +44,14 @@ void hg_ratings_free(Ratings *r) { delete r; }
 int hg_ratings_read_train(Ratings *r, const char *path) { return r->read_train(path); }
 int hg_ratings_read_heldout(Ratings *r, const char *path, int which)
 { return r->read_heldout(path, which == 0 ? &r->validation : &r->test); }
+// -fold-in FILE against the items of `model`: a new Ratings holding the new users (hg_ratings_free), NULL with *rc = -1 / -2
+Ratings *hg_ratings_read_fold_in(const Ratings *model, const char *path, uint64_t *skipped_unknown, int *rc)
+{
+  Ratings *out = new Ratings();
+  *rc = model->read_fold_in(path, out, skipped_unknown);
+  if (*rc) { delete out; return nullptr; }
+  return out;
+}
 uint32_t hg_ratings_n(const Ratings *r) { return r->n; }
 uint32_t hg_ratings_m(const Ratings *r) { return r->m; }
 uint64_t hg_ratings_nnz(const Ratings *r) { return r->col.size(); }

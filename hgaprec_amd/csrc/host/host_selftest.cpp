@@ -102,6 +102,37 @@ static void test_reader()
   CHECK(missing.read_train(path("does-not-exist.tsv")) != 0);
 }
 
+// ---- -fold-in FILE: new users against the items of a data set that has been read -------
+static void test_fold_in_reader()
+{
+  write_text(path("fi_train.tsv"), "1\t70\t5\n1\t30\t4\n2\t90\t3\n");
+  Ratings r; r.cap_n = 10; r.cap_m = 10;
+  CHECK(r.read_train(path("fi_train.tsv")) == 0 && r.m == 3);
+  // first appearance, a duplicated pair (last wins, both copies stay), rating 0, an unknown item, a user with nothing
+  // but unknown items, 300 wraps to 44, no trailing newline
+  write_text(path("fi.tsv"), "50\t30\t2\n40\t70\t1\n50\t555\t5\n50\t30\t4\n60\t556\t1\n40\t90\t0\n50\t90\t300");
+  Ratings f; uint64_t skipped = 99;
+  CHECK(r.read_fold_in(path("fi.tsv"), &f, &skipped) == 0);
+  CHECK(skipped == 2 && f.n == 2 && f.m == 3 && f.seq2item == r.seq2item);
+  CHECK(f.seq2user.size() == 2 && f.seq2user[0] == 50 && f.seq2user[1] == 40);
+  CHECK(f.rowptr.size() == 3 && f.rowptr[1] == 3 && f.rowptr[2] == 4 && f.col.size() == 4 && f.val.size() == 4);
+  if (f.col.size() == 4) {
+    CHECK(f.col[0] == 1 && f.col[1] == 1 && f.col[2] == 2 && f.col[3] == 0);
+    CHECK(f.val[0] == 4 && f.val[1] == 4 && f.val[2] == 44 && f.val[3] == 1);
+  }
+  write_text(path("fi_empty.tsv"), "");
+  Ratings e; skipped = 99;
+  CHECK(r.read_fold_in(path("fi_empty.tsv"), &e, &skipped) == 0 && e.n == 0 && skipped == 0 && e.rowptr.size() == 1 && e.col.empty());
+  write_text(path("fi_junk.tsv"), "1\t30\t3\nabc\t2\n");
+  Ratings j;
+  CHECK(r.read_fold_in(path("fi_junk.tsv"), &j, &skipped) == -2);
+  CHECK(r.read_fold_in(path("fi-does-not-exist.tsv"), &j, &skipped) == -1);
+  std::string big = "4294967295\t30\t4294967295\n99999999999999999999\t70\t1\n" + std::string(100000, '7') + "\t90\t1\n";
+  write_text(path("fi_big.tsv"), big);
+  Ratings b;
+  CHECK(r.read_fold_in(path("fi_big.tsv"), &b, &skipped) == 0 && b.n >= 1 && (uint64_t)b.rowptr[b.n] == b.col.size());
+}
+
 // ---- dataset cache: round trip, then every kind of damaged image ------------
 static void test_cache()
 {
@@ -429,6 +460,7 @@ int main(int argc, char **argv)
   test_idmap();
   test_env();
   test_reader();
+  test_fold_in_reader();
   test_cache();
   test_writers();
   test_state();

@@ -80,7 +80,9 @@ struct Side {
   double bias_rate_add = 0.0;
   uint32_t sweep_blocks = 0;
   bool have_E = false, have_L = false, have_prior = false;
-  bool w_dirty = false;      // L was handed in by hpf_set_state: W must be derived from it
+  bool have_bias_E = false, have_bias_L = false;   // the bias column of E / L was handed in (hpf_fold_in asks for the item side's)
+  bool bias_rate_known = false;   // hpf_fold_in left the bias at rate r_prior + bias_rate_add (readable before the first sweep)
+  bool w_dirty = false;     // L was handed in by hpf_set_state: W must be derived from it
   bool l_stale = false;      // a sweep ran since L was last valid: rebuild L on export
   bool es_stale = false;     // S holds raw phi sums and E predates the last sweep
 };
@@ -337,6 +339,16 @@ bool launch_sweep(int mode, int G, int R, const SweepArgs &a, uint32_t blocks, h
       } else if constexpr (unreachable_sweep(PICKED(m), PICKED(g), PICKED(r))) (void)&row_sweep_kernel<PICKED(g), PICKED(r), PICKED(m)>;
       return false;
     }); }); });
+}
+// fold_in_kernel: R columns per lane (hpf_plan::fold_plan), four waves and their slices of LDS per workgroup
+bool launch_fold(int R, const FoldArgs &a, uint32_t blocks, uint32_t lds_bytes, hipStream_t st)
+{
+  return pick(R, Counts(), [&](auto r) {
+    if constexpr (hpf_plan::has_fold(PICKED(r))) {
+      hipLaunchKernelGGL((fold_in_kernel<PICKED(r)>), dim3(blocks), dim3(64 * hpf_plan::FOLD_WAVES), lds_bytes, st, a);
+      return true;
+    } else return false;
+  });
 }
 int check_launch(hpf_handle *h, const char *what);
 // the fused rank kernels, by the chunks of A a column count keeps in registers (hpf_plan::rank_chunks); launch(nch) names
@@ -1990,6 +2002,9 @@ static int set_state_impl(hpf_handle *h, hpf_state which, const double *host, si
   if (obj <= 1) {
     if (kind == 2) s->have_E = true;
     if (kind == 3) s->have_L = true;
+  } else {
+    if (kind == 2) s->have_bias_E = true;
+    if (kind == 3) s->have_bias_L = true;
   }
   if (kind == 3) s->w_dirty = true;          // Elog of theta/beta or of a bias column
   if (kind != 0) h->derived_dirty = h->sums_dirty = true;
@@ -2042,7 +2057,7 @@ static int get_state_impl(hpf_handle *h, hpf_state which, double *host, size_t c
     const size_t want = gr ? h->K : (size_t)rows * cols;
     if (count != want) return HPF_ERR_INVALID;
     if (obj >= 4) {                           // gpbase.hh:225-231 via hgaprec.cc:1389,1393
-      if (h->iterations == 0) { h->err = "bias rate is defined after the first sweep"; return HPF_ERR_STATE; }
+      if (h->iterations == 0 && !s->bias_rate_known) { h->err = "bias rate is defined after the first sweep"; return HPF_ERR_STATE; }
       return fill(r0 + s->bias_rate_add, rows);
     }
     if (h->iterations == 0) {
@@ -2241,6 +2256,8 @@ int hpf_snapshot_load(hpf_handle *h, const void *host, size_t bytes)
     Side &s = *sides[k]; const uint32_t f = hd.side_flags[k];
     s.have_E = f & 1u; s.have_L = f & 2u; s.have_prior = f & 4u; s.w_dirty = f & 8u; s.l_stale = f & 16u; s.es_stale = f & 32u;
     s.w_from_sweep = (f & 256u) != 0;
+    s.have_bias_E = s.have_E; s.have_bias_L = s.have_L;      // a snapshot does not say them apart: the whole rows came with it
+    s.bias_rate_known = false;
   }
   h->derived_dirty = hd.derived_dirty != 0;
   h->sums_dirty = (hd.more_flags & 1u) != 0;
@@ -2285,6 +2302,142 @@ int hpf_iterate_local_sweep(hpf_handle *h) { return h ? sweep_users(h) : HPF_ERR
 int hpf_iterate_local_items(hpf_handle *h) { return h ? phi_items(h, true) : HPF_ERR_INVALID; }
 int hpf_iterate_local_users(hpf_handle *h) { return h ? iterate_local_users(h) : HPF_ERR_INVALID; }
 int hpf_iterate_global(hpf_handle *h) { return h ? iterate_global(h) : HPF_ERR_INVALID; }
+
+namespace {
+
+// the user side after a fold-in: what hpf_set_state of every user-side array would leave behind
+void fold_mark_state(hpf_handle *h)
+{
+  Side &s = h->u;
+  s.have_E = s.have_L = true;
+  if (h->cfg.hier) s.have_prior = true;
+  if (h->cfg.bias) s.have_bias_E = s.have_bias_L = s.bias_rate_known = true;
+  s.es_stale = s.l_stale = false;
+  s.w_dirty = true; s.w_from_sweep = false;
+  h->derived_dirty = h->sums_dirty = true;
+}
+
+// room for what the rates are exported from before the first sweep (hpf_set_state(THETA_RATE), (XI_SHAPE))
+int fold_export_room(hpf_handle *h)
+{
+  Side &u = h->u;
+  int rc;
+  const size_t want = h->cfg.hier ? (size_t)u.rows * h->K : (size_t)h->K;
+  dfree(u.rate_set); u.rate_set = nullptr;
+  if ((rc = dalloc(h, &u.rate_set, want))) return rc;
+  u.rate_set_count = want;
+  if (h->cfg.hier && !u.prior_shape_set && (rc = dalloc(h, &u.prior_shape_set, u.rows))) return rc;
+  return HPF_OK;
+}
+
+// one launch: all iterations of all users (fold_in_kernel)
+int fold_fused(hpf_handle *h, uint32_t n_iters, double tol, uint32_t *iters_out)
+{
+  const hpf_plan::FoldPlan fp = hpf_plan::fold_plan(h->K, h->cfg.bias != 0);
+  if (!fp.ok) { h->err = "fold_in_kernel: no instance for this column count"; return HPF_ERR_UNSUPPORTED; }
+  Side &u = h->u, &it = h->it;
+  const uint32_t n = u.rows, m = it.rows, ld = h->ld;
+  const double s0 = h->cfg.s_prior, r0 = h->cfg.r_prior;
+  int rc;
+  if ((rc = refresh_elog(h, it))) return rc;                 // E and Elog of the item side as of its last sweep
+  if ((rc = fold_export_room(h))) return rc;
+  Scratch sc(h);
+  double *Wb = nullptr, *part = nullptr, *csum = nullptr; uint32_t *d_iters = nullptr;
+  if ((rc = sc.alloc(&Wb, (size_t)m * fp.ld)) || (rc = sc.alloc(&part, (size_t)it.sweep_blocks * ld)) || (rc = sc.alloc(&csum, ld))) return rc;
+  if (iters_out && (rc = sc.alloc(&d_iters, n))) return rc;
+  hipLaunchKernelGGL(fold_derive_w_kernel, dim3(std::min<uint32_t>((m + 3) / 4, 4096)), dim3(256), 0, h->stream, it.L, Wb, m, ld, fp.ld,
+                     h->K, it.bias_col, it.junk_col);
+  // c[k] = sum_i E[beta_ik], into a temporary: the item side's own column sums stay as they are
+  hipLaunchKernelGGL(colsum_partial_kernel, dim3(it.sweep_blocks), dim3(256), 0, h->stream, it.E, m, ld, h->K, part);
+  hipLaunchKernelGGL(colsum_finalize_kernel, dim3(ld), dim3(256), 0, h->stream, part, it.sweep_blocks, ld, csum, h->flags);
+  if ((rc = check_launch(h, "fold-in set-up"))) return rc;
+  FoldArgs a;
+  a.rowptr = h->rowptr_dev; a.idx = u.idx; a.val = u.val; a.Wb = Wb; a.csum = csum;
+  a.S = u.S; a.E = u.E; a.L = u.L; a.rate = u.rate_set;
+  a.xi_shape = u.prior_shape_set; a.xi_rate = u.prior_rate; a.xi_E = u.prior_E; a.xi_elog = u.prior_elog;
+  a.xi_used = u.prior_used; a.xi_elog_used = u.prior_elog_used;
+  a.iters_out = d_iters; a.flags = h->flags;
+  a.n = n; a.ld = ld; a.ldf = fp.ld; a.K = h->K; a.rows_held = fp.rows_held; a.slice = fp.lds_wave_bytes / 8;
+  a.n_iters = n_iters; a.hier = h->cfg.hier;
+  a.bias_col = u.bias_col; a.junk_col = u.junk_col;
+  a.rate_bias = r0 + u.bias_rate_add;
+  a.s_prior = s0; a.r_prior = r0; a.tol = tol;
+  a.xi_shape_v = s0 + (double)h->K * s0; a.psi_xi_shape = host_digamma(a.xi_shape_v);
+  a.elog_prior = host_digamma(s0) - std::log(r0);
+  if (!launch_fold((int)fp.R, a, fp.grid(n), fp.lds_block_bytes(), h->stream)) { h->err = "fold_in_kernel: no instance for this column count"; return HPF_ERR_UNSUPPORTED; }
+  if ((rc = check_launch(h, "fold_in_kernel"))) return rc;
+  // what the rate was built from, where the exports after a sweep look for it
+  HIPCHK(h, hipMemcpyAsync(u.colsum_used, csum, (size_t)ld * 8, hipMemcpyDeviceToDevice, h->stream));
+  fold_mark_state(h);
+  return copy_back(h, {{iters_out, d_iters, (size_t)n * 4}});
+}
+
+// A/B route (HPF_FOLD_ROUTE=sweeps under HPF_EXPERIMENTAL=1; never chosen by the library): the same call as n_iters x (the
+// user-major phi pass + the user sweep) of the training path, from the prior.  Every user runs n_iters iterations.
+int fold_sweeps(hpf_handle *h, uint32_t n_iters, double tol, uint32_t *iters_out)
+{
+  if (tol > 0.0) { h->err = "HPF_FOLD_ROUTE=sweeps runs every user for n_iters iterations: tol must be 0"; return HPF_ERR_UNSUPPORTED; }
+  Side &u = h->u, &it = h->it;
+  const uint32_t n = u.rows, ld = h->ld;
+  const double s0 = h->cfg.s_prior, r0 = h->cfg.r_prior;
+  int rc;
+  if ((rc = fold_export_room(h))) return rc;
+  hipLaunchKernelGGL(fold_prior_kernel, dim3(grid_for((uint64_t)n * ld)), dim3(256), 0, h->stream, u.S, u.E, u.L,
+                     h->cfg.hier ? u.prior_E : nullptr, u.prior_elog, n, ld, h->K, u.bias_col, s0, s0 / r0, host_digamma(s0) - std::log(r0));
+  if ((rc = check_launch(h, "fold_prior_kernel"))) return rc;
+  fold_mark_state(h);
+  const bool eta_given = it.have_prior;
+  it.have_prior = true;                                      // eta is not read by the user half
+  rc = prepare_derived(h);
+  it.have_prior = eta_given;
+  if (rc) return rc;
+  for (uint32_t t = 0; t < n_iters; ++t)
+    if ((rc = run_phi(h, u, it, h->ev[3])) || (rc = run_sweep(h, u, it.colsum, u.colsum))) return rc;
+  uint32_t fl = 0;
+  HIPCHK(h, hipMemcpyAsync(&fl, h->flags, 4, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  if (fl & 6u) { h->err = "HPF_FOLD_ROUTE=sweeps: the packed rows cannot hold this state (use w_storage = 3)"; return HPF_ERR_UNSUPPORTED; }
+  if ((rc = refresh_elog(h, u))) return rc;                  // shape, E and Elog from the raw sums
+  if (h->cfg.hier) {
+    hipLaunchKernelGGL(build_rate_kernel, dim3(1024), dim3(256), 0, h->stream, u.prior_used, u.colsum_used, n, h->K, u.rate_set);
+    if ((rc = check_launch(h, "build_rate"))) return rc;
+    std::vector<double> shp(std::max<uint32_t>(n, 1), s0 + (double)h->K * s0);
+    if ((rc = h2d(h, u.prior_shape_set, shp.data(), (size_t)n * 8))) return rc;
+  } else {
+    std::vector<double> cs(ld);
+    HIPCHK(h, hipMemcpyAsync(cs.data(), u.colsum_used, (size_t)ld * 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    for (uint32_t k = 0; k < h->K; ++k) cs[k] += r0;
+    if ((rc = h2d(h, u.rate_set, cs.data(), (size_t)h->K * 8))) return rc;
+  }
+  fold_mark_state(h);
+  if (iters_out) std::fill(iters_out, iters_out + n, n_iters);
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  return HPF_OK;
+}
+
+}  // namespace
+
+int hpf_fold_in(hpf_handle *h, uint32_t n_iters, double tol, uint32_t *iters_out)
+{
+  if (!h) return HPF_ERR_INVALID;
+  if (n_iters == 0) { h->err = "hpf_fold_in: n_iters must be at least 1"; return HPF_ERR_INVALID; }
+  if (!(tol >= 0.0)) { h->err = "hpf_fold_in: tol must be a number >= 0"; return HPF_ERR_INVALID; }
+  if (!h->have_csr) { h->err = "hpf_upload_csr has not been called"; return HPF_ERR_STATE; }
+  if (h->phase != 0) { h->err = "hpf_fold_in: call between iterations"; return HPF_ERR_STATE; }
+  const Side &it = h->it;
+  if (h->iterations == 0 && !(it.have_E && it.have_L)) { h->err = "item side not set: hand in BETA_E and BETA_ELOG before folding in"; return HPF_ERR_STATE; }
+  if (h->iterations == 0 && h->cfg.bias && !(it.have_bias_E && it.have_bias_L)) {
+    h->err = "item side not set: hand in IBIAS_E and IBIAS_ELOG before folding in (-bias)"; return HPF_ERR_STATE;
+  }
+  if (h->u.rows == 0) return HPF_OK;
+  int rc;
+  // the folded-in state supersedes whatever the kernels flagged about the old one, like a state handed in
+  if ((rc = recover_if_flushed(h))) return rc;
+  HIPCHK(h, hipMemsetAsync(h->flags, 0, 4, h->stream));
+  if ((rc = h->fold_route == 1 ? fold_sweeps(h, n_iters, tol, iters_out) : fold_fused(h, n_iters, tol, iters_out))) return rc;
+  return check_flags(h);
+}
 
 namespace {
 // per-pair log-likelihoods of cnt pairs whose indices lie on the device, into hout (host; page-locked for a bound set),

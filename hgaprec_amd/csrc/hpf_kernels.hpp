@@ -1441,6 +1441,233 @@ __global__ __launch_bounds__(256) void derive_w_kernel(const double *L, void *W,
 }
 
 // ---------------------------------------------------------------------
+// Fold-in (hpf_fold_in; HGAPRec::test(), hgaprec.cc:2257-2346): every user-side CAVI iteration of a NEW user against a
+// frozen item side, in one launch.  One wave owns one user from the prior to its stop; lane l holds the columns
+// l + 64 t, t < R, of the user's row.  Between iterations the user lives in registers -- own (the W form of theta and of
+// the bias: exp(Elog) over the row maximum), ev (E), sh (shape) and the scalars of xi -- and goes to memory once, when it
+// stops.  The item rows are gathered from a plain fp64 copy Wb = exp(Elog beta - row max) of stride ldf (fold_derive_w_kernel:
+// not the handle's packed W); a user whose rows fit the wave's slice of LDS (len <= rows_held <= 64) gathers them in the
+// first iteration only and reads them back from LDS afterwards -- the same doubles, so both paths give the same bits.  A
+// lane reads from LDS only what it stored itself: no barrier.
+// Per nonzero, in CSR order (two at a time for the latency of the 64-lane sum; the accumulation stays in CSR order):
+//   ssum = sum_c own_c x_c ,  acc_c += x_c * yy / ssum ;  at the end of the row S_c = own_c * acc_c      (phi_batch's form)
+// then steps B, D-user and E of the iteration on the row in registers (row_sweep_kernel's arithmetic, E by an IEEE division).
+// ---------------------------------------------------------------------
+struct FoldArgs {
+  const int64_t  *rowptr;   // [n + 1] CSR of the users
+  const uint32_t *idx;      // item of each nonzero
+  const uint8_t  *val;      // rating (NULL: all ones)
+  const double   *Wb;       // [n_items x ldf] exp(Elog - row max) of the item side, bias and junk columns included
+  const double   *csum;     // [>= K] c_k = sum_i E[beta_ik]
+  double *S, *E, *L;        // [n x ld] out: shape, E, Elog of the user side
+  double *rate;             // out: hier [n x K], else the K-vector (written by user 0's wave)
+  double *xi_shape, *xi_rate, *xi_E, *xi_elog, *xi_used, *xi_elog_used;   // [n] out (hier)
+  uint32_t *iters_out;      // [n] out, may be NULL
+  uint32_t *flags;          // bit 0: a softmax denominator underflowed
+  uint32_t n, ld, ldf, K, rows_held, slice, n_iters, hier;
+  int32_t  bias_col, junk_col;
+  double   rate_bias;       // r_prior + n_items
+  double   s_prior, r_prior, tol;
+  double   xi_shape_v, psi_xi_shape;    // s0 + K s0 and its digamma
+  double   elog_prior;      // psi(s0) - log(r0): Elog of every object at the prior
+};
+
+template <int R>
+__device__ __forceinline__ double fold_dot(const double (&x)[R], const double (&own)[R])
+{
+  double s[2] = {0.0, 0.0};
+#pragma unroll
+  for (int e = 0; e < R; ++e) s[e & 1] = (e < 2) ? own[e] * x[e] : fma(own[e], x[e], s[e & 1]);
+  return group_sum<64>((R > 1) ? s[0] + s[1] : s[0]);
+}
+template <int R>
+__device__ __forceinline__ void fold_add(const double (&x)[R], double (&acc)[R], double ssum, double yy, bool &underflow)
+{
+  const bool ok = ssum > 0.0;
+  underflow |= !ok;
+  const double scale = ok ? yy * fast_rcp(ssum) : 0.0;
+#pragma unroll
+  for (int t = 0; t < R; ++t) acc[t] = fma(x[t], scale, acc[t]);
+}
+
+template <int R>
+__global__ __launch_bounds__(256) void fold_in_kernel(FoldArgs a)
+{
+  extern __shared__ double fold_rows[];                  // four slices of a.slice doubles, one per wave
+  const int lane = threadIdx.x & 63;
+  double *rows = fold_rows + (size_t)(threadIdx.x >> 6) * a.slice;
+  const uint32_t K = a.K, LDF = a.ldf;
+  const double s0 = a.s_prior, r0 = a.r_prior;
+  const bool hier = a.hier != 0;
+  bool underflow = false;
+  const uint32_t w0 = __builtin_amdgcn_readfirstlane((blockIdx.x * blockDim.x + threadIdx.x) >> 6);
+  const uint32_t nw = (gridDim.x * blockDim.x) >> 6;
+
+  for (uint32_t u = w0; u < a.n; u += nw) {
+    const int64_t start = a.rowptr[u];
+    const uint32_t len = (uint32_t)(a.rowptr[u + 1] - start);
+    const bool held = len <= a.rows_held;
+    double own[R], ev[R], sh[R], acc[R];
+    double pr = hier ? s0 / r0 : r0;                     // E[xi] of the previous step (the constant r_prior without hier)
+    double pr_used = r0, pel = a.elog_prior, pel_used = a.elog_prior, xrate = r0;
+    uint32_t cur_i = 0; float cur_y = 0.0f;
+
+    // shape sums S -> shape, E and the W form of the row; rate = prk + use * c_k (the bias column: rb).  Returns
+    // sum_k E (k < K) and leaves max_k |E - E_before| and max_k E in dmax / emax
+    double dmax = 0.0, emax = 0.0;
+    auto update = [&](double prk, double use, double rb) -> double {
+      double wl[R], wmax = 0.0, rsum = 0.0;
+      dmax = 0.0; emax = 0.0;
+#pragma unroll
+      for (int t = 0; t < R; ++t) {
+        const uint32_t c = (uint32_t)lane + 64u * t;
+        const bool fk = c < K, fb = (int32_t)c == a.bias_col;
+        const double cs = fk ? a.csum[c] : 0.0;
+        const double shp = fmax(s0 + own[t] * acc[t], 1e-30);          // GPBase::make_nonzero, as the sweep has it
+        const double rt = fmax(fk ? fma(cs, use, prk) : rb, 1e-30);
+        const PsiRate ps = psi_parts_rate(shp, rt);
+        const double e = (fk || fb) ? shp / rt : 0.0;
+        const double ek = fk ? e : 0.0;
+        dmax = fmax(dmax, fk ? fabs(e - ev[t]) : 0.0);
+        emax = fmax(emax, ek);
+        rsum += ek;
+        const double w = ps.xs * exp_neg(ps.corr) * ps.ri;             // exp(psi(shape) - log(rate))
+        wl[t] = (fk || fb) ? w : ((int32_t)c == a.junk_col ? 1.0 : 0.0);
+        wmax = fmax(wmax, wl[t]);
+        sh[t] = shp; ev[t] = e;
+      }
+      wmax = group_max<64>(wmax);
+      dmax = group_max<64>(dmax);
+      emax = group_max<64>(emax);
+      const double inv = (wmax > 0.0) ? fast_rcp(wmax) : 0.0;
+#pragma unroll
+      for (int t = 0; t < R; ++t) own[t] = wl[t] * inv;
+      return group_sum<64>(rsum);
+    };
+
+    // the prior: every Gamma object at shape s_prior, rate r_prior
+#pragma unroll
+    for (int t = 0; t < R; ++t) { own[t] = 0.0; acc[t] = 0.0; ev[t] = 0.0; }
+    (void)update(r0, 0.0, r0);
+
+    uint32_t it = 0;
+    for (;;) {
+#pragma unroll
+      for (int t = 0; t < R; ++t) acc[t] = 0.0;
+      const bool from_lds = held && it > 0;              // wave-uniform
+      auto get = [&](double (&x)[R], uint32_t j, uint32_t jrow) {
+        if (from_lds) {
+#pragma unroll
+          for (int t = 0; t < R; ++t) { const uint32_t c = (uint32_t)lane + 64u * t; x[t] = (c < LDF) ? rows[(size_t)jrow * LDF + c] : 0.0; }
+        } else {
+          const uint32_t in = (uint32_t)__builtin_amdgcn_readlane((int)cur_i, (int)j);
+          const double *p = a.Wb + (size_t)in * LDF;
+#pragma unroll
+          for (int t = 0; t < R; ++t) { const uint32_t c = (uint32_t)lane + 64u * t; x[t] = (c < LDF) ? p[c] : 0.0; }
+          if (held) {
+#pragma unroll
+            for (int t = 0; t < R; ++t) { const uint32_t c = (uint32_t)lane + 64u * t; if (c < LDF) rows[(size_t)jrow * LDF + c] = x[t]; }
+          }
+        }
+      };
+      auto rating = [&](uint32_t j) -> double { return (double)__int_as_float(__builtin_amdgcn_readlane(__float_as_int(cur_y), (int)j)); };
+      for (uint32_t base = 0; base < len; base += 64u) {
+        const uint32_t cnt = (len - base < 64u) ? len - base : 64u;
+        if (!from_lds) {
+          // the factor is yy = (y > 1 ? y : 1), hgaprec.cc:1355-1356, as in the phi pass
+          cur_i = ((uint32_t)lane < cnt) ? a.idx[start + base + lane] : 0u;
+          cur_y = 1.0f;
+          if (a.val && (uint32_t)lane < cnt) { const uint32_t y = a.val[start + base + lane]; cur_y = (y > 1u) ? (float)y : 1.0f; }
+        }
+        uint32_t j = 0;
+        double xa[R], xb[R];
+        for (; j + 1 < cnt; j += 2) {
+          get(xa, j, base + j);
+          get(xb, j + 1, base + j + 1);
+          const double sa = fold_dot<R>(xa, own), sb = fold_dot<R>(xb, own);
+          fold_add<R>(xa, acc, sa, rating(j), underflow);
+          fold_add<R>(xb, acc, sb, rating(j + 1), underflow);
+        }
+        if (j < cnt) {
+          get(xa, j, base + j);
+          fold_add<R>(xa, acc, fold_dot<R>(xa, own), rating(j), underflow);
+        }
+      }
+      // B, D-user: shape and rate of theta and of the bias; E: xi from the new theta
+      pr_used = pr; pel_used = pel;
+      const double rsum = update(pr, 1.0, a.rate_bias);
+      if (hier) {
+        xrate = r0 + rsum;
+        pr = a.xi_shape_v / xrate;
+        pel = a.psi_xi_shape - log(xrate);
+      }
+      ++it;
+      if (it >= a.n_iters) break;
+      if (a.tol > 0.0 && it >= 2 && dmax <= a.tol * emax) break;
+    }
+
+    // the user has stopped: its state goes out, once
+    const size_t ro = (size_t)u * a.ld;
+#pragma unroll
+    for (int t = 0; t < R; ++t) {
+      const uint32_t c = (uint32_t)lane + 64u * t;
+      if (c >= a.ld) continue;
+      const bool fk = c < K, fb = (int32_t)c == a.bias_col;
+      const double rt = fmax(fk ? pr_used + a.csum[c] : a.rate_bias, 1e-30);
+      a.S[ro + c] = (fk || fb) ? sh[t] : 0.0;
+      a.E[ro + c] = ev[t];
+      a.L[ro + c] = (fk || fb) ? digamma_pos(sh[t]) - log(rt) : 0.0;
+      if (fk && hier) a.rate[(size_t)u * K + c] = rt;
+      if (fk && !hier && u == 0) a.rate[c] = rt;
+    }
+    if (lane == 0) {
+      if (hier) {
+        a.xi_shape[u] = a.xi_shape_v; a.xi_rate[u] = xrate; a.xi_E[u] = pr; a.xi_elog[u] = pel;
+        a.xi_used[u] = pr_used; a.xi_elog_used[u] = pel_used;
+      }
+      if (a.iters_out) a.iters_out[u] = it;
+    }
+  }
+  if (__any(underflow) && lane == 0) atomicOr(a.flags, 1u);
+}
+
+// the item rows the fold-in kernel gathers: Wb = exp(L - rowmax(L)) over the live columns as plain doubles at stride
+// ldf (zeros beyond), from the handle's Elog at stride ld.  A wave per row, like derive_w_kernel.
+__global__ __launch_bounds__(256) void fold_derive_w_kernel(const double *L, double *Wb, uint32_t rows, uint32_t ld, uint32_t ldf,
+                                                            uint32_t K, int32_t bias_col, int32_t junk_col)
+{
+  const int lane = threadIdx.x & 63;
+  const uint32_t wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  const uint32_t nwaves = (gridDim.x * blockDim.x) >> 6;
+  for (uint32_t row = wave; row < rows; row += nwaves) {
+    double m = -1.0e308;
+    for (uint32_t c = lane; c < ld; c += 64) {
+      const bool live = c < K || (int32_t)c == bias_col || (int32_t)c == junk_col;
+      if (live) m = fmax(m, L[(size_t)row * ld + c]);
+    }
+    m = group_max<64>(m);
+    for (uint32_t c = lane; c < ldf; c += 64) {
+      const bool live = c < K || (int32_t)c == bias_col || (int32_t)c == junk_col;
+      Wb[(size_t)row * ldf + c] = (live && c < ld) ? exp(L[(size_t)row * ld + c] - m) : 0.0;
+    }
+  }
+}
+
+// the prior on the user side (fold-in through the training kernels, HPF_FOLD_ROUTE=sweeps): shape s0, E = s0 / r0,
+// Elog = psi(s0) - log(r0) in the live columns of S, E and L; xi likewise
+__global__ void fold_prior_kernel(double *S, double *E, double *L, double *xi_E, double *xi_elog, uint32_t rows, uint32_t ld,
+                                  uint32_t K, int32_t bias_col, double s0, double e0, double l0)
+{
+  const size_t n = (size_t)rows * ld;
+  for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (size_t)gridDim.x * blockDim.x) {
+    const uint32_t c = (uint32_t)(e % ld);
+    const bool live = c < K || (int32_t)c == bias_col;
+    S[e] = live ? s0 : 0.0; E[e] = live ? e0 : 0.0; L[e] = live ? l0 : 0.0;
+    if (c == 0 && xi_E) { xi_E[e / ld] = e0; xi_elog[e / ld] = l0; }
+  }
+}
+
+// ---------------------------------------------------------------------
 // K6: held-out log-likelihood per pair (rating_likelihood_hier,
 // hgaprec.cc:1538-1560; rating_likelihood 1503-1536).  One 16-lane group
 // per pair; the per-pair values are summed on the host in the given order.

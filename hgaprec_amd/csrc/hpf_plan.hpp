@@ -58,6 +58,7 @@ struct Knobs {
   // user pass, a C3 shard: unchanged).  Same segments, same order inside each: the same bits.  HPF_PHI_WG forces 64 | 128 | 256.
   uint32_t phi_wg = 0;
   long long loo_batch = 0;          // HPF_LOO_BATCH: at most so many users per batch of the fused rank calls (<= 0: no limit of its own)
+  int fold_route = 0;               // HPF_FOLD_ROUTE=sweeps: hpf_fold_in through the training kernels (1), for A/B runs; never chosen by the library
 };
 
 // the one place that reads the knobs from the environment
@@ -85,6 +86,7 @@ inline Knobs read_knobs()
   if (const char *e = getenv("HPF_TILE_RUN")) { int v = atoi(e); if (v >= 1) k.tile_min_run = (uint32_t)v; }
   if (const char *e = getenv("HPF_TILE_SHARE")) { int v = atoi(e); if (v >= 0 && v <= 100) k.tile_min_share = v / 100.0; }
   if (const char *e = getenv("HPF_PHI_BLOCKS")) { int v = atoi(e); if (v >= 1) k.phi_blocks = (uint32_t)v; }
+  if (const char *e = getenv("HPF_FOLD_ROUTE")) k.fold_route = !strcmp(e, "sweeps") ? 1 : 0;
   if (const char *e = getenv("HPF_PHI_WG")) { int v = atoi(e); if (v == 64 || v == 128 || v == 256) k.phi_wg = (uint32_t)v; }
   return k;
 }
@@ -191,6 +193,36 @@ inline uint32_t topn_batch_users(uint32_t m, uint32_t n_sel, uint32_t cap, long 
   uint32_t batch = rank_batch_users(m, n_sel, knob);
   while (batch > 64 && topn_batch_bytes(batch, ntiles, cap) > TOPN_BATCH_BYTES) batch = (batch - 1) & ~63u;
   return batch;
+}
+
+// ---- fold-in of new users (hpf_fold_in) ------------------------------------------------------------
+// fold_in_kernel<R>: a wave per user, lane l holds the columns l + 64 t, t < R.  The item rows it gathers are a plain fp64
+// copy of its own stride ld: the live columns K + 2 * bias padded to whole 128-byte lines (independent of how the handle
+// stores W).  Workgroups of FOLD_WAVES waves; every wave owns a slice of LDS in which the gathered rows of its user stay
+// between iterations when all of them fit: rows_held of them, at most the 64 whose ratings one register per lane holds.
+// Three workgroups' slices fit a CU's 160 KiB.  hgaprec_amd/capi.py mirrors the arithmetic (fold_plan).
+constexpr uint32_t FOLD_WAVES = 4, FOLD_SLICE_BYTES = 12288, FOLD_LDS_LIMIT = 65536, FOLD_BLOCKS_MAX = 65536;
+constexpr bool has_fold(int R) { return R >= 1 && R <= 16; }
+struct FoldPlan {
+  uint32_t ld = 0, R = 0;               // row stride of the gathered copy, columns; columns per lane
+  uint32_t lds_wave_bytes = 0;          // a wave's slice of LDS
+  uint32_t rows_held = 0;               // gathered rows a slice holds
+  bool ok = false;                      // false: no kernel instance for this column count
+  uint32_t lds_block_bytes() const { return FOLD_WAVES * lds_wave_bytes; }
+  // workgroups for n users: one wave per user until the grid is FOLD_BLOCKS_MAX workgroups, which then stride
+  uint32_t grid(uint32_t n) const { return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(((uint64_t)n + FOLD_WAVES - 1) / FOLD_WAVES, FOLD_BLOCKS_MAX)); }
+};
+inline FoldPlan fold_plan(uint32_t K, bool bias)
+{
+  FoldPlan p;
+  const uint32_t C = K + (bias ? 2u : 0u);
+  if (K < 1 || C > HPF_MAX_COLUMNS) return p;
+  p.ld = (C + 15u) & ~15u;
+  p.R = (p.ld + 63u) / 64u;
+  p.lds_wave_bytes = FOLD_SLICE_BYTES;
+  p.rows_held = std::min<uint32_t>(64u, p.lds_wave_bytes / (p.ld * 8u));
+  p.ok = has_fold((int)p.R) && p.rows_held >= 1;
+  return p;
 }
 
 // ---- the tiled phi pass: what is tiled, and where its segments run --------------------------------

@@ -32,6 +32,8 @@ def lib():
     L.hg_ratings_free.argtypes = [vp]
     L.hg_ratings_read_train.argtypes = [vp, C.c_char_p]
     L.hg_ratings_read_heldout.argtypes = [vp, C.c_char_p, C.c_int]
+    L.hg_ratings_read_fold_in.argtypes = [vp, C.c_char_p, C.POINTER(C.c_uint64), C.POINTER(C.c_int)]
+    L.hg_ratings_read_fold_in.restype = vp
     L.hg_ratings_n.argtypes = [vp]; L.hg_ratings_n.restype = C.c_uint32
     L.hg_ratings_m.argtypes = [vp]; L.hg_ratings_m.restype = C.c_uint32
     L.hg_ratings_nnz.argtypes = [vp]; L.hg_ratings_nnz.restype = C.c_uint64
@@ -108,6 +110,17 @@ class Ratings:
 
     def read_heldout(self, path, which):
         return self.L.hg_ratings_read_heldout(self._r, str(path).encode(), which)
+
+    def read_fold_in(self, path):
+        """-fold-in FILE: the ratings of new users against this data set's items -> (Ratings of the new users, lines
+        skipped because their item is unknown); (None, -1) when the file cannot be opened, (None, -2) when it is malformed"""
+        skipped, rc = C.c_uint64(0), C.c_int(0)
+        p = self.L.hg_ratings_read_fold_in(self._r, str(path).encode(), C.byref(skipped), C.byref(rc))
+        if not p:
+            return None, rc.value
+        out = Ratings.__new__(Ratings)
+        out.L, out._r = self.L, C.c_void_p(p)
+        return out, skipped.value
 
     n = property(lambda s: s.L.hg_ratings_n(s._r))
     m = property(lambda s: s.L.hg_ratings_m(s._r))

@@ -397,6 +397,30 @@ int  hpf_recommend(hpf_handle *h, const uint32_t *users, uint32_t n_sel,
                    const uint64_t *mask_ptr, const uint32_t *mask_items, uint32_t topn,
                    uint32_t *out_items, double *out_scores);
 
+/* replaces: HGAPRec::test() (hgaprec.cc:2257-2346) -- load the item factors, put the user at the prior
+ * (set_to_prior + set_to_prior_curr, 2278-2279), run user-side CAVI iterations over the user's ratings with the item
+ * side untouched.  The handle's users are the NEW users: their ratings uploaded with hpf_upload_csr[_device] (val = NULL:
+ * every rating is 1), the item side handed in with hpf_set_state -- BETA_E and BETA_ELOG, with bias also IBIAS_E and
+ * IBIAS_ELOG; no user-side state is needed or read.  A missing CSR or item state is HPF_ERR_STATE, n_iters = 0, tol < 0
+ * or a NaN tol HPF_ERR_INVALID, all before anything is launched; zero users is HPF_OK.  Any n_ranks: the local users
+ * only, nothing is exchanged.
+ * Start: every user-side Gamma object (theta; xi with hier; the user bias with bias) at shape s_prior, rate r_prior,
+ * E = s_prior / r_prior, Elog = psi(s_prior) - log(r_prior).  One iteration for user u is the user half of the
+ * reference's: phi over the user's nonzeros in CSR order (K + 2 entries with bias, hgaprec.cc:1347-1353; scaled by y when
+ * y > 1), theta shape = s_prior + sum_i phi_k, bias shape = s_prior + sum_i phi_K; theta rate = E[xi_u] of the PREVIOUS step
+ * + c_k with c_k = sum over ALL items of E[beta_ik] (hier, 1370-1378) or the K-vector r_prior + c_k (vb, 927-956); bias
+ * rate r_prior + n_items (1389); xi shape s_prior + K s_prior, rate r_prior + sum_k E[theta_uk] of the new theta
+ * (1398-1405); E and Elog as gpbase.hh:248-262.  novb changes nothing here.
+ * tol = 0: every user runs n_iters iterations.  tol > 0: user u stops after the first iteration t >= 2 with
+ * max_k |E_t[theta_uk] - E_t-1[theta_uk]| <= tol max_k E_t[theta_uk], after n_iters at the latest.  iters_out[u] (may be
+ * NULL) is the number of iterations u ran.  A user's result depends on nothing but its own ratings and the item side.
+ * Leaves the user side as hpf_set_state of THETA_* (XI_*, UBIAS_*) would: every hpf_get_state, the scoring and ranking
+ * calls and a later hpf_iterate see the folded-in state.  The item side is not written.  Synchronous.  A softmax
+ * denominator that underflows surfaces as in the training passes (HPF_ERR_STATE).
+ * One kernel launch runs all iterations of all users: a wave owns a user from the prior to its stop, with the user's
+ * state in registers and its gathered item rows in LDS when they fit. */
+int  hpf_fold_in(hpf_handle *h, uint32_t n_iters, double tol, uint32_t *iters_out /* n_users, may be NULL */);
+
 /* how the uploaded matrix was cut into work (diagnostics, tests, bench):
  * a "segment" is <= 512 consecutive nonzeros of one row; rows longer than that
  * are "long" (their segment sums are combined by a second kernel) and rows with
