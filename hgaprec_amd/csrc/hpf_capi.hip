@@ -1668,8 +1668,8 @@ int hpf_create(const hpf_config *cfg, hpf_handle **out)
   if ((rc = dalloc(h, &h->u_colsum_prev, ld))) return fail(rc);
   // log y! as HGAPRec::log_factorial does it (hgaprec.cc:1563-1570)
   {
-    double lf[256]; lf[0] = std::log(1.0); lf[1] = lf[0];
-    for (uint32_t y = 2; y < 256; ++y) lf[y] = lf[y - 1] + std::log((double)y);
+    double lf[256];
+    logfact_table(lf);
     if ((rc = dalloc(h, &h->logfact, 256))) return fail(rc);
     if ((rc = dalloc(h, &h->flags, 4))) return fail(rc);
     if (hipMemcpyAsync(h->logfact, lf, sizeof lf, hipMemcpyHostToDevice, h->stream) != hipSuccess) return fail(HPF_ERR_HIP);
@@ -2570,6 +2570,7 @@ int hpf_elbo(hpf_handle *h, double *out)
     factor_args(h, a);
     a.segs = h->u.segs; a.nseg = h->u.nseg; a.col = h->u.pass_idx(); a.val = h->u.pass_val();
     a.Wt = (const double *)h->u.W; a.Wb = (const double *)h->it.W; a.Mt = Mt; a.Mb = Mb; a.partial = part;
+    a.Lt = h->u.L; a.Lb = h->it.L; a.C = h->C;
     hipLaunchKernelGGL(elbo_nnz_w_kernel, dim3(nb_nnz), dim3(256), 0, h->stream, a);
   }
   if (h->nnz && !from_w && h->u.nseg) {

@@ -17,6 +17,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <cmath>
 #include <type_traits>
 
 // Build-time switches (A/B builds of tools/ and profiles/ only; the library ships the defaults)
@@ -1672,6 +1673,13 @@ __global__ void fold_prior_kernel(double *S, double *E, double *L, double *xi_E,
 // hgaprec.cc:1538-1560; rating_likelihood 1503-1536).  One 16-lane group
 // per pair; the per-pair values are summed on the host in the given order.
 // ---------------------------------------------------------------------
+// log y! for y = 0 .. 255 as HGAPRec::log_factorial does it (hgaprec.cc:1563-1570): the serial sum of log i
+inline void logfact_table(double lf[256])
+{
+  lf[0] = std::log(1.0); lf[1] = lf[0];
+  for (uint32_t y = 2; y < 256; ++y) lf[y] = lf[y - 1] + std::log((double)y);
+}
+
 struct LLArgs {
   const uint32_t *u, *i;
   const int32_t  *y;
@@ -1729,6 +1737,20 @@ struct ElboNnzArgs {
   int32_t         ubias_col, ibias_col;
 };
 
+// logsumexp over the C live columns of lt + lb, by the G lanes of a group (every lane gets it): the maximum first, so
+// that no spread of Elog overflows or underflows the sum
+template <int G>
+__device__ __forceinline__ double elog_logsumexp(const double *lt, const double *lb, uint32_t C, int g)
+{
+  double mx = -1.0e308;
+  for (uint32_t c = g; c < C; c += G) mx = fmax(mx, lt[c] + lb[c]);
+  mx = group_max<G>(mx);
+  double se = 0.0;
+  for (uint32_t c = g; c < C; c += G) se += exp(lt[c] + lb[c] - mx);
+  se = group_sum<G>(se);
+  return mx + log(se);
+}
+
 // one wave per segment (its user is known: no search for the owner of a
 // nonzero), the wave's four 16-lane groups take the segment's nonzeros in turn
 __global__ __launch_bounds__(256) void elbo_nnz_kernel(ElboNnzArgs a)
@@ -1749,17 +1771,13 @@ __global__ __launch_bounds__(256) void elbo_nnz_kernel(ElboNnzArgs a)
       const uint32_t it = ok ? a.col[j] : 0u;
       const double y = (ok && a.val) ? (double)a.val[j] : 1.0;
       const double *lb = a.Lb + (size_t)it * a.ld, *eb = a.Eb + (size_t)it * a.ld;
-      double mx = -1.0e308, dot = 0.0;
-      for (uint32_t c = g; c < a.C; c += G) mx = fmax(mx, lt[c] + lb[c]);
-      mx = group_max<G>(mx);
-      double se = 0.0;
-      for (uint32_t c = g; c < a.C; c += G) se += exp(lt[c] + lb[c] - mx);
+      double dot = 0.0;
+      const double lse = elog_logsumexp<G>(lt, lb, a.C, g);
       for (uint32_t c = g; c < a.K; c += G) dot = fma(et[c], eb[c], dot);
-      se = group_sum<G>(se);
       dot = group_sum<G>(dot);
       if (ok && g == 0) {
         const double yy = (y > 1.0) ? y : 1.0;
-        double v = y * yy * (mx + log(se) - log(yy)) - dot;
+        double v = y * yy * (lse - log(yy)) - dot;
         if (a.ubias_col >= 0) v -= et[a.ubias_col] + eb[a.ibias_col];
         acc += v;
       }
@@ -1778,6 +1796,12 @@ __global__ __launch_bounds__(256) void elbo_nnz_kernel(ElboNnzArgs a)
 // maximum of L over the live columns (0 in the other side's bias slot), so
 //   logsumexp(x) = log(sum_k Wt[u,k] * Wb[i,k]) + Mt[u] + Mb[i]
 // -- no exp per element, one pass over the row pair instead of two.  fp64 W only.
+// Where the two rows peak at different columns every product Wt * Wb is small: once their combined spread passes ~745
+// the sum is 0 and its log -inf, and below 2^-1022 it is subnormal and has lost digits.  A nonzero whose sum is not at
+// least ELBO_W_ZMIN -- 2^-960: what subnormal or flushed W cost a sum that large is below 2^-100 of it -- is therefore
+// evaluated in the Elog form of elbo_nnz_kernel instead (a group-uniform branch: the sum is on every lane).
+constexpr double ELBO_W_ZMIN = 0x1p-960;
+
 struct ElboNnzWArgs {
   const Seg      *segs;
   uint32_t        nseg;
@@ -1785,8 +1809,9 @@ struct ElboNnzWArgs {
   const uint8_t  *val;
   const double   *Wt, *Wb, *Et, *Eb;   // [rows x ld]
   const double   *Mt, *Mb;             // [rows] row maxima of Elog
+  const double   *Lt, *Lb;             // [rows x ld] Elog, read only below ELBO_W_ZMIN
   double         *partial;             // [gridDim.x]
-  uint32_t        ld, K;
+  uint32_t        ld, K, C;            // C = live columns (K or K+2)
   int32_t         ubias_col, ibias_col;
 };
 
@@ -1814,9 +1839,12 @@ __global__ __launch_bounds__(256) void elbo_nnz_w_kernel(ElboNnzWArgs a)
       for (uint32_t c = g; c < a.K; c += G) dot = fma(et[c], eb[c], dot);
       z = group_sum<G>(z);
       dot = group_sum<G>(dot);
+      double lse;
+      if (z >= ELBO_W_ZMIN) lse = log(z) + mt + a.Mb[it];
+      else lse = elog_logsumexp<G>(a.Lt + (size_t)sg.row * a.ld, a.Lb + (size_t)it * a.ld, a.C, g);
       if (ok && g == 0) {
         const double yy = (y > 1.0) ? y : 1.0;
-        double v = y * yy * (log(z) + mt + a.Mb[it] - log(yy)) - dot;
+        double v = y * yy * (lse - log(yy)) - dot;
         if (a.ubias_col >= 0) v -= et[a.ubias_col] + eb[a.ibias_col];
         acc += v;
       }

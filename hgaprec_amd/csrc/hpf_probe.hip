@@ -8,7 +8,12 @@
 //
 // All entry points take HOST pointers, allocate, copy, launch one small kernel, synchronise, copy back and
 // return the hipError_t (0 = success).  Arrays hold at most PROBE_MAX_N elements.
+//
+// The second half launches the report kernels themselves -- heldout_ll_kernel, elbo_nnz_kernel, elbo_nnz_w_kernel,
+// rowmax_elog_kernel, elbo_gamma_kernel -- on the caller's arrays and grid (tests/test_gpu_report_terms.py).
 #include "hpf_kernels.hpp"
+
+#include <vector>
 
 using namespace hpf;
 
@@ -324,3 +329,188 @@ PROBE_API int probe_p59_pos(int L, int G, uint32_t *run_time_out, uint32_t *comp
 
 // whether the library was built with the paired dword order (HPF_P59_PAIRED)
 PROBE_API int probe_p59_paired(void) { return HPF_P59_PAIRED ? 1 : 0; }
+
+// ---- the report kernels themselves (tests/test_gpu_report_terms.py): heldout_ll_kernel, elbo_nnz_kernel,
+// elbo_nnz_w_kernel, rowmax_elog_kernel and elbo_gamma_kernel launched on the caller's arrays with the caller's grid.
+// Every index is checked against the arrays here, before anything is launched; matrices hold at most PROBE_MAX_MAT doubles.
+namespace {
+
+constexpr size_t PROBE_MAX_MAT = (size_t)1 << 22;
+constexpr int PROBE_MAX_GRID = 4096;
+
+bool grid_ok(int g) { return g >= 1 && g <= PROBE_MAX_GRID; }
+bool mat_ok(uint32_t rows, uint32_t ld) { return rows >= 1 && ld >= 1 && (size_t)rows * ld <= PROBE_MAX_MAT; }
+bool bias_ok(int32_t ucol, int32_t icol, uint32_t ld)
+{
+  if (ucol < 0 && icol < 0) return true;
+  return ucol >= 0 && icol >= 0 && (uint32_t)ucol < ld && (uint32_t)icol < ld;
+}
+
+template <typename T>
+int to_device(DevBuf &d, const T *src, size_t n)
+{
+  PROBE_TRY(d.alloc(n * sizeof(T)));
+  if (n) PROBE_TRY(hipMemcpy(d.p, src, n * sizeof(T), hipMemcpyHostToDevice));
+  return 0;
+}
+
+// the segment list, the nonzeros and the four factor matrices of a per-nonzero ELBO kernel
+struct NnzInputs {
+  DevBuf segs, col, val, a, b, et, eb;
+  int upload(uint32_t nseg, const int64_t *seg_start, const uint32_t *seg_row, const uint32_t *seg_len, uint64_t nnz,
+             const uint32_t *col_in, const uint8_t *val_in, const double *A, const double *B, const double *Et,
+             const double *Eb, uint32_t rows_t, uint32_t rows_b, uint32_t ld)
+  {
+    std::vector<Seg> sg(nseg);
+    for (uint32_t s = 0; s < nseg; ++s) {
+      if (seg_row[s] >= rows_t || seg_start[s] < 0 || (uint64_t)seg_start[s] + seg_len[s] > nnz) return (int)hipErrorInvalidValue;
+      sg[s].start = seg_start[s]; sg[s].row = seg_row[s]; sg[s].len = seg_len[s]; sg[s].pslot = -1; sg[s].pad = 0;
+    }
+    for (uint64_t j = 0; j < nnz; ++j) if (col_in[j] >= rows_b) return (int)hipErrorInvalidValue;
+    if (int rc = to_device(segs, sg.data(), (size_t)nseg)) return rc;
+    if (int rc = to_device(col, col_in, (size_t)nnz)) return rc;
+    if (val_in) if (int rc = to_device(val, val_in, (size_t)nnz)) return rc;
+    if (int rc = to_device(a, A, (size_t)rows_t * ld)) return rc;
+    if (int rc = to_device(b, B, (size_t)rows_b * ld)) return rc;
+    if (int rc = to_device(et, Et, (size_t)rows_t * ld)) return rc;
+    return to_device(eb, Eb, (size_t)rows_b * ld);
+  }
+};
+
+}  // namespace
+
+// the table of log y!, y = 0 .. 255, that hpf_create hands to heldout_ll_kernel
+PROBE_API void probe_logfact(double *lf256) { logfact_table(lf256); }
+
+// out[p] = heldout_ll_kernel's value of pair p, from a launch of grid_blocks blocks of 256 threads
+PROBE_API int probe_heldout_ll(int grid_blocks, const uint32_t *u, const uint32_t *i, const int32_t *y, uint64_t cnt,
+                               const double *Et, uint32_t n, const double *Eb, uint32_t m, uint32_t ld, uint32_t K,
+                               int32_t ubias_col, int32_t ibias_col, uint32_t binary, const double *logfact, double *out)
+{
+  if (!grid_ok(grid_blocks) || cnt > (uint64_t)PROBE_MAX_N || !mat_ok(n, ld) || !mat_ok(m, ld) || K > ld ||
+      !bias_ok(ubias_col, ibias_col, ld))
+    return (int)hipErrorInvalidValue;
+  for (uint64_t p = 0; p < cnt; ++p) if (u[p] >= n || i[p] >= m) return (int)hipErrorInvalidValue;
+  if (cnt == 0) return 0;
+  DevBuf du, di, dy, det, deb, dlf, dout;
+  if (int rc = to_device(du, u, (size_t)cnt)) return rc;
+  if (int rc = to_device(di, i, (size_t)cnt)) return rc;
+  if (int rc = to_device(dy, y, (size_t)cnt)) return rc;
+  if (int rc = to_device(det, Et, (size_t)n * ld)) return rc;
+  if (int rc = to_device(deb, Eb, (size_t)m * ld)) return rc;
+  if (int rc = to_device(dlf, logfact, 256)) return rc;
+  PROBE_TRY(dout.alloc(cnt * sizeof(double)));
+  PROBE_TRY(hipMemset(dout.p, 0xff, cnt * sizeof(double)));     // a pair the kernel skipped reads back as NaN
+  LLArgs a;
+  a.u = du.as<uint32_t>(); a.i = di.as<uint32_t>(); a.y = dy.as<int32_t>(); a.cnt = cnt;
+  a.Et = det.as<double>(); a.Eb = deb.as<double>(); a.logfact = dlf.as<double>(); a.out = dout.as<double>();
+  a.ld = ld; a.K = K; a.ubias_col = ubias_col; a.ibias_col = ibias_col; a.binary = binary;
+  hipLaunchKernelGGL(heldout_ll_kernel, dim3((unsigned)grid_blocks), dim3(256), 0, 0, a);
+  if (const int rc = finish_launch()) return rc;
+  PROBE_TRY(hipMemcpy(out, dout.p, cnt * sizeof(double), hipMemcpyDeviceToHost));
+  return 0;
+}
+
+// partial[b] = block b's sum of elbo_nnz_kernel over the segments (seg_row, seg_start, seg_len); val may be NULL (all ones)
+PROBE_API int probe_elbo_nnz(int grid_blocks, uint32_t nseg, const int64_t *seg_start, const uint32_t *seg_row,
+                             const uint32_t *seg_len, uint64_t nnz, const uint32_t *col, const uint8_t *val,
+                             const double *Lt, const double *Lb, const double *Et, const double *Eb, uint32_t rows_t,
+                             uint32_t rows_b, uint32_t ld, uint32_t K, uint32_t C, int32_t ubias_col, int32_t ibias_col,
+                             double *partial)
+{
+  if (!grid_ok(grid_blocks) || nseg > (uint32_t)PROBE_MAX_N || nnz > (uint64_t)PROBE_MAX_N || !mat_ok(rows_t, ld) ||
+      !mat_ok(rows_b, ld) || K > C || C > ld || !bias_ok(ubias_col, ibias_col, ld))
+    return (int)hipErrorInvalidValue;
+  NnzInputs in;
+  if (int rc = in.upload(nseg, seg_start, seg_row, seg_len, nnz, col, val, Lt, Lb, Et, Eb, rows_t, rows_b, ld)) return rc;
+  DevBuf dpart;
+  PROBE_TRY(dpart.alloc((size_t)grid_blocks * sizeof(double)));
+  PROBE_TRY(hipMemset(dpart.p, 0xff, (size_t)grid_blocks * sizeof(double)));
+  ElboNnzArgs a;
+  a.segs = in.segs.as<Seg>(); a.nseg = nseg; a.col = in.col.as<uint32_t>(); a.val = val ? in.val.as<uint8_t>() : nullptr;
+  a.Lt = in.a.as<double>(); a.Lb = in.b.as<double>(); a.Et = in.et.as<double>(); a.Eb = in.eb.as<double>();
+  a.partial = dpart.as<double>(); a.ld = ld; a.K = K; a.C = C; a.ubias_col = ubias_col; a.ibias_col = ibias_col;
+  hipLaunchKernelGGL(elbo_nnz_kernel, dim3((unsigned)grid_blocks), dim3(256), 0, 0, a);
+  if (const int rc = finish_launch()) return rc;
+  PROBE_TRY(hipMemcpy(partial, dpart.p, (size_t)grid_blocks * sizeof(double), hipMemcpyDeviceToHost));
+  return 0;
+}
+
+// the same of elbo_nnz_w_kernel: W and the row maxima M as given (hpf_elbo builds them from Elog), Lt / Lb for the
+// nonzeros whose sum of W products is too small
+PROBE_API int probe_elbo_nnz_w(int grid_blocks, uint32_t nseg, const int64_t *seg_start, const uint32_t *seg_row,
+                               const uint32_t *seg_len, uint64_t nnz, const uint32_t *col, const uint8_t *val,
+                               const double *Wt, const double *Wb, const double *Mt, const double *Mb, const double *Lt,
+                               const double *Lb, const double *Et, const double *Eb, uint32_t rows_t, uint32_t rows_b,
+                               uint32_t ld, uint32_t K, uint32_t C, int32_t ubias_col, int32_t ibias_col, double *partial)
+{
+  if (!grid_ok(grid_blocks) || nseg > (uint32_t)PROBE_MAX_N || nnz > (uint64_t)PROBE_MAX_N || !mat_ok(rows_t, ld) ||
+      !mat_ok(rows_b, ld) || K > C || C > ld || !bias_ok(ubias_col, ibias_col, ld))
+    return (int)hipErrorInvalidValue;
+  NnzInputs in;
+  if (int rc = in.upload(nseg, seg_start, seg_row, seg_len, nnz, col, val, Wt, Wb, Et, Eb, rows_t, rows_b, ld)) return rc;
+  DevBuf dmt, dmb, dlt, dlb, dpart;
+  if (int rc = to_device(dmt, Mt, (size_t)rows_t)) return rc;
+  if (int rc = to_device(dmb, Mb, (size_t)rows_b)) return rc;
+  if (int rc = to_device(dlt, Lt, (size_t)rows_t * ld)) return rc;
+  if (int rc = to_device(dlb, Lb, (size_t)rows_b * ld)) return rc;
+  PROBE_TRY(dpart.alloc((size_t)grid_blocks * sizeof(double)));
+  PROBE_TRY(hipMemset(dpart.p, 0xff, (size_t)grid_blocks * sizeof(double)));
+  ElboNnzWArgs a;
+  a.segs = in.segs.as<Seg>(); a.nseg = nseg; a.col = in.col.as<uint32_t>(); a.val = val ? in.val.as<uint8_t>() : nullptr;
+  a.Wt = in.a.as<double>(); a.Wb = in.b.as<double>(); a.Et = in.et.as<double>(); a.Eb = in.eb.as<double>();
+  a.Mt = dmt.as<double>(); a.Mb = dmb.as<double>(); a.Lt = dlt.as<double>(); a.Lb = dlb.as<double>();
+  a.partial = dpart.as<double>(); a.ld = ld; a.K = K; a.C = C; a.ubias_col = ubias_col; a.ibias_col = ibias_col;
+  hipLaunchKernelGGL(elbo_nnz_w_kernel, dim3((unsigned)grid_blocks), dim3(256), 0, 0, a);
+  if (const int rc = finish_launch()) return rc;
+  PROBE_TRY(hipMemcpy(partial, dpart.p, (size_t)grid_blocks * sizeof(double), hipMemcpyDeviceToHost));
+  return 0;
+}
+
+// M[row] = rowmax_elog_kernel's maximum of row `row` of L, launched as hpf_elbo launches it
+PROBE_API int probe_rowmax_elog(const double *L, uint32_t rows, uint32_t ld, uint32_t K, int32_t bias_col, int32_t junk_col,
+                                double *M)
+{
+  if (!mat_ok(rows, ld) || K > ld || bias_col >= (int32_t)ld || junk_col >= (int32_t)ld) return (int)hipErrorInvalidValue;
+  DevBuf dl, dm;
+  if (int rc = to_device(dl, L, (size_t)rows * ld)) return rc;
+  PROBE_TRY(dm.alloc((size_t)rows * sizeof(double)));
+  hipLaunchKernelGGL(rowmax_elog_kernel, dim3((rows + 255) / 256), dim3(256), 0, 0, dl.as<double>(), dm.as<double>(), rows, ld,
+                     K, bias_col, junk_col);
+  if (const int rc = finish_launch()) return rc;
+  PROBE_TRY(hipMemcpy(M, dm.p, (size_t)rows * sizeof(double), hipMemcpyDeviceToHost));
+  return 0;
+}
+
+// partial[b] = block b's sum of elbo_gamma_kernel.  S, E, L: [rows x ld]; colsum_used: [ld]; prior_used, prior_elog_used,
+// prior_E, prior_elog, prior_rate: [rows], read with hier only (may be NULL without)
+PROBE_API int probe_elbo_gamma(int grid_blocks, const double *S, const double *E, const double *L, const double *prior_used,
+                               const double *prior_elog_used, const double *colsum_used, const double *prior_E,
+                               const double *prior_elog, const double *prior_rate, uint32_t rows, uint32_t ld, uint32_t K,
+                               int32_t bias_col, double bias_rate_add, double s_prior, double r_prior, double lg_s_prior,
+                               double prior_shape, double lg_prior_shape, uint32_t hier, double *partial)
+{
+  if (!grid_ok(grid_blocks) || !mat_ok(rows, ld) || K > ld || bias_col >= (int32_t)ld) return (int)hipErrorInvalidValue;
+  if (hier && !(prior_used && prior_elog_used && prior_E && prior_elog && prior_rate)) return (int)hipErrorInvalidValue;
+  DevBuf ds, de, dl, dcs, dpr[5], dpart;
+  const size_t n = (size_t)rows * ld;
+  if (int rc = to_device(ds, S, n)) return rc;
+  if (int rc = to_device(de, E, n)) return rc;
+  if (int rc = to_device(dl, L, n)) return rc;
+  if (int rc = to_device(dcs, colsum_used, (size_t)ld)) return rc;
+  const double *pr[5] = {prior_used, prior_elog_used, prior_E, prior_elog, prior_rate};
+  if (hier) for (int k = 0; k < 5; ++k) if (int rc = to_device(dpr[k], pr[k], (size_t)rows)) return rc;
+  PROBE_TRY(dpart.alloc((size_t)grid_blocks * sizeof(double)));
+  PROBE_TRY(hipMemset(dpart.p, 0xff, (size_t)grid_blocks * sizeof(double)));
+  ElboGammaArgs g;
+  g.S = ds.as<double>(); g.E = de.as<double>(); g.L = dl.as<double>(); g.colsum_used = dcs.as<double>();
+  g.prior_used = dpr[0].as<double>(); g.prior_elog_used = dpr[1].as<double>(); g.prior_E = dpr[2].as<double>();
+  g.prior_elog = dpr[3].as<double>(); g.prior_rate = dpr[4].as<double>();
+  g.partial = dpart.as<double>(); g.rows = rows; g.ld = ld; g.K = K; g.bias_col = bias_col; g.bias_rate_add = bias_rate_add;
+  g.s_prior = s_prior; g.r_prior = r_prior; g.lg_s_prior = lg_s_prior; g.prior_shape = prior_shape;
+  g.lg_prior_shape = lg_prior_shape; g.hier = hier;
+  hipLaunchKernelGGL(elbo_gamma_kernel, dim3((unsigned)grid_blocks), dim3(256), 0, 0, g);
+  if (const int rc = finish_launch()) return rc;
+  PROBE_TRY(hipMemcpy(partial, dpart.p, (size_t)grid_blocks * sizeof(double), hipMemcpyDeviceToHost));
+  return 0;
+}
