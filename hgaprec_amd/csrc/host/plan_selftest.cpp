@@ -15,6 +15,9 @@
 // run as `plan_selftest_asan topn-grid`, for a fixed list of cases a line
 //   tg case-id m n_sel topn fused cap batch blocks splits tiles_per_split candidate-bytes
 // which tests/test_plan_topn.py compares with tests/data/topn_grid_table.txt.
+// Then the fused sweep epilogue (fused_checks) and, run as `plan_selftest_asan fused-sweep`, a line per pinned column count
+//   fs C w_layout phi_G phi_R fused_user fused_item fused_user_under_knob_2
+// which tests/test_fused_sweep_plan.py compares with its own list.
 #include "../hpf_plan.hpp"
 
 #include <string>
@@ -273,8 +276,60 @@ static void topn_checks(bool print_cases)
   }
 }
 
+// The fused sweep epilogue (fused_sweep, has_phi_fused, has_sums): which (side, layout, shape) runs it.  Over every column count:
+// only the user side of p59 rows, only with the knob on, only a shape of the list whose build keeps three waves per SIMD
+// without scratch -- by default only the one measured to pay -- always with a sums kernel for the sweep's shape, never after
+// the fall-back to plain doubles.  With
+// print_cases a line per pinned column count:   fs C w_layout phi_G phi_R fused_user fused_item fused_user_under_knob_2
+static void fused_checks(bool print_cases)
+{
+  Knobs on, off, all; off.fused_sweep = 0; all.fused_sweep = 2;
+  CHECK(on.fused_sweep == 1, "the knob's default");
+  for (uint32_t ws = 0; ws <= 3; ++ws)
+    for (uint32_t C = 1; C <= HPF_MAX_COLUMNS; ++C) {
+      Plan p;
+      if (plan_shapes(C, ws, on, &p) != HPF_OK) continue;
+      const bool fu = fused_sweep(p, on, false);
+      CHECK(!fused_sweep(p, on, true), "ws=%u C=%u: the item side fused", ws, C);
+      CHECK(!fused_sweep(p, off, false) && !fused_sweep(p, off, true), "ws=%u C=%u: fused with the knob off", ws, C);
+      CHECK(!fu || (ws == 0 && p.wl == WL_P59), "ws=%u C=%u wl=%d: fused rows that are not p59", ws, C, p.wl);
+      const bool fa = fused_sweep(p, all, false);                         // HPF_FUSED_SWEEP=2: wherever an instance exists
+      CHECK(!fused_sweep(p, all, true), "ws=%u C=%u: the item side fused under the knob 2", ws, C);
+      CHECK(fa == (p.wl == WL_P59 && has_phi_fused(p.wl, p.phiG, p.phiR) && has_sums(p.sw_mode, p.swG, p.swR)), "ws=%u C=%u", ws, C);
+      CHECK(fu == (fa && fused_pays(p.phiG, p.phiR)) && (!fu || (C >= 81 && C <= 104)), "ws=%u C=%u: the default fuses what was measured to pay", ws, C);
+      if (fa) {
+        CHECK(has_phi_packed(p.wl, p.phiG, p.phiR) && has_sweep(p.sw_mode, p.swG, p.swR), "ws=%u C=%u: no unfused instance beside the fused one", ws, C);
+        CHECK(p.pk.row_bytes <= 1536u, "ws=%u C=%u: a staged row of %u bytes", ws, C, p.pk.row_bytes);
+        CHECK(!fused_sweep(p.as_plain_doubles(), all, false), "ws=%u C=%u: fused after the fall-back", ws, C);
+      }
+    }
+  // the instance list itself: G <= 8 up to six pieces, then 16 x 3, 32 x 2, 64 x 1; nothing for another layout
+  for (int g : {2, 4, 8, 16, 32, 64, 128})
+    for (int l = 0; l <= 10; ++l) {
+      const bool want = (g == 4 || g == 8) ? (l >= 1 && l <= 6) : g == 16 ? (l >= 1 && l <= 3) : g == 32 ? (l >= 1 && l <= 2) : g == 64 ? l == 1 : false;
+      CHECK(has_phi_fused(WL_P59, g, l) == want, "has_phi_fused(p59, %d, %d)", g, l);
+      CHECK(!has_phi_fused(WL_F64, g, l) && !has_phi_fused(WL_F48, g, l) && !has_phi_fused(WL_PLAIN, g, l), "has_phi_fused(other, %d, %d)", g, l);
+    }
+  for (int m : {SW_PLAIN, SW_LDS_F48, SW_F64}) for (int g : {4, 8, 16, 32, 64}) for (int r = 1; r <= 16; ++r) CHECK(!has_sums(m, g, r), "has_sums(%d, %d, %d)", m, g, r);
+  // the shapes of the benchmark's configurations and of the tests: K = 20, 50, 100, 200, plain and with the two bias columns
+  const uint32_t pins[] = {20, 22, 50, 52, 100, 102, 200, 202, 800};
+  for (uint32_t C : pins) {
+    Plan p;
+    CHECK(plan_shapes(C, 0, on, &p) == HPF_OK, "C=%u", C);
+    if (print_cases) printf("fs %u %d %d %d %d %d %d\n", C, p.wl, p.phiG, p.phiR, (int)fused_sweep(p, on, false), (int)fused_sweep(p, on, true), (int)fused_sweep(p, all, false));
+  }
+  { Plan p; CHECK(plan_shapes(100, 0, on, &p) == HPF_OK && p.phiG == 8 && p.phiR == 6 && fused_sweep(p, on, false), "K = 100: (8, 6), fused"); }
+  { Plan p; CHECK(plan_shapes(200, 0, on, &p) == HPF_OK && p.phiG == 16 && p.phiR == 6 && !fused_sweep(p, all, false), "K = 200: (16, 6) spills, unfused"); }
+  { Plan p; CHECK(plan_shapes(50, 0, on, &p) == HPF_OK && p.phiG == 4 && p.phiR == 6 && !fused_sweep(p, on, false) && fused_sweep(p, all, false), "K = 50: (4, 6) loses, unfused by default"); }
+}
+
 int main(int argc, char **argv)
 {
+  if (argc > 1 && !strcmp(argv[1], "fused-sweep")) {
+    fused_checks(true);
+    if (g_fail) { fprintf(stderr, "plan_selftest: %d checks failed\n", g_fail); return 1; }
+    return 0;
+  }
   if (argc > 1 && !strcmp(argv[1], "topn-grid")) {
     topn_checks(true);
     if (g_fail) { fprintf(stderr, "plan_selftest: %d checks failed\n", g_fail); return 1; }
@@ -403,6 +458,7 @@ int main(int argc, char **argv)
   }
   tile_checks(false);
   topn_checks(false);
+  fused_checks(false);
   if (g_fail) { fprintf(stderr, "plan_selftest: %d checks failed\n", g_fail); return 1; }
   printf("# plan_selftest ok: %u points, %u runs\n", points, runs);
   return 0;

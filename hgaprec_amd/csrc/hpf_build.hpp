@@ -486,6 +486,14 @@ __global__ __launch_bounds__(256) void slot_fill_kernel(const int64_t *segptr, u
   }
 }
 
+// rows whose ONE segment stores S itself (pslot < 0): the rows a pass with the fused sweep epilogue writes W for.  One bit
+// per row, OR-ed in (integers: order-free); `done` is zeroed before.
+__global__ __launch_bounds__(256) void mark_done_rows_kernel(const Seg *segs, uint32_t nseg, uint32_t *done)
+{
+  for (uint32_t s = blockIdx.x * blockDim.x + threadIdx.x; s < nseg; s += gridDim.x * blockDim.x)
+    if (segs[s].pslot < 0) atomicOr(&done[segs[s].row >> 5], 1u << (segs[s].row & 31u));
+}
+
 // ---------------------------------------------------------------------
 // dense [rows x cols] block  <->  columns [col0, col0 + cols) of a padded
 // [rows x ld] matrix, rows [r0, r0 + rows).  dense is contiguous.

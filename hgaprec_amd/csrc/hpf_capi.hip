@@ -85,6 +85,10 @@ struct Side {
   bool w_dirty = false;     // L was handed in by hpf_set_state: W must be derived from it
   bool l_stale = false;      // a sweep ran since L was last valid: rebuild L on export
   bool es_stale = false;     // S holds raw phi sums and E predates the last sweep
+  // fused sweep epilogue (hpf_plan::fused_sweep): this side's pass writes W of the rows that are one segment -- a bit per row in
+  // row_done, set with the work lists -- and its sweep is row_sums_kernel
+  bool fused = false;
+  uint32_t *row_done = nullptr;
 };
 
 }  // namespace
@@ -256,7 +260,7 @@ void free_side(Side &s, bool S_external)
   dfree(s.rate_set); dfree(s.prior_shape_set); dfree(s.prior_elog_set);
   dfree(s.segs); dfree(s.longrows); dfree(s.grouprows); dfree(s.hugerows);
   dfree(s.partial); dfree(s.partial2); dfree(s.idx); dfree(s.val);
-  dfree(s.p_idx); dfree(s.p_val); dfree(s.chunks);
+  dfree(s.p_idx); dfree(s.p_val); dfree(s.chunks); dfree(s.row_done);
   s = Side();
 }
 
@@ -306,6 +310,16 @@ bool launch_phipk(int G, int L, int side, const PhiArgs &a, const PhiLaunch &pl)
     } else return false;
   }); }); });
 }
+// the user pass with the fused sweep epilogue (hpf_plan::fused_sweep): p59 rows, side 0
+bool launch_phi_fused(int G, int L, const PhiArgs &a, const PhiLaunch &pl)
+{
+  return pick(G, Groups(), [&](auto g) { return pick(L, Counts(), [&](auto l) {
+    if constexpr (hpf_plan::has_phi_fused(WL_P59, PICKED(g), PICKED(l))) {
+      hipLaunchKernelGGL((phi_pass_fused_kernel<PICKED(g), PICKED(l), 0>), dim3(pl.blocks), dim3(pl.wg), 0, pl.st, a);
+      return true;
+    } else return false;
+  }); });
+}
 bool launch_phi_packed(int wl, int G, int L, int side, const PhiArgs &a, const PhiLaunch &pl)
 {
   switch (wl) {
@@ -338,6 +352,17 @@ bool launch_sweep(int mode, int G, int R, const SweepArgs &a, uint32_t blocks, h
         return true;
       } else if constexpr (unreachable_sweep(PICKED(m), PICKED(g), PICKED(r))) (void)&row_sweep_kernel<PICKED(g), PICKED(r), PICKED(m)>;
       return false;
+    }); }); });
+}
+// row_sums_kernel: the sweep after a pass with the fused epilogue
+bool launch_sums(int mode, int G, int R, const SweepArgs &a, uint32_t blocks, hipStream_t st)
+{
+  return pick(mode, std::integer_sequence<int, SW_LDS_P59, SW_REG_P59>(), [&](auto m) {
+    return pick(G, Groups(), [&](auto g) { return pick(R, Counts(), [&](auto r) {
+      if constexpr (hpf_plan::has_sums(PICKED(m), PICKED(g), PICKED(r))) {
+        hipLaunchKernelGGL((row_sums_kernel<PICKED(g), PICKED(r), PICKED(m)>), dim3(blocks), dim3(256), 0, st, a);
+        return true;
+      } else return false;
     }); }); });
 }
 // fold_in_kernel: R columns per lane (hpf_plan::fold_plan), four waves and their slices of LDS per workgroup
@@ -1003,6 +1028,25 @@ int build_tiled_side(hpf_handle *h, Side &s, const int64_t *ptr, uint32_t rows_o
   return rc;
 }
 
+// Which side runs the fused sweep epilogue (hpf_plan::fused_sweep) and, for it, the rows whose W the pass writes: those that
+// are ONE segment of the final work list, row-major or tiled.  Rows cut into several segments and rows without any keep the
+// full sweep body (row_sums_kernel).  Called whenever the lists or the layout of the rows have changed.
+int mark_fused_rows(hpf_handle *h)
+{
+  Side *sides[2] = {&h->u, &h->it};
+  for (Side *s : sides) {
+    dfree(s->row_done); s->row_done = nullptr;
+    s->fused = hpf_plan::fused_sweep(*h, *h, s == &h->it) && s->rows > 0 && s->nseg > 0;
+    if (!s->fused) continue;
+    int rc;
+    if ((rc = dalloc(h, &s->row_done, ((size_t)s->rows + 31) / 32))) return rc;      // zeroed
+    hipLaunchKernelGGL(mark_done_rows_kernel, dim3(grid_for(s->nseg)), dim3(256), 0, h->stream, s->segs, s->nseg, s->row_done);
+    if ((rc = check_launch(h, "mark_done_rows_kernel"))) return rc;
+  }
+  if (hipStreamSynchronize(h->stream) != hipSuccess) { h->err = "work-list build failed on the device"; return HPF_ERR_HIP; }
+  return HPF_OK;
+}
+
 // the tiled lists of both sides (after device_side_work); a tile is 4 MiB of the rows the pass gathers
 int build_work_lists_tiled(hpf_handle *h, uint64_t nnz)
 {
@@ -1011,7 +1055,8 @@ int build_work_lists_tiled(hpf_handle *h, uint64_t nnz)
   const size_t rowb = h->wl != WL_PLAIN ? (size_t)h->pk.row_bytes : (size_t)h->ld * (h->w32 ? 4 : 8);
   h->notes &= ~15u;
   if ((rc = build_tiled_side(h, h->u, h->rowptr_dev, m, nnz, rowb))) return rc;     // the user pass gathers item rows
-  return build_tiled_side(h, h->it, h->colptr_dev, n, nnz, rowb);
+  if ((rc = build_tiled_side(h, h->it, h->colptr_dev, n, nnz, rowb))) return rc;
+  return mark_fused_rows(h);
 }
 
 // Item-major view of the ratings, built in HBM: h->u.idx / h->u.val (CSR order)
@@ -1226,6 +1271,12 @@ PhiLaunch phi_setup(const hpf_handle *h, const Side &own, const Side &oth, bool 
   a.segs = own.segs; a.nseg = own.nseg; a.idx = own.pass_idx(); a.val = own.pass_val();
   a.W_own = own.W; a.W_oth = oth.W; a.S_own = sums ? own.S : nullptr; a.partial = sums ? own.partial : nullptr; a.flags = h->flags;
   a.chunks = own.chunks; a.ld = h->ld;
+  a.epi = PhiArgs::Epi();
+  if (sums && own.fused) {       // what this side's sweep reads (sweep_args; the user sweep's column sums are the item side's)
+    a.epi.W_out = own.W; a.epi.prior_E = own.prior_E; a.epi.colsum_oth = oth.colsum;
+    a.epi.s_prior = h->cfg.s_prior; a.epi.r_prior = h->cfg.r_prior; a.epi.rate_bias = h->cfg.r_prior + own.bias_rate_add;
+    a.epi.K = h->K; a.epi.hier = h->cfg.hier; a.epi.bias_col = own.bias_col; a.epi.junk_col = own.junk_col;
+  }
   const uint32_t wpb = rows_in_pieces(h) ? h->wg_of(own.chunks != nullptr) / 64 : 4;      // waves per workgroup
   const uint32_t blocks = own.chunks ? own.nchunk_blocks : std::min<uint32_t>((a.nseg + wpb - 1) / wpb, h->phi_blocks * (4 / wpb));
   return {blocks, wpb * 64, h->stream};
@@ -1237,7 +1288,8 @@ int run_phi(hpf_handle *h, Side &own, Side &oth, hipEvent_t after_kernel)
   PhiArgs a;
   const PhiLaunch pl = phi_setup(h, own, oth, true, a);
   if (a.nseg) {
-    const bool ok = rows_in_pieces(h) ? launch_phi_packed(h->wl, h->phiG, h->phiR, side, a, pl)
+    const bool ok = own.fused ? launch_phi_fused(h->phiG, h->phiR, a, pl)
+                  : rows_in_pieces(h) ? launch_phi_packed(h->wl, h->phiG, h->phiR, side, a, pl)
                                       : launch_phi(h->w32, h->phiG, h->phiR, h->phiV, side, a, pl);
     if (!ok) { h->err = "no phi kernel for this configuration"; return HPF_ERR_UNSUPPORTED; }
   } else if (side == 1) {
@@ -1271,6 +1323,7 @@ void sweep_args(hpf_handle *h, Side &s, SweepArgs &a)
   a.rows = s.rows; a.ld = h->ld; a.K = h->K;
   a.bias_col = s.bias_col; a.junk_col = s.junk_col; a.bias_rate_add = s.bias_rate_add;
   a.s_prior = h->cfg.s_prior; a.r_prior = h->cfg.r_prior; a.hier = h->cfg.hier;
+  a.row_done = s.row_done;
 }
 
 int run_sweep(hpf_handle *h, Side &s, const double *colsum_oth, double *colsum_out)
@@ -1280,7 +1333,9 @@ int run_sweep(hpf_handle *h, Side &s, const double *colsum_oth, double *colsum_o
   sweep_args(h, s, a);
   a.colsum_oth = colsum_oth;                 // the kernel also copies it to colsum_used: what the rate was built from (export of *_rate.tsv)
   s.l_stale = true; s.es_stale = true; s.w_from_sweep = true;
-  if (!launch_sweep(h->sw_mode, h->swG, h->swR, a, s.sweep_blocks, st)) {
+  // after a pass with the fused epilogue: the sums of the rows it wrote, the full body for the rest
+  if (!(s.fused ? launch_sums(h->sw_mode, h->swG, h->swR, a, s.sweep_blocks, st)
+                : launch_sweep(h->sw_mode, h->swG, h->swR, a, s.sweep_blocks, st))) {
     h->err = "no sweep kernel for this configuration"; return HPF_ERR_UNSUPPORTED;
   }
   if (h->cfg.hier && s.rows)                // xi / eta: E and Elog from the rate the sweep just wrote

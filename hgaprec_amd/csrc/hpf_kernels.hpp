@@ -139,6 +139,19 @@ struct PhiArgs {
   // walks one tile after another.  NULL: the waves stride over the whole list.
   const uint2    *chunks;
   uint32_t        ld;       // row stride of S_own / partial, columns (layouts whose rows do not fix it: codec_f64)
+  // Fused sweep epilogue (phi_pass_fused_kernel only): what the row sweep of the owner side reads to write W.
+  // A row that is ONE segment has its finished sums in registers at the segment's end; the pass then writes W_own[row] itself
+  // and the sweep that follows only takes that row's sums (row_sums_kernel).  flags[0] bit 3: the epilogue met an element the
+  // p59 rows cannot hold -- PENDING, so that workgroups of the same launch that start later do not skip; the sums kernel
+  // turns it into bit 1 at its entry.
+  struct Epi {
+    void         *W_out;       // = W_own, writable: the only reader of W_own[row] in this launch is the segment's own load
+    const double *prior_E;     // [rows_own] (hier)
+    const double *colsum_oth;  // [ld]
+    double        s_prior, r_prior, rate_bias;
+    uint32_t      K, hier;
+    int32_t       bias_col, junk_col;
+  } epi;
 };
 
 // Entry of every phi-pass kernel.  A sweep that could not store an element in the packed rows raises bit 1;
@@ -553,9 +566,17 @@ __device__ __forceinline__ void phi_batch_packed(const uint32_t (&x)[4 * LT], co
 // lane), the gathered rows in OthC's (LT pieces).  E = OwnC::E element slots are worked on (OthC::E >= E; the
 // library only instantiates OwnC = OthC -- the two-layout form is what the fp64-shadow experiment of round 4
 // ran on, profiles/r04/experiments.md 1).  W_own / W_oth already point at this lane's first piece.
-template <class OwnC, class OthC, int G, int LO, int LT>
+// FUSE (the owner's rows are p59): a segment that is its whole row also writes W_own[row] -- the row sweep's psi / exp / row
+// maximum / packing, by the sweep's own device functions on the totals the lanes hold after the reduce-scatter (the same
+// bits).  pkbuf: this wave's row of LDS (G * LO * 4 dwords), cso: the other side's column sums in LDS (zeros from K on).
+struct PsiRate { double xs, corr, ri; };
+__device__ __forceinline__ PsiRate psi_parts_rate(double x, double rt);
+__device__ __forceinline__ double exp_neg(double c);
+
+template <class OwnC, class OthC, int G, int LO, int LT, bool FUSE = false>
 __device__ __forceinline__ void phi_segments(const PhiArgs &a, const SegRange &sr, const unsigned char *W_own,
-                                             const unsigned char *W_oth, int lane, bool &underflow)
+                                             const unsigned char *W_oth, int lane, bool &underflow,
+                                             uint32_t *pkbuf = nullptr, const double *cso = nullptr)
 {
   constexpr int NG = 64 / G;
   constexpr int E = OwnC::E;
@@ -677,6 +698,50 @@ __device__ __forceinline__ void phi_segments(const PhiArgs &a, const SegRange &s
         const uint32_t e = o + (uint32_t)j;
         if ((uint32_t)j < n && (OwnC::fixed_ld || e * G + (uint32_t)g < LD)) dst[(size_t)e * G] = own[j] * acc[j];
       }
+      if constexpr (FUSE) {
+        static_assert(OwnC::fixed_ld && LO == LT, "the epilogue writes p59 rows");
+        if (sg.pslot < 0) {                                   // wave-uniform: the row is this one segment
+          const PhiArgs::Epi &ep = a.epi;
+          const PackedRow pk = {(uint32_t)G, (uint32_t)E, (uint32_t)LO, (uint32_t)(G * LO * 16), (uint32_t)__builtin_ctz(G)};
+          const double pr = ep.hier ? ep.prior_E[sg.row] : ep.r_prior;
+          // Columns, LDS addresses and masks below depend on the lane alone: left to itself the compiler computes them once
+          // in front of the segment loop and carries them through the batch loop -- in scratch, the registers being taken.
+          // Behind these two empty statements they are a dozen integer instructions per row instead.
+          uint32_t eo = o, en = n, el = (uint32_t)lane;
+          asm volatile("" : "+v"(eo), "+v"(en), "+v"(el));
+          const uint32_t eg = el % (uint32_t)G;
+          double wl[NF], wmax = 0.0;
+#pragma unroll
+          for (int j = 0; j < NF; ++j) {
+            const uint32_t c = (eo + (uint32_t)j) * G + eg;
+            const bool live = (uint32_t)j < en, fac = c < ep.K;
+            double sv = own[j] * acc[j];                      // what went to S: a value of its own, never one factor of an fma
+            asm volatile("" : "+v"(sv));
+            const double sh = fmax(ep.s_prior + sv, 1e-30);
+            double rt = pr + cso[live ? c : 0u];
+            rt = fmax(fac ? rt : ep.rate_bias, 1e-30);
+            const PsiRate ps = psi_parts_rate(sh, rt);
+            double w = ps.xs * exp_neg(ps.corr) * ps.ri;
+            w = (fac || (int32_t)c == ep.bias_col) ? w : ((int32_t)c == ep.junk_col ? 1.0 : 0.0);
+            wl[j] = live ? w : 0.0;
+            wmax = fmax(wmax, wl[j]);
+          }
+          wmax = group_max<64>(wmax);
+          const double inv = (wmax > 0.0) ? fast_rcp(wmax) : 0.0;
+          bool fl = false;
+          packed_clear(pkbuf, pk, el, 64u);
+          __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+          __builtin_amdgcn_wave_barrier();
+#pragma unroll
+          for (int j = 0; j < NF; ++j)
+            if ((uint32_t)j < en) fl |= p59_put(pkbuf, pk, (eo + (uint32_t)j) * G + eg, wl[j] * inv);
+          __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+          __builtin_amdgcn_wave_barrier();
+          packed_copy_out(pkbuf, ep.W_out, sg.row, pk, el, 64u);
+          __builtin_amdgcn_wave_barrier();                    // the next row's clear stays behind this copy
+          if (__any(fl) && el == 0u) atomicOr(a.flags, 8u);
+        }
+      }
     }
 #else
 #pragma unroll
@@ -697,17 +762,33 @@ __device__ __forceinline__ void phi_segments(const PhiArgs &a, const SegRange &s
 // that takes waves away: 3 -> 2 waves cost 7-18 %, every build that spills inside the batch loop loses far more (a scratch
 // reload waits behind every gather in flight), and none reaches the one below (profiles/r06/experiments.md 2, 3;
 // pass_builds_prototype.diff keeps the code).
-template <template <int> class CodecT, int G, int L, int SIDE>
-__global__ __launch_bounds__(256, 3) void phi_pass_packed_kernel(PhiArgs a)
+template <template <int> class CodecT, int G, int L, int SIDE, bool FUSE>
+__device__ __forceinline__ void phi_pass_packed_body(const PhiArgs &a)
 {
+  constexpr int LDC = G * CodecT<L>::E;
+  __shared__ uint32_t pkbuf[FUSE ? 4 * G * L * 4 : 1];     // a packed row per wave (the epilogue builds W_own[row] in it)
+  __shared__ double cso[FUSE ? LDC : 1];                   // the other side's column sums
   if (phi_pass_skips(a, SIDE)) return;
   const int lane = threadIdx.x & 63;
+  if constexpr (FUSE) {
+    for (uint32_t c = threadIdx.x; c < (uint32_t)LDC; c += blockDim.x) cso[c] = c < a.epi.K ? a.epi.colsum_oth[c] : 0.0;
+    __syncthreads();
+  }
   const SegRange sr = seg_range(a);
   bool underflow = false;
-  phi_segments<CodecT<L>, CodecT<L>, G, L, L>(a, sr, (const unsigned char *)a.W_own + (size_t)(lane % G) * 16,
-                                              (const unsigned char *)a.W_oth + (size_t)(lane % G) * 16, lane, underflow);
+  phi_segments<CodecT<L>, CodecT<L>, G, L, L, FUSE>(a, sr, (const unsigned char *)a.W_own + (size_t)(lane % G) * 16,
+                                                    (const unsigned char *)a.W_oth + (size_t)(lane % G) * 16, lane, underflow,
+                                                    FUSE ? pkbuf + (threadIdx.x >> 6) * (G * L * 4) : nullptr, FUSE ? cso : nullptr);
   if (__any(underflow) && lane == 0) atomicOr(a.flags, 1u);
 }
+
+template <template <int> class CodecT, int G, int L, int SIDE>
+__global__ __launch_bounds__(256, 3) void phi_pass_packed_kernel(PhiArgs a) { phi_pass_packed_body<CodecT, G, L, SIDE, false>(a); }
+
+// the pass over p59 rows with the fused sweep epilogue (phi_segments, FUSE).  SIDE stays the LAST template argument: the
+// benchmark's counter passes tell the two passes apart by it
+template <int G, int L, int SIDE>
+__global__ __launch_bounds__(256, 3) void phi_pass_fused_kernel(PhiArgs a) { phi_pass_packed_body<codec_p59, G, L, SIDE, true>(a); }
 
 // ---------------------------------------------------------------------
 // Measurement only (hpf_gather_only): a phi pass with the arithmetic taken out.  Same work
@@ -949,21 +1030,37 @@ __device__ __forceinline__ PsiParts psi_parts(double x)
 //     ri                          relative error <= 2.2 u                                      (asserted: 4 u)
 //     W = xs exp_neg(corr) ri     against exp(psi(x)) / rt, relative error / (u (16 corr + 10)), per band of x:
 //                                 [1e-30, 0.3) 0.31    [0.3, 10) 0.31    [10, 1e3) 0.39    [1e3, 1e300] 0.31   (asserted: 1)
-struct PsiRate { double xs, corr, ri; };
-
-__device__ __forceinline__ PsiRate psi_parts_rate(double x, double rt)
+// The shared reciprocal: r = 1 / (pp * xs * rt) with pp = P(x) (1 where x >= 10) and xs the shifted x.  Both the full sweep
+// (psi_parts_rate) and the sums-only one (rate_rcp) take 1 / rt = r * pq from it: one instruction sequence, the same bits.
+struct RateRcpParts { bool small; double pp, xs, pq, r, dp; };
+__device__ __forceinline__ RateRcpParts rate_rcp_parts(double x, double rt)
 {
-  const bool small = x < 10.0;
+  RateRcpParts q;
+  q.small = x < 10.0;
   const double t = x * (x + 9.0);
   double p = t, dp = 1.0;
   const double cj[4] = {8.0, 14.0, 18.0, 20.0};
 #pragma unroll
   for (int j = 0; j < 4; ++j) { const double f = t + cj[j]; dp = fma(dp, f, p); p *= f; }
-  dp *= fma(2.0, x, 9.0);
-  const double pp = small ? p : 1.0;
-  const double xs = small ? x + 10.0 : x;
-  const double pq = pp * xs;
-  const double r = fast_rcp(pq * rt);
+  q.dp = dp * fma(2.0, x, 9.0);
+  q.pp = q.small ? p : 1.0;
+  q.xs = q.small ? x + 10.0 : x;
+  q.pq = q.pp * q.xs;
+  q.r = fast_rcp(q.pq * rt);
+  return q;
+}
+// 1 / rt alone: what psi_parts_rate returns as ri (the dp chain is dead code here)
+__device__ __forceinline__ double rate_rcp(double x, double rt)
+{
+  const RateRcpParts q = rate_rcp_parts(x, rt);
+  return q.r * q.pq;
+}
+
+__device__ __forceinline__ PsiRate psi_parts_rate(double x, double rt)
+{
+  const RateRcpParts q = rate_rcp_parts(x, rt);
+  const bool small = q.small;
+  const double dp = q.dp, pp = q.pp, xs = q.xs, pq = q.pq, r = q.r;
   PsiRate o;
   o.ri = r * pq;
   const double ipq = r * rt;                    // 1 / (pp * xs)
@@ -1063,6 +1160,7 @@ struct SweepArgs {
   double        bias_rate_add;  // n_other_total for the bias column
   double        s_prior, r_prior;
   uint32_t      hier;
+  const uint32_t *row_done; // row_sums_kernel: bit r % 32 of word r / 32 = the pass before it wrote W[r] (its fused epilogue)
 };
 
 // how a sweep writes the rows of W
@@ -1104,15 +1202,22 @@ __device__ __forceinline__ void p59_place(uint32_t (&D)[4 * L], int e, uint32_t 
 // MODE = SW_PLAIN: W is stored as double (or float, a.w32) and the row stride IS G*R (hpf_create): no column test.
 // Rows in pieces (every other mode): the stride a.ld = G_phi * E may be smaller than G*R; the slots from tb on then
 // also hold columns past the end of the row, whose loads and stores are masked.
-template <int G, int R, int MODE>
-__global__ __launch_bounds__(256) void row_sweep_kernel(SweepArgs a)
+// SUMS (row_sums_kernel): the sweep after a pass with the fused epilogue.  Same grid, same group -> rows mapping, same csum /
+// rsum / red[] / colsum_part order; a wave whose rows ALL had their W written by the pass (a.row_done) computes only
+// ri and e = sh * ri for them -- no series, no exp, no packing, no store to W -- and every other wave runs the full body.
+template <int G, int R, int MODE, bool SUMS>
+__device__ __forceinline__ void row_sweep_rows(const SweepArgs &a)
 {
   constexpr bool PIECES = MODE != SW_PLAIN;
   constexpr bool LDSPK = MODE == SW_LDS_F48 || MODE == SW_LDS_P59;
   const uint32_t LD = PIECES ? a.ld : (uint32_t)(G * R);
   __shared__ uint32_t pkbuf[LDSPK ? 512 * R : 1];  // 256/G groups x (<= 2*G*R dwords of packed row)
   __shared__ double red[4][G * R];       // per-wave column partials
-  if (a.flags[0] & 4u) return;           // a pass has found W unusable (phi_pass_skips): nothing runs until the host has dealt with it
+  const uint32_t fl0 = a.flags[0];
+  if (fl0 & 4u) return;                  // a pass has found W unusable (phi_pass_skips): nothing runs until the host has dealt with it
+  if constexpr (SUMS) {                  // the epilogue's pending bit becomes bit 1 here: no workgroup of that pass is left to skip
+    if ((fl0 & 8u) && blockIdx.x == 0 && threadIdx.x == 0) atomicOr(a.flags, 2u);
+  }
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const int g = lane % G, q = lane / G;
   const uint32_t K = a.K;
@@ -1150,11 +1255,14 @@ __global__ __launch_bounds__(256) void row_sweep_kernel(SweepArgs a)
 #if HPF_SWEEP_PIPE == 2
   double sn2[R]; double pr2 = a.r_prior;
 #endif
+  // SUMS: the done bits of the wave's 64 / G consecutive rows (one word: the run is aligned to its own length), fetched with the row
+  uint32_t dnn = 0u;
   auto fetch_row = [&](uint32_t r_, double (&dst)[R], double &pdst) {
     if (r_ < a.rows) {
 #pragma unroll
       for (int t = 0; t < R; ++t) dst[t] = (!PIECES || (uint32_t)(g + G * t) < LD) ? a.S[(size_t)r_ * LD + g + G * t] : 0.0;
       if (hier) pdst = a.prior_E[r_];
+      if constexpr (SUMS) dnn = a.row_done[(r_ - (uint32_t)q) >> 5];
     }
   };
   fetch_row(grp, snx, prn);
@@ -1167,6 +1275,7 @@ __global__ __launch_bounds__(256) void row_sweep_kernel(SweepArgs a)
 #pragma unroll
     for (int t = 0; t < R; ++t) w[t] = snx[t];
     const double pr = prn;
+    const uint32_t dn = dnn;
 #if HPF_SWEEP_PIPE == 2
 #pragma unroll
     for (int t = 0; t < R; ++t) snx[t] = sn2[t];
@@ -1175,6 +1284,30 @@ __global__ __launch_bounds__(256) void row_sweep_kernel(SweepArgs a)
 #else
     fetch_row(row + ngrp, snx, prn);
 #endif
+    if constexpr (SUMS) {
+      constexpr uint32_t NR = 64 / G;                          // rows of a wave
+      const uint32_t r0 = row - (uint32_t)q, left = a.rows - r0;
+      const uint32_t need = (1u << (left < NR ? left : NR)) - 1u;
+      if (__builtin_amdgcn_readfirstlane((int)(((dn >> (r0 & 31u)) & need) == need))) {
+        double rs = 0.0;
+#pragma unroll
+        for (int t = 0; t < R; ++t) {
+          const bool mixed = (uint32_t)t >= tb;
+          const uint32_t c = g + G * t;
+          const double sh = fmax(s_prior + w[t], 1e-30);
+          double rt = pr + cso[t];
+          if (mixed) { asm volatile(""); rt = (c < K) ? rt : rate_bias; }
+          rt = fmax(rt, 1e-30);
+          const double ri = rate_rcp(sh, rt);
+          double e = sh * ri;
+          if (mixed) { asm volatile(""); e = (c < K) ? e : 0.0; }
+          rs += e; csum[t] += e;
+        }
+        rs = group_sum<G>(rs);
+        if (hier && g == 0) a.prior_rate[row] = a.r_prior + rs;
+        continue;
+      }
+    }
     double wmax = 0.0, rsum = 0.0;
 #pragma unroll
     for (int t = 0; t < R; ++t) {
@@ -1292,6 +1425,12 @@ __global__ __launch_bounds__(256) void row_sweep_kernel(SweepArgs a)
   for (uint32_t c = threadIdx.x; c < LD; c += blockDim.x)
     a.colsum_part[(size_t)blockIdx.x * LD + c] = (c < K) ? red[0][c] + red[1][c] + red[2][c] + red[3][c] : 0.0;
 }
+
+template <int G, int R, int MODE>
+__global__ __launch_bounds__(256) void row_sweep_kernel(SweepArgs a) { row_sweep_rows<G, R, MODE, false>(a); }
+
+template <int G, int R, int MODE>
+__global__ __launch_bounds__(256) void row_sums_kernel(SweepArgs a) { row_sweep_rows<G, R, MODE, true>(a); }
 
 // xi / eta after a sweep (hier): remember what the rate just used (export, ELBO), then
 //   E = (s0 + K s0) / rate ,  Elog = psi(s0 + K s0) - log(rate)        gpbase.hh:877-925

@@ -59,6 +59,11 @@ struct Knobs {
   uint32_t phi_wg = 0;
   long long loo_batch = 0;          // HPF_LOO_BATCH: at most so many users per batch of the fused rank calls (<= 0: no limit of its own)
   int fold_route = 0;               // HPF_FOLD_ROUTE=sweeps: hpf_fold_in through the training kernels (1), for A/B runs; never chosen by the library
+  // HPF_FUSED_SWEEP=0|1|2: the user pass writes W of its single-segment rows in its segment epilogue and the user sweep only
+  // takes their sums (fused_sweep below).  0: never (the A/B switch), 1: where it was measured to pay (fused_pays), 2: wherever
+  // an instance exists (tests, A/B runs of the other shapes).  Every route gives the same bits in every array, so the variable
+  // is read outside the gate.
+  int fused_sweep = 1;
 };
 
 // the one place that reads the knobs from the environment
@@ -66,6 +71,7 @@ inline Knobs read_knobs()
 {
   Knobs k;
   if (const char *e = getenv("HPF_LOO_BATCH")) k.loo_batch = atoll(e);      // outside the gate: the batch size cannot change a result
+  if (const char *e = getenv("HPF_FUSED_SWEEP")) { int v = atoi(e); if (v >= 0 && v <= 2) k.fused_sweep = v; }   // likewise: which kernel writes a row of W cannot
   const char *x = getenv("HPF_EXPERIMENTAL");
   if (!x || atoi(x) != 1) return k;
   if (const char *e = getenv("HPF_H2D")) k.xfer_mode = !strcmp(e, "plain") ? 0 : !strcmp(e, "register") ? 2 : 1;
@@ -99,6 +105,17 @@ constexpr bool has_phi(bool w32, int G, int R, int V) { return is_group(G) && R 
 // phi_pass_packed_kernel: G lanes per nonzero, L 16-byte pieces per lane; nine pieces of plain doubles stand in for p59
 // rows of 17 elements
 constexpr bool has_phi_packed(int wl, int G, int L) { return (wl == WL_P59 || wl == WL_F48 || wl == WL_F64) && is_group(G) && L >= 1 && (L <= 8 || (wl == WL_F64 && L == 9)); }
+// phi_pass_fused_kernel (the packed pass with the sweep epilogue): the p59 shapes whose build keeps the pass's three waves per SIMD
+// (<= 168 VGPRs) WITHOUT scratch and without SGPRs spilled into VGPR lanes -- the compiler's figures decide
+// (-Rpass-analysis=kernel-resource-usage; profiles/r10/experiments.md 1 lists every candidate).  The shapes left out spill
+// (K = 200's (16, 6): 40 bytes per lane) or lose the LDS promotion of their gather registers to the staged row ((16, 4),
+// (32, 4): 80 bytes of scratch inside the batch loop).  A row per wave of the workgroup is staged in LDS: <= 6 KiB, + the
+// column sums: the pass keeps its twelve waves per CU.
+constexpr bool has_phi_fused(int wl, int G, int L)
+{
+  return wl == WL_P59 && has_phi_packed(wl, G, L) &&
+         ((G <= 8 && L <= 6) || (G == 16 && L <= 3) || (G == 32 && L <= 2) || (G == 64 && L == 1));
+}
 // gather_only_kernel: the loads of a pass over rows of 16-byte pieces (plain rows of doubles read in pairs are such rows)
 constexpr bool has_gather_only(int G, int L) { return is_group(G) && L >= 1 && L <= 9; }
 // row_sweep_kernel: G lanes per row with R columns each
@@ -115,6 +132,9 @@ constexpr bool has_sweep(int mode, int G, int R)
   }
   return false;
 }
+
+// row_sums_kernel: the sweep that follows such a pass -- the modes that write p59 rows
+constexpr bool has_sums(int mode, int G, int R) { return (mode == SW_REG_P59 || mode == SW_LDS_P59) && has_sweep(mode, G, R); }
 
 // loo_rank_kernel / rank_queries_kernel: NCH chunks of 32 columns of the A fragments in registers, 0 = re-read per step
 constexpr bool has_rank_chunks(int NCH) { return NCH == 0 || NCH == 1 || NCH == 2 || NCH == 4; }
@@ -546,6 +566,22 @@ inline int plan_shapes(uint32_t C, uint32_t w_storage, const Knobs &kn, Plan *ou
   }
   *out = p;
   return HPF_OK;
+}
+
+// ---- the fused sweep epilogue: which (side, layout, shape) runs it --------------------------------------------------------
+// The USER side of a handle whose rows are p59 (a handle that has fallen back to plain doubles, or was created with them,
+// runs the two kernels apart: the W-only repeat of recover_flush and w_storage = 3 must stay one arithmetic).  The item side
+// stays unfused: its single-segment rows are worth at most 0.05 ms of C2's 8.2 and its pass is the one at the HBM limit.
+// Among the shapes with an instance the library takes the fused route only where it was measured against the unfused build
+// (profiles/r10/experiments.md 3): (8, 6) -- 81..104 columns, K = 100 -- gains 0.12-0.15 ms of C2's 8.2 and is level on a C3
+// shard; (4, 6) -- K = 50, a C5 shard -- LOSES 3.7 % (its pass already carries unhidden arithmetic: the epilogue's ~90 fp64
+// instructions per element weigh twice as much against rows half as long) and stays unfused; the other shapes have not been
+// measured and stay unfused until they are.
+constexpr bool fused_pays(int G, int L) { return G == 8 && L == 6; }
+inline bool fused_sweep(const Plan &p, const Knobs &kn, bool item_side)
+{
+  return kn.fused_sweep != 0 && !item_side && has_phi_fused(p.wl, p.phiG, p.phiR) && has_sums(p.sw_mode, p.swG, p.swR) &&
+         (kn.fused_sweep == 2 || fused_pays(p.phiG, p.phiR));
 }
 
 }  // namespace hpf_plan
