@@ -18,6 +18,7 @@
 // Then the fused sweep epilogue (fused_checks) and, run as `plan_selftest_asan fused-sweep`, a line per pinned column count
 //   fs C w_layout phi_G phi_R fused_user fused_item fused_user_under_knob_2
 // which tests/test_fused_sweep_plan.py compares with its own list.
+// Then the call order of an iteration's steps (phase_checks): every (phase, step) pair of next_phase.
 #include "../hpf_plan.hpp"
 
 #include <string>
@@ -323,6 +324,34 @@ static void fused_checks(bool print_cases)
   { Plan p; CHECK(plan_shapes(50, 0, on, &p) == HPF_OK && p.phiG == 4 && p.phiR == 6 && !fused_sweep(p, on, false) && fused_sweep(p, all, false), "K = 50: (4, 6) loses, unfused by default"); }
 }
 
+// The call order of an iteration's steps (next_phase): every (phase, step) pair against the rule the header states -- the
+// items pass from anywhere, every other step after its predecessor only -- and the three cuts of an iteration the exported
+// calls compose, each from idle back to idle.
+static void phase_checks()
+{
+  for (int phase = -2; phase <= 6; ++phase)
+    for (int s = -1; s <= 4; ++s) {
+      const bool in_range = phase >= 0 && phase <= 3 && s >= 0 && s <= 3;
+      const int want = !in_range ? -1 : s == ITEMS_PASS ? 1 : s == phase ? (phase + 1) % 4 : -1;
+      CHECK(next_phase(phase, (Step)s) == want, "next_phase(%d, %d) = %d, not %d", phase, s, next_phase(phase, (Step)s), want);
+    }
+  // the exported calls as the steps they compose, and a sequence of calls walked from a phase (-1 once a call is refused)
+  using Call = std::vector<Step>;
+  const Call items = {ITEMS_PASS}, phi = {ITEMS_PASS, USERS_PASS}, sweep = {USERS_SWEEP}, users = {USERS_PASS, USERS_SWEEP},
+             local = {ITEMS_PASS, USERS_PASS, USERS_SWEEP}, global = {ITEMS_SWEEP};
+  const auto walk = [](int phase, std::initializer_list<Call> calls) {
+    for (const Call &call : calls) for (Step s : call) if (phase >= 0) phase = next_phase(phase, s);
+    return phase;
+  };
+  CHECK(walk(0, {items, users, global}) == 0 && walk(0, {phi, sweep, global}) == 0 && walk(0, {local, global}) == 0, "the three cuts of an iteration");
+  CHECK(walk(0, {items}) == 1 && walk(0, {phi}) == 2 && walk(0, {items, users}) == 3 && walk(0, {local}) == 3, "the phases on the way");
+  // what tests/test_gpu_parity.py::test_iteration_pieces_and_their_call_order expects to be refused
+  CHECK(walk(0, {global}) == -1 && walk(0, {users}) == -1 && walk(0, {sweep}) == -1, "an iteration begins with its items pass");
+  CHECK(walk(0, {items, sweep}) == -1 && walk(0, {items, users, users}) == -1 && walk(0, {items, global}) == -1 &&
+        walk(0, {phi, global}) == -1 && walk(0, {phi, users}) == -1 && walk(0, {local, sweep}) == -1, "a step out of turn");
+  for (int phase = 0; phase <= 3; ++phase) CHECK(walk(phase, {local, global}) == 0, "an iteration begun again in phase %d", phase);
+}
+
 int main(int argc, char **argv)
 {
   if (argc > 1 && !strcmp(argv[1], "fused-sweep")) {
@@ -459,6 +488,7 @@ int main(int argc, char **argv)
   tile_checks(false);
   topn_checks(false);
   fused_checks(false);
+  phase_checks();
   if (g_fail) { fprintf(stderr, "plan_selftest: %d checks failed\n", g_fail); return 1; }
   printf("# plan_selftest ok: %u points, %u runs\n", points, runs);
   return 0;

@@ -151,8 +151,8 @@ struct hpf_handle : Plan, Knobs {
   // pass | the user pass + the user sweep | the item sweep -- replayed by hpf_iterate_local_items, hpf_iterate_local_users and
   // hpf_iterate_global (and so by hpf_iterate with a communicator) around whatever exchange the caller or the library runs
   hipGraphExec_t split_exec[3] = {nullptr, nullptr, nullptr};
-  bool capturing = false;               // inside stream capture: no events, no counters
-  int phase = 0;                        // 0 idle | 1 items pass done | 2 users pass done | 3 user sweep done; as graph replays: 4 item piece done | 5 user piece done
+  int phase = 0;                        // 0 idle | 1 items pass done | 2 users pass done | 3 user sweep done (hpf_plan::next_phase)
+  bool replaying = false;               // the iteration in flight runs its pieces as graph replays: set by its item step, cleared by its item sweep
   bool ring_graphed[RING] = {};         // slot was a graph replay: only events 0 and 6 exist
   // held-out sets bound once (hpf_heldout_bind): indices and ratings on the device, the per-pair values in a kept
   // page-locked buffer the DMA writes directly
@@ -397,7 +397,7 @@ int recover_flush(hpf_handle *h, uint32_t fl0, uint32_t begun);
 // loop comes through here (or through check_flags) before it touches S, E or W.
 int recover_if_flushed(hpf_handle *h)
 {
-  if (h->in_recovery || h->capturing) return HPF_OK;
+  if (h->in_recovery) return HPF_OK;
   uint32_t f[2] = {0, 0};
   HIPCHK(h, hipMemcpyAsync(f, h->flags, 8, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -1228,7 +1228,7 @@ int prepare_derived(hpf_handle *h)
                          h->wl != WL_PLAIN ? (uint32_t)h->wl : (uint32_t)h->w32,
                          s->rows, h->ld, h->K, s->bias_col, s->junk_col, packed_row(h->pk), h->flags);
     }
-    if (!derived || h->wl != WL_P59 || h->capturing) break;
+    if (!derived || h->wl != WL_P59) break;
     // an Elog spread above 88 inside a row: p59 cannot hold the state -- plain rows then, derived again (recover_flush)
     uint32_t f[2] = {0, 0};
     HIPCHK(h, hipMemcpyAsync(f, h->flags, 8, hipMemcpyDeviceToHost, h->stream));
@@ -1281,7 +1281,8 @@ PhiLaunch phi_setup(const hpf_handle *h, const Side &own, const Side &oth, bool 
   const uint32_t blocks = own.chunks ? own.nchunk_blocks : std::min<uint32_t>((a.nseg + wpb - 1) / wpb, h->phi_blocks * (4 / wpb));
   return {blocks, wpb * 64, h->stream};
 }
-int run_phi(hpf_handle *h, Side &own, Side &oth, hipEvent_t after_kernel)
+// after_kernel: recorded between the pass and its combines; null = not recorded (under capture, fold_sweeps)
+int run_phi(hpf_handle *h, const Side &own, const Side &oth, hipEvent_t after_kernel)
 {
   const int side = &own == &h->it ? 1 : 0;
   hipStream_t st = h->stream;
@@ -1298,7 +1299,7 @@ int run_phi(hpf_handle *h, Side &own, Side &oth, hipEvent_t after_kernel)
     hipLaunchKernelGGL(phi_open_kernel, dim3(1), dim3(64), 0, st, e);
   }
   // the event separates the phi kernel from the combine that follows it
-  if (!h->capturing) HIPCHK(h, hipEventRecord(after_kernel, st));
+  if (after_kernel) HIPCHK(h, hipEventRecord(after_kernel, st));
   auto combine = [&](const LongRow *rows, uint32_t nrows, const double *src, double *dst) {
     hipLaunchKernelGGL(combine_partials_kernel, dim3(std::min<uint32_t>((nrows + 3) / 4, 16384)), dim3(256), 0, st,
                        rows, nrows, src, dst, h->ld, h->flags);
@@ -1313,7 +1314,7 @@ int run_phi(hpf_handle *h, Side &own, Side &oth, hipEvent_t after_kernel)
 }
 
 // how the sweep of this handle writes W, and the arguments that do not change from launch to launch
-void sweep_args(hpf_handle *h, Side &s, SweepArgs &a)
+void sweep_args(const hpf_handle *h, const Side &s, SweepArgs &a)
 {
   a.S = s.S; a.W = s.W; a.w32 = h->w32;
   a.pk = packed_row(h->pk); a.flags = h->flags;
@@ -1326,13 +1327,12 @@ void sweep_args(hpf_handle *h, Side &s, SweepArgs &a)
   a.row_done = s.row_done;
 }
 
-int run_sweep(hpf_handle *h, Side &s, const double *colsum_oth, double *colsum_out)
+int run_sweep(hpf_handle *h, const Side &s, const double *colsum_oth, double *colsum_out)
 {
   hipStream_t st = h->stream;
   SweepArgs a;
   sweep_args(h, s, a);
   a.colsum_oth = colsum_oth;                 // the kernel also copies it to colsum_used: what the rate was built from (export of *_rate.tsv)
-  s.l_stale = true; s.es_stale = true; s.w_from_sweep = true;
   // after a pass with the fused epilogue: the sums of the rows it wrote, the full body for the rest
   if (!(s.fused ? launch_sums(h->sw_mode, h->swG, h->swR, a, s.sweep_blocks, st)
                 : launch_sweep(h->sw_mode, h->swG, h->swR, a, s.sweep_blocks, st))) {
@@ -1347,40 +1347,111 @@ int run_sweep(hpf_handle *h, Side &s, const double *colsum_oth, double *colsum_o
   return check_launch(h, "row sweep");
 }
 
-// Step A is two independent gather passes over the same W_theta / W_beta: the
-// item-major one (beta shape sums, straight into the exchange buffer) runs
-// first so that, with several ranks, its all-reduce can overlap the whole
-// user-side half of the iteration.
-// events: 0 start | 1 phi_item kernel done | 2 its combine done |
-//         3 phi_user kernel done | 4 its combine done | 5 user sweep | 6 item sweep
-//         7 start of the replicated half (after whatever exchange the stream waited for)
-bool want_graph(const hpf_handle *h);
+// ---- one iteration: four steps, launched, captured and replayed alike ----------------------------------------------------
+// The steps (hpf_plan::Step) in stream order, and the events of the ring slot each of them records (event 0, the start of
+// the iteration, is begin_iteration's):
+//   ITEMS_PASS   step A, item-major: beta shape sums, straight into the exchange buffer.  The two gather passes over the
+//                same W_theta / W_beta are independent; this one runs first so that, with several ranks, its all-reduce
+//                can overlap the whole user-side half of the iteration.      1 phi_item kernel done | 2 its combine done
+//   USERS_PASS   step A, user-major: theta shape sums.                       3 phi_user kernel done | 4 its combine done
+//   USERS_SWEEP  steps B (+D user, E): the theta rate uses c = sum_i E[beta]; emits d = sum_u E[theta] into the tail of
+//                the exchange buffer.  Does not touch the item part of the exchange buffer, so its all-reduce may already
+//                be running.  Carries the -novb copy of the old column sums.                               5 user sweep
+//   ITEMS_SWEEP  steps C (+D item, F): the beta rate uses d (all-reduced when n_ranks > 1).
+//                7 start of the replicated half (after whatever exchange the stream waited for) | 6 item sweep
+// enqueue_step puts a step's kernels on the stream and writes no field of the handle or of a Side, so one body serves the
+// eager launch and the capture.  step_done keeps the books of a step that IS on the stream, however it got there -- never
+// under capture.  run_steps checks the call order (hpf_plan::next_phase) and does both for consecutive steps; handed an
+// executable it replays that instead of launching, and the events inside the replayed piece coincide (a piece's time then
+// sits in its first field).  A whole-iteration replay (replay_iteration) has events 0 and 6 only: ring_graphed.
+using hpf_plan::Step;
 void drop_graph(hpf_handle *h);
-int sweep_users(hpf_handle *h);
-int iterate_global(hpf_handle *h);
 
-// the three pieces of a sharded iteration, each captured once (the kernels' arguments stay fixed until the CSR, the rows' layout
-// or the exchange buffer change: drop_graph there).  Piece 1 carries the -novb copy of the old column sums like the eager path.
-int build_split_graphs(hpf_handle *h)
+// events: the ring slot to record into, null under capture
+int enqueue_step(hpf_handle *h, Step step, hipEvent_t *ev)
 {
-  for (int k = 0; k < 3; ++k) {
-    hipGraph_t g = nullptr;
-    HIPCHK(h, hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal));
-    h->capturing = true;
-    int rc = k == 0 ? run_phi(h, h->it, h->u, nullptr) : k == 1 ? run_phi(h, h->u, h->it, nullptr) : iterate_global(h);
-    if (!rc && k == 1) rc = sweep_users(h);
-    h->capturing = false;
-    hipError_t e = hipStreamEndCapture(h->stream, &g);
-    if (!rc && e != hipSuccess) { h->err = std::string("hipStreamEndCapture: ") + hipGetErrorString(e); rc = HPF_ERR_HIP; }
-    if (!rc) {
-      e = hipGraphInstantiate(&h->split_exec[k], g, nullptr, nullptr, 0);
-      if (e != hipSuccess) { h->split_exec[k] = nullptr; h->err = std::string("hipGraphInstantiate: ") + hipGetErrorString(e); rc = HPF_ERR_HIP; }
-    }
-    if (g) (void)hipGraphDestroy(g);
-    if (rc) { drop_graph(h); return rc; }
+  int rc;
+  hipStream_t st = h->stream;
+  switch (step) {
+    case Step::ITEMS_PASS:
+      if ((rc = run_phi(h, h->it, h->u, ev ? ev[1] : nullptr))) return rc;
+      if (ev) HIPCHK(h, hipEventRecord(ev[2], st));
+      break;
+    case Step::USERS_PASS:
+      if ((rc = run_phi(h, h->u, h->it, ev ? ev[3] : nullptr))) return rc;
+      if (ev) HIPCHK(h, hipEventRecord(ev[4], st));
+      break;
+    case Step::USERS_SWEEP:
+      if (h->jacobi)      // keep what _theta.sum_rows() still returns before _theta.swap() (hgaprec.cc:1281-1282)
+        HIPCHK(h, hipMemcpyAsync(h->u_colsum_prev, h->u.colsum, (size_t)h->ld * 8, hipMemcpyDeviceToDevice, st));
+      if ((rc = run_sweep(h, h->u, h->it.colsum, h->u.colsum))) return rc;
+      if (ev) HIPCHK(h, hipEventRecord(ev[5], st));
+      break;
+    case Step::ITEMS_SWEEP:
+      if (ev) HIPCHK(h, hipEventRecord(ev[7], st));
+      if ((rc = run_sweep(h, h->it, h->jacobi ? h->u_colsum_prev : h->u.colsum, h->it.colsum))) return rc;
+      if (ev) HIPCHK(h, hipEventRecord(ev[6], st));
+      break;
   }
   return HPF_OK;
 }
+
+// a sweep of s is on the stream: S holds raw sums, E and Elog predate it, W is the sweep's
+void mark_swept(Side &s) { s.l_stale = true; s.es_stale = true; s.w_from_sweep = true; }
+
+void step_done(hpf_handle *h, Step step)
+{
+  h->phase = hpf_plan::next_phase(h->phase, step);
+  if (step == Step::USERS_SWEEP) mark_swept(h->u);
+  if (step != Step::ITEMS_SWEEP) return;
+  mark_swept(h->it);
+  h->replaying = false;
+  h->ev_count++;
+  h->iterations++;
+  h->iters_counted++;
+}
+
+// The steps first..last captured into an executable (the kernels' arguments stay fixed until the CSR, the rows' layout or
+// the exchange buffer change: drop_graph there).  A failure leaves the handle as it was, without graphs.
+int capture_steps(hpf_handle *h, Step first, Step last, hipGraphExec_t *exec)
+{
+  hipGraph_t g = nullptr;
+  HIPCHK(h, hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal));
+  int rc = HPF_OK;
+  for (int s = first; s <= last && !rc; ++s) rc = enqueue_step(h, (Step)s, nullptr);
+  hipError_t e = hipStreamEndCapture(h->stream, &g);
+  if (!rc && e != hipSuccess) { h->err = std::string("hipStreamEndCapture: ") + hipGetErrorString(e); rc = HPF_ERR_HIP; }
+  if (!rc && (e = hipGraphInstantiate(exec, g, nullptr, nullptr, 0)) != hipSuccess) {
+    *exec = nullptr; h->err = std::string("hipGraphInstantiate: ") + hipGetErrorString(e); rc = HPF_ERR_HIP;
+  }
+  if (g) (void)hipGraphDestroy(g);
+  if (rc) drop_graph(h);
+  return rc;
+}
+
+// The consecutive steps first..last: call order, stream, books.  exec: a graph of exactly these steps to replay in their
+// place, or null.
+int run_steps(hpf_handle *h, Step first, Step last, hipGraphExec_t exec)
+{
+  int rc, ph = h->phase;
+  for (int s = first; s <= last; ++s)
+    if ((ph = hpf_plan::next_phase(ph, (Step)s)) < 0) { h->err = "call order: items pass, users pass, user sweep, iterate_global"; return HPF_ERR_STATE; }
+  if (!exec) {
+    for (int s = first; s <= last; ++s) {
+      if ((rc = enqueue_step(h, (Step)s, h->ev))) return rc;
+      step_done(h, (Step)s);
+    }
+    return HPF_OK;
+  }
+  if (first == Step::ITEMS_SWEEP) HIPCHK(h, hipEventRecord(h->ev[7], h->stream));
+  HIPCHK(h, hipGraphLaunch(exec, h->stream));
+  static const int first_event[4] = {1, 3, 5, 6}, last_event[4] = {2, 4, 5, 6};
+  for (int j = first_event[first]; j <= last_event[last]; ++j) HIPCHK(h, hipEventRecord(h->ev[j], h->stream));
+  for (int s = first; s <= last; ++s) step_done(h, (Step)s);
+  return HPF_OK;
+}
+
+// The cut the piece graphs are captured along: items pass | users pass + user sweep | item sweep.
 // OPT-IN (HPF_GRAPH=1 under HPF_EXPERIMENTAL), never chosen by the library: measured on MI355X (profiles/r06/experiments.md 4)
 // the three replays buy nothing where the pieces are long -- an eighth of C4, 2.50 ms eager against 2.51 -- and LOSE where they
 // are short -- C1 through the pieces: 0.101 ms eager, 0.127 replayed: a replay costs the host 10-16 us, three of them more than
@@ -1388,11 +1459,18 @@ int build_split_graphs(hpf_handle *h)
 // iteration -- one rank -- does pay: 0.085 ms.)
 bool split_graph_on(const hpf_handle *h) { return !h->in_recovery && h->graph_mode == 1; }
 
-// allow_graph: the caller goes on with hpf_iterate_local_users and hpf_iterate_global -- the cut the graphs are captured along
-int phi_items(hpf_handle *h, bool allow_graph = false)
+constexpr Step PIECE[3][2] = {{Step::ITEMS_PASS, Step::ITEMS_PASS}, {Step::USERS_PASS, Step::USERS_SWEEP}, {Step::ITEMS_SWEEP, Step::ITEMS_SWEEP}};
+hipGraphExec_t piece_graph(const hpf_handle *h, int k) { return h->replaying ? h->split_exec[k] : nullptr; }   // null once dropped: the piece then runs eagerly
+
+// How the iteration about to begin wants to run.  PIECES: the caller goes on with hpf_iterate_local_users and
+// hpf_iterate_global (granted where split_graph_on).  WHOLE: hpf_iterate on one rank (want_graph).
+enum Replay { EAGER, PIECES, WHOLE };
+
+// What precedes the first step of an iteration: the state the kernels read is in place, the graphs the iteration will
+// replay exist, its ring slot is chosen and event 0 recorded.
+int begin_iteration(hpf_handle *h, Replay want)
 {
   int rc;
-  if (h->capturing) return run_phi(h, h->it, h->u, nullptr);
   if (!h->have_csr) { h->err = "hpf_upload_csr has not been called"; return HPF_ERR_STATE; }
   // several ranks: a pass that skipped would leave this rank's sums out of the all-reduce, so the host looks at the flag
   // before every iteration (one stream synchronisation) and repairs the rows first; one rank lets the passes skip and
@@ -1408,100 +1486,41 @@ int phi_items(hpf_handle *h, bool allow_graph = false)
     }
   }
   if ((rc = prepare_derived(h))) return rc;
+  if (want == PIECES && !split_graph_on(h)) want = EAGER;
+  for (int k = 0; want == PIECES && k < 3; ++k)
+    if (!h->split_exec[k] && (rc = capture_steps(h, PIECE[k][0], PIECE[k][1], &h->split_exec[k]))) return rc;
+  if (want == WHOLE && !h->graph_exec && (rc = capture_steps(h, Step::ITEMS_PASS, Step::ITEMS_SWEEP, &h->graph_exec))) return rc;
+  const uint32_t slot = h->ev_count % hpf_handle::RING;
   h->tail_partial = false;
-  h->ev = h->evr[h->ev_count % hpf_handle::RING];
-  h->ring_graphed[h->ev_count % hpf_handle::RING] = false;
-  const bool replay = allow_graph && split_graph_on(h);
-  if (replay && !h->split_exec[0] && (rc = build_split_graphs(h))) return rc;
+  h->ev = h->evr[slot];
+  h->ring_graphed[slot] = want == WHOLE;
+  h->replaying = want == PIECES;
   HIPCHK(h, hipEventRecord(h->ev[0], h->stream));
-  if (replay) {
-    // one launch: pass and combines; the per-kernel events coincide (phi_item_ms then holds the whole item half)
-    HIPCHK(h, hipGraphLaunch(h->split_exec[0], h->stream));
-    HIPCHK(h, hipEventRecord(h->ev[1], h->stream));
-    h->phase = 4;                                            // 4: the pieces of this iteration are graph replays
-  } else {
-    if ((rc = run_phi(h, h->it, h->u, h->ev[1]))) return rc;   // step A, beta shape sums
-    h->phase = 1;
-  }
-  HIPCHK(h, hipEventRecord(h->ev[2], h->stream));
   return HPF_OK;
 }
 
-int phi_users(hpf_handle *h)
+int items_pass(hpf_handle *h, Replay want)
 {
-  int rc;
-  if (h->capturing) return run_phi(h, h->u, h->it, nullptr);
-  if (h->phase != 1) { h->err = "call order: items pass, users pass, user sweep, iterate_global"; return HPF_ERR_STATE; }
-  if ((rc = run_phi(h, h->u, h->it, h->ev[3]))) return rc;   // step A, theta shape sums
-  HIPCHK(h, hipEventRecord(h->ev[4], h->stream));
-  h->phase = 2;
-  return HPF_OK;
+  const int rc = begin_iteration(h, want);
+  return rc ? rc : run_steps(h, Step::ITEMS_PASS, Step::ITEMS_PASS, piece_graph(h, 0));
 }
-
-// steps B (+D user, E): theta rate uses c = sum_i E[beta]; emits
-// d = sum_u E[theta] into the tail of the exchange buffer.  Does not touch the
-// item part of the exchange buffer, so its all-reduce may already be running.
-int sweep_users(hpf_handle *h)
-{
-  int rc;
-  if (!h->capturing && h->phase != 2) { h->err = "call order: items pass, users pass, user sweep, iterate_global"; return HPF_ERR_STATE; }
-  if (h->jacobi)        // keep what _theta.sum_rows() still returns before _theta.swap() (hgaprec.cc:1281-1282)
-    HIPCHK(h, hipMemcpyAsync(h->u_colsum_prev, h->u.colsum, (size_t)h->ld * 8, hipMemcpyDeviceToDevice, h->stream));
-  if ((rc = run_sweep(h, h->u, h->it.colsum, h->u.colsum))) return rc;
-  if (h->capturing) return HPF_OK;
-  HIPCHK(h, hipEventRecord(h->ev[5], h->stream));
-  h->phase = 3;
-  return HPF_OK;
-}
-
-int iterate_local_phi(hpf_handle *h)
-{
-  int rc;
-  if ((rc = phi_items(h))) return rc;
-  return phi_users(h);
-}
-
-int iterate_local_users(hpf_handle *h)
-{
-  int rc;
-  if (h->phase == 4) {                                       // the user half as one graph replay
-    HIPCHK(h, hipGraphLaunch(h->split_exec[1], h->stream));
-    for (int j = 3; j <= 5; ++j) HIPCHK(h, hipEventRecord(h->ev[j], h->stream));
-    h->u.l_stale = h->u.es_stale = true; h->u.w_from_sweep = true;
-    h->phase = 5;
-    return HPF_OK;
-  }
-  if ((rc = phi_users(h))) return rc;
-  return sweep_users(h);
-}
-
+int iterate_local_users(hpf_handle *h) { return run_steps(h, Step::USERS_PASS, Step::USERS_SWEEP, piece_graph(h, 1)); }
+int iterate_global(hpf_handle *h) { return run_steps(h, Step::ITEMS_SWEEP, Step::ITEMS_SWEEP, piece_graph(h, 2)); }
 int iterate_local(hpf_handle *h)
 {
-  int rc;
-  if ((rc = iterate_local_phi(h))) return rc;
-  return sweep_users(h);
+  const int rc = items_pass(h, EAGER);
+  return rc ? rc : run_steps(h, Step::USERS_PASS, Step::USERS_SWEEP, nullptr);
 }
-
-int iterate_global(hpf_handle *h)
+// one launch for the whole iteration: only its start and its end are timed
+int replay_iteration(hpf_handle *h)
 {
   int rc;
-  // steps C (+D item, F): beta rate uses d (all-reduced when n_ranks > 1)
-  if (!h->capturing && h->phase != 3 && h->phase != 5) { h->err = "call order: items pass, users pass, user sweep, iterate_global"; return HPF_ERR_STATE; }
-  if (!h->capturing) HIPCHK(h, hipEventRecord(h->ev[7], h->stream));
-  if (!h->capturing && h->phase == 5) {
-    HIPCHK(h, hipGraphLaunch(h->split_exec[2], h->stream));
-    h->it.l_stale = h->it.es_stale = true; h->it.w_from_sweep = true;
-  } else if ((rc = run_sweep(h, h->it, h->jacobi ? h->u_colsum_prev : h->u.colsum, h->it.colsum))) return rc;
-  if (h->capturing) return HPF_OK;
+  if ((rc = begin_iteration(h, WHOLE))) return rc;
+  HIPCHK(h, hipGraphLaunch(h->graph_exec, h->stream));
   HIPCHK(h, hipEventRecord(h->ev[6], h->stream));
-  h->phase = 0;
-  h->ev_count++;
-  h->iterations++;
-  h->iters_counted++;
+  for (int s = Step::ITEMS_PASS; s <= Step::ITEMS_SWEEP; ++s) step_done(h, (Step)s);
   return HPF_OK;
 }
-
-void drop_graph(hpf_handle *h);
 
 // p59 rows -> plain doubles in the same shape (codec_f64): W reallocated, the work lists cut again
 // for the new row size -- exactly what a handle created with w_storage = 3 holds
@@ -1581,48 +1600,6 @@ bool want_graph(const hpf_handle *h)
 {
   if (h->graph_mode >= 0) return h->graph_mode == 1;
   return h->nnz <= h->graph_nnz_max;
-}
-
-// one iteration (both phi passes, both sweeps) captured once; every kernel
-// argument is a pointer or scalar that stays fixed until the CSR or the
-// exchange buffer is replaced (drop_graph there)
-int build_graph(hpf_handle *h)
-{
-  hipGraph_t g = nullptr;
-  HIPCHK(h, hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal));
-  h->capturing = true;
-  int rc = iterate_local(h);
-  if (!rc) rc = iterate_global(h);
-  h->capturing = false;
-  hipError_t e = hipStreamEndCapture(h->stream, &g);
-  if (rc) { if (g) (void)hipGraphDestroy(g); return rc; }
-  if (e != hipSuccess) { h->err = std::string("hipStreamEndCapture: ") + hipGetErrorString(e); return HPF_ERR_HIP; }
-  e = hipGraphInstantiate(&h->graph_exec, g, nullptr, nullptr, 0);
-  (void)hipGraphDestroy(g);
-  if (e != hipSuccess) { h->graph_exec = nullptr; h->err = std::string("hipGraphInstantiate: ") + hipGetErrorString(e); return HPF_ERR_HIP; }
-  return HPF_OK;
-}
-
-int iterate_graph(hpf_handle *h, int n_iters)
-{
-  int rc;
-  if (!h->have_csr) { h->err = "hpf_upload_csr has not been called"; return HPF_ERR_STATE; }
-  if ((rc = prepare_derived(h))) return rc;
-  if (!h->graph_exec && (rc = build_graph(h))) return rc;
-  for (int t = 0; t < n_iters; ++t) {
-    const uint32_t slot = h->ev_count % hpf_handle::RING;
-    h->ev = h->evr[slot];
-    h->ring_graphed[slot] = true;
-    HIPCHK(h, hipEventRecord(h->ev[0], h->stream));
-    HIPCHK(h, hipGraphLaunch(h->graph_exec, h->stream));
-    HIPCHK(h, hipEventRecord(h->ev[6], h->stream));
-    h->u.l_stale = h->u.es_stale = h->it.l_stale = h->it.es_stale = true;
-    h->u.w_from_sweep = h->it.w_from_sweep = true;
-    h->ev_count++;
-    h->iterations++;
-    h->iters_counted++;
-  }
-  return HPF_OK;
 }
 
 }  // namespace
@@ -1803,7 +1780,7 @@ int hpf_allreduce_items_begin(hpf_handle *h)
 {
   if (!h) return HPF_ERR_INVALID;
   if (!h->comm) { h->err = "hpf_comm_init has not been called"; return HPF_ERR_STATE; }
-  if (h->phase != 1 && h->phase != 4) { h->err = "hpf_allreduce_items_begin follows hpf_iterate_local_items"; return HPF_ERR_STATE; }
+  if (h->phase != 1) { h->err = "hpf_allreduce_items_begin follows hpf_iterate_local_items"; return HPF_ERR_STATE; }
   if (!h->comm_stream) {
     HIPCHK(h, hipStreamCreateWithFlags(&h->comm_stream, hipStreamNonBlocking));
     HIPCHK(h, hipEventCreateWithFlags(&h->ev_ready, hipEventDisableTiming));
@@ -2328,34 +2305,33 @@ int hpf_snapshot_load(hpf_handle *h, const void *host, size_t bytes)
 int hpf_iterate(hpf_handle *h, int n_iters)
 {
   if (!h || n_iters < 0) return HPF_ERR_INVALID;
-  if (h->cfg.n_ranks != 1 || h->comm) {
-    // several ranks -- or one with a communicator of its own (a one-rank RCCL communicator: tests, bench.py --comm library on one
-    // GPU) --: whole iterations only when the library owns the exchange
-    if (!h->comm) { h->err = "hpf_iterate with n_ranks > 1 needs hpf_comm_init (or use iterate_local / your all-reduce / iterate_global)"; return HPF_ERR_INVALID; }
-    for (int t = 0; t < n_iters; ++t) {
-      int rc;
-      if ((rc = phi_items(h, true))) return rc;
-      if ((rc = hpf_allreduce_items_begin(h))) return rc;
-      if ((rc = iterate_local_users(h))) return rc;
-      if ((rc = hpf_allreduce_exchange(h))) return rc;
-      if ((rc = iterate_global(h))) return rc;
-    }
-    return HPF_OK;
-  }
-  if (n_iters > 0 && want_graph(h)) return iterate_graph(h, n_iters);
+  // several ranks -- or one with a communicator of its own (a one-rank RCCL communicator: tests, bench.py --comm library on one
+  // GPU) --: whole iterations only when the library owns the exchange
+  const bool exchange = h->cfg.n_ranks != 1 || h->comm;
+  if (exchange && !h->comm) { h->err = "hpf_iterate with n_ranks > 1 needs hpf_comm_init (or use iterate_local / your all-reduce / iterate_global)"; return HPF_ERR_INVALID; }
   for (int t = 0; t < n_iters; ++t) {
     int rc;
-    if ((rc = iterate_local(h))) return rc;
-    if ((rc = iterate_global(h))) return rc;
+    if (exchange) {
+      if ((rc = items_pass(h, PIECES)) || (rc = hpf_allreduce_items_begin(h)) || (rc = iterate_local_users(h)) ||
+          (rc = hpf_allreduce_exchange(h)) || (rc = iterate_global(h))) return rc;
+    } else if (want_graph(h)) {
+      if ((rc = replay_iteration(h))) return rc;
+    } else if ((rc = iterate_local(h)) || (rc = iterate_global(h))) return rc;
   }
   return HPF_OK;
 }
 
-int hpf_iterate_local(hpf_handle *h) { return h ? iterate_local(h) : HPF_ERR_INVALID; }
-int hpf_iterate_local_phi(hpf_handle *h) { return h ? iterate_local_phi(h) : HPF_ERR_INVALID; }
-int hpf_iterate_local_sweep(hpf_handle *h) { return h ? sweep_users(h) : HPF_ERR_INVALID; }
-int hpf_iterate_local_items(hpf_handle *h) { return h ? phi_items(h, true) : HPF_ERR_INVALID; }
+// the pieces of an iteration, for a caller that owns the exchange: compositions of the four steps (hpf_plan::next_phase)
+int hpf_iterate_local_items(hpf_handle *h) { return h ? items_pass(h, PIECES) : HPF_ERR_INVALID; }
+int hpf_iterate_local_phi(hpf_handle *h)
+{
+  if (!h) return HPF_ERR_INVALID;
+  const int rc = items_pass(h, EAGER);
+  return rc ? rc : run_steps(h, Step::USERS_PASS, Step::USERS_PASS, nullptr);
+}
+int hpf_iterate_local_sweep(hpf_handle *h) { return h ? run_steps(h, Step::USERS_SWEEP, Step::USERS_SWEEP, nullptr) : HPF_ERR_INVALID; }
 int hpf_iterate_local_users(hpf_handle *h) { return h ? iterate_local_users(h) : HPF_ERR_INVALID; }
+int hpf_iterate_local(hpf_handle *h) { return h ? iterate_local(h) : HPF_ERR_INVALID; }
 int hpf_iterate_global(hpf_handle *h) { return h ? iterate_global(h) : HPF_ERR_INVALID; }
 
 namespace {
@@ -2447,7 +2423,8 @@ int fold_sweeps(hpf_handle *h, uint32_t n_iters, double tol, uint32_t *iters_out
   it.have_prior = eta_given;
   if (rc) return rc;
   for (uint32_t t = 0; t < n_iters; ++t)
-    if ((rc = run_phi(h, u, it, h->ev[3])) || (rc = run_sweep(h, u, it.colsum, u.colsum))) return rc;
+    if ((rc = run_phi(h, u, it, nullptr)) || (rc = run_sweep(h, u, it.colsum, u.colsum))) return rc;
+  mark_swept(u);                                             // refresh_elog below rebuilds E and Elog from the sums
   uint32_t fl = 0;
   HIPCHK(h, hipMemcpyAsync(&fl, h->flags, 4, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));

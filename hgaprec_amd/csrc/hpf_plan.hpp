@@ -3,7 +3,7 @@
 // and launch grid of the fused rank kernels (rank_batch_users, rank_grid, rank_chunks), the score batch of the unfused ones
 // (score_batch_rows), the fused range, candidate buffers, grid and batches of hpf_recommend (topn_fused, topn_cap, topn_grid,
 // topn_batch_users), and the tiled pass: whether a side is tiled and with which tiles (tile_policy, tiling_fits) and which
-// XCD queue and chunk every segment runs in (plan_tile_queues).
+// XCD queue and chunk every segment runs in (plan_tile_queues); and the call order of an iteration's steps (next_phase).
 // Plain C++17 without a HIP header: hpf_capi.hip builds its handle and its dispatcher from it, host/plan_selftest.cpp
 // walks every column count on a CPU, pins the tile policy, checks the invariants of the queue plan over a seeded sweep and
 // prints the plan of a fixed list of cases (tests/data/tile_queue_table.txt, recorded before the arithmetic moved here).
@@ -582,6 +582,26 @@ inline bool fused_sweep(const Plan &p, const Knobs &kn, bool item_side)
 {
   return kn.fused_sweep != 0 && !item_side && has_phi_fused(p.wl, p.phiG, p.phiR) && has_sums(p.sw_mode, p.swG, p.swR) &&
          (kn.fused_sweep == 2 || fused_pays(p.phiG, p.phiR));
+}
+
+// ---- the call order of an iteration's steps ------------------------------------------------------------------------------
+// An iteration is four steps on one stream; the exported calls are compositions of them:
+//   hpf_iterate_local_items  ITEMS_PASS                     hpf_iterate_local_sweep  USERS_SWEEP
+//   hpf_iterate_local_phi    ITEMS_PASS USERS_PASS          hpf_iterate_local_users  USERS_PASS USERS_SWEEP
+//   hpf_iterate_local        ITEMS_PASS USERS_PASS USERS_SWEEP                       hpf_iterate_global  ITEMS_SWEEP
+// so an iteration is local_items | local_users | global, local_phi | local_sweep | global or local | global.
+// phase: 0 idle | 1 items pass done | 2 users pass done | 3 user sweep done.  Every other step follows its predecessor only;
+// the items pass may be called in any phase (an iteration that was begun and not finished is begun again).
+enum Step : int { ITEMS_PASS = 0, USERS_PASS = 1, USERS_SWEEP = 2, ITEMS_SWEEP = 3 };
+// the phase after `step` is on the stream, -1: a call-order error
+constexpr int next_phase(int phase, Step step)
+{
+  constexpr int next[4][4] = {          // [phase][step]
+    {1, -1, -1, -1},
+    {1, 2, -1, -1},
+    {1, -1, 3, -1},
+    {1, -1, -1, 0}};
+  return phase < 0 || phase > 3 || step < ITEMS_PASS || step > ITEMS_SWEEP ? -1 : next[phase][step];
 }
 
 }  // namespace hpf_plan

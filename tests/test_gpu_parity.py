@@ -376,6 +376,61 @@ def test_a_rank_of_several_replays_its_three_pieces_bit_identically(orc, monkeyp
     assert infos[1][1]["phi_item_ms"] > 0 and infos[1][1]["sweep_item_ms"] > 0 and infos[1][1]["iteration_ms"] > 0
 
 
+def _rank_of_two_holding_every_user(orc):
+    """one "rank" of two that holds every user, hier and bias on: the handle of the test above"""
+    from hgaprec_amd.capi import Hpf
+    n, m, K = 400, 300, 20
+    rowptr, col, val = make_problem(n, m, 9000, 4)
+    M = orc.Model(n, m, K, True, True, False)
+    M.set_csr(rowptr, col, val); M.initialize(4)
+    D = Hpf(n, m, K, hier=True, bias=True, n_ranks=2, rank=0, n_users_total=n)
+    D.upload_csr(rowptr, col, val)
+    copy_state(M, D, True, True)
+    return D
+
+
+def test_a_piece_whose_graph_was_dropped_between_the_pieces_runs_eagerly(orc, monkeypatch):
+    """The graphs of the three pieces go whenever a kernel argument may have changed (here: the index stream poked and put
+    back between the item piece and the user piece of a replayed iteration).  The later pieces of that iteration then launch
+    the same steps eagerly -- same kernels, same order, the same bits -- and the next iteration captures and replays again."""
+    monkeypatch.setenv("HPF_EXPERIMENTAL", "1")
+    outs = []
+    for mode in ("0", "1"):
+        monkeypatch.setenv("HPF_GRAPH", mode)
+        D = _rank_of_two_holding_every_user(orc)
+        for _ in range(2):
+            D.iterate_local_items(); D.iterate_local_users(); D.iterate_global()
+        D.iterate_local_items()
+        old, _ = D.debug_poke_index(0, 0, 1)
+        D.debug_poke_index(0, 0, old)
+        D.iterate_local_users(); D.iterate_global()
+        D.iterate_local_items(); D.iterate_local_users(); D.iterate_global()
+        replay = D.work_info()["graph_replay"]
+        outs.append([D.get_state(w) for w in ("THETA_E", "BETA_E", "THETA_SHAPE", "BETA_SHAPE")])
+        D.close()
+    assert replay == 2
+    for a, b in zip(*outs):
+        assert np.array_equal(a, b)
+
+
+def test_exports_between_the_pieces_of_a_replayed_iteration(orc, monkeypatch):
+    """A side counts as swept once its sweep is on the stream, not when the sweep is captured: in the iteration that captures
+    the three graphs, the user side exported after its (replayed) sweep is rebuilt from the new sums, and the item side
+    exported before its sweep is still the state handed in -- as on a handle that launches every step."""
+    monkeypatch.setenv("HPF_EXPERIMENTAL", "1")
+    outs = []
+    for mode in ("0", "1"):
+        monkeypatch.setenv("HPF_GRAPH", mode)
+        D = _rank_of_two_holding_every_user(orc)
+        D.iterate_local_items(); D.iterate_local_users()
+        mid = [D.get_state(w) for w in ("THETA_E", "THETA_ELOG", "BETA_ELOG")]
+        D.iterate_global()
+        outs.append(mid + [D.get_state(w) for w in ("THETA_E", "BETA_E", "THETA_SHAPE", "BETA_SHAPE")])
+        D.close()
+    for a, b in zip(*outs):
+        assert np.array_equal(a, b)
+
+
 @pytest.mark.parametrize("hier,bias", [(True, True), (False, False)])
 def test_snapshot_restore_continues_bit_identically(orc, hier, bias):
     # hpf_snapshot_save / _load: the loop's device arrays verbatim.  A second handle that
