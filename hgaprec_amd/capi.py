@@ -41,8 +41,12 @@ EXPORTS = [
     "hpf_get_work_info", "hpf_upload_csr_device", "hpf_get_csc", "hpf_set_state_device", "hpf_get_state_device",
     "hpf_iteration_times", "hpf_debug_poke_index", "hpf_start_sums", "hpf_host_alloc", "hpf_host_free",
     "hpf_heldout_bind", "hpf_heldout_ll_bound",
-    "hpf_predict", "hpf_loo_ranks", "hpf_rank_queries", "hpf_recommend", "hpf_fold_in",
+    "hpf_predict", "hpf_loo_ranks", "hpf_rank_queries", "hpf_recommend", "hpf_fold_in", "hpf_similar",
 ]
+
+# hpf_similar: the metrics (hpf_similarity in include/hpf.h) and the largest topn (TOPN_FUSED_MAX: only the fused route exists)
+SIMILARITY = {"cosine": 0, "dot": 1}
+SIMILAR_MAX = 256
 
 # queries of one row of rank_queries_kernel (RQ_QCAP in csrc/hpf_kernels.hpp): hpf_rank_queries cuts a user with more
 # into several rows; tests put their query counts around it
@@ -239,6 +243,8 @@ def load_library(path: os.PathLike | None = None) -> C.CDLL:
         lib.hpf_recommend.argtypes = [vp, u32p, C.c_uint32, u64p, u32p, C.c_uint32, u32p, dp]
     if hasattr(lib, "hpf_fold_in"):
         lib.hpf_fold_in.argtypes = [vp, C.c_uint32, C.c_double, u32p]
+    if hasattr(lib, "hpf_similar"):
+        lib.hpf_similar.argtypes = [vp, C.c_int, u32p, C.c_uint32, C.c_uint32, C.c_int, u32p, dp]
     lib.hpf_comm_unique_id.argtypes = [vp]
     lib.hpf_comm_init.argtypes = [vp, vp]
     lib.hpf_allreduce_exchange.argtypes = [vp]
@@ -578,6 +584,25 @@ class Hpf:
         self._check(self.lib.hpf_recommend(self._h, _ptr(users, C.c_uint32), users.size, pmp, pmi, topn & 0xffffffff,
                                            _ptr(items, C.c_uint32), _ptr(sc, C.c_double)))
         return items, sc
+
+    def similar(self, side, ids, topn, metric="cosine"):
+        """the topn nearest OTHER rows of one side for every selected row (hpf_similar).  side 0: rows of E[theta] (this
+        handle's users), 1: rows of E[beta]; metric "cosine" or "dot" (or its number), over the K factor columns
+        -> (ids, scores), each [len(ids), topn]; entries beyond rows - 1 are (0xffffffff, 0.0)"""
+        ids = np.ascontiguousarray(ids, dtype=np.uint32)
+        if ids.ndim != 1:
+            raise ValueError("ids: a one-dimensional array")
+        if isinstance(metric, str):
+            if metric not in SIMILARITY:
+                raise ValueError("metric: 'cosine' or 'dot'")
+            metric = SIMILARITY[metric]
+        topn = int(topn)
+        shape = (ids.size, topn if 0 < topn <= SIMILAR_MAX else 0)
+        out = np.empty(shape, dtype=np.uint32)
+        sc = np.empty(shape, dtype=np.float64)
+        self._check(self.lib.hpf_similar(self._h, int(side), _ptr(ids, C.c_uint32), ids.size, topn & 0xffffffff, int(metric),
+                                         _ptr(out, C.c_uint32), _ptr(sc, C.c_double)))
+        return out, sc
 
     def fold_in(self, n_iters=10, tol=0.0, want_iters=True):
         """fold this handle's users in against the item side handed in (hpf_fold_in): from the prior, n_iters user-side

@@ -80,6 +80,26 @@ int Env::parse(int argc, char **argv, bool echo, std::string *bad)
       }
       recommend = (uint32_t)nrec;
     }
+    else if (!strcmp(s, "-similar-items") || !strcmp(s, "-similar-users")) {   // extension: the N nearest rows of every row of a saved model
+      const bool items = !strcmp(s, "-similar-items");
+      const char *v = next(); char *end = nullptr;
+      const long nsim = strtol(v, &end, 10);
+      if (!*v || *end || nsim < 1 || nsim > 256) {
+        usage_error = std::string(s) + " needs the number of neighbours per " + (items ? "item" : "user") + ", 1 .. 256";
+        if (bad) *bad = s;
+        return 2;
+      }
+      (items ? similar_items : similar_users) = (uint32_t)nsim;
+    }
+    else if (!strcmp(s, "-similar-metric")) {
+      const char *v = next();
+      if (strcmp(v, "cosine") && strcmp(v, "dot")) {
+        usage_error = "-similar-metric is cosine (the default) or dot";
+        if (bad) *bad = s;
+        return 2;
+      }
+      similar_metric = v;
+    }
     else if (!strcmp(s, "-fold-in")) {                            // extension: fold the users of FILE into a saved model
       const char *v = next();
       if (!*v || *v == '-') {

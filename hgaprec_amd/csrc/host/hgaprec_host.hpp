@@ -69,8 +69,14 @@ struct Env {
   std::string fold_in;
   uint32_t fold_iters = 10;
   double fold_tol = 0.0;
+  // extension: -similar-items N / -similar-users N [-similar-metric cosine|dot] write the N nearest other items of every
+  // item (users of every user) of a saved model in factor space through hpf_similar: similar_items.tsv / .txt,
+  // similar_users.tsv / .txt.  Score modes too; both may be given in one run.  N outside 1 .. 256, no N or another metric:
+  // parse() returns 2 and says why in usage_error
+  uint32_t similar_items = 0, similar_users = 0;
+  std::string similar_metric = "cosine";
   std::string usage_error;
-  bool score_mode() const { return gen_ranking || rmse || msr || eval_all || recommend > 0 || !fold_in.empty(); }
+  bool score_mode() const { return gen_ranking || rmse || msr || eval_all || recommend > 0 || !fold_in.empty() || similar_items > 0 || similar_users > 0; }
 
   std::string prefix;          // output directory (Env::prefix)
   FILE *plogf = nullptr;       // param.txt

@@ -13,7 +13,7 @@
 // stand-in (`-comm host`, for tests on a single GPU).  The output files are
 // the same as in a single-GPU run.
 //
-// Scoring a saved model: -gen-ranking / -rmse / -msr / -eval-all / -recommend read the data like a training run, load
+// Scoring a saved model: -gen-ranking / -rmse / -msr / -eval-all / -recommend / -similar-items / -similar-users read the data like a training run, load
 // the factor files a run has written (from the current directory like the reference, or from
 // -model-dir DIR) into the handle's expectations, write ONE report and exit (Driver::score).  -fold-in FILE reads the
 // item side of those files as shape and rate and folds the users of FILE in on a second handle (Driver::fold_in_report).
@@ -887,6 +887,41 @@ struct Driver {
     env.lerr("-recommend: %u users, %llu lines in recommend.tsv", n, lines);
   }
 
+  // -similar-items N / -similar-users N (extension): "more like this item" and "users like this one" -- the N nearest other
+  // rows of E[beta] (E[theta]) to every row, by cosine or dot product over the K factor columns, through hpf_similar.
+  // similar_items.tsv: item id, neighbour item id, score -- items in seq order, each list best first, ids and score printed
+  // as recommend.tsv prints them, the padding of a list beyond rows - 1 never printed; similar_items.txt: rows, lines, N,
+  // metric.  similar_users.* the same for users.  A chunk of rows is written before the next is ranked.
+  void similar_report(bool items) {
+    const uint32_t N = items ? env.similar_items : env.similar_users, CH = 1u << 16;
+    const uint32_t rows = items ? m : n;
+    const std::vector<uint32_t> &ids = items ? rt.seq2item : rt.seq2user;
+    const int metric = env.similar_metric == "dot" ? HPF_SIM_DOT : HPF_SIM_COSINE;
+    const std::string base = items ? "/similar_items" : "/similar_users";
+    const std::string rpath = env.file_str(base + ".tsv"), cpath = env.file_str(base + ".txt");
+    FILE *f = open_or_die(rpath, "w");
+    std::vector<uint32_t> sel, nb; std::vector<double> scores;
+    unsigned long long lines = 0;
+    for (uint32_t r0 = 0; r0 < rows; r0 += CH) {
+      const uint32_t r1 = std::min(rows, r0 + CH);
+      sel.clear();
+      for (uint32_t r = r0; r < r1; ++r) sel.push_back(r);
+      nb.resize(sel.size() * (size_t)N); scores.resize(sel.size() * (size_t)N);
+      int rc = hpf_similar(h, items ? 1 : 0, sel.data(), (uint32_t)sel.size(), N, metric, nb.data(), scores.data());
+      if (rc) die("hpf_similar", rc);
+      for (size_t b = 0; b < sel.size(); ++b)
+        for (uint32_t j = 0; j + 1 < rows && j < N; ++j) {
+          fprintf(f, "%d\t%d\t%.5f\n", ids[sel[b]], ids[nb[b * N + j]], scores[b * N + j]);
+          ++lines;
+        }
+    }
+    close_or_die(f, rpath);
+    FILE *cf = open_or_die(cpath, "w");
+    fprintf(cf, "%u\t%llu\t%u\t%s\n", rows, lines, N, env.similar_metric.c_str());
+    close_or_die(cf, cpath);
+    env.lerr("-similar-%s: %u rows, %llu lines in %s.tsv", items ? "items" : "users", rows, lines, base.c_str() + 1);
+  }
+
   // -fold-in FILE (extension; HGAPRec::test(), hgaprec.cc:2257-2346): the users of FILE, who need not be in -dir, folded
   // into the saved model.  The item side comes from -model-dir as SHAPE and RATE (E alone does not give Elog) through the
   // strict readers; the host forms E = shape / rate and Elog = psi(shape) - log(rate) and hands them to a second handle
@@ -1021,6 +1056,10 @@ struct Driver {
     else if (env.msr) gen_msr_csv();
     else if (env.eval_all) eval_all_report();
     else if (env.recommend) recommend_report();
+    else if (env.similar_items || env.similar_users) {
+      if (env.similar_items) similar_report(true);
+      if (env.similar_users) similar_report(false);
+    }
     else gen_ranking_for_users();
     finish(0);
   }
@@ -1265,13 +1304,14 @@ int main(int argc, char **argv)
   if (!env.unsupported.empty()) {
     fprintf(stderr, "error: option %s selects a mode outside the MI355X hot-path build "
                     "(supported: -dir -n -m -k -hier -bias -binary-data -rfreq -max-iterations "
-                    "-seed -label -rating-threshold -logl -novb -a -b -c -d, -gen-ranking -rmse -msr -eval-all -recommend -fold-in -fold-iters -fold-tol -model-dir, "
+                    "-seed -label -rating-threshold -logl -novb -a -b -c -d, -gen-ranking -rmse -msr -eval-all -recommend -fold-in -fold-iters -fold-tol "
+                    "-similar-items -similar-users -similar-metric -model-dir, "
                     "-ngpus -comm -single-allreduce -device)\n", env.unsupported.c_str());
     return 2;
   }
   if (env.score_mode()) {
     if (env.ngpus > 1 || world > 1) {
-      fprintf(stderr, "error: -gen-ranking / -rmse / -msr / -eval-all / -recommend / -fold-in score a saved model on ONE GPU: run them without -ngpus\n");
+      fprintf(stderr, "error: -gen-ranking / -rmse / -msr / -eval-all / -recommend / -fold-in / -similar-items / -similar-users score a saved model on ONE GPU: run them without -ngpus\n");
       return 1;
     }
     // the start of a run truncates validation.txt, precision.txt and friends in its output directory: that directory

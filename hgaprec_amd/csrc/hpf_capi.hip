@@ -2901,10 +2901,65 @@ int hpf_recommend(hpf_handle *h, const uint32_t *users, uint32_t n_sel, const ui
     a.splits = g.splits; a.topn = topn; a.cap = cap; a.lg_cap = hpf_plan::log2_of(cap);
     if ((rc = launch_rank(h, "topn_sweep_kernel", [&](auto nch) {
           hipLaunchKernelGGL(topn_sweep_kernel<decltype(nch)::value>, dim3(g.blocks, g.splits), dim3(256), 0, h->stream, a);
-          hipLaunchKernelGGL(topn_merge_kernel, dim3(rows), dim3(256), (size_t)NP * 12, h->stream, a, NP);
+          hipLaunchKernelGGL(topn_merge_kernel, dim3(rows), dim3(256), (size_t)NP * 12, h->stream, a, NP, std::min(topn, m));
         }, "topn_sweep_kernel/topn_merge_kernel"))) return rc;
   }
   return copy_back(h, {{out_items, d_items, (size_t)n_sel * topn * 4}, {out_scores, d_sc, (size_t)n_sel * topn * 8}});
+}
+
+// The topn nearest OTHER rows of one side for every selected row: hpf_recommend's sweep, selection and merge with query
+// rows and swept rows from one matrix -- the side's E for the dot product, its rows at unit length (unit_rows_kernel; a
+// temporary of this call) for the cosine.  No bit rows, no bias, the row itself left out: min(topn, rows - 1) entries a list.
+int hpf_similar(hpf_handle *h, int side, const uint32_t *ids, uint32_t n_sel, uint32_t topn, int metric,
+                uint32_t *out_ids, double *out_scores)
+{
+  if (!h) return HPF_ERR_INVALID;
+  if (side != 0 && side != 1) { h->err = "hpf_similar: side is 0 (users) or 1 (items)"; return HPF_ERR_INVALID; }
+  if (metric != HPF_SIM_COSINE && metric != HPF_SIM_DOT) { h->err = "hpf_similar: unknown metric"; return HPF_ERR_INVALID; }
+  if (!hpf_plan::topn_fused(topn)) { h->err = "hpf_similar: topn is 1 .. 256"; return HPF_ERR_INVALID; }
+  if (n_sel && (!ids || !out_ids || !out_scores)) { h->err = "hpf_similar: null pointer"; return HPF_ERR_INVALID; }
+  if (!n_sel) return HPF_OK;
+  Side &s = side ? h->it : h->u;
+  const uint32_t m = s.rows, ntiles = (m + 63) / 64;
+  if (h->ld & 1u) { h->err = "hpf_similar: odd row stride"; return HPF_ERR_UNSUPPORTED; }
+  if (!s.have_E && h->iterations == 0) { h->err = "E state not set"; return HPF_ERR_STATE; }
+  for (uint32_t b = 0; b < n_sel; ++b)
+    if (ids[b] >= m) { h->err = side ? "item index out of range" : "user index out of range"; return HPF_ERR_INVALID; }
+  int rc;
+  if ((rc = check_flags(h)) || (rc = refresh_es(h, s))) return rc;
+  FusedCtx c(h);
+  double *d_unit = nullptr;
+  if ((rc = c.upload(ids, n_sel, nullptr, nullptr))) return rc;
+  if (metric == HPF_SIM_COSINE) {
+    if ((rc = c.alloc(&d_unit, (size_t)m * h->ld))) return rc;
+    hipLaunchKernelGGL(unit_rows_kernel, dim3(std::min<uint32_t>((m + 15) / 16, 16384)), dim3(256), 0, h->stream, s.E, d_unit, m, h->ld, h->K);
+    if ((rc = check_launch(h, "unit_rows_kernel"))) return rc;
+  }
+  const uint32_t cap = hpf_plan::topn_cap(topn);
+  c.batch = hpf_plan::topn_batch_users(m, n_sel, cap, h->loo_batch);
+  // segments (row, split) of a batch, as hpf_recommend sizes them
+  const hpf_plan::RankGrid gfull = hpf_plan::topn_grid(std::min(c.batch, n_sel), ntiles, cap);
+  const size_t nseg = (size_t)c.batch * gfull.splits;
+  unsigned long long *d_ckey = nullptr; uint32_t *d_citem = nullptr, *d_ccount = nullptr, *d_items = nullptr; double *d_sc = nullptr;
+  if ((rc = c.alloc(&d_ckey, nseg * cap)) || (rc = c.alloc(&d_citem, nseg * cap)) || (rc = c.alloc(&d_ccount, nseg)) ||
+      (rc = c.alloc(&d_items, (size_t)n_sel * topn)) || (rc = c.alloc(&d_sc, (size_t)n_sel * topn))) return rc;
+  const uint32_t NP = hpf_plan::pow2_ceil(topn);
+  for (uint32_t b0 = 0; b0 < n_sel; b0 += c.batch) {
+    const uint32_t rows = std::min(n_sel - b0, c.batch);
+    hpf_plan::RankGrid g = hpf_plan::topn_grid(rows, ntiles, cap);
+    if ((size_t)rows * g.splits > nseg) { g.splits = gfull.splits; g.tiles_per_split = gfull.tiles_per_split; }
+    TopnArgs a;
+    a.Et = a.Eb = d_unit ? d_unit : s.E; a.ld = h->ld; a.K = h->K; a.ubias_col = a.ibias_col = -1;
+    a.users = c.d_users + b0; a.bits = nullptr; a.ckey = d_ckey; a.citem = d_citem; a.ccount = d_ccount;
+    a.out_items = d_items + (size_t)b0 * topn; a.out_scores = d_sc + (size_t)b0 * topn;
+    a.n_sel = rows; a.m = m; a.words = 0; a.tiles_per_split = g.tiles_per_split;
+    a.splits = g.splits; a.topn = topn; a.cap = cap; a.lg_cap = hpf_plan::log2_of(cap);
+    if ((rc = launch_rank(h, "similar_sweep_kernel", [&](auto nch) {
+          hipLaunchKernelGGL(similar_sweep_kernel<decltype(nch)::value>, dim3(g.blocks, g.splits), dim3(256), 0, h->stream, a);
+          hipLaunchKernelGGL(topn_merge_kernel, dim3(rows), dim3(256), (size_t)NP * 12, h->stream, a, NP, std::min(topn, m - 1));
+        }, "similar_sweep_kernel/topn_merge_kernel"))) return rc;
+  }
+  return copy_back(h, {{out_ids, d_items, (size_t)n_sel * topn * 4}, {out_scores, d_sc, (size_t)n_sel * topn * 8}});
 }
 
 int hpf_get_work_info(hpf_handle *h, hpf_work_info *out)

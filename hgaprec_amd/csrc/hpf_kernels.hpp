@@ -2842,12 +2842,35 @@ __device__ __forceinline__ uint32_t topn_compact(unsigned long long *gk, uint32_
   return keep;
 }
 
+// What stands between the sweep's dot product and a candidate's key, by caller.  hpf_recommend: + (E_ubias + E_ibias) with
+// -bias, +0.0 where the user's mask word of the tile names the item, nothing left out.  hpf_similar (query rows and swept
+// rows from ONE matrix, a.Et == a.Eb): no bias, no bit rows (a.bits is not read), and the swept row whose id is the query
+// row's own is no candidate.
+struct RecommendEpi {
+  static constexpr bool SKIP_SELF = false;
+  static __device__ __forceinline__ bool bias(const TopnArgs &a) { return a.ubias_col >= 0; }
+  static __device__ __forceinline__ double ubias(const TopnArgs &a, uint32_t us, bool ok) { return user_bias(a, us, ok); }
+  static __device__ __forceinline__ double ibias(const TopnArgs &a, uint32_t it, bool ok) { return item_bias(a, it, ok); }
+  static __device__ __forceinline__ unsigned long long mask_word(const TopnArgs &a, uint32_t us, uint32_t tl, bool live)
+  {
+    return live ? a.bits[(size_t)us * a.words + tl] : 0ull;
+  }
+};
+struct SimilarEpi {
+  static constexpr bool SKIP_SELF = true;
+  static __device__ __forceinline__ bool bias(const TopnArgs &) { return false; }
+  static __device__ __forceinline__ double ubias(const TopnArgs &, uint32_t, bool) { return 0.0; }
+  static __device__ __forceinline__ double ibias(const TopnArgs &, uint32_t, bool) { return 0.0; }
+  static __device__ __forceinline__ unsigned long long mask_word(const TopnArgs &, uint32_t, uint32_t, bool) { return 0ull; }
+};
+
 // Workgroup = 4 waves = 64 users (16 per wave) x one split of the item range, as loo_rank_kernel.  A wave owns its 16
 // users' segments: no other wave reads or writes them.  Per user in LDS: the entries its segment holds and the least key
 // still accepted, `lo`.  lo = 0 until the first compaction (every item is a candidate), then the worst kept key + 1: items
 // ascend through a split, so a later item that ties the worst kept key comes behind it and cannot be among the best.
-template <int NCH>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void topn_sweep_kernel(TopnArgs a)
+// The body of topn_sweep_kernel (Epi = RecommendEpi) and of similar_sweep_kernel (SimilarEpi).
+template <int NCH, typename Epi>
+__device__ __forceinline__ void topn_sweep_body(const TopnArgs &a)
 {
   __shared__ double tile[64 * LOO_LDS_STRIDE];
   __shared__ unsigned long long scr_k[4 * TOPN_CAP_MAX];          // per wave: the entries being sorted
@@ -2855,6 +2878,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void t
   __shared__ unsigned long long s_lo[64];
   __shared__ uint32_t s_cnt[64];
   __shared__ double s_ub[64];                                       // E_ubias of the user
+  __shared__ uint32_t s_self[64];                                   // SKIP_SELF: the user's own row among the swept ones
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const int r16 = lane & 15, kq = lane >> 4;
   const uint32_t ub0 = blockIdx.x * 64;                          // first user of this workgroup
@@ -2869,7 +2893,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void t
   if (tid < 64) {
     const uint32_t us = ub0 + tid;
     s_cnt[tid] = 0u; s_lo[tid] = 0ull;
-    s_ub[tid] = user_bias(a, us, us < a.n_sel);
+    s_ub[tid] = Epi::ubias(a, us, us < a.n_sel);
+    if (Epi::SKIP_SELF) s_self[tid] = us < a.n_sel ? a.users[us] : 0xffffffffu;
   }
   __syncthreads();
 
@@ -2880,23 +2905,24 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void t
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
       const uint32_t it = i0 + 16 * t + r16;
-      bi[t] = item_bias(a, it, it < a.m);
+      bi[t] = Epi::ibias(a, it, it < a.m);
     }
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const uint32_t lr = wv * 16 + kq + 4 * r, us = ub0 + lr;
       const bool live = us < a.n_sel;
-      const unsigned long long w = live ? a.bits[(size_t)us * a.words + tl] : 0ull;
+      const unsigned long long w = Epi::mask_word(a, us, tl, live);
       const unsigned long long lo = s_lo[lr];
       const double ub = s_ub[lr];
+      const uint32_t self = Epi::SKIP_SELF ? s_self[lr] : 0u;
       uint32_t cnt = s_cnt[lr];                                  // <= cap - 64: the 64 items of a tile fit
       // first entry of the segment (a batch's buffers hold < 2^26 entries: hpf_plan::topn_batch_users)
       const uint32_t e0 = live ? (us * a.splits + blockIdx.y) << a.lg_cap : 0u;
 #pragma unroll
       for (int t = 0; t < 4; ++t) {
         const uint32_t it = i0 + 16 * t + r16;
-        const unsigned long long k = epilogue_key(acc[t][r], a.ubias_col >= 0, ub, bi[t], w, 16 * t + r16);
-        const bool take = live && it < a.m && k >= lo;
+        const unsigned long long k = epilogue_key(acc[t][r], Epi::bias(a), ub, bi[t], w, 16 * t + r16);
+        const bool take = live && it < a.m && k >= lo && !(Epi::SKIP_SELF && it == self);
         const uint32_t grp = (uint32_t)(__ballot(take) >> (16 * kq)) & 0xffffu;   // the 16 lanes that share this user
         if (take) {
           const uint32_t slot = cnt + (uint32_t)__popc(grp & ((1u << r16) - 1u));
@@ -2936,6 +2962,68 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void t
   }
 }
 
+// hpf_recommend's sweep
+template <int NCH>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void topn_sweep_kernel(TopnArgs a)
+{
+  topn_sweep_body<NCH, RecommendEpi>(a);
+}
+
+// ---------------------------------------------------------------------
+// Nearest rows in factor space (hpf_similar, -similar-items / -similar-users).
+//   unit_rows_kernel     U = the rows of E over the K factor columns at unit length, for the cosine
+//   similar_sweep_kernel topn_sweep_kernel's sweep and selection with query rows and swept rows from ONE matrix (U, or E
+//                        itself for the dot product), the query row left out of its own list; topn_merge_kernel follows
+// ---------------------------------------------------------------------
+template <int NCH>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void similar_sweep_kernel(TopnArgs a)
+{
+  topn_sweep_body<NCH, SimilarEpi>(a);
+}
+
+constexpr int UNIT_G = 16;            // lanes per row: one DPP row; 16 lanes x 16 bytes = two 128-byte lines per step
+
+// U[r, k] = x_k / sqrt(sum_k x_k^2), x_k = E[r, k] 2^-e with 2^e the power of two of the row's largest entry: x_k is exact
+// (unless it falls below the normal range, 2^-1022 of the largest entry, where it no longer matters), the largest is in
+// [1, 2), every square is <= 4 and the sum <= 4 K; a square that underflows adds nothing.  So a row scaled by a power of
+// two has the same U, bit for bit.  sqrt and / are the correctly rounded ones.  Lane g of a row's 16 adds the squares of
+// columns 2 g, 2 g + 1, 2 g + 32, ... in that order, group_sum adds the 16: the order depends on K alone.  An all-zero row
+// gives zeros; columns >= K (bias, padding) are written as zeros.  E finite and >= +0.0, ld even.
+__global__ __launch_bounds__(256) void unit_rows_kernel(const double *E, double *U, uint32_t rows, uint32_t ld, uint32_t K)
+{
+  const uint32_t g = threadIdx.x & (UNIT_G - 1);
+  const uint32_t per_block = 256 / UNIT_G;
+  for (uint32_t r = blockIdx.x * per_block + threadIdx.x / UNIT_G; r < rows; r += gridDim.x * per_block) {   // the same r in a row's 16 lanes
+    const double *pe = E + (size_t)r * ld;
+    double *pu = U + (size_t)r * ld;
+    auto piece = [&](uint32_t c) {                               // columns c, c + 1 of the row; c is even and ld is even
+      double2 v = *(const double2 *)(pe + c);
+      if (c + 1 >= K) v.y = 0.0;
+      return v;
+    };
+    double mx = 0.0;
+    for (uint32_t c = 2 * g; c < K; c += 2 * UNIT_G) { const double2 v = piece(c); mx = fmax(mx, fmax(v.x, v.y)); }
+    mx = group_max<UNIT_G>(mx);
+    int e = 0;
+    (void)frexp(mx, &e);                                         // mx = f 2^e, f in [0.5, 1): the largest x is 2 f
+    double s = 0.0;
+    for (uint32_t c = 2 * g; c < K; c += 2 * UNIT_G) {
+      const double2 v = piece(c);
+      const double x = ldexp(v.x, 1 - e), y = ldexp(v.y, 1 - e);
+      s += x * x; s += y * y;
+    }
+    const double nrm = sqrt(group_sum<UNIT_G>(s));
+    for (uint32_t c = 2 * g; c < ld; c += 2 * UNIT_G) {
+      double2 u = make_double2(0.0, 0.0);
+      if (c < K && mx > 0.0) {
+        const double2 v = piece(c);
+        u.x = ldexp(v.x, 1 - e) / nrm; u.y = ldexp(v.y, 1 - e) / nrm;
+      }
+      *(double2 *)(pu + c) = u;
+    }
+  }
+}
+
 // The segments of one user as block_topn's list: entry i is slot i % cap of segment i / cap, present when the slot is below
 // the segment's count.  Segments are sorted and cover ascending item ranges, so walking i upwards meets equal keys in
 // ascending item order -- which is all block_topn asks of a list.
@@ -2948,14 +3036,15 @@ struct SegmentEntries {
   __device__ __forceinline__ uint32_t item(uint32_t i) const { return gi[i]; }
 };
 
-// One workgroup per user: block_topn over what the sweep left of it.  NP = pow2 >= topn.
-__global__ __launch_bounds__(256) void topn_merge_kernel(TopnArgs a, uint32_t NP)
+// One workgroup per user: block_topn over what the sweep left of it.  NP = pow2 >= topn; Ne = the entries a list has before
+// its padding: min(topn, m) for hpf_recommend, min(topn, m - 1) for hpf_similar (the row itself is no candidate).
+__global__ __launch_bounds__(256) void topn_merge_kernel(TopnArgs a, uint32_t NP, uint32_t Ne)
 {
   const uint32_t b = blockIdx.x;
   if (b >= a.n_sel) return;
   const size_t e0 = ((size_t)b * a.splits) << a.lg_cap;
   block_topn(SegmentEntries{a.ckey + e0, a.citem + e0, a.ccount + (size_t)b * a.splits, a.splits << a.lg_cap, a.cap, a.lg_cap},
-             a.topn, a.topn < a.m ? a.topn : a.m, NP, a.out_items + (size_t)b * a.topn, a.out_scores + (size_t)b * a.topn);
+             a.topn, Ne, NP, a.out_items + (size_t)b * a.topn, a.out_scores + (size_t)b * a.topn);
 }
 
 // materialise the per-element rate matrix for export (htheta_rate.tsv):

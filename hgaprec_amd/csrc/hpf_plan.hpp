@@ -175,6 +175,7 @@ inline uint32_t score_batch_rows(uint32_t m, uint32_t n_sel)
 }
 
 // ---- top-N for every user (hpf_recommend) ---------------------------------------------------------
+// hpf_similar plans with the same functions, m = the rows of the side it ranks
 // Up to TOPN_FUSED_MAX the call is fused (topn_sweep_kernel + topn_merge_kernel); above it, up to TOPN_MAX, it runs the
 // materialising route of hpf_rank_topn.  hgaprec_amd/capi.py mirrors the cut as RECOMMEND_FUSED_MAX.
 constexpr uint32_t TOPN_MAX = 1024, TOPN_FUSED_MAX = 256;

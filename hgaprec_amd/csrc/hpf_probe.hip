@@ -10,9 +10,11 @@
 // return the hipError_t (0 = success).  Arrays hold at most PROBE_MAX_N elements.
 //
 // The second half launches the report kernels themselves -- heldout_ll_kernel, elbo_nnz_kernel, elbo_nnz_w_kernel,
-// rowmax_elog_kernel, elbo_gamma_kernel -- on the caller's arrays and grid (tests/test_gpu_report_terms.py).
+// rowmax_elog_kernel, elbo_gamma_kernel -- on the caller's arrays and grid (tests/test_gpu_report_terms.py), and
+// unit_rows_kernel as hpf_similar launches it (probe_unit_rows; tests/test_gpu_similar.py).
 #include "hpf_kernels.hpp"
 
+#include <algorithm>
 #include <vector>
 
 using namespace hpf;
@@ -479,6 +481,22 @@ PROBE_API int probe_rowmax_elog(const double *L, uint32_t rows, uint32_t ld, uin
                      K, bias_col, junk_col);
   if (const int rc = finish_launch()) return rc;
   PROBE_TRY(hipMemcpy(M, dm.p, (size_t)rows * sizeof(double), hipMemcpyDeviceToHost));
+  return 0;
+}
+
+// U = unit_rows_kernel's rows of E ([rows x ld], ld even, K <= ld factor columns), launched as hpf_similar launches it
+PROBE_API int probe_unit_rows(const double *E, uint32_t rows, uint32_t ld, uint32_t K, double *U)
+{
+  if (!mat_ok(rows, ld) || (ld & 1u) || K < 1 || K > ld) return (int)hipErrorInvalidValue;
+  DevBuf de, du;
+  const size_t n = (size_t)rows * ld;
+  if (int rc = to_device(de, E, n)) return rc;
+  PROBE_TRY(du.alloc(n * sizeof(double)));
+  PROBE_TRY(hipMemset(du.p, 0xff, n * sizeof(double)));           // an element the kernel skipped reads back as NaN
+  hipLaunchKernelGGL(unit_rows_kernel, dim3(std::min<uint32_t>((rows + 15) / 16, 16384)), dim3(256), 0, 0, de.as<double>(),
+                     du.as<double>(), rows, ld, K);
+  if (const int rc = finish_launch()) return rc;
+  PROBE_TRY(hipMemcpy(U, du.p, n * sizeof(double), hipMemcpyDeviceToHost));
   return 0;
 }
 

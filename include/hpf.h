@@ -397,6 +397,33 @@ int  hpf_recommend(hpf_handle *h, const uint32_t *users, uint32_t n_sel,
                    const uint64_t *mask_ptr, const uint32_t *mask_items, uint32_t topn,
                    uint32_t *out_items, double *out_scores);
 
+/* (an extension; the reference has no counterpart.)  Nearest neighbours in factor space: for selected row ids[b] of one
+ * side -- 0: the rows of E[theta] of this handle's users (with several ranks the LOCAL users only; nothing is
+ * exchanged), 1: the rows of E[beta] -- the topn OTHER rows of the same side, by score descending, ties by ascending id:
+ * the ranking calls' one ordering rule, taken on the bit pattern of the computed fp64 score.  The score is taken over
+ * the K factor columns only; bias columns take no part.
+ *   HPF_SIM_DOT     s(a, b) = sum_k E_ak E_bk, out of the same MFMA chain as hpf_scores (bit for bit what hpf_scores
+ *                   returns on a handle whose E[theta] and E[beta] are both this matrix, without bias).
+ *   HPF_SIM_COSINE  the same chain over the rows at unit length, U_ak = x_k / sqrt(sum_k x_k^2) with x_k = E_ak 2^-e and
+ *                   2^e the power of two of the row's largest entry: no square and no sum overflows, and a row scaled by
+ *                   a power of two has the same U bit for bit; sqrt and the division are correctly rounded, the sum is
+ *                   taken in an order fixed by K (run to run the same bits).  |U_ak - exact| <= (K/2 + 3) 2^-53 exact,
+ *                   and a returned cosine is within (2K + 8) 2^-53 of the exact one.  An all-zero row is all-zero in U:
+ *                   its cosine with every row is +0.0, never NaN.
+ * The row itself is never in its own list -- left out, not counted as +0.0.  Another row with identical factors is
+ * listed, with the score it gets.  An id may be selected twice; both output rows are then equal.  Entries beyond
+ * rows - 1 are (0xffffffff, 0.0), as in hpf_rank_topn.  Domain: the ranking calls' -- E finite and >= +0.0.
+ * topn is 1 .. 256 (only the fused route exists).  topn outside that, a side or metric not listed above, an id out of
+ * range, or a null pointer with n_sel > 0 is HPF_ERR_INVALID before anything is launched; n_sel = 0 is HPF_OK; no E on
+ * that side (neither hpf_set_state of it nor an iteration) is HPF_ERR_STATE; an odd row stride is HPF_ERR_UNSUPPORTED,
+ * as for the other fused calls.  Needs no CSR.  Synchronous.  The model state is not written.
+ * Device memory beyond inputs and outputs: for the cosine one rows x ld matrix of unit rows, freed when the call
+ * returns; the candidate buffers of a batch of selected rows as in hpf_recommend (<= 512 MB; HPF_LOO_BATCH makes the
+ * batches smaller).  No bit rows; nothing of size n_sel x rows. */
+typedef enum { HPF_SIM_COSINE = 0, HPF_SIM_DOT = 1 } hpf_similarity;
+int  hpf_similar(hpf_handle *h, int side, const uint32_t *ids, uint32_t n_sel,
+                 uint32_t topn, int metric, uint32_t *out_ids, double *out_scores);
+
 /* replaces: HGAPRec::test() (hgaprec.cc:2257-2346) -- load the item factors, put the user at the prior
  * (set_to_prior + set_to_prior_curr, 2278-2279), run user-side CAVI iterations over the user's ratings with the item
  * side untouched.  The handle's users are the NEW users: their ratings uploaded with hpf_upload_csr[_device] (val = NULL:
