@@ -832,6 +832,35 @@ int Ratings::write_marginals(const std::string &byusers, const std::string &byit
   return 0;
 }
 
+uint32_t Ratings::r(uint32_t u, uint32_t item) const
+{
+  uint32_t v = 0;                                // duplicates carry the same (last) value
+  for (int64_t j = rowptr[u]; j < rowptr[u + 1]; ++j) if (col[(size_t)j] == item) v = val[(size_t)j];
+  return v;
+}
+
+uint32_t Ratings::ranked_items(uint32_t u) const
+{
+  std::vector<uint32_t> seen;
+  for (int64_t j = rowptr[u]; j < rowptr[u + 1]; ++j) if (val[(size_t)j] > 0) seen.push_back(col[(size_t)j]);
+  std::sort(seen.begin(), seen.end());
+  return m - (uint32_t)(std::unique(seen.begin(), seen.end()) - seen.begin());
+}
+
+const std::vector<uint32_t> &Ratings::item_degrees() const
+{
+  if (item_deg_.size() != m) { item_deg_.assign(m, 0); for (uint32_t c : col) item_deg_[c]++; }
+  return item_deg_;
+}
+
+size_t HeldOut::lower(uint32_t user, uint32_t item) const
+{
+  size_t a = 0, b = u.size();
+  while (a < b) { const size_t mid = (a + b) / 2;
+    if (u[mid] < user || (u[mid] == user && i[mid] < item)) a = mid + 1; else b = mid; }
+  return a;
+}
+
 // ======================================================================
 // MT19937 (Matsumoto & Nishimura; GSL's gsl_rng_mt19937 conventions)
 // ======================================================================
@@ -1377,6 +1406,22 @@ int shape_over_rate(double *E, uint32_t rows, uint32_t cols, const double *rate,
   return 0;
 }
 
+int gamma_expectations(double *E, double *Elog, const double *rate, size_t rows, size_t cols, bool rate_per_column,
+                       const std::string &rate_path, std::string *err)
+{
+  for (size_t i = 0; i < rows; ++i)
+    for (size_t c = 0; c < cols; ++c) {
+      const double sh = E[i * cols + c], rv = rate[rate_per_column ? c : i * cols + c];
+      if (!(sh > 0.0) || !(rv > 0.0)) {
+        if (err) *err = rate_path + ": a shape or a rate that is not > 0 (row " + std::to_string(i) + ")";
+        return -1;
+      }
+      E[i * cols + c] = sh / rv;
+      Elog[i * cols + c] = digamma(sh) - std::log(rv);
+    }
+  return 0;
+}
+
 // ======================================================================
 // stop rule (hgaprec.cc:1476-1492)
 // ======================================================================
@@ -1425,6 +1470,39 @@ void eval_from_ranks(const uint64_t *q_ptr, const uint32_t *rank, const uint32_t
     t.precision10 /= t.users; t.precision100 /= t.users; t.recall100 /= t.users; t.mrr /= t.users; t.meanrank /= t.users;
   }
   if (means) *means = t;
+}
+
+// ---- the loops of the reports
+void chunk_offsets(const uint64_t *ptr, size_t b0, size_t b1, std::vector<uint64_t> *out)
+{
+  out->resize(b1 - b0 + 1);
+  for (size_t b = b0; b <= b1; ++b) (*out)[b - b0] = ptr[b] - ptr[b0];
+}
+
+void MaskLists::fill(const HeldOut &ho, const uint32_t *list, size_t cnt, uint32_t lo, uint32_t hi, uint32_t rebase)
+{
+  users.clear(); items.clear(); ptr.assign(1, 0);
+  auto add = [&](uint32_t u) {
+    users.push_back(u - rebase);
+    for (size_t a = ho.lower(u, 0); a < ho.u.size() && ho.u[a] == u; ++a) items.push_back(ho.i[a]);
+    ptr.push_back(items.size());
+  };
+  if (!list) for (uint32_t u = lo; u < hi; ++u) add(u);
+  else for (size_t j = 0; j < cnt; ++j) if (list[j] >= lo && list[j] < hi) add(list[j]);
+}
+
+uint64_t write_topn(FILE *f, const uint32_t *sel, size_t n_sel, const uint32_t *items, const double *scores, uint32_t N, uint32_t real,
+                    const uint32_t *row_ids, const uint32_t *item_ids, const std::function<bool(uint32_t, uint32_t)> &keep)
+{
+  uint64_t lines = 0;
+  for (size_t b = 0; b < n_sel; ++b)
+    for (uint32_t j = 0; j < real && j < N; ++j) {
+      const uint32_t it = items[b * N + j];
+      if (keep && !keep(sel[b], it)) continue;
+      fprintf(f, "%d\t%d\t%.5f\n", row_ids[sel[b]], item_ids[it], scores[b * N + j]);
+      ++lines;
+    }
+  return lines;
 }
 
 

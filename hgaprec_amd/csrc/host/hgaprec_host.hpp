@@ -6,10 +6,13 @@
 //   Mt19937    the gsl_rng_default stream                    (hgaprec.cc:34-38)
 //   GammaInit  HGAPRec::initialize draw order                (hgaprec.cc:153-204, gpbase.hh:292-340,939-949)
 //   save_*     factor TSV writers                            (matrix.hh:725-744,1140-1166)
+//   reports    the loops the CLI's reports on a saved model share (chunk walk, mask lists, list writer)
 // The device side is reached only through include/hpf.h.
 #pragma once
+#include <algorithm>
 #include <cstdint>
 #include <cstdio>
+#include <functional>
 #include <string>
 #include <memory>
 #include <utility>
@@ -104,6 +107,7 @@ struct Env {
 struct HeldOut {          // std::map<Rating,int> flattened in key order
   std::vector<uint32_t> u, i;
   std::vector<int32_t> y;
+  size_t lower(uint32_t user, uint32_t item) const;   // the first pair that is not before (user, item)
 };
 
 struct Ratings {
@@ -135,6 +139,12 @@ struct Ratings {
   // ratings.cc:217-271
   int write_marginals(const std::string &byusers, const std::string &byitems,
                       uint32_t *longest_users, uint32_t *longest_items) const;
+  // the rating stored for (user u, item) in the training set, 0 if absent; of a duplicated pair the last one
+  uint32_t r(uint32_t u, uint32_t item) const;
+  // the items the reference counts as "ranked" for user u (r(u, item) == 0): m minus the distinct training items with a
+  // rating > 0 (compute_itemrank, hgaprec.cc:1628-1680)
+  uint32_t ranked_items(uint32_t u) const;
+  const std::vector<uint32_t> &item_degrees() const;   // _movies[item]->size(), counted at the first call
 
   // binary dataset image (extension): everything read_train + both
   // read_heldout calls produce.  dir = the -dir argument (source TSVs are
@@ -165,6 +175,7 @@ struct Ratings {
   uint32_t input_rating_class(uint32_t v) const;
   void build_csr();                            // tr_u_ / tr_i_ / tr_y_ -> rowptr, col, val (and frees the triples)
   std::vector<uint32_t> tr_u_, tr_i_, tr_y_;   // training triples in file order
+  mutable std::vector<uint32_t> item_deg_;
 };
 
 // ------------------------------------------------------------ MT19937 -----
@@ -248,6 +259,11 @@ int load_vector(const std::string &path, double *out, uint32_t rows,
 // without -hier: E[r][c] = shape[r][c] / rate[c] in place (GPMatrixGR::compute_expectations, gpbase.hh:755-764).  A
 // rate that is not finite and > 0, or a quotient that is not finite, returns -1 with *err = "<rate_path>: line c+1: ..."
 int shape_over_rate(double *E, uint32_t rows, uint32_t cols, const double *rate, const std::string &rate_path, std::string *err);
+// -fold-in: both Gamma expectations of a side read as shape and rate.  E holds the shapes on entry and shape / rate on
+// return, Elog = digamma(shape) - log(rate); the rate is one value per element, or per column (a K-vector).  A shape or a
+// rate that is not > 0 returns -1 with *err = "<rate_path>: a shape or a rate that is not > 0 (row r)"
+int gamma_expectations(double *E, double *Elog, const double *rate, size_t rows, size_t cols, bool rate_per_column,
+                       const std::string &rate_path, std::string *err);
 
 // ------------------------------------------- held-out series / stopping ---
 // HGAPRec::compute_likelihood bookkeeping (hgaprec.cc:1466-1500)
@@ -275,6 +291,32 @@ struct EvalMeans { uint64_t users, pairs; double precision10, precision100, reca
 // A user without a query (q_ptr[b] == q_ptr[b+1]) gets zeros and best_rank = 0 and adds 0 to every mean.
 void eval_from_ranks(const uint64_t *q_ptr, const uint32_t *rank, const uint32_t *nranked, size_t n_users,
                      EvalUser *per_user, EvalMeans *means);
+
+// ------------------------------------------- the loops of the reports -----
+// What the ranking reports of the CLI share.  A report ranks its rows a chunk at a time (host memory is O(chunk), one
+// library call per chunk): f(r0, r1) for the rows [r0, r1) of [0, rows), in order.
+constexpr size_t REPORT_CHUNK = 1u << 16;
+template <class F>
+void for_chunks(size_t rows, F &&f, size_t chunk = REPORT_CHUNK)
+{
+  for (size_t r0 = 0; r0 < rows; r0 += chunk) f(r0, std::min(rows, r0 + chunk));
+}
+// the offsets ptr[b0 .. b1] of a chunk, counted from the chunk's first entry (b1 - b0 + 1 of them)
+void chunk_offsets(const uint64_t *ptr, size_t b0, size_t b1, std::vector<uint64_t> *out);
+// The held-out items of a run of users in the form the ranking calls take (mask_ptr, mask_items; is_validation()): of
+// list[0 .. cnt) the users inside [lo, hi), in the list's order -- list == nullptr: every user of [lo, hi).  users holds
+// them minus `rebase` (a rank's local indices).
+struct MaskLists {
+  std::vector<uint32_t> users, items;
+  std::vector<uint64_t> ptr;
+  void fill(const HeldOut &ho, const uint32_t *list, size_t cnt, uint32_t lo, uint32_t hi, uint32_t rebase = 0);
+};
+// Top-N lists as lines "row id \t entry id \t %.5f": list b belongs to row sel[b] and has items[b * N + j], scores[b * N + j],
+// j < N, of which the first `real` exist (the rest is padding and never printed); ids through row_ids / item_ids.  Only
+// the entries keep(sel[b], item) accepts are written (no keep: all).  Returns the number of lines.
+uint64_t write_topn(FILE *f, const uint32_t *sel, size_t n_sel, const uint32_t *items, const double *scores, uint32_t N,
+                    uint32_t real, const uint32_t *row_ids, const uint32_t *item_ids,
+                    const std::function<bool(uint32_t, uint32_t)> &keep = nullptr);
 
 // ------------------------------------------------------------- Comm --------
 // Host-side collectives of a multi-process run (one process per GPU): a TCP

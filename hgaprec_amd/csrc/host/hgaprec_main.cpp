@@ -13,24 +13,19 @@
 // stand-in (`-comm host`, for tests on a single GPU).  The output files are
 // the same as in a single-GPU run.
 //
-// Scoring a saved model: -gen-ranking / -rmse / -msr / -eval-all / -recommend / -similar-items / -similar-users read the data like a training run, load
-// the factor files a run has written (from the current directory like the reference, or from
-// -model-dir DIR) into the handle's expectations, write ONE report and exit (Driver::score).  -fold-in FILE reads the
-// item side of those files as shape and rate and folds the users of FILE in on a second handle (Driver::fold_in_report).
+// Scoring a saved model (-gen-ranking / -rmse / -msr / -eval-all / -recommend / -fold-in / -similar-items /
+// -similar-users) sets the run up the same way and then writes ONE report instead of training: score(), score_modes.cpp.
+// What both halves share -- flags, ratings, handle, the ways to fail -- is struct Cli (hgaprec_cli.hpp).
 //
 // Out of scope: competitor bridges, MLE/Canny ablations, -test; their
 // flags are recognised and refused.
-#include "../../../include/hpf.h"
-#include "hgaprec_host.hpp"
+#include "hgaprec_cli.hpp"
 
 #include <algorithm>
 #include <cassert>
 #include <cmath>
 #include <chrono>
-#include <cerrno>
 #include <csignal>
-#include <cstdlib>
-#include <cstring>
 #include <ctime>
 #include <mutex>
 #include <set>
@@ -119,8 +114,8 @@ static void own_part(const std::string &p) {
   g_own_parts->insert(p);
 }
 
-struct Driver {
-  Env &env; Ratings &rt; Comm &comm; hpf_handle *h = nullptr;
+struct Driver : Cli {
+  Comm &comm;
   uint32_t n, m, k, iter = 0;          // n: ALL users; lo..hi: this rank's range
   uint32_t lo = 0, hi = 0;
   bool use_rccl = false;
@@ -130,36 +125,17 @@ struct Driver {
   StopRule stop;
   Mt19937 rng;                         // gsl_rng *_r: keeps running after initialize()
   std::vector<uint32_t> sampled;       // _sampled_users (std::map keys: sorted, unique), GLOBAL seq ids
-  std::vector<uint32_t> item_deg;      // _movies[m]->size()
   HeldOut lvalid, ltest;               // this rank's held-out pairs, LOCAL user indices
   std::vector<double> xbuf;            // host staging of the exchange buffer (-comm host)
   SaveBuf save_u[3], save_i[3];        // host copies of an object's shape / rate / expectation while they are written
   std::set<std::string> part_files;    // (rank 0, several ranks) files whose per-rank parts are lying beside them until the run ends
   std::thread save_prealloc;           // page-locking them (0.2 s per GB) runs beside the start state, not inside the first save
 
-  Driver(Env &e, Ratings &r, Comm &c) : env(e), rt(r), comm(c), n(r.n), m(r.m), k(e.k), start(time(0)) {}
+  Driver(Env &e, Ratings &r, Comm &c) : Cli(e, r, c.rank), comm(c), n(r.n), m(r.m), k(e.k), start(time(0)) {}
 
   bool root() const { return comm.rank == 0; }
   uint32_t duration() const { return (uint32_t)(time(0) - start); }      // hgaprec.hh:164-169
 
-  void die(const char *what, int rc) {
-    fprintf(stderr, "error: [rank %d] %s: %s (%s)\n", comm.rank, what, hpf_strerror(rc), h ? hpf_last_error(h) : "");
-    exit(-1);
-  }
-  // output failures are fatal and say which file: a truncated factor file or a
-  // missing part must never end in exit code 0
-  [[noreturn]] void io_die(const char *what, const std::string &path) {
-    fprintf(stderr, "error: [rank %d] %s %s: %s\n", comm.rank, what, path.c_str(), strerror(errno));
-    exit(-1);
-  }
-  FILE *open_or_die(const std::string &path, const char *mode) {
-    FILE *f = fopen(path.c_str(), mode);
-    if (!f) io_die("cannot open", path);
-    return f;
-  }
-  void close_or_die(FILE *f, const std::string &path) {
-    if (ferror(f) | fclose(f)) io_die("cannot write", path);
-  }
   void comm_check(int rc, const char *what) {
     if (rc) { fprintf(stderr, "error: [rank %d] %s: peer lost\n", comm.rank, what); exit(-1); }
   }
@@ -226,15 +202,7 @@ struct Driver {
     slice(rt.validation, lo, hi, &lvalid);
     slice(rt.test, lo, hi, &ltest);
 
-    hpf_config cfg; memset(&cfg, 0, sizeof cfg);
-    cfg.struct_size = sizeof cfg;
-    cfg.n_users = hi - lo; cfg.n_items = m; cfg.K = k;
-    cfg.hier = env.hier; cfg.bias = env.bias; cfg.binary = env.binary_data;
-    cfg.novb = env.vb ? 0u : 1u;              // read by the library only where the reference reads it (vb_bias)
-    cfg.tiling = env.no_tiles ? 1u : 0u;
-    cfg.w_storage = env.w48 ? 2u : env.plain_rows ? 3u : 0u; // 0 / 3: exact fp64 either way (3 = never pack the rows); 2: -w48, opt-in, lossy
-    cfg.n_users_total = n; cfg.device = env.device; cfg.n_ranks = (uint32_t)comm.world; cfg.rank = (uint32_t)comm.rank;
-    cfg.s_prior = 0.3; cfg.r_prior = 0.3;
+    const hpf_config cfg = config(hi - lo, n, (uint32_t)comm.world, (uint32_t)comm.rank);
     int rc = hpf_create(&cfg, &h);
     if (rc) die("hpf_create (is an MI355X visible? there is no CPU fallback)", rc);
     std::vector<int64_t> rp(rt.rowptr.begin() + lo, rt.rowptr.begin() + hi + 1);
@@ -275,10 +243,6 @@ struct Driver {
     g_clock.other();
     initialize_state(rng, n, m, k, env.hier, env.bias, &s, lo, hi);
     g_clock.mark("start state (MT19937, host)");
-    auto put = [&](hpf_state w, const StateArray &v) {
-      int rc = hpf_set_state(h, w, v.data(), v.size());
-      if (rc) die("hpf_set_state", rc);
-    };
     put(HPF_THETA_SHAPE, s.theta_shape); put(HPF_THETA_RATE, s.theta_rate);
     put(HPF_THETA_E, s.theta_E); put(HPF_THETA_ELOG, s.theta_Elog);
     put(HPF_BETA_SHAPE, s.beta_shape); put(HPF_BETA_RATE, s.beta_rate);
@@ -521,32 +485,8 @@ struct Driver {
   }
 
   // ---- ranking evaluation: compute_precision / compute_itemrank --------
-  bool test_hit(int v) const {                   // ratings.hh:183-189
-    return env.binary_data ? v >= 1 : (uint32_t)v >= env.rating_threshold;
-  }
-  // rating stored for (global user u, item it) in the training set, 0 if absent (Ratings::r)
-  uint32_t train_r(uint32_t u, uint32_t it) const {
-    uint32_t r = 0;                              // duplicates carry the same (last) value
-    for (int64_t j = rt.rowptr[u]; j < rt.rowptr[u + 1]; ++j) if (rt.col[(size_t)j] == it) r = rt.val[(size_t)j];
-    return r;
-  }
-  static size_t lower(const HeldOut &ho, uint32_t u, uint32_t i) {
-    size_t a = 0, b = ho.u.size();
-    while (a < b) { size_t mid = (a + b) / 2;
-      if (ho.u[mid] < u || (ho.u[mid] == u && ho.i[mid] < i)) a = mid + 1; else b = mid; }
-    return a;
-  }
   // this rank's part of the sampled users (local indices) + their validation items (is_validation())
-  void local_sample(std::vector<uint32_t> &lus, std::vector<uint64_t> &mptr, std::vector<uint32_t> &mitems) const {
-    lus.clear(); mitems.clear(); mptr.assign(1, 0);
-    for (uint32_t u : sampled) {
-      if (u < lo || u >= hi) continue;
-      lus.push_back(u - lo);
-      for (size_t a = lower(rt.validation, u, 0); a < rt.validation.u.size() && rt.validation.u[a] == u; ++a)
-        mitems.push_back(rt.validation.i[a]);
-      mptr.push_back(mitems.size());
-    }
-  }
+  MaskLists local_sample() const { MaskLists ml; ml.fill(rt.validation, sampled.data(), sampled.size(), lo, hi, lo); return ml; }
 
   void compute_precision(bool save_ranking_file) {          // hgaprec.cc:1703-1848
     if (iter % 100 == 0 && iter > 0) save_ranking_file = true;
@@ -561,10 +501,10 @@ struct Driver {
       } while (sampled.size() < 1000 && sampled.size() < n / 2);
     }
     const uint32_t N = 100;                      // _topN_by_user
-    std::vector<uint32_t> lus; std::vector<uint64_t> mptr; std::vector<uint32_t> mitems;
-    local_sample(lus, mptr, mitems);
+    const MaskLists ml = local_sample();
+    const std::vector<uint32_t> &lus = ml.users;
     std::vector<uint32_t> items(lus.size() * N); std::vector<double> scores(lus.size() * N);
-    int rc = hpf_rank_topn(h, lus.data(), (uint32_t)lus.size(), mptr.data(), mitems.data(), N,
+    int rc = hpf_rank_topn(h, lus.data(), (uint32_t)lus.size(), ml.ptr.data(), ml.items.data(), N,
                            items.data(), scores.data());
     if (rc) die("hpf_rank_topn", rc);
     double acc[3] = {0, 0, 0};                   // mhits10, mhits100, total_users
@@ -574,13 +514,13 @@ struct Driver {
       for (uint32_t j = 0; j < m && j < N; ++j) {
         const uint32_t it = items[b * N + j]; const double pred = scores[b * N + j];
         int v = 0;
-        const size_t a = lower(rt.test, u, it);
+        const size_t a = rt.test.lower(u, it);
         if (a < rt.test.u.size() && rt.test.u[a] == u && rt.test.i[a] == it) {
           v = test_hit(rt.test.y[a]) ? 1 : 0;
           if (j < 10) { if (v > 0) { hits10++; hits100++; } }
           else if (j < 100) { if (v > 0) hits100++; }
         }
-        if (f && train_r(u, it) == 0) fprintf(f, "%d\t%d\t%.5f\t%d\n", rt.seq2user[u], rt.seq2item[it], pred, v);
+        if (f && rt.r(u, it) == 0) fprintf(f, "%d\t%d\t%.5f\t%d\n", rt.seq2user[u], rt.seq2item[it], pred, v);
       }
       acc[0] += (double)hits10 / 10; acc[1] += (double)hits100 / 100; acc[2] += 1;
     }
@@ -599,29 +539,25 @@ struct Driver {
     if (!final) return;
     const std::string ipath = env.file_str("/itemrank.tsv");
     FILE *f = open_or_die(my_path(ipath), "w");
-    if (item_deg.empty()) { item_deg.assign(m, 0); for (uint32_t c : rt.col) item_deg[c]++; }
-    std::vector<uint32_t> lus; std::vector<uint64_t> mptr; std::vector<uint32_t> mitems;
-    local_sample(lus, mptr, mitems);
+    const std::vector<uint32_t> &item_deg = rt.item_degrees();
+    const MaskLists ml = local_sample();
+    const std::vector<uint32_t> &lus = ml.users;
     std::vector<uint32_t> qs, qi;                 // one query per test item that is a hit
     for (size_t b = 0; b < lus.size(); ++b) {
       const uint32_t u = lus[b] + lo;
-      for (size_t a = lower(rt.test, u, 0); a < rt.test.u.size() && rt.test.u[a] == u; ++a)
+      for (size_t a = rt.test.lower(u, 0); a < rt.test.u.size() && rt.test.u[a] == u; ++a)
         if (test_hit(rt.test.y[a])) { qs.push_back((uint32_t)b); qi.push_back(rt.test.i[a]); }
     }
     std::vector<uint32_t> rank(qs.size()); std::vector<double> pred(qs.size());
-    int rc = hpf_item_ranks(h, lus.data(), (uint32_t)lus.size(), mptr.data(), mitems.data(),
+    int rc = hpf_item_ranks(h, lus.data(), (uint32_t)lus.size(), ml.ptr.data(), ml.items.data(),
                             qs.data(), qi.data(), (uint32_t)qs.size(), rank.data(), pred.data());
     if (rc) die("hpf_item_ranks", rc);
     double acc[3] = {0, 0, 0};                   // sum_rank, sum_reciprocal_rank, total_users
-    std::vector<uint32_t> ord, seen;
+    std::vector<uint32_t> ord;
     for (size_t b = 0, q0 = 0; b < lus.size(); ++b) {
       size_t q1 = q0; while (q1 < qs.size() && qs[q1] == b) ++q1;
       const uint32_t u = lus[b] + lo;
-      // items the reference counts as "ranked": Ratings::r(n,m) == 0
-      seen.clear();
-      for (int64_t j = rt.rowptr[u]; j < rt.rowptr[u + 1]; ++j) if (rt.val[(size_t)j] > 0) seen.push_back(rt.col[(size_t)j]);
-      std::sort(seen.begin(), seen.end());
-      const uint32_t nranked = m - (uint32_t)(std::unique(seen.begin(), seen.end()) - seen.begin());
+      const uint32_t nranked = rt.ranked_items(u);
       ord.resize(q1 - q0);
       for (size_t t = 0; t < ord.size(); ++t) ord[t] = (uint32_t)(q0 + t);
       std::sort(ord.begin(), ord.end(), [&](uint32_t x, uint32_t y) { return rank[x] < rank[y]; });
@@ -665,405 +601,6 @@ struct Driver {
 
   void do_on_stop() { save_model(); gen_ranking_for_users(); }          // hgaprec.cc:1572-1577
 
-  // ---- scoring a saved model: -gen-ranking, -rmse, -msr (one GPU) --------
-  std::string model_path(const char *name) const { return (env.model_dir.empty() ? std::string(".") : env.model_dir) + "/" + name; }
-  [[noreturn]] void model_die(const std::string &msg) {
-    fprintf(stderr, "error: cannot load the model: %s\n", msg.c_str());
-    exit(1);
-  }
-  // HGAPRec::load_beta_and_theta (hgaprec.cc:2114-2135): the expectations of the factor files into the handle's *_E.
-  // -hier: htheta.tsv / hbeta.tsv hold E; without: E = shape / rate[k], as GPMatrixGR::load -> compute_expectations
-  // does (gpbase.hh:755-764); -bias: the one value column of thetabias.tsv / betabias.tsv.  thetarate.tsv / betarate.tsv
-  // are read when they are there (scoring never touches them).  Stricter than the reference (hgaprec_host.cpp,
-  // load_matrix): a missing file, a short file, a short row, or ids that are not those of the ratings just read stop the run.
-  void load_model() {
-    auto put = [&](hpf_state w, const std::vector<double> &v) {
-      int rc = hpf_set_state(h, w, v.data(), v.size());
-      if (rc) die("hpf_set_state", rc);
-    };
-    std::string err;
-    auto side = [&](bool user_side) {
-      const uint32_t rows = user_side ? n : m;
-      const std::vector<uint32_t> &ids = user_side ? rt.seq2user : rt.seq2item;
-      const std::string base = env.hier ? (user_side ? "htheta" : "hbeta") : (user_side ? "theta" : "beta");
-      std::vector<double> E((size_t)rows * k);
-      if (env.hier) {
-        if (load_matrix(model_path((base + ".tsv").c_str()), E.data(), rows, k, ids.data(), (uint32_t)ids.size(), &err)) model_die(err);
-      } else {
-        std::vector<double> rate(k);
-        if (load_matrix(model_path((base + "_shape.tsv").c_str()), E.data(), rows, k, ids.data(), (uint32_t)ids.size(), &err)) model_die(err);
-        const std::string rate_path = model_path((base + "_rate.tsv").c_str());
-        if (load_vector(rate_path, rate.data(), k, nullptr, 0, &err)) model_die(err);   // a K-vector: its id column is seq2id[k]
-        if (shape_over_rate(E.data(), rows, k, rate.data(), rate_path, &err)) model_die(err);   // a zero rate would rank the item first
-      }
-      put(user_side ? HPF_THETA_E : HPF_BETA_E, E);
-      if (env.hier) {
-        const std::string rp = model_path(user_side ? "thetarate.tsv" : "betarate.tsv");
-        if (access(rp.c_str(), R_OK) == 0) {
-          std::vector<double> v(rows);
-          if (load_vector(rp, v.data(), rows, ids.data(), (uint32_t)ids.size(), &err)) model_die(err);
-          put(user_side ? HPF_XI_E : HPF_ETA_E, v);
-        }
-      }
-      if (env.bias) {
-        std::vector<double> v(rows);
-        if (load_vector(model_path(user_side ? "thetabias.tsv" : "betabias.tsv"), v.data(), rows, ids.data(), (uint32_t)ids.size(), &err)) model_die(err);
-        put(user_side ? HPF_UBIAS_E : HPF_IBIAS_E, v);
-      }
-    };
-    side(false);
-    side(true);
-    env.lerr("loaded the model from %s", env.model_dir.empty() ? "." : env.model_dir.c_str());
-  }
-
-  // HGAPRec::compute_rmse (hgaprec.cc:1579-1604).  DEVIATION: the reference's -rmse never loads the model (main.cc:254-257
-  // constructs and calls compute_rmse; load_beta_and_theta() is commented out at hgaprec.cc:1587), so it scores the empty
-  // start objects.  This build loads the model first.
-  void compute_rmse() {
-    const HeldOut &ho = rt.test;
-    std::vector<double> pred(ho.u.size());
-    int rc = hpf_predict(h, ho.u.data(), ho.i.data(), ho.u.size(), pred.data());
-    if (rc) die("hpf_predict", rc);
-    const std::string spath = env.file_str("/test_scores.tsv");
-    FILE *f = open_or_die(spath, "w");
-    double s = .0;
-    for (size_t p = 0; p < pred.size(); ++p) {                // map order, summed serially
-      const uint8_t v = (uint8_t)ho.y[p];                     // yval_t v = i->second
-      const double u = pred[p];
-      s += (u - v) * (u - v);
-      fprintf(f, "%d\t%.5f\n", v, u);
-    }
-    close_or_die(f, spath);
-    const std::string rpath = env.file_str("/rmse.txt");
-    FILE *rf = open_or_die(rpath, "w");
-    fprintf(rf, "%.5f\n", sqrt(s / pred.size()));
-    close_or_die(rf, rpath);
-  }
-
-  // HGAPRec::gen_msr_csv (hgaprec.cc:1993-2085): per user, where the held-out item -- the LAST test pair of the user in
-  // (user, item) order, hgaprec.cc:140-145 -- stands among the items [0, m - 1) (the reference's loop never scores item
-  // m - 1).  The reference asserts on a user without a test pair; here the run stops before pred.csv exists.
-  void gen_msr_csv() {
-    std::vector<uint32_t> heldout(n, 0xffffffffu);
-    for (size_t p = 0; p < rt.test.u.size(); ++p) heldout[rt.test.u[p]] = rt.test.i[p];     // sorted by (user, item): the last one stays
-    for (uint32_t u = 0; u < n; ++u)
-      if (heldout[u] == 0xffffffffu) {
-        fprintf(stderr, "error: -msr: user %u (seq %u) has no pair in test.tsv\n", rt.seq2user[u], u);
-        exit(1);
-      }
-    if (item_deg.empty()) { item_deg.assign(m, 0); for (uint32_t c : rt.col) item_deg[c]++; }
-    std::vector<uint32_t> valid_users(m, 0);                 // _validation_users_of_movie
-    for (uint32_t it : rt.validation.i) valid_users[it]++;
-    std::vector<uint32_t> rank(n), masked(n);                // O(n) results; the scores of a chunk never leave the device
-    std::vector<double> sc;
-    const uint32_t limit = m - 1, CH = 1u << 16;
-    std::vector<uint32_t> us; std::vector<uint64_t> mptr; std::vector<uint32_t> mitems;
-    // m == 1: the reference's loop over [0, m - 1) scores nothing and leaves rank 0 (a limit of 0 would mean "all items")
-    for (uint32_t u0 = 0; u0 < n && limit > 0; u0 += CH) {
-      const uint32_t u1 = std::min(n, u0 + CH);
-      us.clear(); mitems.clear(); mptr.assign(1, 0);
-      for (uint32_t u = u0; u < u1; ++u) {
-        us.push_back(u);
-        for (size_t a = lower(rt.validation, u, 0); a < rt.validation.u.size() && rt.validation.u[a] == u; ++a)
-          mitems.push_back(rt.validation.i[a]);
-        mptr.push_back(mitems.size());
-      }
-      sc.resize(us.size());
-      int rc = hpf_loo_ranks(h, us.data(), (uint32_t)us.size(), mptr.data(), mitems.data(), heldout.data() + u0, limit,
-                             rank.data() + u0, sc.data(), masked.data() + u0);
-      if (rc) die("hpf_loo_ranks", rc);
-    }
-    const std::string path = env.file_str("/pred.csv");
-    FILE *f = open_or_die(path, "w");
-    fprintf(f, "User\tHeldOutItem\tHeldOutItemIndex\tUserNegatives\tUserCount\tItemCount\n");
-    for (uint32_t u = 0; u < n; ++u) {
-      const uint32_t t = heldout[u], training = masked[u], negatives = limit - masked[u];
-      fprintf(f, "%d\t%d\t%d\t%d\t%d\t%d\n", rt.seq2user[u], rt.seq2item[t], rank[u], negatives, training,
-              valid_users[t] + item_deg[t]);
-    }
-    close_or_die(f, path);
-  }
-
-  // -eval-all (extension): compute_itemrank's question -- where does each test item that is a hit stand in its user's
-  // full item order, training items with a rating > 0 and validation items zeroed -- for EVERY user with such an item
-  // instead of a sample, through hpf_rank_queries (the user's scores are computed once for all its items, and no score
-  // reaches memory).  itemrank_all.tsv has itemrank.tsv's lines; eval_users.tsv the integers per user; eval_all.txt the
-  // means (eval_from_ranks, hgaprec_host.hpp).
-  void eval_all_report() {
-    if (item_deg.empty()) { item_deg.assign(m, 0); for (uint32_t c : rt.col) item_deg[c]++; }
-    std::vector<uint32_t> eu;                                 // evaluated users, seq order
-    std::vector<uint64_t> qptr(1, 0); std::vector<uint32_t> qi;
-    for (uint32_t u = 0; u < n; ++u) {
-      for (size_t a = lower(rt.test, u, 0); a < rt.test.u.size() && rt.test.u[a] == u; ++a)
-        if (test_hit(rt.test.y[a])) qi.push_back(rt.test.i[a]);
-      if (qi.size() > qptr.back()) { eu.push_back(u); qptr.push_back(qi.size()); }
-    }
-    std::vector<uint32_t> rank(qi.size()); std::vector<double> pred(qi.size());
-    const uint32_t CH = 1u << 16;
-    std::vector<uint64_t> mptr, cq; std::vector<uint32_t> mitems;
-    for (size_t b0 = 0; b0 < eu.size(); b0 += CH) {
-      const size_t b1 = std::min(eu.size(), b0 + CH);
-      mitems.clear(); mptr.assign(1, 0); cq.clear();
-      for (size_t b = b0; b < b1; ++b) {
-        const uint32_t u = eu[b];
-        for (size_t a = lower(rt.validation, u, 0); a < rt.validation.u.size() && rt.validation.u[a] == u; ++a)
-          mitems.push_back(rt.validation.i[a]);
-        mptr.push_back(mitems.size());
-        cq.push_back(qptr[b] - qptr[b0]);
-      }
-      cq.push_back(qptr[b1] - qptr[b0]);
-      int rc = hpf_rank_queries(h, eu.data() + b0, (uint32_t)(b1 - b0), mptr.data(), mitems.data(), cq.data(),
-                                qi.data() + qptr[b0], rank.data() + qptr[b0], pred.data() + qptr[b0]);
-      if (rc) die("hpf_rank_queries", rc);
-    }
-    std::vector<uint32_t> nranked(eu.size()), seen;
-    for (size_t b = 0; b < eu.size(); ++b) {                  // Ratings::r(n,m) == 0, as in compute_itemrank
-      const uint32_t u = eu[b];
-      seen.clear();
-      for (int64_t j = rt.rowptr[u]; j < rt.rowptr[u + 1]; ++j) if (rt.val[(size_t)j] > 0) seen.push_back(rt.col[(size_t)j]);
-      std::sort(seen.begin(), seen.end());
-      nranked[b] = m - (uint32_t)(std::unique(seen.begin(), seen.end()) - seen.begin());
-    }
-    std::vector<EvalUser> pu(eu.size()); EvalMeans mean;
-    eval_from_ranks(qptr.data(), rank.data(), nranked.data(), eu.size(), pu.data(), &mean);
-
-    const std::string ipath = env.file_str("/itemrank_all.tsv"), upath = env.file_str("/eval_users.tsv"),
-                      apath = env.file_str("/eval_all.txt");
-    FILE *f = open_or_die(ipath, "w"), *uf = open_or_die(upath, "w");
-    std::vector<uint64_t> ord;
-    for (size_t b = 0; b < eu.size(); ++b) {
-      const uint32_t u = eu[b];
-      ord.resize(qptr[b + 1] - qptr[b]);
-      for (size_t t = 0; t < ord.size(); ++t) ord[t] = qptr[b] + t;
-      std::stable_sort(ord.begin(), ord.end(), [&](uint64_t x, uint64_t y) { return rank[x] < rank[y]; });
-      for (uint64_t q : ord) fprintf(f, "%d\t%d\t%.5f\t%d\t%d\n", u, qi[q], pred[q], rank[q], item_deg[qi[q]]);
-      fprintf(uf, "%u\t%u\t%u\t%u\t%u\t%u\t%llu\n", u, rt.seq2user[u], pu[b].ntest, pu[b].hits10, pu[b].hits100,
-              pu[b].best_rank, (unsigned long long)pu[b].sum_rank);
-    }
-    close_or_die(f, ipath);
-    close_or_die(uf, upath);
-    FILE *af = open_or_die(apath, "w");
-    fprintf(af, "%llu\t%llu\t%.5f\t%.5f\t%.5f\t%.5f\t%.5f\n", (unsigned long long)mean.users, (unsigned long long)mean.pairs,
-            mean.precision10, mean.precision100, mean.recall100, mean.mrr, mean.meanrank);
-    close_or_die(af, apath);
-    env.lerr("-eval-all: %llu users, %llu test items ranked", (unsigned long long)mean.users, (unsigned long long)mean.pairs);
-  }
-
-  // -recommend N (extension): what a recommender is for -- the N best items of EVERY user, training items with a
-  // rating > 0 and the user's validation items zeroed exactly as compute_precision zeroes them for its sample -- through
-  // hpf_recommend (no score reaches memory up to N = 256).  recommend.tsv has the first three columns of ranking.tsv under
-  // ranking.tsv's rule (train_r(u, it) == 0; the padding beyond m items is never printed), users in seq order;
-  // recommend.txt users, lines and N.  A chunk of users is written before the next is ranked: host memory is O(chunk x N).
-  void recommend_report() {
-    const uint32_t N = env.recommend, CH = 1u << 16;
-    const std::string rpath = env.file_str("/recommend.tsv"), cpath = env.file_str("/recommend.txt");
-    FILE *f = open_or_die(rpath, "w");
-    std::vector<uint32_t> us, mitems, items; std::vector<uint64_t> mptr; std::vector<double> scores;
-    unsigned long long lines = 0;
-    for (uint32_t u0 = 0; u0 < n; u0 += CH) {
-      const uint32_t u1 = std::min(n, u0 + CH);
-      us.clear(); mitems.clear(); mptr.assign(1, 0);
-      for (uint32_t u = u0; u < u1; ++u) {
-        us.push_back(u);
-        for (size_t a = lower(rt.validation, u, 0); a < rt.validation.u.size() && rt.validation.u[a] == u; ++a)
-          mitems.push_back(rt.validation.i[a]);
-        mptr.push_back(mitems.size());
-      }
-      items.resize(us.size() * (size_t)N); scores.resize(us.size() * (size_t)N);
-      int rc = hpf_recommend(h, us.data(), (uint32_t)us.size(), mptr.data(), mitems.data(), N, items.data(), scores.data());
-      if (rc) die("hpf_recommend", rc);
-      for (size_t b = 0; b < us.size(); ++b) {
-        const uint32_t u = us[b];
-        for (uint32_t j = 0; j < m && j < N; ++j) {
-          const uint32_t it = items[b * N + j];
-          if (train_r(u, it) == 0) { fprintf(f, "%d\t%d\t%.5f\n", rt.seq2user[u], rt.seq2item[it], scores[b * N + j]); ++lines; }
-        }
-      }
-    }
-    close_or_die(f, rpath);
-    FILE *cf = open_or_die(cpath, "w");
-    fprintf(cf, "%u\t%llu\t%u\n", n, lines, N);
-    close_or_die(cf, cpath);
-    env.lerr("-recommend: %u users, %llu lines in recommend.tsv", n, lines);
-  }
-
-  // -similar-items N / -similar-users N (extension): "more like this item" and "users like this one" -- the N nearest other
-  // rows of E[beta] (E[theta]) to every row, by cosine or dot product over the K factor columns, through hpf_similar.
-  // similar_items.tsv: item id, neighbour item id, score -- items in seq order, each list best first, ids and score printed
-  // as recommend.tsv prints them, the padding of a list beyond rows - 1 never printed; similar_items.txt: rows, lines, N,
-  // metric.  similar_users.* the same for users.  A chunk of rows is written before the next is ranked.
-  void similar_report(bool items) {
-    const uint32_t N = items ? env.similar_items : env.similar_users, CH = 1u << 16;
-    const uint32_t rows = items ? m : n;
-    const std::vector<uint32_t> &ids = items ? rt.seq2item : rt.seq2user;
-    const int metric = env.similar_metric == "dot" ? HPF_SIM_DOT : HPF_SIM_COSINE;
-    const std::string base = items ? "/similar_items" : "/similar_users";
-    const std::string rpath = env.file_str(base + ".tsv"), cpath = env.file_str(base + ".txt");
-    FILE *f = open_or_die(rpath, "w");
-    std::vector<uint32_t> sel, nb; std::vector<double> scores;
-    unsigned long long lines = 0;
-    for (uint32_t r0 = 0; r0 < rows; r0 += CH) {
-      const uint32_t r1 = std::min(rows, r0 + CH);
-      sel.clear();
-      for (uint32_t r = r0; r < r1; ++r) sel.push_back(r);
-      nb.resize(sel.size() * (size_t)N); scores.resize(sel.size() * (size_t)N);
-      int rc = hpf_similar(h, items ? 1 : 0, sel.data(), (uint32_t)sel.size(), N, metric, nb.data(), scores.data());
-      if (rc) die("hpf_similar", rc);
-      for (size_t b = 0; b < sel.size(); ++b)
-        for (uint32_t j = 0; j + 1 < rows && j < N; ++j) {
-          fprintf(f, "%d\t%d\t%.5f\n", ids[sel[b]], ids[nb[b * N + j]], scores[b * N + j]);
-          ++lines;
-        }
-    }
-    close_or_die(f, rpath);
-    FILE *cf = open_or_die(cpath, "w");
-    fprintf(cf, "%u\t%llu\t%u\t%s\n", rows, lines, N, env.similar_metric.c_str());
-    close_or_die(cf, cpath);
-    env.lerr("-similar-%s: %u rows, %llu lines in %s.tsv", items ? "items" : "users", rows, lines, base.c_str() + 1);
-  }
-
-  // -fold-in FILE (extension; HGAPRec::test(), hgaprec.cc:2257-2346): the users of FILE, who need not be in -dir, folded
-  // into the saved model.  The item side comes from -model-dir as SHAPE and RATE (E alone does not give Elog) through the
-  // strict readers; the host forms E = shape / rate and Elog = psi(shape) - log(rate) and hands them to a second handle
-  // that holds the new users; hpf_fold_in runs -fold-iters iterations from the prior (-fold-tol: a stopping time per
-  // user).  Output: the user-side files of save_model under the prefix foldin_, through the same writers; foldin.txt
-  // (users, nonzeros, lines skipped for an unknown item, T, X, iterations min / mean / max); with -recommend N also
-  // foldin_recommend.tsv / .txt, recommend_report's lines for the new users with their given ratings masked.
-  void fold_in_report() {
-    Ratings nu; uint64_t skipped = 0;
-    const int frc = rt.read_fold_in(env.fold_in, &nu, &skipped);
-    if (frc) { fprintf(stderr, "error: -fold-in: cannot %s %s\n", frc == -1 ? "open" : "parse", env.fold_in.c_str()); exit(1); }
-    std::string err;
-    const std::vector<uint32_t> &iid = rt.seq2item;
-    std::vector<double> E((size_t)m * k), L((size_t)m * k), rate(env.hier ? (size_t)m * k : (size_t)k);
-    const std::string base = env.hier ? "hbeta" : "beta";
-    const std::string rate_path = model_path((base + "_rate.tsv").c_str());
-    if (load_matrix(model_path((base + "_shape.tsv").c_str()), E.data(), m, k, iid.data(), (uint32_t)iid.size(), &err)) model_die(err);
-    if (env.hier ? load_matrix(rate_path, rate.data(), m, k, iid.data(), (uint32_t)iid.size(), &err)
-                 : load_vector(rate_path, rate.data(), k, nullptr, 0, &err)) model_die(err);
-    auto expectations = [&](double *e, double *l, const double *r, size_t rows, size_t cols, bool vec, const std::string &what) {
-      for (size_t i = 0; i < rows; ++i)
-        for (size_t c = 0; c < cols; ++c) {
-          const double sh = e[i * cols + c], rv = r[vec ? c : i * cols + c];
-          if (!(sh > 0.0) || !(rv > 0.0)) model_die(what + ": a shape or a rate that is not > 0 (row " + std::to_string(i) + ")");
-          e[i * cols + c] = sh / rv;
-          l[i * cols + c] = digamma(sh) - std::log(rv);
-        }
-    };
-    expectations(E.data(), L.data(), rate.data(), m, k, !env.hier, rate_path);
-    std::vector<double> bE, bL;
-    if (env.bias) {
-      bE.resize(m); bL.resize(m);
-      std::vector<double> br(m);
-      const std::string bp = model_path("betabias_rate.tsv");
-      if (load_matrix(model_path("betabias_shape.tsv"), bE.data(), m, 1, iid.data(), (uint32_t)iid.size(), &err)) model_die(err);
-      if (load_matrix(bp, br.data(), m, 1, iid.data(), (uint32_t)iid.size(), &err)) model_die(err);
-      expectations(bE.data(), bL.data(), br.data(), m, 1, false, bp);
-    }
-    env.lerr("-fold-in: item side loaded from %s", env.model_dir.empty() ? "." : env.model_dir.c_str());
-
-    hpf_handle *train = h;                       // die() reports the handle in h
-    hpf_config cfg; memset(&cfg, 0, sizeof cfg);
-    cfg.struct_size = sizeof cfg;
-    cfg.n_users = nu.n; cfg.n_items = m; cfg.K = k;
-    cfg.hier = env.hier; cfg.bias = env.bias; cfg.binary = env.binary_data;
-    cfg.n_users_total = nu.n; cfg.device = env.device; cfg.n_ranks = 1; cfg.rank = 0;
-    cfg.tiling = env.no_tiles ? 1u : 0u;
-    cfg.w_storage = env.w48 ? 2u : env.plain_rows ? 3u : 0u;
-    cfg.s_prior = 0.3; cfg.r_prior = 0.3;
-    h = nullptr;
-    int rc = hpf_create(&cfg, &h);
-    if (rc) die("hpf_create (-fold-in)", rc);
-    rc = hpf_upload_csr(h, nu.rowptr.data(), nu.col.data(), env.binary_data ? nullptr : nu.val.data());
-    if (rc) die("hpf_upload_csr (-fold-in)", rc);
-    auto put = [&](hpf_state w, const std::vector<double> &v) {
-      const int r2 = hpf_set_state(h, w, v.data(), v.size());
-      if (r2) die("hpf_set_state", r2);
-    };
-    put(HPF_BETA_E, E); put(HPF_BETA_ELOG, L);
-    if (env.bias) { put(HPF_IBIAS_E, bE); put(HPF_IBIAS_ELOG, bL); }
-    std::vector<uint32_t> iters(nu.n);
-    rc = hpf_fold_in(h, env.fold_iters, env.fold_tol, iters.data());
-    if (rc) die("hpf_fold_in", rc);
-
-    // the user-side files of save_model, prefix foldin_
-    const std::vector<uint32_t> &uid = nu.seq2user;
-    std::vector<double> buf;
-    auto write = [&](const std::string &name, hpf_state w, uint32_t rows, uint32_t cols, bool as_vector) {
-      buf.resize((size_t)rows * cols);
-      const int r2 = hpf_get_state(h, w, buf.data(), buf.size());
-      if (r2) die("hpf_get_state", r2);
-      const std::string path = env.file_str("/foldin_" + name);
-      if (as_vector ? save_vector(path, buf.data(), rows, uid.data(), (uint32_t)uid.size())
-                    : save_matrix(path, buf.data(), rows, cols, uid.data(), (uint32_t)uid.size())) io_die("cannot write", path);
-    };
-    const char *suf[3] = {"_shape.tsv", "_rate.tsv", ".tsv"};
-    const std::string tb = env.hier ? "htheta" : "theta";
-    for (int j = 0; j < 3; ++j) {
-      if (j == 1 && !env.hier) write(tb + suf[j], HPF_THETA_RATE, k, 1, true);      // GPMatrixGR rate: the K-vector
-      else write(tb + suf[j], (hpf_state)(HPF_THETA_SHAPE + j), nu.n, k, false);
-      if (env.hier) write(std::string("thetarate") + suf[j], (hpf_state)(HPF_XI_SHAPE + j), nu.n, 1, true);
-      if (env.bias) write(std::string("thetabias") + suf[j], (hpf_state)(HPF_UBIAS_SHAPE + j), nu.n, 1, false);
-    }
-    uint32_t imin = 0, imax = 0; double isum = 0;
-    for (uint32_t u = 0; u < nu.n; ++u) { imin = u ? std::min(imin, iters[u]) : iters[u]; imax = std::max(imax, iters[u]); isum += iters[u]; }
-    const std::string cpath = env.file_str("/foldin.txt");
-    FILE *cf = open_or_die(cpath, "w");
-    fprintf(cf, "%u\t%llu\t%llu\t%u\t%g\t%u\t%.5f\t%u\n", nu.n, (unsigned long long)nu.col.size(), (unsigned long long)skipped,
-            env.fold_iters, env.fold_tol, imin, nu.n ? isum / nu.n : 0.0, imax);
-    close_or_die(cf, cpath);
-    env.lerr("-fold-in: %u users, %llu ratings, %llu lines skipped (unknown item), iterations %u .. %u", nu.n,
-             (unsigned long long)nu.col.size(), (unsigned long long)skipped, imin, imax);
-
-    if (env.recommend) {
-      const uint32_t N = env.recommend, CH = 1u << 16;
-      const std::string rpath = env.file_str("/foldin_recommend.tsv"), tpath = env.file_str("/foldin_recommend.txt");
-      FILE *f = open_or_die(rpath, "w");
-      std::vector<uint32_t> us, items; std::vector<uint64_t> mptr; std::vector<double> scores;
-      unsigned long long lines = 0;
-      for (uint32_t u0 = 0; u0 < nu.n; u0 += CH) {
-        const uint32_t u1 = std::min(nu.n, u0 + CH);
-        us.clear();
-        for (uint32_t u = u0; u < u1; ++u) us.push_back(u);
-        mptr.assign(us.size() + 1, 0);               // no list beyond the given ratings, which the call masks itself
-        items.resize(us.size() * (size_t)N); scores.resize(us.size() * (size_t)N);
-        rc = hpf_recommend(h, us.data(), (uint32_t)us.size(), mptr.data(), nullptr, N, items.data(), scores.data());
-        if (rc) die("hpf_recommend", rc);
-        for (size_t b = 0; b < us.size(); ++b) {
-          const uint32_t u = us[b];
-          for (uint32_t j = 0; j < m && j < N; ++j) {
-            const uint32_t it = items[b * N + j];
-            uint32_t given = 0;
-            for (int64_t q = nu.rowptr[u]; q < nu.rowptr[u + 1]; ++q) if (nu.col[(size_t)q] == it) given = nu.val[(size_t)q];
-            if (given == 0) { fprintf(f, "%d\t%d\t%.5f\n", uid[u], rt.seq2item[it], scores[b * N + j]); ++lines; }
-          }
-        }
-      }
-      close_or_die(f, rpath);
-      FILE *tf2 = open_or_die(tpath, "w");
-      fprintf(tf2, "%u\t%llu\t%u\n", nu.n, lines, N);
-      close_or_die(tf2, tpath);
-    }
-    hpf_destroy(h);
-    h = train;
-  }
-
-  // one report on the loaded state, in the reference's order of tests (main.cc:254-285, then -gen-ranking)
-  void score() {
-    if (!env.fold_in.empty()) { fold_in_report(); finish(0); return; }      // needs the item side only, as shape and rate
-    load_model();
-    if (env.rmse) compute_rmse();
-    else if (env.msr) gen_msr_csv();
-    else if (env.eval_all) eval_all_report();
-    else if (env.recommend) recommend_report();
-    else if (env.similar_items || env.similar_users) {
-      if (env.similar_items) similar_report(true);
-      if (env.similar_users) similar_report(false);
-    }
-    else gen_ranking_for_users();
-    finish(0);
-  }
-
   // the library moved the rows of W from the packed form to plain doubles (a state p59 cannot hold): say so once
   void note_fallback() {
     hpf_work_info wi;
@@ -1100,11 +637,7 @@ struct Driver {
     if (!validation) return false;
     int why = -1;
     const bool st = stop.update(iter, a, &why);   // same value on every rank => same decision
-    if (root()) {
-      FILE *f = open_or_die(env.file_str("/max.txt"), "w");
-      fprintf(f, "%d\t%d\t%.5f\t%d\n", iter, duration(), a, why);
-      close_or_die(f, env.file_str("/max.txt"));
-    }
+    if (root()) write_line(env.file_str("/max.txt"), "%d\t%d\t%.5f\t%d\n", iter, duration(), a, why);
     if (st) { g_clock.part_begin(); do_on_stop(); g_clock.part_end(4); return true; }
     return false;
   }
@@ -1436,7 +969,7 @@ int main(int argc, char **argv)
   Driver d(env, ratings, comm);
   d.use_rccl = world > 1 && env.comm_mode != "host";
   d.construct();
-  if (env.score_mode()) { d.score(); return 0; }             // one report on the loaded model: never the training loop
+  if (env.score_mode()) { score(d, [&]() { d.gen_ranking_for_users(); }); d.finish(0); }   // one report on the loaded model: never the training loop
   d.run();
   return 0;
 }

@@ -148,6 +148,63 @@ int hg_shape_over_rate(double *E, uint32_t rows, uint32_t cols, const double *ra
   return rc;
 }
 
+// E = shape / rate in place and Elog beside it, the rate per element or (per_column) a K-vector: 0, or -1 with the message
+int hg_gamma_expectations(double *E, double *Elog, const double *rate, uint64_t rows, uint64_t cols, int per_column,
+                          const char *rate_path, char *err, size_t errcap)
+{
+  std::string e;
+  const int rc = gamma_expectations(E, Elog, rate, (size_t)rows, (size_t)cols, per_column != 0, rate_path, &e);
+  if (err && errcap) { strncpy(err, e.c_str(), errcap - 1); err[errcap - 1] = 0; }
+  return rc;
+}
+
+// ---- the loops of the reports
+uint32_t hg_ratings_r(const Ratings *r, uint32_t u, uint32_t item) { return r->r(u, item); }
+uint32_t hg_ratings_ranked_items(const Ratings *r, uint32_t u) { return r->ranked_items(u); }
+const uint32_t *hg_ratings_item_degrees(const Ratings *r) { return r->item_degrees().data(); }
+// for_chunks: out[2 * j], out[2 * j + 1] = the j-th visit (as far as cap pairs go); chunk 0 = the default.  Returns the visits
+uint64_t hg_chunk_walk(uint64_t rows, uint64_t chunk, uint64_t *out, uint64_t cap)
+{
+  uint64_t cnt = 0;
+  auto visit = [&](size_t r0, size_t r1) { if (cnt < cap) { out[2 * cnt] = r0; out[2 * cnt + 1] = r1; } ++cnt; };
+  if (chunk) for_chunks((size_t)rows, visit, (size_t)chunk); else for_chunks((size_t)rows, visit);
+  return cnt;
+}
+void hg_chunk_offsets(const uint64_t *ptr, uint64_t b0, uint64_t b1, uint64_t *out)
+{
+  std::vector<uint64_t> v;
+  chunk_offsets(ptr, (size_t)b0, (size_t)b1, &v);
+  memcpy(out, v.data(), v.size() * sizeof(uint64_t));
+}
+// MaskLists::fill over the validation (which = 0) or test pairs; list may be NULL (the range [lo, hi))
+MaskLists *hg_mask_lists_new(const Ratings *r, int which, const uint32_t *list, uint64_t cnt, uint32_t lo, uint32_t hi, uint32_t rebase)
+{
+  MaskLists *ml = new MaskLists();
+  ml->fill(which ? r->test : r->validation, list, (size_t)cnt, lo, hi, rebase);
+  return ml;
+}
+void hg_mask_lists_free(MaskLists *ml) { delete ml; }
+// part 0 users (uint32), 1 ptr (uint64), 2 items (uint32): the elements, *p their address
+uint64_t hg_mask_lists_get(const MaskLists *ml, int part, const void **p)
+{
+  if (part == 1) { *p = ml->ptr.data(); return ml->ptr.size(); }
+  const std::vector<uint32_t> &v = part ? ml->items : ml->users;
+  *p = v.data();
+  return v.size();
+}
+// write_topn into a new file; given != NULL: only the entries with given->r(row, item) == 0, the rule of recommend.tsv.
+// Returns the lines, -1 when the file cannot be written
+int64_t hg_write_topn(const char *path, const Ratings *given, const uint32_t *sel, uint64_t n_sel, const uint32_t *items,
+                      const double *scores, uint32_t N, uint32_t real, const uint32_t *row_ids, const uint32_t *item_ids)
+{
+  FILE *f = fopen(path, "w");
+  if (!f) return -1;
+  std::function<bool(uint32_t, uint32_t)> keep;
+  if (given) keep = [given](uint32_t u, uint32_t it) { return given->r(u, it) == 0; };
+  const uint64_t lines = write_topn(f, sel, (size_t)n_sel, items, scores, N, real, row_ids, item_ids, keep);
+  return (ferror(f) | fclose(f)) ? -1 : (int64_t)lines;
+}
+
 // -eval-all's arithmetic from ranks to metrics.  per_user: n_users x 6 integers (ntest, hits10, hits100, best_rank,
 // sum_rank, nranked as given); means: users, pairs, precision@10, precision@100, recall@100, mrr, meanrank
 void hg_eval_from_ranks(const uint64_t *q_ptr, const uint32_t *rank, const uint32_t *nranked, uint64_t n_users,

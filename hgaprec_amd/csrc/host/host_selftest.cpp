@@ -451,6 +451,144 @@ static void test_loader()
   CHECK(shape_over_rate(E, 2, 2, rate, "beta_rate.tsv", &err) == 0 && E[0] == 0.5 && E[1] == 0.5 && E[2] == 1.5 && E[3] == 0.0);
 }
 
+// ---- the loops the reports share: chunk walk, mask lists, Ratings::r / ranked_items, list writer, expectations ----
+static void test_reports()
+{
+  // a dozen users by hand: user 1 and 5 and 8 have no validation item, user 2 has several and no training item, user 3 a
+  // duplicated pair (last rating 2), user 6 a stored rating of 0
+  const uint32_t n = 12, m = 9;
+  const std::vector<std::vector<std::pair<uint32_t, uint8_t>>> rows = {
+    {{0, 3}, {2, 1}, {5, 2}}, {{1, 1}}, {}, {{4, 5}, {7, 1}, {4, 2}}, {{0, 1}, {1, 1}, {2, 1}, {3, 1}}, {{8, 4}},
+    {{6, 0}, {7, 3}}, {{3, 2}}, {{0, 1}, {8, 1}}, {{5, 5}}, {{2, 2}, {3, 3}}, {{7, 1}}};
+  const std::vector<std::vector<uint32_t>> valid = {{1}, {}, {0, 4, 7}, {0}, {5, 6}, {}, {2}, {0, 1}, {}, {3}, {8}, {0}};
+  Ratings rt; rt.n = n; rt.m = m; rt.rowptr.assign(1, 0);
+  std::vector<std::vector<uint32_t>> dense(n, std::vector<uint32_t>(m, 0));
+  std::vector<uint32_t> deg(m, 0);
+  for (uint32_t u = 0; u < n; ++u) {
+    for (auto &e : rows[u]) { rt.col.push_back(e.first); rt.val.push_back(e.second); dense[u][e.first] = e.second; deg[e.first]++; }
+    rt.rowptr.push_back((int64_t)rt.col.size());
+    for (uint32_t it : valid[u]) { rt.validation.u.push_back(u); rt.validation.i.push_back(it); rt.validation.y.push_back(1); }
+    rt.seq2user.push_back(100 + 3 * u);
+  }
+  for (uint32_t i = 0; i < m; ++i) rt.seq2item.push_back(900 - i);
+
+  // Ratings::r, ranked_items, item_degrees against the dense matrix
+  for (uint32_t u = 0; u < n; ++u) {
+    uint32_t pos = 0;
+    for (uint32_t i = 0; i < m; ++i) { CHECK(rt.r(u, i) == dense[u][i]); pos += dense[u][i] > 0; }
+    CHECK(rt.ranked_items(u) == m - pos);
+  }
+  CHECK(rt.r(3, 4) == 2 && rt.ranked_items(2) == m && rt.ranked_items(6) == m - 1 && rt.item_degrees() == deg);
+
+  // the walk: every row once, in order; nothing for no rows; 65 536 rows a chunk unless told otherwise
+  for (size_t total : {(size_t)0, (size_t)1, (size_t)12, (size_t)13})
+    for (size_t ch : {(size_t)1, (size_t)3, (size_t)5, (size_t)12, (size_t)100}) {
+      size_t next = 0, visits = 0;
+      for_chunks(total, [&](size_t r0, size_t r1) { CHECK(r0 == next && r1 > r0 && r1 - r0 <= ch && r1 <= total); next = r1; ++visits; }, ch);
+      CHECK(next == total && visits == (total + ch - 1) / ch);
+    }
+  {
+    std::vector<std::pair<size_t, size_t>> seen;
+    for_chunks(70000, [&](size_t r0, size_t r1) { seen.push_back({r0, r1}); });
+    CHECK(seen.size() == 2 && seen[0] == std::make_pair((size_t)0, (size_t)65536) && seen[1] == std::make_pair((size_t)65536, (size_t)70000));
+  }
+
+  // mask lists and -eval-all's query offsets, chunk by chunk, put together again == the one-chunk result == the lists above
+  const std::vector<uint32_t> scattered = {9, 2, 4, 0, 11, 7, 2, 5};
+  for (int use_list = 0; use_list < 2; ++use_list) {
+    const size_t cnt = use_list ? scattered.size() : n;
+    auto user_at = [&](size_t b) { return use_list ? scattered[b] : (uint32_t)b; };
+    std::vector<uint64_t> qptr(1, 0);                       // 0, 1, 2, 0, 1, ... queries a user
+    for (size_t b = 0; b < cnt; ++b) qptr.push_back(qptr.back() + (user_at(b) + b) % 3);
+    MaskLists one;
+    one.fill(rt.validation, use_list ? scattered.data() : nullptr, use_list ? cnt : 0, 0, n);
+    CHECK(one.users.size() == cnt && one.ptr.size() == cnt + 1 && one.ptr[0] == 0);
+    for (size_t b = 0; b < cnt && b < one.users.size(); ++b) {
+      CHECK(one.users[b] == user_at(b));
+      CHECK(std::vector<uint32_t>(one.items.begin() + one.ptr[b], one.items.begin() + one.ptr[b + 1]) == valid[user_at(b)]);
+    }
+    for (size_t ch : {(size_t)1, (size_t)3, (size_t)5, (size_t)12, (size_t)64}) {
+      MaskLists cat, ml; std::vector<uint64_t> cq, catq(1, 0);
+      cat.ptr.assign(1, 0);
+      for_chunks(cnt, [&](size_t b0, size_t b1) {
+        if (use_list) ml.fill(rt.validation, scattered.data() + b0, b1 - b0, 0, n);
+        else ml.fill(rt.validation, nullptr, 0, (uint32_t)b0, (uint32_t)b1);
+        CHECK(ml.ptr.size() == b1 - b0 + 1 && ml.ptr[0] == 0 && ml.ptr.back() == ml.items.size());
+        cat.users.insert(cat.users.end(), ml.users.begin(), ml.users.end());
+        for (size_t j = 1; j < ml.ptr.size(); ++j) cat.ptr.push_back(cat.items.size() + ml.ptr[j]);
+        cat.items.insert(cat.items.end(), ml.items.begin(), ml.items.end());
+        chunk_offsets(qptr.data(), b0, b1, &cq);
+        CHECK(cq.size() == b1 - b0 + 1 && cq[0] == 0);
+        for (size_t j = 1; j < cq.size(); ++j) catq.push_back(qptr[b0] + cq[j]);
+      }, ch);
+      CHECK(cat.users == one.users && cat.ptr == one.ptr && cat.items == one.items && catq == qptr);
+    }
+  }
+  {
+    MaskLists ml;                                           // a rank's part of a sample: users outside [3, 9) dropped, the rest local
+    ml.fill(rt.validation, scattered.data(), scattered.size(), 3, 9, 3);
+    CHECK((ml.users == std::vector<uint32_t>{1, 4, 2}) && (ml.items == std::vector<uint32_t>{5, 6, 0, 1}) &&
+          (ml.ptr == std::vector<uint64_t>{0, 2, 4, 4}));
+  }
+
+  // the list writer: only the real entries, only what the predicate keeps, the line count
+  {
+    const uint32_t N = 4, bad = 0xffffffffu;
+    const std::vector<uint32_t> sel = {3, 0, 2};
+    for (uint32_t real : {0u, 2u, 4u, 9u}) {
+      const uint32_t shown = std::min(real, N);
+      std::vector<uint32_t> items = {4, 1, 7, 8, 5, 0, 6, 2, 3, 3, 0, 1};
+      std::vector<double> scores(items.size());
+      for (size_t e = 0; e < items.size(); ++e) { scores[e] = 1.0 / (double)(e + 3); if (e % N >= shown) items[e] = bad; }   // padding: never looked at
+      for (int with_keep = 0; with_keep < 2; ++with_keep) {
+        std::string want; uint64_t want_lines = 0; char line[96];
+        for (size_t b = 0; b < sel.size(); ++b)
+          for (uint32_t j = 0; j < shown; ++j) {
+            const uint32_t it = items[b * N + j];
+            if (with_keep && dense[sel[b]][it] != 0) continue;
+            snprintf(line, sizeof line, "%d\t%d\t%.5f\n", rt.seq2user[sel[b]], rt.seq2item[it], scores[b * N + j]);
+            want += line; ++want_lines;
+          }
+        FILE *f = fopen(path("topn.tsv").c_str(), "w");
+        CHECK(f != nullptr);
+        if (!f) continue;
+        const uint64_t lines = with_keep
+          ? write_topn(f, sel.data(), sel.size(), items.data(), scores.data(), N, real, rt.seq2user.data(), rt.seq2item.data(),
+                       [&](uint32_t u, uint32_t it) { return rt.r(u, it) == 0; })
+          : write_topn(f, sel.data(), sel.size(), items.data(), scores.data(), N, real, rt.seq2user.data(), rt.seq2item.data());
+        fclose(f);
+        CHECK(lines == want_lines && read_text(path("topn.tsv")) == want);
+        if (real == 4) CHECK(with_keep ? lines == 7 : lines == 12);     // (3,4), (3,7), (0,5), (0,0), (0,2) are training pairs
+      }
+    }
+  }
+
+  // Gamma expectations: the formula, the rate as a matrix and as a K-vector, the domain
+  {
+    const size_t R = 3, K = 2;
+    const double shape[6] = {0.3, 1.5, 2.0, 7.25, 1e-3, 40.0}, rmat[6] = {0.5, 2.0, 1.0, 3.5, 1e-2, 8.0}, rvec[2] = {0.75, 4.0};
+    std::string err;
+    for (int vec = 0; vec < 2; ++vec) {
+      double E[6], L[6];
+      memcpy(E, shape, sizeof E);
+      CHECK(gamma_expectations(E, L, vec ? rvec : rmat, R, K, vec != 0, "hbeta_rate.tsv", &err) == 0);
+      for (size_t e = 0; e < 6; ++e) {
+        const double rv = vec ? rvec[e % K] : rmat[e];
+        CHECK(E[e] == shape[e] / rv && L[e] == digamma(shape[e]) - std::log(rv));
+      }
+      for (double v : {0.0, -1.0, (double)NAN})
+        for (int in_rate = 0; in_rate < 2; ++in_rate) {
+          double r2[6];
+          memcpy(E, shape, sizeof E); memcpy(r2, rmat, sizeof r2);
+          if (in_rate) { if (vec) { r2[0] = rvec[0]; r2[1] = v; } else r2[5] = v; } else E[5] = v;
+          // the bad value is in row 2 -- a bad entry of the K-vector shows in row 0 already
+          CHECK(gamma_expectations(E, L, r2, R, K, vec != 0, "some/hbeta_rate.tsv", &err) == -1);
+          CHECK(err.find("some/hbeta_rate.tsv: ") == 0 && err.find(in_rate && vec ? "(row 0)" : "(row 2)") != std::string::npos);
+        }
+    }
+  }
+}
+
 int main(int argc, char **argv)
 {
   char tmpl[] = "/tmp/hgaprec_selftest_XXXXXX";
@@ -466,6 +604,7 @@ int main(int argc, char **argv)
   test_state();
   test_threads();
   test_loader();
+  test_reports();
   test_comm();
   if (g_fail) { fprintf(stderr, "host_selftest: %d check(s) failed\n", g_fail); return 1; }
   printf("host_selftest ok\n");

@@ -1,0 +1,313 @@
+// score_modes.cpp -- the reports of `hgaprec` on a saved model: -rmse / -msr / -eval-all / -recommend / -similar-items /
+// -similar-users / -fold-in (and -gen-ranking, which is the training run's own ranking on the loaded state).  Each
+// reads the data like a training run, loads the factor files a run has written (from the current directory like the
+// reference, or from -model-dir DIR), writes ONE report and returns.  One GPU; nothing of the training loop is seen here.
+#include "hgaprec_cli.hpp"
+
+#include <cmath>
+#include <unistd.h>
+
+namespace hgaprec {
+namespace {
+
+struct ScoreModes : Cli {
+  const uint32_t n, m, k;
+  explicit ScoreModes(const Cli &c) : Cli(c), n(c.rt.n), m(c.rt.m), k(c.env.k) {}
+
+  std::string model_path(const std::string &name) const { return (env.model_dir.empty() ? std::string(".") : env.model_dir) + "/" + name; }
+  // a factor file of the model, rows x cols, through the strict reader (hgaprec_host.cpp, load_matrix); returns its path.
+  // ids: what its id column must hold -- nullptr for a K-vector, whose id column is seq2id[k] and is not compared
+  std::string load(const std::string &name, std::vector<double> &out, uint32_t rows, uint32_t cols, const std::vector<uint32_t> *ids) const {
+    const std::string path = model_path(name);
+    std::string err;
+    out.resize((size_t)rows * cols);
+    if (load_matrix(path, out.data(), rows, cols, ids ? ids->data() : nullptr, ids ? (uint32_t)ids->size() : 0, &err)) model_die(err);
+    return path;
+  }
+
+  // HGAPRec::load_beta_and_theta (hgaprec.cc:2114-2135): the expectations of the factor files into the handle's *_E.
+  // -hier: htheta.tsv / hbeta.tsv hold E; without: E = shape / rate[k], as GPMatrixGR::load -> compute_expectations
+  // does (gpbase.hh:755-764); -bias: the one value column of thetabias.tsv / betabias.tsv.  thetarate.tsv / betarate.tsv
+  // are read when they are there (scoring never touches them).  Stricter than the reference (hgaprec_host.cpp,
+  // load_matrix): a missing file, a short file, a short row, or ids that are not those of the ratings just read stop the run.
+  void load_model() {
+    std::string err;
+    auto side = [&](bool user_side) {
+      const uint32_t rows = user_side ? n : m;
+      const std::vector<uint32_t> &ids = user_side ? rt.seq2user : rt.seq2item;
+      const std::string base = env.hier ? (user_side ? "htheta" : "hbeta") : (user_side ? "theta" : "beta");
+      std::vector<double> E, v;
+      if (env.hier) load(base + ".tsv", E, rows, k, &ids);
+      else {
+        load(base + "_shape.tsv", E, rows, k, &ids);
+        const std::string rate_path = load(base + "_rate.tsv", v, k, 1, nullptr);
+        if (shape_over_rate(E.data(), rows, k, v.data(), rate_path, &err)) model_die(err);   // a zero rate would rank the item first
+      }
+      put(user_side ? HPF_THETA_E : HPF_BETA_E, E);
+      if (env.hier && access(model_path(user_side ? "thetarate.tsv" : "betarate.tsv").c_str(), R_OK) == 0) {
+        load(user_side ? "thetarate.tsv" : "betarate.tsv", v, rows, 1, &ids);
+        put(user_side ? HPF_XI_E : HPF_ETA_E, v);
+      }
+      if (env.bias) {
+        load(user_side ? "thetabias.tsv" : "betabias.tsv", v, rows, 1, &ids);
+        put(user_side ? HPF_UBIAS_E : HPF_IBIAS_E, v);
+      }
+    };
+    side(false);
+    side(true);
+    env.lerr("loaded the model from %s", env.model_dir.empty() ? "." : env.model_dir.c_str());
+  }
+
+  // HGAPRec::compute_rmse (hgaprec.cc:1579-1604).  DEVIATION: the reference's -rmse never loads the model (main.cc:254-257
+  // constructs and calls compute_rmse; load_beta_and_theta() is commented out at hgaprec.cc:1587), so it scores the empty
+  // start objects.  This build loads the model first.
+  void compute_rmse() {
+    const HeldOut &ho = rt.test;
+    std::vector<double> pred(ho.u.size());
+    int rc = hpf_predict(h, ho.u.data(), ho.i.data(), ho.u.size(), pred.data());
+    if (rc) die("hpf_predict", rc);
+    const std::string spath = env.file_str("/test_scores.tsv");
+    FILE *f = open_or_die(spath, "w");
+    double s = .0;
+    for (size_t p = 0; p < pred.size(); ++p) {                // map order, summed serially
+      const uint8_t v = (uint8_t)ho.y[p];                     // yval_t v = i->second
+      const double u = pred[p];
+      s += (u - v) * (u - v);
+      fprintf(f, "%d\t%.5f\n", v, u);
+    }
+    close_or_die(f, spath);
+    write_line(env.file_str("/rmse.txt"), "%.5f\n", sqrt(s / pred.size()));
+  }
+
+  // HGAPRec::gen_msr_csv (hgaprec.cc:1993-2085): per user, where the held-out item -- the LAST test pair of the user in
+  // (user, item) order, hgaprec.cc:140-145 -- stands among the items [0, m - 1) (the reference's loop never scores item
+  // m - 1).  The reference asserts on a user without a test pair; here the run stops before pred.csv exists.
+  void gen_msr_csv() {
+    std::vector<uint32_t> heldout(n, 0xffffffffu);
+    for (size_t p = 0; p < rt.test.u.size(); ++p) heldout[rt.test.u[p]] = rt.test.i[p];     // sorted by (user, item): the last one stays
+    for (uint32_t u = 0; u < n; ++u)
+      if (heldout[u] == 0xffffffffu) {
+        fprintf(stderr, "error: -msr: user %u (seq %u) has no pair in test.tsv\n", rt.seq2user[u], u);
+        exit(1);
+      }
+    const std::vector<uint32_t> &item_deg = rt.item_degrees();
+    std::vector<uint32_t> valid_users(m, 0);                 // _validation_users_of_movie
+    for (uint32_t it : rt.validation.i) valid_users[it]++;
+    std::vector<uint32_t> rank(n), masked(n);                // O(n) results; the scores of a chunk never leave the device
+    std::vector<double> sc;
+    const uint32_t limit = m - 1;
+    MaskLists ml;
+    // m == 1: the reference's loop over [0, m - 1) scores nothing and leaves rank 0 (a limit of 0 would mean "all items")
+    for_chunks(limit > 0 ? n : 0, [&](size_t u0, size_t u1) {
+      ml.fill(rt.validation, nullptr, 0, (uint32_t)u0, (uint32_t)u1);
+      sc.resize(ml.users.size());
+      int rc = hpf_loo_ranks(h, ml.users.data(), (uint32_t)ml.users.size(), ml.ptr.data(), ml.items.data(), heldout.data() + u0, limit,
+                             rank.data() + u0, sc.data(), masked.data() + u0);
+      if (rc) die("hpf_loo_ranks", rc);
+    });
+    const std::string path = env.file_str("/pred.csv");
+    FILE *f = open_or_die(path, "w");
+    fprintf(f, "User\tHeldOutItem\tHeldOutItemIndex\tUserNegatives\tUserCount\tItemCount\n");
+    for (uint32_t u = 0; u < n; ++u) {
+      const uint32_t t = heldout[u], training = masked[u], negatives = limit - masked[u];
+      fprintf(f, "%d\t%d\t%d\t%d\t%d\t%d\n", rt.seq2user[u], rt.seq2item[t], rank[u], negatives, training,
+              valid_users[t] + item_deg[t]);
+    }
+    close_or_die(f, path);
+  }
+
+  // -eval-all (extension): compute_itemrank's question -- where does each test item that is a hit stand in its user's
+  // full item order, training items with a rating > 0 and validation items zeroed -- for EVERY user with such an item
+  // instead of a sample, through hpf_rank_queries (the user's scores are computed once for all its items, and no score
+  // reaches memory).  itemrank_all.tsv has itemrank.tsv's lines; eval_users.tsv the integers per user; eval_all.txt the
+  // means (eval_from_ranks, hgaprec_host.hpp).
+  void eval_all_report() {
+    const std::vector<uint32_t> &item_deg = rt.item_degrees();
+    std::vector<uint32_t> eu;                                 // evaluated users, seq order
+    std::vector<uint64_t> qptr(1, 0); std::vector<uint32_t> qi;
+    for (uint32_t u = 0; u < n; ++u) {
+      for (size_t a = rt.test.lower(u, 0); a < rt.test.u.size() && rt.test.u[a] == u; ++a)
+        if (test_hit(rt.test.y[a])) qi.push_back(rt.test.i[a]);
+      if (qi.size() > qptr.back()) { eu.push_back(u); qptr.push_back(qi.size()); }
+    }
+    std::vector<uint32_t> rank(qi.size()); std::vector<double> pred(qi.size());
+    MaskLists ml; std::vector<uint64_t> cq;
+    for_chunks(eu.size(), [&](size_t b0, size_t b1) {
+      ml.fill(rt.validation, eu.data() + b0, b1 - b0, 0, n);
+      chunk_offsets(qptr.data(), b0, b1, &cq);
+      int rc = hpf_rank_queries(h, ml.users.data(), (uint32_t)(b1 - b0), ml.ptr.data(), ml.items.data(), cq.data(),
+                                qi.data() + qptr[b0], rank.data() + qptr[b0], pred.data() + qptr[b0]);
+      if (rc) die("hpf_rank_queries", rc);
+    });
+    std::vector<uint32_t> nranked(eu.size());
+    for (size_t b = 0; b < eu.size(); ++b) nranked[b] = rt.ranked_items(eu[b]);     // as in compute_itemrank
+    std::vector<EvalUser> pu(eu.size()); EvalMeans mean;
+    eval_from_ranks(qptr.data(), rank.data(), nranked.data(), eu.size(), pu.data(), &mean);
+
+    const std::string ipath = env.file_str("/itemrank_all.tsv"), upath = env.file_str("/eval_users.tsv");
+    FILE *f = open_or_die(ipath, "w"), *uf = open_or_die(upath, "w");
+    std::vector<uint64_t> ord;
+    for (size_t b = 0; b < eu.size(); ++b) {
+      const uint32_t u = eu[b];
+      ord.resize(qptr[b + 1] - qptr[b]);
+      for (size_t t = 0; t < ord.size(); ++t) ord[t] = qptr[b] + t;
+      std::stable_sort(ord.begin(), ord.end(), [&](uint64_t x, uint64_t y) { return rank[x] < rank[y]; });
+      for (uint64_t q : ord) fprintf(f, "%d\t%d\t%.5f\t%d\t%d\n", u, qi[q], pred[q], rank[q], item_deg[qi[q]]);
+      fprintf(uf, "%u\t%u\t%u\t%u\t%u\t%u\t%llu\n", u, rt.seq2user[u], pu[b].ntest, pu[b].hits10, pu[b].hits100,
+              pu[b].best_rank, (unsigned long long)pu[b].sum_rank);
+    }
+    close_or_die(f, ipath);
+    close_or_die(uf, upath);
+    write_line(env.file_str("/eval_all.txt"), "%llu\t%llu\t%.5f\t%.5f\t%.5f\t%.5f\t%.5f\n", (unsigned long long)mean.users,
+               (unsigned long long)mean.pairs, mean.precision10, mean.precision100, mean.recall100, mean.mrr, mean.meanrank);
+    env.lerr("-eval-all: %llu users, %llu test items ranked", (unsigned long long)mean.users, (unsigned long long)mean.pairs);
+  }
+
+  // -recommend N (extension): what a recommender is for -- the N best items of EVERY user, training items with a
+  // rating > 0 and the user's validation items zeroed exactly as compute_precision zeroes them for its sample -- through
+  // hpf_recommend (no score reaches memory up to N = 256).  <stem>.tsv has the first three columns of ranking.tsv under
+  // ranking.tsv's rule (given.r(u, it) == 0; the padding beyond m items is never printed), users in seq order; <stem>.txt
+  // users, lines and N.  A chunk of users is written before the next is ranked: host memory is O(chunk x N).
+  // -fold-in's tail is the same report for the new users: their own handle and ratings, and no list beyond the given
+  // ratings, which the call masks itself (mask == nullptr).
+  unsigned long long recommend_lists(const Ratings &given, const HeldOut *mask, const std::string &stem) {
+    const uint32_t N = env.recommend;
+    const std::string rpath = env.file_str(stem + ".tsv");
+    FILE *f = open_or_die(rpath, "w");
+    MaskLists ml; std::vector<uint32_t> items; std::vector<double> scores;
+    const HeldOut none;
+    unsigned long long lines = 0;
+    for_chunks(given.n, [&](size_t u0, size_t u1) {
+      ml.fill(mask ? *mask : none, nullptr, 0, (uint32_t)u0, (uint32_t)u1);
+      items.resize(ml.users.size() * (size_t)N); scores.resize(ml.users.size() * (size_t)N);
+      int rc = hpf_recommend(h, ml.users.data(), (uint32_t)ml.users.size(), ml.ptr.data(), mask ? ml.items.data() : nullptr, N,
+                             items.data(), scores.data());
+      if (rc) die("hpf_recommend", rc);
+      lines += write_topn(f, ml.users.data(), ml.users.size(), items.data(), scores.data(), N, m, given.seq2user.data(),
+                          rt.seq2item.data(), [&](uint32_t u, uint32_t it) { return given.r(u, it) == 0; });
+    });
+    close_or_die(f, rpath);
+    write_line(env.file_str(stem + ".txt"), "%u\t%llu\t%u\n", given.n, lines, N);
+    return lines;
+  }
+  void recommend_report() {
+    const unsigned long long lines = recommend_lists(rt, &rt.validation, "/recommend");
+    env.lerr("-recommend: %u users, %llu lines in recommend.tsv", n, lines);
+  }
+
+  // -similar-items N / -similar-users N (extension): "more like this item" and "users like this one" -- the N nearest other
+  // rows of E[beta] (E[theta]) to every row, by cosine or dot product over the K factor columns, through hpf_similar.
+  // similar_items.tsv: item id, neighbour item id, score -- items in seq order, each list best first, ids and score printed
+  // as recommend.tsv prints them, the padding of a list beyond rows - 1 never printed; similar_items.txt: rows, lines, N,
+  // metric.  similar_users.* the same for users.  A chunk of rows is written before the next is ranked.
+  void similar_report(bool items) {
+    const uint32_t N = items ? env.similar_items : env.similar_users;
+    const uint32_t rows = items ? m : n;
+    const std::vector<uint32_t> &ids = items ? rt.seq2item : rt.seq2user;
+    const int metric = env.similar_metric == "dot" ? HPF_SIM_DOT : HPF_SIM_COSINE;
+    const std::string base = items ? "/similar_items" : "/similar_users";
+    const std::string rpath = env.file_str(base + ".tsv");
+    FILE *f = open_or_die(rpath, "w");
+    std::vector<uint32_t> sel, nb; std::vector<double> scores;
+    unsigned long long lines = 0;
+    for_chunks(rows, [&](size_t r0, size_t r1) {
+      sel.clear();
+      for (size_t r = r0; r < r1; ++r) sel.push_back((uint32_t)r);
+      nb.resize(sel.size() * (size_t)N); scores.resize(sel.size() * (size_t)N);
+      int rc = hpf_similar(h, items ? 1 : 0, sel.data(), (uint32_t)sel.size(), N, metric, nb.data(), scores.data());
+      if (rc) die("hpf_similar", rc);
+      lines += write_topn(f, sel.data(), sel.size(), nb.data(), scores.data(), N, rows - 1, ids.data(), ids.data());
+    });
+    close_or_die(f, rpath);
+    write_line(env.file_str(base + ".txt"), "%u\t%llu\t%u\t%s\n", rows, lines, N, env.similar_metric.c_str());
+    env.lerr("-similar-%s: %u rows, %llu lines in %s.tsv", items ? "items" : "users", rows, lines, base.c_str() + 1);
+  }
+
+  // -fold-in FILE (extension; HGAPRec::test(), hgaprec.cc:2257-2346): the users of FILE, who need not be in -dir, folded
+  // into the saved model.  The item side comes from -model-dir as SHAPE and RATE (E alone does not give Elog) through the
+  // strict readers; the host forms E = shape / rate and Elog = psi(shape) - log(rate) and hands them to a second handle
+  // that holds the new users; hpf_fold_in runs -fold-iters iterations from the prior (-fold-tol: a stopping time per
+  // user).  Output: the user-side files of save_model under the prefix foldin_, through the same writers; foldin.txt
+  // (users, nonzeros, lines skipped for an unknown item, T, X, iterations min / mean / max); with -recommend N also
+  // foldin_recommend.tsv / .txt, recommend_report's lines for the new users with their given ratings masked.
+  void fold_in_report() {
+    Ratings nu; uint64_t skipped = 0;
+    const int frc = rt.read_fold_in(env.fold_in, &nu, &skipped);
+    if (frc) { fprintf(stderr, "error: -fold-in: cannot %s %s\n", frc == -1 ? "open" : "parse", env.fold_in.c_str()); exit(1); }
+    std::string err;
+    std::vector<double> E, L((size_t)m * k), rate;
+    const std::string base = env.hier ? "hbeta" : "beta";
+    load(base + "_shape.tsv", E, m, k, &rt.seq2item);
+    const std::string rate_path = env.hier ? load(base + "_rate.tsv", rate, m, k, &rt.seq2item) : load(base + "_rate.tsv", rate, k, 1, nullptr);
+    if (gamma_expectations(E.data(), L.data(), rate.data(), m, k, !env.hier, rate_path, &err)) model_die(err);
+    std::vector<double> bE, bL(env.bias ? m : 0);
+    if (env.bias) {
+      load("betabias_shape.tsv", bE, m, 1, &rt.seq2item);
+      const std::string bp = load("betabias_rate.tsv", rate, m, 1, &rt.seq2item);
+      if (gamma_expectations(bE.data(), bL.data(), rate.data(), m, 1, false, bp, &err)) model_die(err);
+    }
+    env.lerr("-fold-in: item side loaded from %s", env.model_dir.empty() ? "." : env.model_dir.c_str());
+
+    ScoreModes f(*this);                         // the second handle: its die() reports that handle
+    f.h = nullptr;
+    hpf_config cfg = config(nu.n, nu.n);
+    cfg.novb = 0;                                // the new users are never iterated by vb_bias()
+    int rc = hpf_create(&cfg, &f.h);
+    if (rc) f.die("hpf_create (-fold-in)", rc);
+    rc = hpf_upload_csr(f.h, nu.rowptr.data(), nu.col.data(), env.binary_data ? nullptr : nu.val.data());
+    if (rc) f.die("hpf_upload_csr (-fold-in)", rc);
+    f.put(HPF_BETA_E, E); f.put(HPF_BETA_ELOG, L);
+    if (env.bias) { f.put(HPF_IBIAS_E, bE); f.put(HPF_IBIAS_ELOG, bL); }
+    std::vector<uint32_t> iters(nu.n);
+    rc = hpf_fold_in(f.h, env.fold_iters, env.fold_tol, iters.data());
+    if (rc) f.die("hpf_fold_in", rc);
+
+    // the user-side files of save_model, prefix foldin_
+    const std::vector<uint32_t> &uid = nu.seq2user;
+    std::vector<double> buf;
+    auto write = [&](const std::string &name, hpf_state w, uint32_t rows, uint32_t cols, bool as_vector) {
+      buf.resize((size_t)rows * cols);
+      const int r2 = hpf_get_state(f.h, w, buf.data(), buf.size());
+      if (r2) f.die("hpf_get_state", r2);
+      const std::string path = env.file_str("/foldin_" + name);
+      if (as_vector ? save_vector(path, buf.data(), rows, uid.data(), (uint32_t)uid.size())
+                    : save_matrix(path, buf.data(), rows, cols, uid.data(), (uint32_t)uid.size())) io_die("cannot write", path);
+    };
+    const char *suf[3] = {"_shape.tsv", "_rate.tsv", ".tsv"};
+    const std::string tb = env.hier ? "htheta" : "theta";
+    for (int j = 0; j < 3; ++j) {
+      if (j == 1 && !env.hier) write(tb + suf[j], HPF_THETA_RATE, k, 1, true);      // GPMatrixGR rate: the K-vector
+      else write(tb + suf[j], (hpf_state)(HPF_THETA_SHAPE + j), nu.n, k, false);
+      if (env.hier) write(std::string("thetarate") + suf[j], (hpf_state)(HPF_XI_SHAPE + j), nu.n, 1, true);
+      if (env.bias) write(std::string("thetabias") + suf[j], (hpf_state)(HPF_UBIAS_SHAPE + j), nu.n, 1, false);
+    }
+    uint32_t imin = 0, imax = 0; double isum = 0;
+    for (uint32_t u = 0; u < nu.n; ++u) { imin = u ? std::min(imin, iters[u]) : iters[u]; imax = std::max(imax, iters[u]); isum += iters[u]; }
+    write_line(env.file_str("/foldin.txt"), "%u\t%llu\t%llu\t%u\t%g\t%u\t%.5f\t%u\n", nu.n, (unsigned long long)nu.col.size(),
+               (unsigned long long)skipped, env.fold_iters, env.fold_tol, imin, nu.n ? isum / nu.n : 0.0, imax);
+    env.lerr("-fold-in: %u users, %llu ratings, %llu lines skipped (unknown item), iterations %u .. %u", nu.n,
+             (unsigned long long)nu.col.size(), (unsigned long long)skipped, imin, imax);
+    if (env.recommend) f.recommend_lists(nu, nullptr, "/foldin_recommend");
+    hpf_destroy(f.h);
+  }
+};
+
+}  // namespace
+
+void score(Cli &c, const std::function<void()> &gen_ranking)
+{
+  ScoreModes s(c);
+  if (!c.env.fold_in.empty()) return s.fold_in_report();      // needs the item side only, as shape and rate
+  s.load_model();
+  if (c.env.rmse) s.compute_rmse();
+  else if (c.env.msr) s.gen_msr_csv();
+  else if (c.env.eval_all) s.eval_all_report();
+  else if (c.env.recommend) s.recommend_report();
+  else if (c.env.similar_items || c.env.similar_users) {
+    if (c.env.similar_items) s.similar_report(true);
+    if (c.env.similar_users) s.similar_report(false);
+  }
+  else gen_ranking();
+}
+
+}  // namespace hgaprec

@@ -1205,6 +1205,41 @@ int copy_back(hpf_handle *h, std::initializer_list<HostOut> outs)
   return HPF_OK;
 }
 
+// What hpf_recommend and hpf_similar share: a streaming selection behind a sweep over the m rows of Eb (`sweep(nch, grid, a)`
+// launches the caller's kernel) and a merge of each row's splits (topn_merge_kernel) -- per batch the candidate buffers
+// (hpf_plan::topn_batch_users), nothing of n_sel x m.  `a` comes with the factor pointers, the bias columns and the bit rows
+// of the caller; batch(b0, rows) readies the bit rows of a batch.  A list has `real` entries; the rest is padding.
+template <typename Batch, typename Sweep>
+int topn_run(FusedCtx &c, TopnArgs a, uint32_t m, uint32_t n_sel, uint32_t topn, uint32_t real, const char *kernel,
+             Batch &&batch, Sweep &&sweep, uint32_t *out_items, double *out_scores)
+{
+  hpf_handle *h = c.h; int rc;
+  const uint32_t ntiles = (m + 63) / 64, cap = hpf_plan::topn_cap(topn), NP = hpf_plan::pow2_ceil(topn);
+  static_assert(hpf_plan::topn_cap(hpf_plan::TOPN_FUSED_MAX) == TOPN_CAP_MAX, "a wave's LDS scratch holds the largest candidate buffer");
+  c.batch = hpf_plan::topn_batch_users(m, n_sel, cap, h->loo_batch);      // <= the users the bit rows were sized for
+  // segments (row, split) of a batch: a full batch's; a shorter last batch takes its own grid where that needs no more
+  const hpf_plan::RankGrid gfull = hpf_plan::topn_grid(std::min(c.batch, n_sel), ntiles, cap);
+  const size_t nseg = (size_t)c.batch * gfull.splits;
+  uint32_t *d_items = nullptr; double *d_sc = nullptr;
+  if ((rc = c.alloc(&a.ckey, nseg * cap)) || (rc = c.alloc(&a.citem, nseg * cap)) || (rc = c.alloc(&a.ccount, nseg)) ||
+      (rc = c.alloc(&d_items, (size_t)n_sel * topn)) || (rc = c.alloc(&d_sc, (size_t)n_sel * topn))) return rc;
+  a.m = m; a.topn = topn; a.cap = cap; a.lg_cap = hpf_plan::log2_of(cap);
+  const std::string what = std::string(kernel) + "/topn_merge_kernel";
+  for (uint32_t b0 = 0; b0 < n_sel; b0 += c.batch) {
+    const uint32_t rows = std::min(n_sel - b0, c.batch);
+    if ((rc = batch(b0, rows))) return rc;
+    hpf_plan::RankGrid g = hpf_plan::topn_grid(rows, ntiles, cap);
+    if ((size_t)rows * g.splits > nseg) { g.splits = gfull.splits; g.tiles_per_split = gfull.tiles_per_split; }
+    a.users = c.d_users + b0; a.out_items = d_items + (size_t)b0 * topn; a.out_scores = d_sc + (size_t)b0 * topn;
+    a.n_sel = rows; a.tiles_per_split = g.tiles_per_split; a.splits = g.splits;
+    if ((rc = launch_rank(h, kernel, [&](auto nch) {
+          sweep(nch, dim3(g.blocks, g.splits), a);
+          hipLaunchKernelGGL(topn_merge_kernel, dim3(rows), dim3(256), (size_t)NP * 12, h->stream, a, NP, real);
+        }, what.c_str()))) return rc;
+  }
+  return copy_back(h, {{out_items, d_items, (size_t)n_sel * topn * 4}, {out_scores, d_sc, (size_t)n_sel * topn * 8}});
+}
+
 int prepare_derived(hpf_handle *h)
 {
   if (!h->derived_dirty) return HPF_OK;
@@ -2864,47 +2899,27 @@ int hpf_rank_queries(hpf_handle *h, const uint32_t *users, uint32_t n_sel, const
   return copy_back(h, {{out_rank, d_rank, (size_t)nq * 4}, {out_score, d_sc, (size_t)nq * 8}});
 }
 
-// Top-N for every selected user.  Up to hpf_plan::TOPN_FUSED_MAX: the sweep of the other two fused calls with a streaming
-// selection behind it (topn_sweep_kernel) and a merge of each user's splits (topn_merge_kernel) -- per batch the bit rows
-// and the candidate buffers (hpf_plan::topn_batch_users), nothing of n_sel x n_items.  Above it: hpf_rank_topn's route.
+// Top-N for every selected user.  Up to hpf_plan::TOPN_FUSED_MAX: the sweep of the other two fused calls behind the bit
+// rows of a batch of users (topn_sweep_kernel, topn_run).  Above it: hpf_rank_topn's route.
 int hpf_recommend(hpf_handle *h, const uint32_t *users, uint32_t n_sel, const uint64_t *mask_ptr,
                   const uint32_t *mask_items, uint32_t topn, uint32_t *out_items, double *out_scores)
 {
   if (!h || topn == 0 || topn > hpf_plan::TOPN_MAX || (n_sel && (!users || !out_items || !out_scores))) return HPF_ERR_INVALID;
   if (!n_sel) return HPF_OK;
   if (!hpf_plan::topn_fused(topn)) return hpf_rank_topn(h, users, n_sel, mask_ptr, mask_items, topn, out_items, out_scores);
-  const uint32_t m = h->it.rows, ntiles = (m + 63) / 64;
+  const uint32_t m = h->it.rows;
   if (h->ld & 1u) { h->err = "hpf_recommend: odd row stride"; return HPF_ERR_UNSUPPORTED; }
   if (int rc = fused_ready(h, users, n_sel, mask_ptr, mask_items)) return rc;
   FusedCtx c(h); int rc;
   if ((rc = c.upload(users, n_sel, mask_ptr, mask_items)) || (rc = c.bit_rows(n_sel))) return rc;
-  const uint32_t cap = hpf_plan::topn_cap(topn);
-  static_assert(hpf_plan::topn_cap(hpf_plan::TOPN_FUSED_MAX) == TOPN_CAP_MAX, "a wave's LDS scratch holds the largest candidate buffer");
-  c.batch = hpf_plan::topn_batch_users(m, n_sel, cap, h->loo_batch);      // <= the users the bit rows were sized for
-  // segments (user, split) of a batch: a full batch's; a shorter last batch takes its own grid where that needs no more
-  const hpf_plan::RankGrid gfull = hpf_plan::topn_grid(std::min(c.batch, n_sel), ntiles, cap);
-  const size_t nseg = (size_t)c.batch * gfull.splits;
-  unsigned long long *d_ckey = nullptr; uint32_t *d_citem = nullptr, *d_ccount = nullptr, *d_items = nullptr; double *d_sc = nullptr;
-  if ((rc = c.alloc(&d_ckey, nseg * cap)) || (rc = c.alloc(&d_citem, nseg * cap)) || (rc = c.alloc(&d_ccount, nseg)) ||
-      (rc = c.alloc(&d_items, (size_t)n_sel * topn)) || (rc = c.alloc(&d_sc, (size_t)n_sel * topn))) return rc;
-  const uint32_t NP = hpf_plan::pow2_ceil(topn);
-  for (uint32_t b0 = 0; b0 < n_sel; b0 += c.batch) {
-    const uint32_t rows = std::min(n_sel - b0, c.batch);
-    if ((rc = c.mask_batch(b0, rows))) return rc;
-    hpf_plan::RankGrid g = hpf_plan::topn_grid(rows, ntiles, cap);
-    if ((size_t)rows * g.splits > nseg) { g.splits = gfull.splits; g.tiles_per_split = gfull.tiles_per_split; }
-    TopnArgs a;
-    factor_args(h, a);
-    a.users = c.d_users + b0; a.bits = c.d_bits; a.ckey = d_ckey; a.citem = d_citem; a.ccount = d_ccount;
-    a.out_items = d_items + (size_t)b0 * topn; a.out_scores = d_sc + (size_t)b0 * topn;
-    a.n_sel = rows; a.m = m; a.words = c.words; a.tiles_per_split = g.tiles_per_split;
-    a.splits = g.splits; a.topn = topn; a.cap = cap; a.lg_cap = hpf_plan::log2_of(cap);
-    if ((rc = launch_rank(h, "topn_sweep_kernel", [&](auto nch) {
-          hipLaunchKernelGGL(topn_sweep_kernel<decltype(nch)::value>, dim3(g.blocks, g.splits), dim3(256), 0, h->stream, a);
-          hipLaunchKernelGGL(topn_merge_kernel, dim3(rows), dim3(256), (size_t)NP * 12, h->stream, a, NP, std::min(topn, m));
-        }, "topn_sweep_kernel/topn_merge_kernel"))) return rc;
-  }
-  return copy_back(h, {{out_items, d_items, (size_t)n_sel * topn * 4}, {out_scores, d_sc, (size_t)n_sel * topn * 8}});
+  TopnArgs a;
+  factor_args(h, a);
+  a.bits = c.d_bits; a.words = c.words;
+  return topn_run(c, a, m, n_sel, topn, std::min(topn, m), "topn_sweep_kernel",
+                  [&](uint32_t b0, uint32_t rows) { return c.mask_batch(b0, rows); },
+                  [&](auto nch, dim3 grid, const TopnArgs &ta) {
+                    hipLaunchKernelGGL(topn_sweep_kernel<decltype(nch)::value>, grid, dim3(256), 0, h->stream, ta);
+                  }, out_items, out_scores);
 }
 
 // The topn nearest OTHER rows of one side for every selected row: hpf_recommend's sweep, selection and merge with query
@@ -2920,7 +2935,7 @@ int hpf_similar(hpf_handle *h, int side, const uint32_t *ids, uint32_t n_sel, ui
   if (n_sel && (!ids || !out_ids || !out_scores)) { h->err = "hpf_similar: null pointer"; return HPF_ERR_INVALID; }
   if (!n_sel) return HPF_OK;
   Side &s = side ? h->it : h->u;
-  const uint32_t m = s.rows, ntiles = (m + 63) / 64;
+  const uint32_t m = s.rows;
   if (h->ld & 1u) { h->err = "hpf_similar: odd row stride"; return HPF_ERR_UNSUPPORTED; }
   if (!s.have_E && h->iterations == 0) { h->err = "E state not set"; return HPF_ERR_STATE; }
   for (uint32_t b = 0; b < n_sel; ++b)
@@ -2935,31 +2950,14 @@ int hpf_similar(hpf_handle *h, int side, const uint32_t *ids, uint32_t n_sel, ui
     hipLaunchKernelGGL(unit_rows_kernel, dim3(std::min<uint32_t>((m + 15) / 16, 16384)), dim3(256), 0, h->stream, s.E, d_unit, m, h->ld, h->K);
     if ((rc = check_launch(h, "unit_rows_kernel"))) return rc;
   }
-  const uint32_t cap = hpf_plan::topn_cap(topn);
-  c.batch = hpf_plan::topn_batch_users(m, n_sel, cap, h->loo_batch);
-  // segments (row, split) of a batch, as hpf_recommend sizes them
-  const hpf_plan::RankGrid gfull = hpf_plan::topn_grid(std::min(c.batch, n_sel), ntiles, cap);
-  const size_t nseg = (size_t)c.batch * gfull.splits;
-  unsigned long long *d_ckey = nullptr; uint32_t *d_citem = nullptr, *d_ccount = nullptr, *d_items = nullptr; double *d_sc = nullptr;
-  if ((rc = c.alloc(&d_ckey, nseg * cap)) || (rc = c.alloc(&d_citem, nseg * cap)) || (rc = c.alloc(&d_ccount, nseg)) ||
-      (rc = c.alloc(&d_items, (size_t)n_sel * topn)) || (rc = c.alloc(&d_sc, (size_t)n_sel * topn))) return rc;
-  const uint32_t NP = hpf_plan::pow2_ceil(topn);
-  for (uint32_t b0 = 0; b0 < n_sel; b0 += c.batch) {
-    const uint32_t rows = std::min(n_sel - b0, c.batch);
-    hpf_plan::RankGrid g = hpf_plan::topn_grid(rows, ntiles, cap);
-    if ((size_t)rows * g.splits > nseg) { g.splits = gfull.splits; g.tiles_per_split = gfull.tiles_per_split; }
-    TopnArgs a;
-    a.Et = a.Eb = d_unit ? d_unit : s.E; a.ld = h->ld; a.K = h->K; a.ubias_col = a.ibias_col = -1;
-    a.users = c.d_users + b0; a.bits = nullptr; a.ckey = d_ckey; a.citem = d_citem; a.ccount = d_ccount;
-    a.out_items = d_items + (size_t)b0 * topn; a.out_scores = d_sc + (size_t)b0 * topn;
-    a.n_sel = rows; a.m = m; a.words = 0; a.tiles_per_split = g.tiles_per_split;
-    a.splits = g.splits; a.topn = topn; a.cap = cap; a.lg_cap = hpf_plan::log2_of(cap);
-    if ((rc = launch_rank(h, "similar_sweep_kernel", [&](auto nch) {
-          hipLaunchKernelGGL(similar_sweep_kernel<decltype(nch)::value>, dim3(g.blocks, g.splits), dim3(256), 0, h->stream, a);
-          hipLaunchKernelGGL(topn_merge_kernel, dim3(rows), dim3(256), (size_t)NP * 12, h->stream, a, NP, std::min(topn, m - 1));
-        }, "similar_sweep_kernel/topn_merge_kernel"))) return rc;
-  }
-  return copy_back(h, {{out_ids, d_items, (size_t)n_sel * topn * 4}, {out_scores, d_sc, (size_t)n_sel * topn * 8}});
+  TopnArgs a;
+  a.Et = a.Eb = d_unit ? d_unit : s.E; a.ld = h->ld; a.K = h->K; a.ubias_col = a.ibias_col = -1;
+  a.bits = nullptr; a.words = 0;
+  return topn_run(c, a, m, n_sel, topn, std::min(topn, m - 1), "similar_sweep_kernel",
+                  [](uint32_t, uint32_t) { return (int)HPF_OK; },
+                  [&](auto nch, dim3 grid, const TopnArgs &ta) {
+                    hipLaunchKernelGGL(similar_sweep_kernel<decltype(nch)::value>, grid, dim3(256), 0, h->stream, ta);
+                  }, out_ids, out_scores);
 }
 
 int hpf_get_work_info(hpf_handle *h, hpf_work_info *out)

@@ -72,6 +72,18 @@ def lib():
     u64p = C.POINTER(C.c_uint64)
     L.hg_eval_from_ranks.argtypes = [u64p, u32p, u32p, C.c_uint64, u64p, dp]
     L.hg_eval_from_ranks.restype = None
+    L.hg_gamma_expectations.argtypes = [dp, dp, dp, C.c_uint64, C.c_uint64, C.c_int, C.c_char_p, C.c_char_p, C.c_size_t]
+    L.hg_ratings_r.argtypes = [vp, C.c_uint32, C.c_uint32]; L.hg_ratings_r.restype = C.c_uint32
+    L.hg_ratings_ranked_items.argtypes = [vp, C.c_uint32]; L.hg_ratings_ranked_items.restype = C.c_uint32
+    L.hg_ratings_item_degrees.argtypes = [vp]; L.hg_ratings_item_degrees.restype = u32p
+    L.hg_chunk_walk.argtypes = [C.c_uint64, C.c_uint64, u64p, C.c_uint64]; L.hg_chunk_walk.restype = C.c_uint64
+    L.hg_chunk_offsets.argtypes = [u64p, C.c_uint64, C.c_uint64, u64p]; L.hg_chunk_offsets.restype = None
+    L.hg_mask_lists_new.argtypes = [vp, C.c_int, u32p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32]
+    L.hg_mask_lists_new.restype = vp
+    L.hg_mask_lists_free.argtypes = [vp]; L.hg_mask_lists_free.restype = None
+    L.hg_mask_lists_get.argtypes = [vp, C.c_int, C.POINTER(vp)]; L.hg_mask_lists_get.restype = C.c_uint64
+    L.hg_write_topn.argtypes = [C.c_char_p, vp, u32p, C.c_uint64, u32p, dp, C.c_uint32, C.c_uint32, u32p, u32p]
+    L.hg_write_topn.restype = C.c_int64
     _lib = L
     return L
 
@@ -164,6 +176,35 @@ class Ratings:
         out = np.empty(max(self.n, 1), np.uint32)
         c = self.L.hg_ratings_test_users(self._r, str(path).encode(), out.ctypes.data_as(C.POINTER(C.c_uint32)), out.size)
         return None if c < 0 else out[:c].copy()
+
+    def r(self, u, item) -> int:
+        """the training rating stored for (u, item), 0 if absent; of a duplicated pair the last one (Ratings::r)"""
+        return self.L.hg_ratings_r(self._r, int(u), int(item))
+
+    def ranked_items(self, u) -> int:
+        """m minus the distinct training items of u with a rating > 0"""
+        return self.L.hg_ratings_ranked_items(self._r, int(u))
+
+    def item_degrees(self):
+        return np.ctypeslib.as_array(self.L.hg_ratings_item_degrees(self._r), shape=(max(self.m, 1),))[: self.m].copy()
+
+    def mask_lists(self, which=0, users=None, lo=0, hi=None, rebase=0):
+        """MaskLists::fill over the validation (which = 0) or test pairs: of `users` those inside [lo, hi) -- users None:
+        the whole range -- -> (users - rebase, mask_ptr, mask_items)"""
+        hi = self.n if hi is None else hi
+        lst = None if users is None else np.ascontiguousarray(users, np.uint32)
+        ml = C.c_void_p(self.L.hg_mask_lists_new(self._r, which, None if lst is None else lst.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                                 0 if lst is None else lst.size, lo, hi, rebase))
+        try:
+            out = []
+            for part, dt in enumerate((np.uint32, np.uint64, np.uint32)):
+                p = C.c_void_p()
+                cnt = self.L.hg_mask_lists_get(ml, part, C.byref(p))
+                out.append(np.ctypeslib.as_array(C.cast(p, C.POINTER(np.ctypeslib.as_ctypes_type(dt))), shape=(cnt,)).copy()
+                           if cnt else np.zeros(0, dt))
+            return tuple(out)
+        finally:
+            self.L.hg_mask_lists_free(ml)
 
     def __del__(self):
         try:
@@ -268,6 +309,54 @@ def shape_over_rate(shape, rate, rate_path="rate.tsv") -> np.ndarray:
     if lib().hg_shape_over_rate(E.ctypes.data_as(dp), E.shape[0], E.shape[1], r.ctypes.data_as(dp), str(rate_path).encode(), err, 1024):
         raise ValueError(err.value.decode())
     return E
+
+
+def gamma_expectations(shape, rate, rate_path="rate.tsv"):
+    """-fold-in's item side as the CLI forms it: (shape / rate, digamma(shape) - log(rate)); rate shaped like shape, or one
+    value per column.  Raises ValueError ("<rate_path>: ... (row r)") for a shape or a rate that is not > 0"""
+    E = np.array(shape, np.float64, order="C", ndmin=2)
+    r = np.ascontiguousarray(rate, np.float64)
+    if r.shape != E.shape and r.shape != (E.shape[1],):
+        raise ValueError("rate: shaped like shape, or one value per column")
+    L = np.empty_like(E)
+    err = C.create_string_buffer(1024)
+    dp = C.POINTER(C.c_double)
+    if lib().hg_gamma_expectations(E.ctypes.data_as(dp), L.ctypes.data_as(dp), r.ctypes.data_as(dp), E.shape[0], E.shape[1],
+                                   int(r.ndim == 1), str(rate_path).encode(), err, 1024):
+        raise ValueError(err.value.decode())
+    return E, L
+
+
+def chunk_walk(rows, chunk=0):
+    """the reports' walk over [0, rows) in chunks (chunk 0: the default size) -> [(r0, r1), ...]"""
+    cnt = lib().hg_chunk_walk(rows, chunk, None, 0)
+    out = np.zeros(2 * max(cnt, 1), np.uint64)
+    lib().hg_chunk_walk(rows, chunk, out.ctypes.data_as(C.POINTER(C.c_uint64)), cnt)
+    return [(int(out[2 * j]), int(out[2 * j + 1])) for j in range(cnt)]
+
+
+def chunk_offsets(ptr, b0, b1):
+    """ptr[b0 .. b1] counted from ptr[b0]"""
+    p = np.ascontiguousarray(ptr, np.uint64)
+    out = np.empty(b1 - b0 + 1, np.uint64)
+    lib().hg_chunk_offsets(p.ctypes.data_as(C.POINTER(C.c_uint64)), b0, b1, out.ctypes.data_as(C.POINTER(C.c_uint64)))
+    return out
+
+
+def write_topn(path, sel, items, scores, real, row_ids, item_ids, given=None) -> int:
+    """the reports' list writer: items / scores are (len(sel), N), the first `real` entries of a list exist; given: a
+    Ratings whose r(row, item) == 0 an entry must meet to be written.  Returns the number of lines"""
+    s = np.ascontiguousarray(sel, np.uint32)
+    it = np.ascontiguousarray(items, np.uint32).reshape(s.size, -1)
+    sc = np.ascontiguousarray(scores, np.float64).reshape(s.size, -1)
+    ri, ii = np.ascontiguousarray(row_ids, np.uint32), np.ascontiguousarray(item_ids, np.uint32)
+    u32p = C.POINTER(C.c_uint32)
+    n = lib().hg_write_topn(str(path).encode(), None if given is None else given._r, s.ctypes.data_as(u32p), s.size,
+                            it.ctypes.data_as(u32p), sc.ctypes.data_as(C.POINTER(C.c_double)), it.shape[1], int(real),
+                            ri.ctypes.data_as(u32p), ii.ctypes.data_as(u32p))
+    if n < 0:
+        raise OSError(f"cannot write {path}")
+    return n
 
 
 def format_fixed8(values):
