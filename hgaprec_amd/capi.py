@@ -42,11 +42,17 @@ EXPORTS = [
     "hpf_iteration_times", "hpf_debug_poke_index", "hpf_start_sums", "hpf_host_alloc", "hpf_host_free",
     "hpf_heldout_bind", "hpf_heldout_ll_bound",
     "hpf_predict", "hpf_loo_ranks", "hpf_rank_queries", "hpf_recommend", "hpf_fold_in", "hpf_similar",
+    "hpf_explain", "hpf_factor_top",
 ]
 
 # hpf_similar: the metrics (hpf_similarity in include/hpf.h) and the largest topn (TOPN_FUSED_MAX: only the fused route exists)
 SIMILARITY = {"cosine": 0, "dot": 1}
 SIMILAR_MAX = 256
+
+# hpf_explain: the most terms of a score it returns (HPF_EXPLAIN_MAX in include/hpf.h); hpf_factor_top: the longest list of a
+# factor (hpf_rank_topn's limit)
+EXPLAIN_MAX = 32
+FACTOR_TOP_MAX = 1024
 
 # queries of one row of rank_queries_kernel (RQ_QCAP in csrc/hpf_kernels.hpp): hpf_rank_queries cuts a user with more
 # into several rows; tests put their query counts around it
@@ -97,6 +103,25 @@ def fold_plan(K, bias=False):
 def fold_grid(n):
     """workgroups hpf_fold_in launches for n users"""
     return max(1, min((n + FOLD_WAVES - 1) // FOLD_WAVES, FOLD_BLOCKS_MAX))
+
+
+# hpf_explain (hpf_plan::explain_plan in csrc/hpf_plan.hpp): a wave per pair, workgroups of EXPLAIN_WAVES waves, a run of
+# EXPLAIN_RUN consecutive pairs per wave and trip, at most EXPLAIN_BLOCKS_MAX workgroups
+EXPLAIN_WAVES, EXPLAIN_RUN, EXPLAIN_BLOCKS_MAX = 4, 8, 2048
+
+
+def explain_plan(K, bias=False):
+    """shape of explain_kernel for K factors: the terms of a score (K + 2 with bias) and the terms per lane R"""
+    C_ = K + (2 if bias else 0)
+    if K < 1 or C_ > 1024:
+        raise ValueError("no explain kernel for this column count")
+    return {"terms": C_, "R": (C_ + 63) // 64}
+
+
+def explain_grid(cnt):
+    """workgroups hpf_explain launches for cnt pairs; a trip of that grid covers grid * EXPLAIN_WAVES * EXPLAIN_RUN pairs"""
+    per = EXPLAIN_WAVES * EXPLAIN_RUN
+    return max(1, min((cnt + per - 1) // per, EXPLAIN_BLOCKS_MAX))
 
 
 class _PinnedBlock:
@@ -245,6 +270,9 @@ def load_library(path: os.PathLike | None = None) -> C.CDLL:
         lib.hpf_fold_in.argtypes = [vp, C.c_uint32, C.c_double, u32p]
     if hasattr(lib, "hpf_similar"):
         lib.hpf_similar.argtypes = [vp, C.c_int, u32p, C.c_uint32, C.c_uint32, C.c_int, u32p, dp]
+    if hasattr(lib, "hpf_explain"):
+        lib.hpf_explain.argtypes = [vp, u32p, u32p, C.c_size_t, C.c_uint32, u32p, dp]
+        lib.hpf_factor_top.argtypes = [vp, C.c_int, C.c_uint32, u32p, dp]
     lib.hpf_comm_unique_id.argtypes = [vp]
     lib.hpf_comm_init.argtypes = [vp, vp]
     lib.hpf_allreduce_exchange.argtypes = [vp]
@@ -603,6 +631,32 @@ class Hpf:
         self._check(self.lib.hpf_similar(self._h, int(side), _ptr(ids, C.c_uint32), ids.size, topn & 0xffffffff, int(metric),
                                          _ptr(out, C.c_uint32), _ptr(sc, C.c_double)))
         return out, sc
+
+    def explain(self, u, i, T):
+        """the T largest terms of every pair's score (hpf_explain): E[theta_u k] * E[beta_i k] for k < K and, with bias,
+        term K = E[ubias_u] and term K + 1 = E[ibias_i]; u is a local user index
+        -> (factors[cnt, T] uint32, contrib[cnt, T] float64), best first; entries beyond K + 2 * bias are (0xffffffff, 0.0)"""
+        u = np.ascontiguousarray(u, dtype=np.uint32)
+        i = np.ascontiguousarray(i, dtype=np.uint32)
+        if u.shape != i.shape or u.ndim != 1:
+            raise ValueError("u and i: one-dimensional arrays of the same length")
+        T = int(T)
+        shape = (u.size, T if 0 < T <= EXPLAIN_MAX else 0)
+        factors = np.empty(shape, dtype=np.uint32)
+        contrib = np.empty(shape, dtype=np.float64)
+        self._check(self.lib.hpf_explain(self._h, _ptr(u, C.c_uint32), _ptr(i, C.c_uint32), u.size, T & 0xffffffff,
+                                         _ptr(factors, C.c_uint32), _ptr(contrib, C.c_double)))
+        return factors, contrib
+
+    def factor_top(self, side, topn):
+        """the topn heaviest rows of every factor column of one side (hpf_factor_top).  side 0: rows of E[theta] (this
+        handle's users), 1: rows of E[beta] -> (ids[K, topn], vals[K, topn]); entries beyond the rows are (0xffffffff, 0.0)"""
+        topn = int(topn)
+        shape = (self.K, topn if 0 < topn <= FACTOR_TOP_MAX else 0)
+        ids = np.empty(shape, dtype=np.uint32)
+        vals = np.empty(shape, dtype=np.float64)
+        self._check(self.lib.hpf_factor_top(self._h, int(side), topn & 0xffffffff, _ptr(ids, C.c_uint32), _ptr(vals, C.c_double)))
+        return ids, vals
 
     def fold_in(self, n_iters=10, tol=0.0, want_iters=True):
         """fold this handle's users in against the item side handed in (hpf_fold_in): from the prior, n_iters user-side

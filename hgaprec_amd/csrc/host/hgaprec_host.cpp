@@ -91,6 +91,27 @@ int Env::parse(int argc, char **argv, bool echo, std::string *bad)
       }
       (items ? similar_items : similar_users) = (uint32_t)nsim;
     }
+    else if (!strcmp(s, "-topic-items") || !strcmp(s, "-topic-users")) {       // extension: the N heaviest rows of every factor of a saved model
+      const bool items = !strcmp(s, "-topic-items");
+      const char *v = next(); char *end = nullptr;
+      const long ntop = strtol(v, &end, 10);
+      if (!*v || *end || ntop < 1 || ntop > 1024) {
+        usage_error = std::string(s) + " needs the number of " + (items ? "items" : "users") + " per factor, 1 .. 1024";
+        if (bad) *bad = s;
+        return 2;
+      }
+      (items ? topic_items : topic_users) = (uint32_t)ntop;
+    }
+    else if (!strcmp(s, "-explain")) {                            // extension: the T largest terms of every recommended item's score
+      const char *v = next(); char *end = nullptr;
+      const long t = strtol(v, &end, 10);
+      if (!*v || *end || t < 1 || t > 32) {
+        usage_error = "-explain needs the number of terms per recommended item, 1 .. 32";
+        if (bad) *bad = s;
+        return 2;
+      }
+      explain = (uint32_t)t;
+    }
     else if (!strcmp(s, "-similar-metric")) {
       const char *v = next();
       if (strcmp(v, "cosine") && strcmp(v, "dot")) {
@@ -147,6 +168,11 @@ int Env::parse(int argc, char **argv, bool echo, std::string *bad)
       if (bad) *bad = s;
       return 1;
     }
+  }
+  if (explain && !recommend) {                                    // wherever the two stand on the line
+    usage_error = "-explain goes with -recommend N: it explains the recommended items";
+    if (bad) *bad = "-explain";
+    return 2;
   }
   return 0;
 }
@@ -1492,14 +1518,14 @@ void MaskLists::fill(const HeldOut &ho, const uint32_t *list, size_t cnt, uint32
 }
 
 uint64_t write_topn(FILE *f, const uint32_t *sel, size_t n_sel, const uint32_t *items, const double *scores, uint32_t N, uint32_t real,
-                    const uint32_t *row_ids, const uint32_t *item_ids, const std::function<bool(uint32_t, uint32_t)> &keep)
+                    const uint32_t *row_ids, const uint32_t *item_ids, const std::function<bool(uint32_t, uint32_t)> &keep, int digits)
 {
   uint64_t lines = 0;
   for (size_t b = 0; b < n_sel; ++b)
     for (uint32_t j = 0; j < real && j < N; ++j) {
       const uint32_t it = items[b * N + j];
       if (keep && !keep(sel[b], it)) continue;
-      fprintf(f, "%d\t%d\t%.5f\n", row_ids[sel[b]], item_ids[it], scores[b * N + j]);
+      fprintf(f, "%d\t%d\t%.*f\n", row_ids[sel[b]], item_ids[it], digits, scores[b * N + j]);
       ++lines;
     }
   return lines;

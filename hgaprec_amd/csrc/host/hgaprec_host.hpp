@@ -78,8 +78,17 @@ struct Env {
   // parse() returns 2 and says why in usage_error
   uint32_t similar_items = 0, similar_users = 0;
   std::string similar_metric = "cosine";
+  // extension: -topic-items N / -topic-users N write the N heaviest items (users) of every factor of a saved model through
+  // hpf_factor_top: topic_items.tsv / .txt, topic_users.tsv / .txt.  Score modes too; both may be given in one run.
+  // -explain T goes with -recommend N only (also behind -fold-in): the T largest terms of every recommended item's score
+  // through hpf_explain, recommend_explain.tsv / .txt beside recommend.tsv.  N outside 1 .. 1024, T outside 1 .. 32, no
+  // number, or -explain without -recommend: parse() returns 2 and says why in usage_error
+  uint32_t topic_items = 0, topic_users = 0, explain = 0;
   std::string usage_error;
-  bool score_mode() const { return gen_ranking || rmse || msr || eval_all || recommend > 0 || !fold_in.empty() || similar_items > 0 || similar_users > 0; }
+  bool score_mode() const {
+    return gen_ranking || rmse || msr || eval_all || recommend > 0 || !fold_in.empty() || similar_items > 0 || similar_users > 0 ||
+           topic_items > 0 || topic_users > 0;
+  }
 
   std::string prefix;          // output directory (Env::prefix)
   FILE *plogf = nullptr;       // param.txt
@@ -311,12 +320,12 @@ struct MaskLists {
   std::vector<uint64_t> ptr;
   void fill(const HeldOut &ho, const uint32_t *list, size_t cnt, uint32_t lo, uint32_t hi, uint32_t rebase = 0);
 };
-// Top-N lists as lines "row id \t entry id \t %.5f": list b belongs to row sel[b] and has items[b * N + j], scores[b * N + j],
+// Top-N lists as lines "row id \t entry id \t %.5f" (`digits` decimals: 5 unless given): list b belongs to row sel[b] and has items[b * N + j], scores[b * N + j],
 // j < N, of which the first `real` exist (the rest is padding and never printed); ids through row_ids / item_ids.  Only
 // the entries keep(sel[b], item) accepts are written (no keep: all).  Returns the number of lines.
 uint64_t write_topn(FILE *f, const uint32_t *sel, size_t n_sel, const uint32_t *items, const double *scores, uint32_t N,
                     uint32_t real, const uint32_t *row_ids, const uint32_t *item_ids,
-                    const std::function<bool(uint32_t, uint32_t)> &keep = nullptr);
+                    const std::function<bool(uint32_t, uint32_t)> &keep = nullptr, int digits = 5);
 
 // ------------------------------------------------------------- Comm --------
 // Host-side collectives of a multi-process run (one process per GPU): a TCP

@@ -1,5 +1,5 @@
-// score_modes.cpp -- the reports of `hgaprec` on a saved model: -rmse / -msr / -eval-all / -recommend / -similar-items /
-// -similar-users / -fold-in (and -gen-ranking, which is the training run's own ranking on the loaded state).  Each
+// score_modes.cpp -- the reports of `hgaprec` on a saved model: -rmse / -msr / -eval-all / -recommend [-explain] /
+// -similar-items / -similar-users / -topic-items / -topic-users / -fold-in (and -gen-ranking, which is the training run's own ranking on the loaded state).  Each
 // reads the data like a training run, loads the factor files a run has written (from the current directory like the
 // reference, or from -model-dir DIR), writes ONE report and returns.  One GPU; nothing of the training loop is seen here.
 #include "hgaprec_cli.hpp"
@@ -170,13 +170,19 @@ struct ScoreModes : Cli {
   // users, lines and N.  A chunk of users is written before the next is ranked: host memory is O(chunk x N).
   // -fold-in's tail is the same report for the new users: their own handle and ratings, and no list beyond the given
   // ratings, which the call masks itself (mask == nullptr).
+  // -explain T (extension): behind each chunk's lists the same walk hands the (user, item) pairs of the lines it has just
+  // written -- write_topn's rule, so no padding and no given item -- to hpf_explain and writes <stem>_explain.tsv: user id,
+  // item id, factor, contribution (%.8f), pairs in <stem>.tsv's order, each pair's T largest terms best first; with -bias
+  // the factors K and K + 1 are the user and the item bias.  <stem>_explain.txt: pairs, lines, T.  <stem>.tsv is written
+  // by the same calls as without the flag.
   unsigned long long recommend_lists(const Ratings &given, const HeldOut *mask, const std::string &stem) {
-    const uint32_t N = env.recommend;
-    const std::string rpath = env.file_str(stem + ".tsv");
-    FILE *f = open_or_die(rpath, "w");
-    MaskLists ml; std::vector<uint32_t> items; std::vector<double> scores;
+    const uint32_t N = env.recommend, T = env.explain;
+    const std::string rpath = env.file_str(stem + ".tsv"), epath = env.file_str(stem + "_explain.tsv");
+    FILE *f = open_or_die(rpath, "w"), *ef = T ? open_or_die(epath, "w") : nullptr;
+    MaskLists ml; std::vector<uint32_t> items, eu, ei, fac; std::vector<double> scores, con;
     const HeldOut none;
-    unsigned long long lines = 0;
+    unsigned long long lines = 0, epairs = 0, elines = 0;
+    const std::function<bool(uint32_t, uint32_t)> keep = [&](uint32_t u, uint32_t it) { return given.r(u, it) == 0; };
     for_chunks(given.n, [&](size_t u0, size_t u1) {
       ml.fill(mask ? *mask : none, nullptr, 0, (uint32_t)u0, (uint32_t)u1);
       items.resize(ml.users.size() * (size_t)N); scores.resize(ml.users.size() * (size_t)N);
@@ -184,10 +190,27 @@ struct ScoreModes : Cli {
                              items.data(), scores.data());
       if (rc) die("hpf_recommend", rc);
       lines += write_topn(f, ml.users.data(), ml.users.size(), items.data(), scores.data(), N, m, given.seq2user.data(),
-                          rt.seq2item.data(), [&](uint32_t u, uint32_t it) { return given.r(u, it) == 0; });
+                          rt.seq2item.data(), keep);
+      if (!ef) return;
+      eu.clear(); ei.clear();
+      for (size_t b = 0; b < ml.users.size(); ++b)
+        for (uint32_t j = 0; j < m && j < N; ++j)                 // the entries write_topn has written
+          if (keep(ml.users[b], items[b * N + j])) { eu.push_back(ml.users[b]); ei.push_back(items[b * N + j]); }
+      fac.resize(eu.size() * (size_t)T); con.resize(eu.size() * (size_t)T);
+      rc = hpf_explain(h, eu.data(), ei.data(), eu.size(), T, fac.data(), con.data());
+      if (rc) die("hpf_explain", rc);
+      for (size_t p = 0; p < eu.size(); ++p)
+        for (uint32_t r = 0; r < T && fac[p * T + r] != 0xffffffffu; ++r, ++elines)
+          fprintf(ef, "%d\t%d\t%d\t%.8f\n", given.seq2user[eu[p]], rt.seq2item[ei[p]], fac[p * T + r], con[p * T + r]);
+      epairs += eu.size();
     });
     close_or_die(f, rpath);
     write_line(env.file_str(stem + ".txt"), "%u\t%llu\t%u\n", given.n, lines, N);
+    if (ef) {
+      close_or_die(ef, epath);
+      write_line(env.file_str(stem + "_explain.txt"), "%llu\t%llu\t%u\n", epairs, elines, T);
+      env.lerr("-explain: %llu pairs, %llu lines in %s_explain.tsv", epairs, elines, stem.c_str() + 1);
+    }
     return lines;
   }
   void recommend_report() {
@@ -223,13 +246,36 @@ struct ScoreModes : Cli {
     env.lerr("-similar-%s: %u rows, %llu lines in %s.tsv", items ? "items" : "users", rows, lines, base.c_str() + 1);
   }
 
+  // -topic-items N / -topic-users N (extension): what a factor is -- the N rows of E[beta] (E[theta]) that load most on each
+  // of the K factors, through hpf_factor_top.  topic_items.tsv: factor, item id, value (%.8f) -- factors ascending, each
+  // list best first, ids printed as recommend.tsv prints them, the padding of a list beyond the rows never printed;
+  // topic_items.txt: factors, lines, N.  topic_users.* the same for users.  One call: K lists of N are O(K x N) on the host.
+  void topic_report(bool items) {
+    const uint32_t N = items ? env.topic_items : env.topic_users;
+    const uint32_t rows = items ? m : n;
+    const std::vector<uint32_t> &ids = items ? rt.seq2item : rt.seq2user;
+    const std::string base = items ? "/topic_items" : "/topic_users";
+    std::vector<uint32_t> top((size_t)k * N), factors(k);
+    std::vector<double> vals((size_t)k * N);
+    for (uint32_t c = 0; c < k; ++c) factors[c] = c;
+    int rc = hpf_factor_top(h, items ? 1 : 0, N, top.data(), vals.data());
+    if (rc) die("hpf_factor_top", rc);
+    const std::string rpath = env.file_str(base + ".tsv");
+    FILE *f = open_or_die(rpath, "w");
+    const unsigned long long lines = write_topn(f, factors.data(), k, top.data(), vals.data(), N, rows, factors.data(), ids.data(), nullptr, 8);
+    close_or_die(f, rpath);
+    write_line(env.file_str(base + ".txt"), "%u\t%llu\t%u\n", k, lines, N);
+    env.lerr("-topic-%s: %u factors, %llu lines in %s.tsv", items ? "items" : "users", k, lines, base.c_str() + 1);
+  }
+
   // -fold-in FILE (extension; HGAPRec::test(), hgaprec.cc:2257-2346): the users of FILE, who need not be in -dir, folded
   // into the saved model.  The item side comes from -model-dir as SHAPE and RATE (E alone does not give Elog) through the
   // strict readers; the host forms E = shape / rate and Elog = psi(shape) - log(rate) and hands them to a second handle
   // that holds the new users; hpf_fold_in runs -fold-iters iterations from the prior (-fold-tol: a stopping time per
   // user).  Output: the user-side files of save_model under the prefix foldin_, through the same writers; foldin.txt
   // (users, nonzeros, lines skipped for an unknown item, T, X, iterations min / mean / max); with -recommend N also
-  // foldin_recommend.tsv / .txt, recommend_report's lines for the new users with their given ratings masked.
+  // foldin_recommend.tsv / .txt, recommend_report's lines for the new users with their given ratings masked (and with -explain T
+  // foldin_recommend_explain.tsv / .txt).
   void fold_in_report() {
     Ratings nu; uint64_t skipped = 0;
     const int frc = rt.read_fold_in(env.fold_in, &nu, &skipped);
@@ -306,6 +352,10 @@ void score(Cli &c, const std::function<void()> &gen_ranking)
   else if (c.env.similar_items || c.env.similar_users) {
     if (c.env.similar_items) s.similar_report(true);
     if (c.env.similar_users) s.similar_report(false);
+  }
+  else if (c.env.topic_items || c.env.topic_users) {
+    if (c.env.topic_items) s.topic_report(true);
+    if (c.env.topic_users) s.topic_report(false);
   }
   else gen_ranking();
 }

@@ -375,6 +375,16 @@ bool launch_fold(int R, const FoldArgs &a, uint32_t blocks, uint32_t lds_bytes, 
     } else return false;
   });
 }
+// explain_kernel: R terms per lane (hpf_plan::explain_plan), four waves per workgroup
+bool launch_explain(int R, const ExplainArgs &a, uint32_t blocks, hipStream_t st)
+{
+  return pick(R, Counts(), [&](auto r) {
+    if constexpr (hpf_plan::has_explain(PICKED(r))) {
+      hipLaunchKernelGGL((explain_kernel<PICKED(r)>), dim3(blocks), dim3(64 * hpf_plan::EXPLAIN_WAVES), 0, st, a);
+      return true;
+    } else return false;
+  });
+}
 int check_launch(hpf_handle *h, const char *what);
 // the fused rank kernels, by the chunks of A a column count keeps in registers (hpf_plan::rank_chunks); launch(nch) names
 // the kernel template: loo_rank_kernel<nch>, rank_queries_kernel<nch> or topn_sweep_kernel<nch>.  Fails where the column
@@ -2958,6 +2968,71 @@ int hpf_similar(hpf_handle *h, int side, const uint32_t *ids, uint32_t n_sel, ui
                   [&](auto nch, dim3 grid, const TopnArgs &ta) {
                     hipLaunchKernelGGL(similar_sweep_kernel<decltype(nch)::value>, grid, dim3(256), 0, h->stream, ta);
                   }, out_ids, out_scores);
+}
+
+// The T largest terms of every pair's score (explain_kernel): hpf_predict's readiness path and argument checks, no CSR,
+// the state only read.
+static_assert(HPF_EXPLAIN_MAX == hpf_plan::EXPLAIN_MAX && HPF_EXPLAIN_MAX <= 64, "a lane of the wave per returned term");
+int hpf_explain(hpf_handle *h, const uint32_t *u, const uint32_t *i, size_t cnt, uint32_t T, uint32_t *out_factor, double *out_contrib)
+{
+  if (!h) return HPF_ERR_INVALID;
+  if (T < 1 || T > HPF_EXPLAIN_MAX) { h->err = "hpf_explain: T is 1 .. 32"; return HPF_ERR_INVALID; }
+  if (cnt == 0) return HPF_OK;
+  if (!u || !i || !out_factor || !out_contrib) { h->err = "hpf_explain: null pointer"; return HPF_ERR_INVALID; }
+  int rc;
+  if ((rc = need_e(h))) return rc;
+  for (size_t p = 0; p < cnt; ++p)
+    if (u[p] >= h->u.rows || i[p] >= h->it.rows) { h->err = "hpf_explain: index out of range"; return HPF_ERR_INVALID; }
+  const hpf_plan::ExplainPlan ep = hpf_plan::explain_plan(h->K, h->cfg.bias != 0);
+  // the bias terms are numbered by their columns: K the user's, K + 1 the item's (hpf_create)
+  if (!ep.ok || ep.terms > h->ld || (h->cfg.bias && (h->u.bias_col != (int32_t)h->K || h->it.bias_col != (int32_t)h->K + 1))) {
+    h->err = "explain_kernel: no instance for this column count"; return HPF_ERR_UNSUPPORTED;
+  }
+  if ((rc = scoring_ready(h))) return rc;
+  Scratch sc(h);
+  ExplainArgs a;
+  factor_args(h, a);
+  uint32_t *du = nullptr, *di = nullptr;
+  if ((rc = sc.alloc(&du, cnt, u)) || (rc = sc.alloc(&di, cnt, i)) || (rc = sc.alloc(&a.out_factor, cnt * T)) || (rc = sc.alloc(&a.out_contrib, cnt * T))) return rc;
+  a.u = du; a.i = di; a.cnt = cnt; a.T = T; a.run = hpf_plan::EXPLAIN_RUN;
+  if (!launch_explain((int)ep.R, a, ep.grid(cnt), h->stream)) { h->err = "explain_kernel: no instance for this column count"; return HPF_ERR_UNSUPPORTED; }
+  if ((rc = check_launch(h, "explain_kernel"))) return rc;
+  return copy_back(h, {{out_factor, a.out_factor, cnt * T * 4}, {out_contrib, a.out_contrib, cnt * T * 8}});
+}
+
+// The topn heaviest rows of every factor column of one side: a batch of columns transposed into a temporary of this call
+// (transpose_cols_kernel; hpf_plan::factor_top_batch), then hpf_rank_topn's selection, a workgroup per column over its
+// contiguous row (topn_kernel: block_topn as it stands).  Bias columns are never transposed.
+int hpf_factor_top(hpf_handle *h, int side, uint32_t topn, uint32_t *out_ids, double *out_vals)
+{
+  if (!h) return HPF_ERR_INVALID;
+  if (side != 0 && side != 1) { h->err = "hpf_factor_top: side is 0 (users) or 1 (items)"; return HPF_ERR_INVALID; }
+  if (topn < 1 || topn > hpf_plan::FACTOR_TOP_MAX) { h->err = "hpf_factor_top: topn is 1 .. 1024"; return HPF_ERR_INVALID; }
+  if (!out_ids || !out_vals) { h->err = "hpf_factor_top: null pointer"; return HPF_ERR_INVALID; }
+  Side &s = side ? h->it : h->u;
+  if (!s.have_E && h->iterations == 0) { h->err = "E state not set"; return HPF_ERR_STATE; }
+  int rc;
+  if ((rc = check_flags(h)) || (rc = refresh_es(h, s))) return rc;
+  const uint32_t rows = s.rows, K = h->K, NP = hpf_plan::pow2_ceil(topn);
+  const uint32_t batch = hpf_plan::factor_top_batch(rows, K, h->ftop_batch);
+  static_assert(hpf_plan::FACTOR_TOP_TILE == 32, "transpose_cols_kernel's tile");
+  // a launch holds fewer than 2^32 work-items: a batch is <= 2^26 doubles unless one column alone is longer
+  if ((((uint64_t)rows + 31) / 32) * (((uint64_t)batch + 31) / 32) * 256 >= (1ull << 32)) { h->err = "hpf_factor_top: too many rows for one launch"; return HPF_ERR_UNSUPPORTED; }
+  Scratch sc(h);
+  double *d_cols = nullptr, *d_vals = nullptr; uint32_t *d_ids = nullptr;
+  if ((rc = sc.alloc(&d_cols, (size_t)batch * std::max<uint32_t>(rows, 1))) || (rc = sc.alloc(&d_ids, (size_t)K * topn)) || (rc = sc.alloc(&d_vals, (size_t)K * topn))) return rc;
+  for (uint32_t k0 = 0; k0 < K; k0 += batch) {
+    const uint32_t nc = std::min(batch, K - k0);
+    if (rows) {
+      hipLaunchKernelGGL(transpose_cols_kernel, dim3((rows + hpf_plan::FACTOR_TOP_TILE - 1) / hpf_plan::FACTOR_TOP_TILE, (nc + hpf_plan::FACTOR_TOP_TILE - 1) / hpf_plan::FACTOR_TOP_TILE),
+                         dim3(256), 0, h->stream, s.E, d_cols, rows, h->ld, k0, nc);
+      if ((rc = check_launch(h, "transpose_cols_kernel"))) return rc;
+    }
+    hipLaunchKernelGGL(topn_kernel, dim3(nc), dim3(256), (size_t)NP * 12, h->stream, d_cols, nc, rows, topn, NP,
+                       d_ids + (size_t)k0 * topn, d_vals + (size_t)k0 * topn);
+    if ((rc = check_launch(h, "topn_kernel"))) return rc;
+  }
+  return copy_back(h, {{out_ids, d_ids, (size_t)K * topn * 4}, {out_vals, d_vals, (size_t)K * topn * 8}});
 }
 
 int hpf_get_work_info(hpf_handle *h, hpf_work_info *out)

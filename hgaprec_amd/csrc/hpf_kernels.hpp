@@ -3047,6 +3047,132 @@ __global__ __launch_bounds__(256) void topn_merge_kernel(TopnArgs a, uint32_t NP
              a.topn, Ne, NP, a.out_items + (size_t)b * a.topn, a.out_scores + (size_t)b * a.topn);
 }
 
+// ---------------------------------------------------------------------
+// Why a score is what it is (hpf_explain, hpf_factor_top; -explain, -topic-items / -topic-users).
+//   explain_kernel      the T largest of the K (+ 2) non-negative terms of a pair's score, a wave per pair
+//   transpose_cols_kernel  a batch of columns of E as rows, through LDS; topn_kernel (block_topn) then takes the heaviest
+//                       rows of each column from a contiguous row
+// ---------------------------------------------------------------------
+struct ExplainArgs {
+  const uint32_t *u, *i;       // [cnt] the pairs
+  uint64_t        cnt;
+  const double   *Et, *Eb;     // [n x ld], [m x ld]
+  uint32_t       *out_factor;  // [cnt x T]
+  double         *out_contrib; // [cnt x T]
+  uint32_t        ld, K, T, run;          // run: consecutive pairs a wave takes per trip (hpf_plan::EXPLAIN_RUN)
+  int32_t         ubias_col, ibias_col;   // K and K + 1 with -bias (the terms' numbers), -1 without
+};
+
+// the largest key of the wave, in every lane (keys are unsigned 64-bit patterns: score_key)
+__device__ __forceinline__ unsigned long long wave_max_key(unsigned long long k)
+{
+  auto mx = [](unsigned long long a, double b) { const unsigned long long kb = (unsigned long long)__double_as_longlong(b); return a > kb ? a : kb; };
+  auto as_d = [](unsigned long long a) { return __longlong_as_double((long long)a); };     // bits only: a move, no arithmetic
+  k = mx(k, dpp_mov<0xB1>(as_d(k)));
+  k = mx(k, dpp_mov<0x4E>(as_d(k)));
+  k = mx(k, dpp_mov<0x141>(as_d(k)));
+  k = mx(k, dpp_mov<0x140>(as_d(k)));
+  k = mx(k, __shfl_xor(as_d(k), 16, 64));
+  k = mx(k, __shfl_xor(as_d(k), 32, 64));
+  return k;
+}
+// the smallest id of the wave, in every lane
+__device__ __forceinline__ uint32_t wave_min_id(uint32_t v)
+{
+  auto mn = [](uint32_t a, int b) { return a < (uint32_t)b ? a : (uint32_t)b; };
+  v = mn(v, __builtin_amdgcn_update_dpp(0, (int)v, 0xB1, 0xf, 0xf, true));
+  v = mn(v, __builtin_amdgcn_update_dpp(0, (int)v, 0x4E, 0xf, 0xf, true));
+  v = mn(v, __builtin_amdgcn_update_dpp(0, (int)v, 0x141, 0xf, 0xf, true));
+  v = mn(v, __builtin_amdgcn_update_dpp(0, (int)v, 0x140, 0xf, 0xf, true));
+  v = mn(v, __shfl_xor((int)v, 16, 64));
+  v = mn(v, __shfl_xor((int)v, 32, 64));
+  return v;
+}
+
+// One wave per pair; lane l holds the terms l + 64 t, t < R: c_k = E[theta_u k] * E[beta_i k] for k < K -- ONE IEEE
+// multiplication, nothing added to it, so the double handed out is the host's product bit for bit -- and with -bias the
+// copies E[ubias_u] (term K) and E[ibias_i] (term K + 1), the reference's K + 2 layout (hgaprec.cc:1347-1353).  Then up to T
+// rounds: every lane offers the best of its live terms (the first of equal keys: the smallest id a lane holds), the wave
+// takes the largest key (wave_max_key) and among the lanes that offered it the smallest id (wave_min_id) -- ranks_before's
+// order -- and the lane that owns the winner retires it: a bit of a per-lane mask, so no register is indexed by a
+// run-time value.  Lane r keeps the result of round r and the wave stores its T results at once; rounds beyond the terms
+// a score has leave the padding (0xffffffff, 0.0).  A wave walks `run` consecutive pairs and reloads the user's row only
+// when the user changes (a recommend list is a run of one user).  Reads E only.
+template <int R>
+__global__ __launch_bounds__(256) void explain_kernel(ExplainArgs a)
+{
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint64_t w0 = (uint64_t)__builtin_amdgcn_readfirstlane((int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6));
+  const uint64_t nw = ((uint64_t)gridDim.x * blockDim.x) >> 6;
+  const uint32_t K = a.K, C = K + (a.ubias_col >= 0 ? 2u : 0u);
+  const uint32_t rounds = a.T < C ? a.T : C;
+  uint32_t live0 = 0;                                      // bit t: term lane + 64 t exists
+#pragma unroll
+  for (int t = 0; t < R; ++t) live0 |= (lane + 64u * t < C) ? (1u << t) : 0u;
+
+  for (uint64_t base = w0 * a.run; base < a.cnt; base += nw * a.run) {
+    double th[R];
+    uint32_t cur_u = 0xffffffffu;
+    for (uint32_t j = 0; j < a.run && base + j < a.cnt; ++j) {
+      const uint64_t p = base + j;
+      const uint32_t u = (uint32_t)__builtin_amdgcn_readfirstlane((int)a.u[p]), it = (uint32_t)__builtin_amdgcn_readfirstlane((int)a.i[p]);
+      if (u != cur_u) {                                    // wave-uniform
+        const double *et = a.Et + (size_t)u * a.ld;
+#pragma unroll
+        for (int t = 0; t < R; ++t) { const uint32_t c = lane + 64u * t; th[t] = (c < C) ? et[c] : 0.0; }
+        cur_u = u;
+      }
+      const double *eb = a.Eb + (size_t)it * a.ld;
+      unsigned long long key[R];
+#pragma unroll
+      for (int t = 0; t < R; ++t) {
+        const uint32_t c = lane + 64u * t;
+        const double b = (c < C) ? eb[c] : 0.0;
+        const double term = (int32_t)c == a.ubias_col ? th[t] : (int32_t)c == a.ibias_col ? b : th[t] * b;
+        key[t] = score_key(term);
+      }
+      uint32_t live = live0, res_id = 0xffffffffu;
+      unsigned long long res_key = 0ull;
+      for (uint32_t r = 0; r < rounds; ++r) {
+        unsigned long long bk = 0ull; uint32_t bid = 0xffffffffu;
+#pragma unroll
+        for (int t = 0; t < R; ++t) {
+          const bool take = ((live >> t) & 1u) && (bid == 0xffffffffu || key[t] > bk);
+          bk = take ? key[t] : bk; bid = take ? lane + 64u * t : bid;
+        }
+        const unsigned long long wk = wave_max_key(bk);
+        const uint32_t wid = wave_min_id((bk == wk) ? bid : 0xffffffffu);     // r < C: a live term exists
+        if (lane == (wid & 63u)) live &= ~(1u << (wid >> 6));
+        if (lane == r) { res_id = wid; res_key = wk; }
+      }
+      if (lane < a.T) {
+        a.out_factor[p * a.T + lane] = res_id;
+        a.out_contrib[p * a.T + lane] = __longlong_as_double((long long)res_key);
+      }
+    }
+  }
+}
+
+// out[(c - c0) x rows + r] = E[r x ld + c] for the columns c0 <= c < c0 + nc: a tile of 32 rows x 32 columns per workgroup
+// through LDS (33 doubles a row: the transposed read meets 32 different banks), 256-byte runs on both sides
+__global__ __launch_bounds__(256) void transpose_cols_kernel(const double *E, double *out, uint32_t rows, uint32_t ld, uint32_t c0, uint32_t nc)
+{
+  __shared__ double tile[32][33];
+  const uint32_t tx = threadIdx.x & 31u, ty = threadIdx.x >> 5;
+  const uint32_t r0 = blockIdx.x * 32u, k0 = blockIdx.y * 32u;
+#pragma unroll
+  for (uint32_t j = 0; j < 32; j += 8) {
+    const uint32_t r = r0 + ty + j, c = k0 + tx;
+    tile[ty + j][tx] = (r < rows && c < nc) ? E[(size_t)r * ld + c0 + c] : 0.0;
+  }
+  __syncthreads();
+#pragma unroll
+  for (uint32_t j = 0; j < 32; j += 8) {
+    const uint32_t c = k0 + ty + j, r = r0 + tx;
+    if (r < rows && c < nc) out[(size_t)c * rows + r] = tile[tx][ty + j];
+  }
+}
+
 // materialise the per-element rate matrix for export (htheta_rate.tsv):
 // rate[row,k] = prior_used[row] + colsum[k]   (gpbase.hh:163-173,218-223)
 __global__ void build_rate_kernel(const double *prior_used, const double *colsum,

@@ -58,6 +58,7 @@ struct Knobs {
   // user pass, a C3 shard: unchanged).  Same segments, same order inside each: the same bits.  HPF_PHI_WG forces 64 | 128 | 256.
   uint32_t phi_wg = 0;
   long long loo_batch = 0;          // HPF_LOO_BATCH: at most so many users per batch of the fused rank calls (<= 0: no limit of its own)
+  long long ftop_batch = 0;         // HPF_FACTOR_TOP_BATCH: at most so many columns per transposed batch of hpf_factor_top (<= 0: no limit of its own)
   int fold_route = 0;               // HPF_FOLD_ROUTE=sweeps: hpf_fold_in through the training kernels (1), for A/B runs; never chosen by the library
   // HPF_FUSED_SWEEP=0|1|2: the user pass writes W of its single-segment rows in its segment epilogue and the user sweep only
   // takes their sums (fused_sweep below).  0: never (the A/B switch), 1: where it was measured to pay (fused_pays), 2: wherever
@@ -92,6 +93,7 @@ inline Knobs read_knobs()
   if (const char *e = getenv("HPF_TILE_RUN")) { int v = atoi(e); if (v >= 1) k.tile_min_run = (uint32_t)v; }
   if (const char *e = getenv("HPF_TILE_SHARE")) { int v = atoi(e); if (v >= 0 && v <= 100) k.tile_min_share = v / 100.0; }
   if (const char *e = getenv("HPF_PHI_BLOCKS")) { int v = atoi(e); if (v >= 1) k.phi_blocks = (uint32_t)v; }
+  if (const char *e = getenv("HPF_FACTOR_TOP_BATCH")) k.ftop_batch = atoll(e);
   if (const char *e = getenv("HPF_FOLD_ROUTE")) k.fold_route = !strcmp(e, "sweeps") ? 1 : 0;
   if (const char *e = getenv("HPF_PHI_WG")) { int v = atoi(e); if (v == 64 || v == 128 || v == 256) k.phi_wg = (uint32_t)v; }
   return k;
@@ -244,6 +246,46 @@ inline FoldPlan fold_plan(uint32_t K, bool bias)
   p.rows_held = std::min<uint32_t>(64u, p.lds_wave_bytes / (p.ld * 8u));
   p.ok = has_fold((int)p.R) && p.rows_held >= 1;
   return p;
+}
+
+// ---- why a score is what it is (hpf_explain, hpf_factor_top) --------------------------------------
+// explain_kernel<R>: a wave per pair, lane l holds the terms l + 64 t, t < R, of the pair's score -- the K products and,
+// with bias, the two bias terms K and K + 1 -- read straight from the handle's E (whatever its row stride; no copy).
+// Workgroups of EXPLAIN_WAVES waves; a wave takes EXPLAIN_RUN consecutive pairs per trip, so that the run of pairs a
+// recommend list makes keeps its user's row in registers; at most EXPLAIN_BLOCKS_MAX workgroups (eight per CU), which then
+// stride.  hgaprec_amd/capi.py mirrors the arithmetic (explain_plan).
+constexpr uint32_t EXPLAIN_MAX = 32;      // HPF_EXPLAIN_MAX of hpf.h (pinned there by hpf_capi.hip): a lane per returned term
+constexpr uint32_t EXPLAIN_WAVES = 4, EXPLAIN_RUN = 8, EXPLAIN_BLOCKS_MAX = 2048;
+constexpr bool has_explain(int R) { return R >= 1 && R <= 16; }
+struct ExplainPlan {
+  uint32_t terms = 0, R = 0;            // terms of a score: K + 2 * bias; terms per lane
+  bool ok = false;                      // false: no kernel instance for this column count
+  static constexpr uint32_t pairs_per_block() { return EXPLAIN_WAVES * EXPLAIN_RUN; }
+  // workgroups for cnt pairs: a run per wave until the grid is EXPLAIN_BLOCKS_MAX workgroups
+  uint32_t grid(uint64_t cnt) const { return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((cnt + pairs_per_block() - 1) / pairs_per_block(), EXPLAIN_BLOCKS_MAX)); }
+  // pairs one trip of that grid covers: above it the waves stride
+  uint64_t pairs_per_trip(uint64_t cnt) const { return (uint64_t)grid(cnt) * pairs_per_block(); }
+};
+inline ExplainPlan explain_plan(uint32_t K, bool bias)
+{
+  ExplainPlan p;
+  const uint32_t C = K + (bias ? 2u : 0u);
+  if (K < 1 || C > HPF_MAX_COLUMNS) return p;
+  p.terms = C;
+  p.R = (C + 63u) / 64u;
+  p.ok = has_explain((int)p.R);
+  return p;
+}
+
+// hpf_factor_top: columns transposed at once into the temporary [batch x rows] the selection reads, <= 512 MB of it (one
+// column where a single one is longer); `knob` (HPF_FACTOR_TOP_BATCH, a TEST knob) makes the batch smaller
+constexpr uint32_t FACTOR_TOP_MAX = TOPN_MAX, FACTOR_TOP_TILE = 32;
+constexpr uint64_t FACTOR_TOP_BYTES = (uint64_t)512 << 20;
+inline uint32_t factor_top_batch(uint32_t rows, uint32_t K, long long knob)
+{
+  uint64_t b = std::max<uint64_t>(1, FACTOR_TOP_BYTES / (8ull * std::max<uint32_t>(rows, 1)));
+  if (knob > 0) b = std::min<uint64_t>(b, (uint64_t)knob);
+  return (uint32_t)std::min<uint64_t>(b, std::max<uint32_t>(K, 1));
 }
 
 // ---- the tiled phi pass: what is tiled, and where its segments run --------------------------------

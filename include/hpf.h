@@ -424,6 +424,37 @@ typedef enum { HPF_SIM_COSINE = 0, HPF_SIM_DOT = 1 } hpf_similarity;
 int  hpf_similar(hpf_handle *h, int side, const uint32_t *ids, uint32_t n_sel,
                  uint32_t topn, int metric, uint32_t *out_ids, double *out_scores);
 
+/* (an extension; the reference has no counterpart.)  Why a score is what it is: the T largest of the terms whose sum a
+ * pair's score is.  For pair p the terms are c_k = E[theta_u k] * E[beta_i k], k < K -- each ONE IEEE fp64 multiplication,
+ * nothing fused into it and no reciprocal: the double returned is, bit for bit, the product a host forms from the two
+ * hpf_get_state rows -- and with bias two more in the reference's K + 2 layout (hgaprec.cc:1347-1353): term K is
+ * E[ubias_u] and term K + 1 is E[ibias_i], copied.  out_factor[p x T + r] / out_contrib[p x T + r] are the r-th term of
+ * pair p in the ranking calls' one order, taken on the bit pattern: the larger term first, of equal terms the smaller
+ * factor number.  Entries beyond the K + 2 * bias terms a score has are (0xffffffff, 0.0).  Domain: the ranking calls' --
+ * E finite and >= +0.0 (a product may be subnormal or +0.0 and is ordered by its pattern like the rest).
+ * u is a LOCAL user index.  A pair may be given twice; both rows are then equal.  T is 1 .. HPF_EXPLAIN_MAX.  T outside
+ * that, a user or an item out of range, or a null pointer with cnt > 0 is HPF_ERR_INVALID before anything is launched;
+ * cnt = 0 is HPF_OK; no E on either side is HPF_ERR_STATE, as for hpf_predict.  Needs no CSR.  Synchronous.  The model
+ * state is not written.
+ * The sum of a row with T = K + 2 * bias is NOT held to the bits of hpf_predict for the pair: that call adds the same
+ * products in another order and fused (sixteen chains of FMAs, a tree, then the biases).  All terms are >= 0, so the two
+ * agree to the roundings each takes: |hpf_predict - sum| <= (ceil(K / 16) + 10) 2^-53 sum for an exactly added row.
+ * A wave per pair, the terms in registers; device memory beyond inputs and outputs: none. */
+#define HPF_EXPLAIN_MAX 32
+int  hpf_explain(hpf_handle *h, const uint32_t *u, const uint32_t *i, size_t cnt, uint32_t T,
+                 uint32_t *out_factor /* cnt x T */, double *out_contrib /* cnt x T */);
+/* (an extension.)  What a factor is: for every factor column k < K of one side -- 0: the rows of E[theta] of this handle's
+ * users (with several ranks the LOCAL users only; nothing is exchanged, as for hpf_similar), 1: the rows of E[beta] -- the
+ * topn rows with the largest E[r, k], ids ascending among equal values: out_ids[k x topn + j] / out_vals[k x topn + j].
+ * The values are copies.  Bias columns take no part.  Entries beyond the row count are (0xffffffff, 0.0).  Domain: the
+ * ranking calls'.  topn is 1 .. 1024, the limit of hpf_rank_topn, whose selection it is (one workgroup per column).  A
+ * side not listed, topn outside that or a null pointer is HPF_ERR_INVALID before anything is launched; no E on that side
+ * is HPF_ERR_STATE.  Needs no CSR.  Synchronous.  The model state is not written.
+ * Device memory beyond the outputs: a batch of columns transposed to rows, <= 512 MB (one column where a single column
+ * is longer), freed when the call returns; more than 2^32 / 8 rows in one column is HPF_ERR_UNSUPPORTED. */
+int  hpf_factor_top(hpf_handle *h, int side, uint32_t topn,
+                    uint32_t *out_ids /* K x topn */, double *out_vals /* K x topn */);
+
 /* replaces: HGAPRec::test() (hgaprec.cc:2257-2346) -- load the item factors, put the user at the prior
  * (set_to_prior + set_to_prior_curr, 2278-2279), run user-side CAVI iterations over the user's ratings with the item
  * side untouched.  The handle's users are the NEW users: their ratings uploaded with hpf_upload_csr[_device] (val = NULL:
