@@ -415,6 +415,11 @@ int recover_if_flushed(hpf_handle *h)
   return recover_flush(h, f[0], f[1]);
 }
 
+// for an export that reads what only the sweeps write (a rate's column sums, the xi / eta vectors, the exchange buffer): the
+// iterations a fall-back made the passes skip are run first.  Between iterations only -- inside one the item side's S
+// already holds the sums of the iteration in flight, not those its last sweep read.
+int recover_between_iterations(hpf_handle *h) { return h->phase == 0 ? recover_if_flushed(h) : HPF_OK; }
+
 // surfaces a numerical breakdown the kernels flagged (synchronises the stream)
 int check_flags(hpf_handle *h)
 {
@@ -1887,6 +1892,7 @@ int hpf_start_sums(hpf_handle *h)
 int hpf_exchange_read(hpf_handle *h, double *host, size_t count)
 {
   if (!h || !host || count != h->exch_count) return HPF_ERR_INVALID;
+  { int rc = recover_between_iterations(h); if (rc) return rc; }
   HIPCHK(h, hipMemcpyAsync(host, h->exch, count * 8, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   return HPF_OK;
@@ -2042,12 +2048,16 @@ static int set_state_impl(hpf_handle *h, hpf_state which, const double *host, si
   auto put2d = [&](double *dev, uint32_t c0) -> int {
     return on_device ? copy_in_dev(h, dev, h->ld, c0, host, rows, cols) : copy_in(h, dev, h->ld, c0, host, rows, cols);
   };
+  // a call that is refused -- or, the bias rate, accepted and ignored -- leaves the handle as it was, the flag word included
+  const bool gr_rate = (obj <= 1 && kind == 1 && !h->cfg.hier);
+  const size_t want = (obj == 2 || obj == 3) ? (size_t)rows : gr_rate ? (size_t)h->K : (size_t)rows * cols;
+  if (count != want) return HPF_ERR_INVALID;
+  if (kind == 1 && obj >= 4) return HPF_OK;   // bias rate is the constant 0.3 + m / 0.3 + n
   // a new state supersedes whatever the kernels flagged about the old one -- but iterations a flushed entry made the
   // passes skip are part of the old one: they are run first (recover_flush)
   if ((rc = recover_if_flushed(h))) return rc;
   HIPCHK(h, hipMemsetAsync(h->flags, 0, 4, h->stream));
   if (obj == 2 || obj == 3) {                 // xi / eta vectors
-    if (count != rows) return HPF_ERR_INVALID;
     double **dst = nullptr;
     switch (kind) {
       case 0: dst = &s->prior_shape_set; break;
@@ -2058,21 +2068,17 @@ static int set_state_impl(hpf_handle *h, hpf_state which, const double *host, si
     if (!*dst && (rc = dalloc(h, dst, rows))) return rc;
     return put(*dst, host, (size_t)rows * 8);
   }
-  const bool gr_rate = (obj <= 1 && kind == 1 && !h->cfg.hier);
   if (kind == 1) {                            // rate: kept only for export before iteration 0
-    const size_t want = gr_rate ? h->K : (size_t)rows * cols;
-    if (count != want) return HPF_ERR_INVALID;
-    if (obj >= 4) return HPF_OK;              // bias rate is the constant 0.3 + m / 0.3 + n
     dfree(s->rate_set); s->rate_set = nullptr;
     if ((rc = dalloc(h, &s->rate_set, want))) return rc;
     s->rate_set_count = want;
     return put(s->rate_set, host, want * 8);
   }
-  if (count != (size_t)rows * cols) return HPF_ERR_INVALID;
   if ((rc = refresh_es(h, *s))) return rc;     // the rest of S / E must be current before patching
   double *dev = kind == 0 ? s->S : kind == 2 ? s->E : s->L;
-  if (kind == 3 && s->l_stale) {
-    // the rest of L predates the last sweep: rebuild it before patching in the new part
+  if ((kind == 3 || kind == 0) && s->l_stale) {
+    // Elog: the rest of L predates the last sweep, rebuild it before patching in the new part.  Shape: L is rebuilt from
+    // S, and a shape handed in is not the sweep's -- an Elog exported later must not depend on whether one was exported before
     if ((rc = refresh_elog(h, *s))) return rc;
   }
   if ((rc = put2d(dev, (uint32_t)col0))) return rc;
@@ -2117,8 +2123,12 @@ static int get_state_impl(hpf_handle *h, hpf_state which, double *host, size_t c
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return HPF_OK;
   };
+  // the exports below read neither S, E nor W, but the xi / eta vectors and the column sums a rate is built from are the
+  // sweeps' too: iterations a fall-back made the passes skip are run first (not check_flags: an underflow report is
+  // about E, and these exports never failed on it)
   if (obj == 2 || obj == 3) {
     if (count != rows) return HPF_ERR_INVALID;
+    { int rc = recover_between_iterations(h); if (rc) return rc; }
     if (kind == 2 || kind == 1) return get(host, kind == 2 ? s->prior_E : s->prior_rate, (size_t)rows * 8);
     if (kind == 3) return get(host, s->prior_elog, (size_t)rows * 8);   // set by the host, then maintained by the sweep
     if (h->iterations == 0) {
@@ -2133,6 +2143,7 @@ static int get_state_impl(hpf_handle *h, hpf_state which, double *host, size_t c
     const bool gr = (obj <= 1 && !h->cfg.hier);
     const size_t want = gr ? h->K : (size_t)rows * cols;
     if (count != want) return HPF_ERR_INVALID;
+    { int rc = recover_between_iterations(h); if (rc) return rc; }
     if (obj >= 4) {                           // gpbase.hh:225-231 via hgaprec.cc:1389,1393
       if (h->iterations == 0 && !s->bias_rate_known) { h->err = "bias rate is defined after the first sweep"; return HPF_ERR_STATE; }
       return fill(r0 + s->bias_rate_add, rows);
@@ -2246,6 +2257,8 @@ void fill_snap_header(hpf_handle *h, SnapHeader *hd)
 int hpf_snapshot_size(hpf_handle *h, size_t *bytes)
 {
   if (!h || !bytes) return HPF_ERR_INVALID;
+  // a fall-back that is due changes the size of W: it happens here, so that hpf_snapshot_save finds the size it is handed
+  { int rc = recover_between_iterations(h); if (rc) return rc; }
   SnapHeader hd; fill_snap_header(h, &hd);
   *bytes = (size_t)hd.total_bytes;
   return HPF_OK;

@@ -176,10 +176,13 @@ int  hpf_get_csc(hpf_handle *h, int64_t *colptr, uint32_t *users, uint8_t *vals)
 
 /* replaces: the result of HGAPRec::initialize (hgaprec.cc:153-204) -- the host
  * draws the MT19937 stream and hands over E / Elog (and shapes, for export).
- * count must equal the element count of that array. */
+ * count must equal the element count of that array.
+ * A refused call (a wrong count, a state that is not part of the model) and the bias-rate set, which is accepted and
+ * ignored, leave the handle untouched: the model, what is pending and a report of an underflow not yet delivered. */
 int  hpf_set_state(hpf_handle *h, hpf_state which, const double *host, size_t count);
 /* replaces: reads of shape_curr()/rate_curr()/expected_v()/expected_logv()
- * by save_model (hgaprec.cc:2137-2158) */
+ * by save_model (hgaprec.cc:2137-2158).
+ * Every export, between iterations, is of the last iteration hpf_iterate returned for, whatever was exported before. */
 int  hpf_get_state(hpf_handle *h, hpf_state which, double *host, size_t count);
 /* the same with DEVICE pointers (dense row-major doubles in HBM, same element
  * counts): no PCIe round trip for callers whose state is already resident */
