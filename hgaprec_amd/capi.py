@@ -42,7 +42,7 @@ EXPORTS = [
     "hpf_iteration_times", "hpf_debug_poke_index", "hpf_start_sums", "hpf_host_alloc", "hpf_host_free",
     "hpf_heldout_bind", "hpf_heldout_ll_bound",
     "hpf_predict", "hpf_loo_ranks", "hpf_rank_queries", "hpf_recommend", "hpf_fold_in", "hpf_similar",
-    "hpf_explain", "hpf_factor_top",
+    "hpf_explain", "hpf_factor_top", "hpf_fold_in_items",
 ]
 
 # hpf_similar: the metrics (hpf_similarity in include/hpf.h) and the largest topn (TOPN_FUSED_MAX: only the fused route exists)
@@ -103,6 +103,36 @@ def fold_plan(K, bias=False):
 def fold_grid(n):
     """workgroups hpf_fold_in launches for n users"""
     return max(1, min((n + FOLD_WAVES - 1) // FOLD_WAVES, FOLD_BLOCKS_MAX))
+
+
+# hpf_fold_in_items (hpf_plan::fold_items_plan): a row of at least FOLD_LONG_MIN nonzeros goes to fold_in_long_kernel, a
+# workgroup of fold_long_waves(R) waves per row, at most FOLD_LONG_BLOCKS_MAX workgroups
+FOLD_LONG_MIN, FOLD_LONG_BLOCKS_MAX = 256, 4096
+
+
+def fold_long_waves(R):
+    """waves of a workgroup of fold_in_long_kernel<R, WAVES>: eight while the build needs no scratch, else four"""
+    return 8 if R <= 8 else 4
+
+
+def fold_part(length, waves, w):
+    """[begin, end) of the nonzeros of a row of `length` that wave w of `waves` walks: whole 64-blocks, contiguous"""
+    blocks = (length + 63) // 64
+    per = (blocks + waves - 1) // waves
+    return min(min(w * per, blocks) * 64, length), min(min((w + 1) * per, blocks) * 64, length)
+
+
+def fold_items_plan(K, bias=False):
+    """shape of hpf_fold_in_items for K factors: fold_plan's (the wave kernel), and for the long rows the waves of a
+    workgroup, its LDS bytes (the waves' partial rows and the stop word) and the threshold"""
+    p = fold_plan(K, bias)
+    waves = fold_long_waves(p["R"])
+    return dict(p, waves=waves, lds_long_bytes=waves * p["R"] * 64 * 8 + 16, long_min=FOLD_LONG_MIN)
+
+
+def fold_long_grid(n_long):
+    """workgroups fold_in_long_kernel is launched with for n_long long rows (0: no launch)"""
+    return min(n_long, FOLD_LONG_BLOCKS_MAX)
 
 
 # hpf_explain (hpf_plan::explain_plan in csrc/hpf_plan.hpp): a wave per pair, workgroups of EXPLAIN_WAVES waves, a run of
@@ -268,6 +298,8 @@ def load_library(path: os.PathLike | None = None) -> C.CDLL:
         lib.hpf_recommend.argtypes = [vp, u32p, C.c_uint32, u64p, u32p, C.c_uint32, u32p, dp]
     if hasattr(lib, "hpf_fold_in"):
         lib.hpf_fold_in.argtypes = [vp, C.c_uint32, C.c_double, u32p]
+    if hasattr(lib, "hpf_fold_in_items"):
+        lib.hpf_fold_in_items.argtypes = [vp, C.c_uint32, C.c_double, u32p]
     if hasattr(lib, "hpf_similar"):
         lib.hpf_similar.argtypes = [vp, C.c_int, u32p, C.c_uint32, C.c_uint32, C.c_int, u32p, dp]
     if hasattr(lib, "hpf_explain"):
@@ -665,6 +697,15 @@ class Hpf:
         iters = np.zeros(self.n_users, dtype=np.uint32) if want_iters else None
         self._check(self.lib.hpf_fold_in(self._h, int(n_iters) & 0xffffffff, float(tol),
                                          _ptr(iters, C.c_uint32) if want_iters else None))
+        return iters
+
+    def fold_in_items(self, n_iters=10, tol=0.0, want_iters=True):
+        """fold this handle's items in against the user side handed in (hpf_fold_in_items): from the prior, n_iters item-side
+        iterations (tol > 0: an item stops once its E[beta] moves by no more than tol of its largest entry)
+        -> the iterations every item ran (None with want_iters=False: iters_out = NULL)"""
+        iters = np.zeros(self.n_items, dtype=np.uint32) if want_iters else None
+        self._check(self.lib.hpf_fold_in_items(self._h, int(n_iters) & 0xffffffff, float(tol),
+                                               _ptr(iters, C.c_uint32) if want_iters else None))
         return iters
 
     def item_ranks(self, users, q_sel, q_item, mask_ptr=None, mask_items=None):

@@ -130,6 +130,15 @@ int Env::parse(int argc, char **argv, bool echo, std::string *bad)
       }
       fold_in = v;
     }
+    else if (!strcmp(s, "-fold-in-items")) {                      // extension: fold the items of FILE into a saved model
+      const char *v = next();
+      if (!*v || *v == '-') {
+        usage_error = "-fold-in-items needs the file with the new items' ratings (user id, item id, rating)";
+        if (bad) *bad = s;
+        return 2;
+      }
+      fold_in_items = v;
+    }
     else if (!strcmp(s, "-fold-iters")) {
       const char *v = next(); char *end = nullptr;
       const long t = strtol(v, &end, 10);
@@ -168,6 +177,12 @@ int Env::parse(int argc, char **argv, bool echo, std::string *bad)
       if (bad) *bad = s;
       return 1;
     }
+  }
+  if (!fold_in_items.empty() && (gen_ranking || rmse || msr || eval_all || recommend || !fold_in.empty() || similar_items || similar_users ||
+                                 topic_items || topic_users)) {
+    usage_error = "-fold-in-items runs alone: not with -fold-in and not with another score mode";
+    if (bad) *bad = "-fold-in-items";
+    return 2;
   }
   if (explain && !recommend) {                                    // wherever the two stand on the line
     usage_error = "-explain goes with -recommend N: it explains the recommended items";
@@ -611,6 +626,46 @@ int Ratings::read_fold_in(const std::string &path, Ratings *out, uint64_t *skipp
     if (!out->user2seq.find(uid, &us)) {
       if (out->n == 0xffffffffu) break;
       us = out->n; out->user2seq.put(uid, us); out->seq2user.push_back(uid); out->n++;
+    }
+    out->nratings++;
+    out->tr_u_.push_back(us); out->tr_i_.push_back(ms); out->tr_y_.push_back(rating);
+  }
+  fclose(f);
+  out->build_csr();
+  return 0;
+}
+
+// -fold-in-items FILE: the mirror -- ratings of items that need not be in the data set this object holds, by ITS users.
+// The same token rules.  Per record, in this order: a user the data set does not know -> skipped and counted; a rating of
+// class 0 -> dropped; otherwise the item gets the next sequence number at its first accepted record -- the item id is
+// taken as given, whether or not the data set knows it, and an item all of whose lines were skipped or dropped does not
+// exist.  out: m, seq2item and a CSR over this object's n users (rows in file order, every copy of a duplicated pair with
+// the LAST rating); n and seq2user are this object's.
+int Ratings::read_fold_in_items(const std::string &path, Ratings *out, uint64_t *skipped_unknown) const
+{
+  FILE *f = fopen(path.c_str(), "r");
+  if (!f) return -1;
+  *out = Ratings();
+  out->binary = binary; out->rating_threshold = rating_threshold;
+  out->cap_n = n; out->cap_m = 0xffffffffu; out->n = n; out->seq2user = seq2user;
+  *skipped_unknown = 0;
+  Tok tk(f);
+  uint32_t uid = 0, mid = 0, rating = 0;
+  while (!tk.at_eof()) {
+    const int r1 = tk.next_u32(&uid);
+    const int r2 = r1 == 1 ? tk.next_u32(&mid) : 0;
+    const int r3 = r2 == 1 ? tk.next_u32(&rating) : (r2 < 0 ? -1 : 0);
+    if (r1 == 0 || r2 == 0 || r3 == 0) {
+      fprintf(stderr, "error: malformed line in ratings file\n");
+      fclose(f);
+      return -2;
+    }
+    uint32_t us = 0, ms = 0;
+    if (!user2seq.find(uid, &us)) { ++*skipped_unknown; continue; }
+    if (input_rating_class(rating) == 0) continue;
+    if (!out->item2seq.find(mid, &ms)) {
+      if (out->m == 0xffffffffu) break;
+      ms = out->m; out->item2seq.put(mid, ms); out->seq2item.push_back(mid); out->m++;
     }
     out->nratings++;
     out->tr_u_.push_back(us); out->tr_i_.push_back(ms); out->tr_y_.push_back(rating);

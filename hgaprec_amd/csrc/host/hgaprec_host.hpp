@@ -70,6 +70,11 @@ struct Env {
   // user-side files of save_model under the prefix foldin_, foldin.txt and, with -recommend N, foldin_recommend.tsv / .txt.
   // A score mode too.  No FILE, T outside 1 .. 10^6 or X outside 0 .. 1: parse() returns 2 and says why in usage_error
   std::string fold_in;
+  // extension: -fold-in-items FILE [-fold-iters T] [-fold-tol X] is the mirror for a catalogue that grows: the ITEMS of FILE --
+  // which need not be in -dir -- rated by users of -dir, folded in through hpf_fold_in_items against the frozen user side;
+  // writes the item-side files of save_model under the prefix foldin_ and foldin_items.txt.  A score mode that runs alone:
+  // with -fold-in or any other score mode parse() returns 2 and says why in usage_error
+  std::string fold_in_items;
   uint32_t fold_iters = 10;
   double fold_tol = 0.0;
   // extension: -similar-items N / -similar-users N [-similar-metric cosine|dot] write the N nearest other items of every
@@ -86,7 +91,7 @@ struct Env {
   uint32_t topic_items = 0, topic_users = 0, explain = 0;
   std::string usage_error;
   bool score_mode() const {
-    return gen_ranking || rmse || msr || eval_all || recommend > 0 || !fold_in.empty() || similar_items > 0 || similar_users > 0 ||
+    return gen_ranking || rmse || msr || eval_all || recommend > 0 || !fold_in.empty() || !fold_in_items.empty() || similar_items > 0 || similar_users > 0 ||
            topic_items > 0 || topic_users > 0;
   }
 
@@ -142,6 +147,11 @@ struct Ratings {
   // item is unknown are skipped and counted; ratings the train reader drops are dropped; a user none of whose lines is
   // accepted does not exist; an empty file is zero users.  0 / -1 (cannot open) / -2 (malformed)
   int read_fold_in(const std::string &path, Ratings *out, uint64_t *skipped_unknown) const;
+  // -fold-in-items FILE (extension): the mirror -- lines of ITEMS that need not be in this data set, against THIS data
+  // set's users.  out: the new items -- m, seq2item in order of first appearance (the item id taken as given) -- and a CSR
+  // over this object's n users whose columns are new-item numbers; n and seq2user are this object's.  Lines whose user is
+  // unknown are skipped and counted; the rest as read_fold_in.  0 / -1 / -2
+  int read_fold_in_items(const std::string &path, Ratings *out, uint64_t *skipped_unknown) const;
   // ratings.cc:273-292: seq ids (sorted, unique) of the listed users that
   // appear in the training set.  -1 if the file cannot be opened
   int read_test_users(const std::string &path, std::vector<uint32_t> *out) const;

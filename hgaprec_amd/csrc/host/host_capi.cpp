@@ -52,6 +52,14 @@ Ratings *hg_ratings_read_fold_in(const Ratings *model, const char *path, uint64_
   if (*rc) { delete out; return nullptr; }
   return out;
 }
+// -fold-in-items FILE against the users of `model`: a new Ratings holding the new items over model's users
+Ratings *hg_ratings_read_fold_in_items(const Ratings *model, const char *path, uint64_t *skipped_unknown, int *rc)
+{
+  Ratings *out = new Ratings();
+  *rc = model->read_fold_in_items(path, out, skipped_unknown);
+  if (*rc) { delete out; return nullptr; }
+  return out;
+}
 uint32_t hg_ratings_n(const Ratings *r) { return r->n; }
 uint32_t hg_ratings_m(const Ratings *r) { return r->m; }
 uint64_t hg_ratings_nnz(const Ratings *r) { return r->col.size(); }

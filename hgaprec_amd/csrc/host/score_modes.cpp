@@ -1,5 +1,5 @@
 // score_modes.cpp -- the reports of `hgaprec` on a saved model: -rmse / -msr / -eval-all / -recommend [-explain] /
-// -similar-items / -similar-users / -topic-items / -topic-users / -fold-in (and -gen-ranking, which is the training run's own ranking on the loaded state).  Each
+// -similar-items / -similar-users / -topic-items / -topic-users / -fold-in / -fold-in-items (and -gen-ranking, which is the training run's own ranking on the loaded state).  Each
 // reads the data like a training run, loads the factor files a run has written (from the current directory like the
 // reference, or from -model-dir DIR), writes ONE report and returns.  One GPU; nothing of the training loop is seen here.
 #include "hgaprec_cli.hpp"
@@ -276,65 +276,84 @@ struct ScoreModes : Cli {
   // (users, nonzeros, lines skipped for an unknown item, T, X, iterations min / mean / max); with -recommend N also
   // foldin_recommend.tsv / .txt, recommend_report's lines for the new users with their given ratings masked (and with -explain T
   // foldin_recommend_explain.tsv / .txt).
-  void fold_in_report() {
+  //
+  // -fold-in-items FILE (extension) is the mirror, for a catalogue that grows: the ITEMS of FILE, which need not be in -dir,
+  // rated by users of -dir (Ratings::read_fold_in_items).  The USER side comes from -model-dir as shape and rate
+  // (htheta / theta, with -bias thetabias), the second handle holds the n users x the new items, hpf_fold_in_items runs
+  // the iterations.  Output: the item-side files of save_model under foldin_ (foldin_hbeta*.tsv, foldin_betarate*.tsv,
+  // foldin_betabias*.tsv) and foldin_items.txt (items, ratings, lines skipped for an unknown user, T, X, iterations
+  // min / mean / max).
+  void fold_in_report(bool items) {
+    const char *flag = items ? "-fold-in-items" : "-fold-in";
+    const std::string &file = items ? env.fold_in_items : env.fold_in;
     Ratings nu; uint64_t skipped = 0;
-    const int frc = rt.read_fold_in(env.fold_in, &nu, &skipped);
-    if (frc) { fprintf(stderr, "error: -fold-in: cannot %s %s\n", frc == -1 ? "open" : "parse", env.fold_in.c_str()); exit(1); }
+    const int frc = items ? rt.read_fold_in_items(file, &nu, &skipped) : rt.read_fold_in(file, &nu, &skipped);
+    if (frc) { fprintf(stderr, "error: %s: cannot %s %s\n", flag, frc == -1 ? "open" : "parse", file.c_str()); exit(1); }
+    // the frozen side: the items of the model for new users, its users for new items
+    const uint32_t fr = items ? n : m;
+    const std::vector<uint32_t> &fids = items ? rt.seq2user : rt.seq2item;
+    const std::string fbase = items ? (env.hier ? "htheta" : "theta") : (env.hier ? "hbeta" : "beta");
+    const std::string fbias = items ? "thetabias" : "betabias";
     std::string err;
-    std::vector<double> E, L((size_t)m * k), rate;
-    const std::string base = env.hier ? "hbeta" : "beta";
-    load(base + "_shape.tsv", E, m, k, &rt.seq2item);
-    const std::string rate_path = env.hier ? load(base + "_rate.tsv", rate, m, k, &rt.seq2item) : load(base + "_rate.tsv", rate, k, 1, nullptr);
-    if (gamma_expectations(E.data(), L.data(), rate.data(), m, k, !env.hier, rate_path, &err)) model_die(err);
-    std::vector<double> bE, bL(env.bias ? m : 0);
+    std::vector<double> E, L((size_t)fr * k), rate;
+    load(fbase + "_shape.tsv", E, fr, k, &fids);
+    const std::string rate_path = env.hier ? load(fbase + "_rate.tsv", rate, fr, k, &fids) : load(fbase + "_rate.tsv", rate, k, 1, nullptr);
+    if (gamma_expectations(E.data(), L.data(), rate.data(), fr, k, !env.hier, rate_path, &err)) model_die(err);
+    std::vector<double> bE, bL(env.bias ? fr : 0);
     if (env.bias) {
-      load("betabias_shape.tsv", bE, m, 1, &rt.seq2item);
-      const std::string bp = load("betabias_rate.tsv", rate, m, 1, &rt.seq2item);
-      if (gamma_expectations(bE.data(), bL.data(), rate.data(), m, 1, false, bp, &err)) model_die(err);
+      load(fbias + "_shape.tsv", bE, fr, 1, &fids);
+      const std::string bp = load(fbias + "_rate.tsv", rate, fr, 1, &fids);
+      if (gamma_expectations(bE.data(), bL.data(), rate.data(), fr, 1, false, bp, &err)) model_die(err);
     }
-    env.lerr("-fold-in: item side loaded from %s", env.model_dir.empty() ? "." : env.model_dir.c_str());
+    env.lerr("%s: %s side loaded from %s", flag, items ? "user" : "item", env.model_dir.empty() ? "." : env.model_dir.c_str());
 
+    // the folded-in side: nu.n new users, or nu.m new items (rows of the second handle)
+    const uint32_t rows = items ? nu.m : nu.n;
+    std::vector<uint32_t> iters(rows);
     ScoreModes f(*this);                         // the second handle: its die() reports that handle
     f.h = nullptr;
-    hpf_config cfg = config(nu.n, nu.n);
-    cfg.novb = 0;                                // the new users are never iterated by vb_bias()
-    int rc = hpf_create(&cfg, &f.h);
-    if (rc) f.die("hpf_create (-fold-in)", rc);
-    rc = hpf_upload_csr(f.h, nu.rowptr.data(), nu.col.data(), env.binary_data ? nullptr : nu.val.data());
-    if (rc) f.die("hpf_upload_csr (-fold-in)", rc);
-    f.put(HPF_BETA_E, E); f.put(HPF_BETA_ELOG, L);
-    if (env.bias) { f.put(HPF_IBIAS_E, bE); f.put(HPF_IBIAS_ELOG, bL); }
-    std::vector<uint32_t> iters(nu.n);
-    rc = hpf_fold_in(f.h, env.fold_iters, env.fold_tol, iters.data());
-    if (rc) f.die("hpf_fold_in", rc);
+    if (!items || rows) {                        // (a handle of zero items does not exist: nothing to fold in, empty files)
+      hpf_config cfg = config(nu.n, nu.n);
+      cfg.n_items = nu.m;
+      cfg.novb = 0;                              // the new rows are never iterated by vb_bias()
+      int rc = hpf_create(&cfg, &f.h);
+      if (rc) f.die("hpf_create (fold-in)", rc);
+      rc = hpf_upload_csr(f.h, nu.rowptr.data(), nu.col.data(), env.binary_data ? nullptr : nu.val.data());
+      if (rc) f.die("hpf_upload_csr (fold-in)", rc);
+      f.put(items ? HPF_THETA_E : HPF_BETA_E, E); f.put(items ? HPF_THETA_ELOG : HPF_BETA_ELOG, L);
+      if (env.bias) { f.put(items ? HPF_UBIAS_E : HPF_IBIAS_E, bE); f.put(items ? HPF_UBIAS_ELOG : HPF_IBIAS_ELOG, bL); }
+      rc = items ? hpf_fold_in_items(f.h, env.fold_iters, env.fold_tol, iters.data()) : hpf_fold_in(f.h, env.fold_iters, env.fold_tol, iters.data());
+      if (rc) f.die(items ? "hpf_fold_in_items" : "hpf_fold_in", rc);
+    }
 
-    // the user-side files of save_model, prefix foldin_
-    const std::vector<uint32_t> &uid = nu.seq2user;
+    // that side's files of save_model, prefix foldin_
+    const std::vector<uint32_t> &ids = items ? nu.seq2item : nu.seq2user;
     std::vector<double> buf;
-    auto write = [&](const std::string &name, hpf_state w, uint32_t rows, uint32_t cols, bool as_vector) {
-      buf.resize((size_t)rows * cols);
-      const int r2 = hpf_get_state(f.h, w, buf.data(), buf.size());
+    auto write = [&](const std::string &name, hpf_state w, uint32_t nrows, uint32_t cols, bool as_vector) {
+      buf.assign((size_t)nrows * cols, 0.0);
+      const int r2 = f.h ? hpf_get_state(f.h, w, buf.data(), buf.size()) : 0;
       if (r2) f.die("hpf_get_state", r2);
       const std::string path = env.file_str("/foldin_" + name);
-      if (as_vector ? save_vector(path, buf.data(), rows, uid.data(), (uint32_t)uid.size())
-                    : save_matrix(path, buf.data(), rows, cols, uid.data(), (uint32_t)uid.size())) io_die("cannot write", path);
+      if (as_vector ? save_vector(path, buf.data(), nrows, ids.data(), (uint32_t)ids.size())
+                    : save_matrix(path, buf.data(), nrows, cols, ids.data(), (uint32_t)ids.size())) io_die("cannot write", path);
     };
     const char *suf[3] = {"_shape.tsv", "_rate.tsv", ".tsv"};
-    const std::string tb = env.hier ? "htheta" : "theta";
+    const std::string tb = items ? (env.hier ? "hbeta" : "beta") : (env.hier ? "htheta" : "theta");
+    const hpf_state obj = items ? HPF_BETA_SHAPE : HPF_THETA_SHAPE, prior = items ? HPF_ETA_SHAPE : HPF_XI_SHAPE, biasw = items ? HPF_IBIAS_SHAPE : HPF_UBIAS_SHAPE;
     for (int j = 0; j < 3; ++j) {
-      if (j == 1 && !env.hier) write(tb + suf[j], HPF_THETA_RATE, k, 1, true);      // GPMatrixGR rate: the K-vector
-      else write(tb + suf[j], (hpf_state)(HPF_THETA_SHAPE + j), nu.n, k, false);
-      if (env.hier) write(std::string("thetarate") + suf[j], (hpf_state)(HPF_XI_SHAPE + j), nu.n, 1, true);
-      if (env.bias) write(std::string("thetabias") + suf[j], (hpf_state)(HPF_UBIAS_SHAPE + j), nu.n, 1, false);
+      if (j == 1 && !env.hier) { if (f.h) write(tb + suf[j], (hpf_state)(obj + 1), k, 1, true); }     // GPMatrixGR rate: the K-vector
+      else write(tb + suf[j], (hpf_state)(obj + j), rows, k, false);
+      if (env.hier) write(std::string(items ? "betarate" : "thetarate") + suf[j], (hpf_state)(prior + j), rows, 1, true);
+      if (env.bias) write(std::string(items ? "betabias" : "thetabias") + suf[j], (hpf_state)(biasw + j), rows, 1, false);
     }
     uint32_t imin = 0, imax = 0; double isum = 0;
-    for (uint32_t u = 0; u < nu.n; ++u) { imin = u ? std::min(imin, iters[u]) : iters[u]; imax = std::max(imax, iters[u]); isum += iters[u]; }
-    write_line(env.file_str("/foldin.txt"), "%u\t%llu\t%llu\t%u\t%g\t%u\t%.5f\t%u\n", nu.n, (unsigned long long)nu.col.size(),
-               (unsigned long long)skipped, env.fold_iters, env.fold_tol, imin, nu.n ? isum / nu.n : 0.0, imax);
-    env.lerr("-fold-in: %u users, %llu ratings, %llu lines skipped (unknown item), iterations %u .. %u", nu.n,
-             (unsigned long long)nu.col.size(), (unsigned long long)skipped, imin, imax);
-    if (env.recommend) f.recommend_lists(nu, nullptr, "/foldin_recommend");
-    hpf_destroy(f.h);
+    for (uint32_t u = 0; u < rows; ++u) { imin = u ? std::min(imin, iters[u]) : iters[u]; imax = std::max(imax, iters[u]); isum += iters[u]; }
+    write_line(env.file_str(items ? "/foldin_items.txt" : "/foldin.txt"), "%u\t%llu\t%llu\t%u\t%g\t%u\t%.5f\t%u\n", rows, (unsigned long long)nu.col.size(),
+               (unsigned long long)skipped, env.fold_iters, env.fold_tol, imin, rows ? isum / rows : 0.0, imax);
+    env.lerr("%s: %u %s, %llu ratings, %llu lines skipped (unknown %s), iterations %u .. %u", flag, rows, items ? "items" : "users",
+             (unsigned long long)nu.col.size(), (unsigned long long)skipped, items ? "user" : "item", imin, imax);
+    if (!items && env.recommend) f.recommend_lists(nu, nullptr, "/foldin_recommend");
+    if (f.h) hpf_destroy(f.h);
   }
 };
 
@@ -343,7 +362,8 @@ struct ScoreModes : Cli {
 void score(Cli &c, const std::function<void()> &gen_ranking)
 {
   ScoreModes s(c);
-  if (!c.env.fold_in.empty()) return s.fold_in_report();      // needs the item side only, as shape and rate
+  if (!c.env.fold_in.empty()) return s.fold_in_report(false);      // needs the item side only, as shape and rate
+  if (!c.env.fold_in_items.empty()) return s.fold_in_report(true);  // ... the user side only
   s.load_model();
   if (c.env.rmse) s.compute_rmse();
   else if (c.env.msr) s.gen_msr_csv();

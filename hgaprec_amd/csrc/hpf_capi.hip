@@ -375,6 +375,17 @@ bool launch_fold(int R, const FoldArgs &a, uint32_t blocks, uint32_t lds_bytes, 
     } else return false;
   });
 }
+// fold_in_long_kernel: R columns per lane, hpf_plan::fold_long_waves(R) waves per workgroup and their partial rows in LDS
+bool launch_fold_long(int R, const FoldArgs &a, uint32_t blocks, uint32_t lds_bytes, hipStream_t st)
+{
+  return pick(R, Counts(), [&](auto r) {
+    constexpr int WAVES = hpf_plan::fold_long_waves(PICKED(r));
+    if constexpr (hpf_plan::has_fold_long(PICKED(r), WAVES)) {
+      hipLaunchKernelGGL((fold_in_long_kernel<PICKED(r), WAVES>), dim3(blocks), dim3(64 * WAVES), lds_bytes, st, a);
+      return true;
+    } else return false;
+  });
+}
 // explain_kernel: R terms per lane (hpf_plan::explain_plan), four waves per workgroup
 bool launch_explain(int R, const ExplainArgs &a, uint32_t blocks, hipStream_t st)
 {
@@ -2394,10 +2405,14 @@ int hpf_iterate_global(hpf_handle *h) { return h ? iterate_global(h) : HPF_ERR_I
 
 namespace {
 
-// the user side after a fold-in: what hpf_set_state of every user-side array would leave behind
-void fold_mark_state(hpf_handle *h)
+// The two fold-in calls are one routine over (own, oth): the side that is folded in, with the pointers of its rows into
+// own.idx / own.val, against the frozen one.  hpf_fold_in: (u, it, the CSR's row pointers); hpf_fold_in_items: (it, u, the
+// item-major view's column pointers), and the rows with at least long_min nonzeros go to fold_in_long_kernel (0: none do).
+struct FoldCall { Side &own, &oth; const int64_t *ptr; uint32_t long_min; const char *who; };
+
+// the folded-in side after the call: what hpf_set_state of every array of that side would leave behind
+void fold_mark_state(hpf_handle *h, Side &s)
 {
-  Side &s = h->u;
   s.have_E = s.have_L = true;
   if (h->cfg.hier) s.have_prior = true;
   if (h->cfg.bias) s.have_bias_E = s.have_bias_L = s.bias_rate_known = true;
@@ -2407,9 +2422,8 @@ void fold_mark_state(hpf_handle *h)
 }
 
 // room for what the rates are exported from before the first sweep (hpf_set_state(THETA_RATE), (XI_SHAPE))
-int fold_export_room(hpf_handle *h)
+int fold_export_room(hpf_handle *h, Side &u)
 {
-  Side &u = h->u;
   int rc;
   const size_t want = h->cfg.hier ? (size_t)u.rows * h->K : (size_t)h->K;
   dfree(u.rate_set); u.rate_set = nullptr;
@@ -2419,69 +2433,95 @@ int fold_export_room(hpf_handle *h)
   return HPF_OK;
 }
 
-// one launch: all iterations of all users (fold_in_kernel)
-int fold_fused(hpf_handle *h, uint32_t n_iters, double tol, uint32_t *iters_out)
+// all iterations of all rows of the folded-in side: fold_in_kernel, one launch; with long rows (fc.long_min) followed by
+// fold_in_long_kernel over the list of them
+int fold_fused(hpf_handle *h, const FoldCall &fc, uint32_t n_iters, double tol, uint32_t *iters_out)
 {
-  const hpf_plan::FoldPlan fp = hpf_plan::fold_plan(h->K, h->cfg.bias != 0);
-  if (!fp.ok) { h->err = "fold_in_kernel: no instance for this column count"; return HPF_ERR_UNSUPPORTED; }
-  Side &u = h->u, &it = h->it;
-  const uint32_t n = u.rows, m = it.rows, ld = h->ld;
+  const hpf_plan::FoldItemsPlan fp = hpf_plan::fold_items_plan(h->K, h->cfg.bias != 0, fc.long_min);
+  if (!fp.wave.ok || (fc.long_min && !fp.ok)) { h->err = "fold_in_kernel: no instance for this column count"; return HPF_ERR_UNSUPPORTED; }
+  Side &u = fc.own, &it = fc.oth;
+  const uint32_t n = u.rows, m = it.rows, ld = h->ld, ldf = fp.wave.ld;
   const double s0 = h->cfg.s_prior, r0 = h->cfg.r_prior;
   int rc;
-  if ((rc = refresh_elog(h, it))) return rc;                 // E and Elog of the item side as of its last sweep
-  if ((rc = fold_export_room(h))) return rc;
+  if ((rc = refresh_elog(h, it))) return rc;                 // E and Elog of the frozen side as of its last sweep
+  if ((rc = fold_export_room(h, u))) return rc;
   Scratch sc(h);
-  double *Wb = nullptr, *part = nullptr, *csum = nullptr; uint32_t *d_iters = nullptr;
-  if ((rc = sc.alloc(&Wb, (size_t)m * fp.ld)) || (rc = sc.alloc(&part, (size_t)it.sweep_blocks * ld)) || (rc = sc.alloc(&csum, ld))) return rc;
+  double *Wb = nullptr, *part = nullptr, *csum = nullptr; uint32_t *d_iters = nullptr, *d_long = nullptr, *d_nlong = nullptr;
+  if ((rc = sc.alloc(&Wb, (size_t)m * ldf)) || (rc = sc.alloc(&part, (size_t)it.sweep_blocks * ld)) || (rc = sc.alloc(&csum, ld))) return rc;
   if (iters_out && (rc = sc.alloc(&d_iters, n))) return rc;
-  hipLaunchKernelGGL(fold_derive_w_kernel, dim3(std::min<uint32_t>((m + 3) / 4, 4096)), dim3(256), 0, h->stream, it.L, Wb, m, ld, fp.ld,
+  hipLaunchKernelGGL(fold_derive_w_kernel, dim3(std::max<uint32_t>(1, std::min<uint32_t>((m + 3) / 4, 4096))), dim3(256), 0, h->stream, it.L, Wb, m, ld, ldf,
                      h->K, it.bias_col, it.junk_col);
-  // c[k] = sum_i E[beta_ik], into a temporary: the item side's own column sums stay as they are
+  // c[k] = sum over the frozen side's rows of E, into a temporary: that side's own column sums stay as they are
   hipLaunchKernelGGL(colsum_partial_kernel, dim3(it.sweep_blocks), dim3(256), 0, h->stream, it.E, m, ld, h->K, part);
   hipLaunchKernelGGL(colsum_finalize_kernel, dim3(ld), dim3(256), 0, h->stream, part, it.sweep_blocks, ld, csum, h->flags);
   if ((rc = check_launch(h, "fold-in set-up"))) return rc;
+  uint32_t n_long = 0;
+  if (fc.long_min) {
+    if ((rc = sc.alloc(&d_long, n)) || (rc = sc.alloc(&d_nlong, 1))) return rc;
+    hipLaunchKernelGGL(fold_long_list_kernel, dim3(grid_for(n)), dim3(256), 0, h->stream, fc.ptr, n, fc.long_min, d_long, d_nlong);
+    if ((rc = check_launch(h, "fold_long_list_kernel"))) return rc;
+    HIPCHK(h, hipMemcpyAsync(&n_long, d_nlong, 4, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+  }
   FoldArgs a;
-  a.rowptr = h->rowptr_dev; a.idx = u.idx; a.val = u.val; a.Wb = Wb; a.csum = csum;
+  a.rowptr = fc.ptr; a.idx = u.idx; a.val = u.val; a.Wb = Wb; a.csum = csum;
   a.S = u.S; a.E = u.E; a.L = u.L; a.rate = u.rate_set;
   a.xi_shape = u.prior_shape_set; a.xi_rate = u.prior_rate; a.xi_E = u.prior_E; a.xi_elog = u.prior_elog;
   a.xi_used = u.prior_used; a.xi_elog_used = u.prior_elog_used;
   a.iters_out = d_iters; a.flags = h->flags;
-  a.n = n; a.ld = ld; a.ldf = fp.ld; a.K = h->K; a.rows_held = fp.rows_held; a.slice = fp.lds_wave_bytes / 8;
+  a.n = n; a.ld = ld; a.ldf = ldf; a.K = h->K; a.rows_held = fp.wave.rows_held; a.slice = fp.wave.lds_wave_bytes / 8;
   a.n_iters = n_iters; a.hier = h->cfg.hier;
+  a.len_max = fc.long_min ? fc.long_min - 1 : 0xffffffffu; a.long_rows = d_long; a.n_long = n_long;
   a.bias_col = u.bias_col; a.junk_col = u.junk_col;
   a.rate_bias = r0 + u.bias_rate_add;
   a.s_prior = s0; a.r_prior = r0; a.tol = tol;
   a.xi_shape_v = s0 + (double)h->K * s0; a.psi_xi_shape = host_digamma(a.xi_shape_v);
   a.elog_prior = host_digamma(s0) - std::log(r0);
-  if (!launch_fold((int)fp.R, a, fp.grid(n), fp.lds_block_bytes(), h->stream)) { h->err = "fold_in_kernel: no instance for this column count"; return HPF_ERR_UNSUPPORTED; }
+  if (!launch_fold((int)fp.wave.R, a, fp.wave.grid(n), fp.wave.lds_block_bytes(), h->stream)) { h->err = "fold_in_kernel: no instance for this column count"; return HPF_ERR_UNSUPPORTED; }
   if ((rc = check_launch(h, "fold_in_kernel"))) return rc;
+  if (n_long) {
+    if (!launch_fold_long((int)fp.wave.R, a, fp.grid_long(n_long), fp.lds_long_bytes(), h->stream)) { h->err = "fold_in_long_kernel: no instance for this column count"; return HPF_ERR_UNSUPPORTED; }
+    if ((rc = check_launch(h, "fold_in_long_kernel"))) return rc;
+  }
   // what the rate was built from, where the exports after a sweep look for it
   HIPCHK(h, hipMemcpyAsync(u.colsum_used, csum, (size_t)ld * 8, hipMemcpyDeviceToDevice, h->stream));
-  fold_mark_state(h);
+  fold_mark_state(h, u);
   return copy_back(h, {{iters_out, d_iters, (size_t)n * 4}});
 }
 
 // A/B route (HPF_FOLD_ROUTE=sweeps under HPF_EXPERIMENTAL=1; never chosen by the library): the same call as n_iters x (the
-// user-major phi pass + the user sweep) of the training path, from the prior.  Every user runs n_iters iterations.
-int fold_sweeps(hpf_handle *h, uint32_t n_iters, double tol, uint32_t *iters_out)
+// phi pass over the folded-in side's rows + its sweep) of the training path, from the prior.  Every row runs n_iters iterations.
+int fold_sweeps(hpf_handle *h, const FoldCall &fc, uint32_t n_iters, double tol, uint32_t *iters_out)
 {
-  if (tol > 0.0) { h->err = "HPF_FOLD_ROUTE=sweeps runs every user for n_iters iterations: tol must be 0"; return HPF_ERR_UNSUPPORTED; }
-  Side &u = h->u, &it = h->it;
+  if (tol > 0.0) { h->err = "HPF_FOLD_ROUTE=sweeps runs every row for n_iters iterations: tol must be 0"; return HPF_ERR_UNSUPPORTED; }
+  Side &u = fc.own, &it = fc.oth;
+  const bool items = &u == &h->it;
   const uint32_t n = u.rows, ld = h->ld;
   const double s0 = h->cfg.s_prior, r0 = h->cfg.r_prior;
   int rc;
-  if ((rc = fold_export_room(h))) return rc;
+  if ((rc = fold_export_room(h, u))) return rc;
   hipLaunchKernelGGL(fold_prior_kernel, dim3(grid_for((uint64_t)n * ld)), dim3(256), 0, h->stream, u.S, u.E, u.L,
                      h->cfg.hier ? u.prior_E : nullptr, u.prior_elog, n, ld, h->K, u.bias_col, s0, s0 / r0, host_digamma(s0) - std::log(r0));
   if ((rc = check_launch(h, "fold_prior_kernel"))) return rc;
-  fold_mark_state(h);
-  const bool eta_given = it.have_prior;
-  it.have_prior = true;                                      // eta is not read by the user half
+  fold_mark_state(h, u);
+  const bool prior_given = it.have_prior;
+  it.have_prior = true;                                      // the frozen side's xi / eta is not read by the other half
   rc = prepare_derived(h);
-  it.have_prior = eta_given;
+  it.have_prior = prior_given;
   if (rc) return rc;
+  // the sums of the frozen side the sweep's rate reads: the item side's are prepare_derived's; the user side's own are the
+  // product of a user sweep, so an item call takes them into a temporary
+  Scratch sc(h);
+  double *csum = it.colsum;
+  if (items) {
+    double *part = nullptr;
+    if ((rc = refresh_es(h, it)) || (rc = sc.alloc(&part, (size_t)it.sweep_blocks * ld)) || (rc = sc.alloc(&csum, ld))) return rc;
+    hipLaunchKernelGGL(colsum_partial_kernel, dim3(it.sweep_blocks), dim3(256), 0, h->stream, it.E, it.rows, ld, h->K, part);
+    hipLaunchKernelGGL(colsum_finalize_kernel, dim3(ld), dim3(256), 0, h->stream, part, it.sweep_blocks, ld, csum, h->flags);
+    if ((rc = check_launch(h, "fold-in set-up"))) return rc;
+  }
   for (uint32_t t = 0; t < n_iters; ++t)
-    if ((rc = run_phi(h, u, it, nullptr)) || (rc = run_sweep(h, u, it.colsum, u.colsum))) return rc;
+    if ((rc = run_phi(h, u, it, nullptr)) || (rc = run_sweep(h, u, csum, u.colsum))) return rc;
   mark_swept(u);                                             // refresh_elog below rebuilds E and Elog from the sums
   uint32_t fl = 0;
   HIPCHK(h, hipMemcpyAsync(&fl, h->flags, 4, hipMemcpyDeviceToHost, h->stream));
@@ -2500,10 +2540,37 @@ int fold_sweeps(hpf_handle *h, uint32_t n_iters, double tol, uint32_t *iters_out
     for (uint32_t k = 0; k < h->K; ++k) cs[k] += r0;
     if ((rc = h2d(h, u.rate_set, cs.data(), (size_t)h->K * 8))) return rc;
   }
-  fold_mark_state(h);
+  fold_mark_state(h, u);
   if (iters_out) std::fill(iters_out, iters_out + n, n_iters);
   HIPCHK(h, hipStreamSynchronize(h->stream));
   return HPF_OK;
+}
+
+// what the two calls check, each before anything is launched, and the route
+int fold_call(hpf_handle *h, const FoldCall &fc, uint32_t n_iters, double tol, uint32_t *iters_out)
+{
+  const std::string who = fc.who;
+  const bool items = &fc.own == &h->it;
+  if (n_iters == 0) { h->err = who + ": n_iters must be at least 1"; return HPF_ERR_INVALID; }
+  if (!(tol >= 0.0)) { h->err = who + ": tol must be a number >= 0"; return HPF_ERR_INVALID; }
+  if (!h->have_csr) { h->err = "hpf_upload_csr has not been called"; return HPF_ERR_STATE; }
+  if (h->phase != 0) { h->err = who + ": call between iterations"; return HPF_ERR_STATE; }
+  const Side &it = fc.oth;
+  if (h->iterations == 0 && !(it.have_E && it.have_L)) {
+    h->err = items ? "user side not set: hand in THETA_E and THETA_ELOG before folding in" : "item side not set: hand in BETA_E and BETA_ELOG before folding in";
+    return HPF_ERR_STATE;
+  }
+  if (h->iterations == 0 && h->cfg.bias && !(it.have_bias_E && it.have_bias_L)) {
+    h->err = items ? "user side not set: hand in UBIAS_E and UBIAS_ELOG before folding in (-bias)" : "item side not set: hand in IBIAS_E and IBIAS_ELOG before folding in (-bias)";
+    return HPF_ERR_STATE;
+  }
+  if (fc.own.rows == 0) return HPF_OK;
+  int rc;
+  // the folded-in state supersedes whatever the kernels flagged about the old one, like a state handed in
+  if ((rc = recover_if_flushed(h))) return rc;
+  HIPCHK(h, hipMemsetAsync(h->flags, 0, 4, h->stream));
+  if ((rc = h->fold_route == 1 ? fold_sweeps(h, fc, n_iters, tol, iters_out) : fold_fused(h, fc, n_iters, tol, iters_out))) return rc;
+  return check_flags(h);
 }
 
 }  // namespace
@@ -2511,22 +2578,16 @@ int fold_sweeps(hpf_handle *h, uint32_t n_iters, double tol, uint32_t *iters_out
 int hpf_fold_in(hpf_handle *h, uint32_t n_iters, double tol, uint32_t *iters_out)
 {
   if (!h) return HPF_ERR_INVALID;
-  if (n_iters == 0) { h->err = "hpf_fold_in: n_iters must be at least 1"; return HPF_ERR_INVALID; }
-  if (!(tol >= 0.0)) { h->err = "hpf_fold_in: tol must be a number >= 0"; return HPF_ERR_INVALID; }
-  if (!h->have_csr) { h->err = "hpf_upload_csr has not been called"; return HPF_ERR_STATE; }
-  if (h->phase != 0) { h->err = "hpf_fold_in: call between iterations"; return HPF_ERR_STATE; }
-  const Side &it = h->it;
-  if (h->iterations == 0 && !(it.have_E && it.have_L)) { h->err = "item side not set: hand in BETA_E and BETA_ELOG before folding in"; return HPF_ERR_STATE; }
-  if (h->iterations == 0 && h->cfg.bias && !(it.have_bias_E && it.have_bias_L)) {
-    h->err = "item side not set: hand in IBIAS_E and IBIAS_ELOG before folding in (-bias)"; return HPF_ERR_STATE;
-  }
-  if (h->u.rows == 0) return HPF_OK;
-  int rc;
-  // the folded-in state supersedes whatever the kernels flagged about the old one, like a state handed in
-  if ((rc = recover_if_flushed(h))) return rc;
-  HIPCHK(h, hipMemsetAsync(h->flags, 0, 4, h->stream));
-  if ((rc = h->fold_route == 1 ? fold_sweeps(h, n_iters, tol, iters_out) : fold_fused(h, n_iters, tol, iters_out))) return rc;
-  return check_flags(h);
+  return fold_call(h, {h->u, h->it, h->rowptr_dev, 0u, "hpf_fold_in"}, n_iters, tol, iters_out);
+}
+
+int hpf_fold_in_items(hpf_handle *h, uint32_t n_iters, double tol, uint32_t *iters_out)
+{
+  if (!h) return HPF_ERR_INVALID;
+  // users are sharded across ranks: an item's sums would need an exchange per iteration
+  if (h->cfg.n_ranks > 1) { h->err = "hpf_fold_in_items: one rank only"; return HPF_ERR_UNSUPPORTED; }
+  const uint32_t long_min = h->fold_long_min ? h->fold_long_min : hpf_plan::FOLD_LONG_MIN;
+  return fold_call(h, {h->it, h->u, h->colptr_dev, long_min, "hpf_fold_in_items"}, n_iters, tol, iters_out);
 }
 
 namespace {

@@ -20,6 +20,8 @@
 #include <cmath>
 #include <type_traits>
 
+#include "hpf_plan.hpp"   // plain C++: the constexpr arithmetic a kernel shares with its plan (fold_part)
+
 // Build-time switches (A/B builds of tools/ and profiles/ only; the library ships the defaults)
 #ifndef HPF_REDUCE_SCATTER
 #define HPF_REDUCE_SCATTER 1   // end of a segment in the packed passes: 1 = the groups' accumulators reduced halving the element list
@@ -1592,10 +1594,12 @@ __global__ __launch_bounds__(256) void derive_w_kernel(const double *L, void *W,
 // Per nonzero, in CSR order (two at a time for the latency of the 64-lane sum; the accumulation stays in CSR order):
 //   ssum = sum_c own_c x_c ,  acc_c += x_c * yy / ssum ;  at the end of the row S_c = own_c * acc_c      (phi_batch's form)
 // then steps B, D-user and E of the iteration on the row in registers (row_sweep_kernel's arithmetic, E by an IEEE division).
+// hpf_fold_in_items is the same with the sides exchanged: the rows are the new ITEMS in item-major order, the gathered copy
+// is built from the user side, and an item with many ratings goes to fold_in_long_kernel below.
 // ---------------------------------------------------------------------
 struct FoldArgs {
-  const int64_t  *rowptr;   // [n + 1] CSR of the users
-  const uint32_t *idx;      // item of each nonzero
+  const int64_t  *rowptr;   // [n + 1] CSR of the users (hpf_fold_in_items: the column pointers of the item-major view)
+  const uint32_t *idx;      // item (user) of each nonzero
   const uint8_t  *val;      // rating (NULL: all ones)
   const double   *Wb;       // [n_items x ldf] exp(Elog - row max) of the item side, bias and junk columns included
   const double   *csum;     // [>= K] c_k = sum_i E[beta_ik]
@@ -1605,8 +1609,10 @@ struct FoldArgs {
   uint32_t *iters_out;      // [n] out, may be NULL
   uint32_t *flags;          // bit 0: a softmax denominator underflowed
   uint32_t n, ld, ldf, K, rows_held, slice, n_iters, hier;
+  uint32_t len_max;         // fold_in_kernel skips the rows with more nonzeros: fold_in_long_kernel's (0xffffffff: none)
+  const uint32_t *long_rows; uint32_t n_long;   // fold_in_long_kernel: its rows
   int32_t  bias_col, junk_col;
-  double   rate_bias;       // r_prior + n_items
+  double   rate_bias;       // r_prior + n_items (the owner is a user) / + n_users_total (an item)
   double   s_prior, r_prior, tol;
   double   xi_shape_v, psi_xi_shape;    // s0 + K s0 and its digamma
   double   elog_prior;      // psi(s0) - log(r0): Elog of every object at the prior
@@ -1630,15 +1636,158 @@ __device__ __forceinline__ void fold_add(const double (&x)[R], double (&acc)[R],
   for (int t = 0; t < R; ++t) acc[t] = fma(x[t], scale, acc[t]);
 }
 
+// The state of one row between iterations, a copy per lane: its columns l + 64 t (own: the W form, ev: E, sh: shape) and
+// the scalars of xi / eta.  fold_in_kernel keeps one per wave, fold_in_long_kernel the same one in every wave of a workgroup.
+template <int R>
+struct FoldRow {
+  double own[R], ev[R], sh[R], acc[R];
+  double pr, pr_used, pel, pel_used, xrate;              // E[xi] of the previous step (the constant r_prior without hier) ...
+  double dmax, emax;                                     // max_k |E - E_before| and max_k E of the last update
+};
+
+// shape sums acc -> shape, E and the W form of the row; rate = prk + use * c_k (the bias column: rb).  Returns
+// sum_k E (k < K) and leaves max_k |E - E_before| and max_k E in dmax / emax
+template <int R>
+__device__ __forceinline__ double fold_update(const FoldArgs &a, int lane, FoldRow<R> &r, double prk, double use, double rb)
+{
+  const uint32_t K = a.K;
+  const double s0 = a.s_prior;
+  double wl[R], wmax = 0.0, rsum = 0.0;
+  double dmax = 0.0, emax = 0.0;
+#pragma unroll
+  for (int t = 0; t < R; ++t) {
+    const uint32_t c = (uint32_t)lane + 64u * t;
+    const bool fk = c < K, fb = (int32_t)c == a.bias_col;
+    const double cs = fk ? a.csum[c] : 0.0;
+    const double shp = fmax(s0 + r.own[t] * r.acc[t], 1e-30);        // GPBase::make_nonzero, as the sweep has it
+    const double rt = fmax(fk ? fma(cs, use, prk) : rb, 1e-30);
+    const PsiRate ps = psi_parts_rate(shp, rt);
+    const double e = (fk || fb) ? shp / rt : 0.0;
+    const double ek = fk ? e : 0.0;
+    dmax = fmax(dmax, fk ? fabs(e - r.ev[t]) : 0.0);
+    emax = fmax(emax, ek);
+    rsum += ek;
+    const double w = ps.xs * exp_neg(ps.corr) * ps.ri;               // exp(psi(shape) - log(rate))
+    wl[t] = (fk || fb) ? w : ((int32_t)c == a.junk_col ? 1.0 : 0.0);
+    wmax = fmax(wmax, wl[t]);
+    r.sh[t] = shp; r.ev[t] = e;
+  }
+  wmax = group_max<64>(wmax);
+  r.dmax = group_max<64>(dmax);
+  r.emax = group_max<64>(emax);
+  const double inv = (wmax > 0.0) ? fast_rcp(wmax) : 0.0;
+#pragma unroll
+  for (int t = 0; t < R; ++t) r.own[t] = wl[t] * inv;
+  return group_sum<64>(rsum);
+}
+
+// the prior: every Gamma object at shape s_prior, rate r_prior
+template <int R>
+__device__ __forceinline__ void fold_start(const FoldArgs &a, int lane, FoldRow<R> &r)
+{
+  const double r0 = a.r_prior;
+  r.pr = a.hier ? a.s_prior / r0 : r0;
+  r.pr_used = r0; r.pel = a.elog_prior; r.pel_used = a.elog_prior; r.xrate = r0;
+#pragma unroll
+  for (int t = 0; t < R; ++t) { r.own[t] = 0.0; r.acc[t] = 0.0; r.ev[t] = 0.0; }
+  (void)fold_update<R>(a, lane, r, r0, 0.0, r0);
+}
+
+// the nonzeros [begin, end) of the row that starts at `start` (begin a multiple of 64), in order, two in flight, into r.acc.
+// held: the row fits the wave's slice `rows` of LDS -- gathered and stored there when !from_lds, read back from there
+// otherwise (cur_i / cur_y then still hold the row's indices and ratings)
+template <int R>
+__device__ __forceinline__ void fold_walk(const FoldArgs &a, int lane, FoldRow<R> &r, int64_t start, uint32_t begin, uint32_t end,
+                                          bool held, bool from_lds, double *rows, uint32_t &cur_i, float &cur_y, bool &underflow)
+{
+  const uint32_t LDF = a.ldf;
+  auto get = [&](double (&x)[R], uint32_t j, uint32_t jrow) {
+    if (from_lds) {
+#pragma unroll
+      for (int t = 0; t < R; ++t) { const uint32_t c = (uint32_t)lane + 64u * t; x[t] = (c < LDF) ? rows[(size_t)jrow * LDF + c] : 0.0; }
+    } else {
+      const uint32_t in = (uint32_t)__builtin_amdgcn_readlane((int)cur_i, (int)j);
+      const double *p = a.Wb + (size_t)in * LDF;
+#pragma unroll
+      for (int t = 0; t < R; ++t) { const uint32_t c = (uint32_t)lane + 64u * t; x[t] = (c < LDF) ? p[c] : 0.0; }
+      if (held) {
+#pragma unroll
+        for (int t = 0; t < R; ++t) { const uint32_t c = (uint32_t)lane + 64u * t; if (c < LDF) rows[(size_t)jrow * LDF + c] = x[t]; }
+      }
+    }
+  };
+  auto rating = [&](uint32_t j) -> double { return (double)__int_as_float(__builtin_amdgcn_readlane(__float_as_int(cur_y), (int)j)); };
+  for (uint32_t base = begin; base < end; base += 64u) {
+    const uint32_t cnt = (end - base < 64u) ? end - base : 64u;
+    if (!from_lds) {
+      // the factor is yy = (y > 1 ? y : 1), hgaprec.cc:1355-1356, as in the phi pass
+      cur_i = ((uint32_t)lane < cnt) ? a.idx[start + base + lane] : 0u;
+      cur_y = 1.0f;
+      if (a.val && (uint32_t)lane < cnt) { const uint32_t y = a.val[start + base + lane]; cur_y = (y > 1u) ? (float)y : 1.0f; }
+    }
+    uint32_t j = 0;
+    double xa[R], xb[R];
+    for (; j + 1 < cnt; j += 2) {
+      get(xa, j, base + j);
+      get(xb, j + 1, base + j + 1);
+      const double sa = fold_dot<R>(xa, r.own), sb = fold_dot<R>(xb, r.own);
+      fold_add<R>(xa, r.acc, sa, rating(j), underflow);
+      fold_add<R>(xb, r.acc, sb, rating(j + 1), underflow);
+    }
+    if (j < cnt) {
+      get(xa, j, base + j);
+      fold_add<R>(xa, r.acc, fold_dot<R>(xa, r.own), rating(j), underflow);
+    }
+  }
+}
+
+// B, D-owner: shape and rate of the row and of its bias from the sums in r.acc; E: xi / eta from the new row
+template <int R>
+__device__ __forceinline__ void fold_step(const FoldArgs &a, int lane, FoldRow<R> &r)
+{
+  r.pr_used = r.pr; r.pel_used = r.pel;
+  const double rsum = fold_update<R>(a, lane, r, r.pr, 1.0, a.rate_bias);
+  if (a.hier) {
+    r.xrate = a.r_prior + rsum;
+    r.pr = a.xi_shape_v / r.xrate;
+    r.pel = a.psi_xi_shape - log(r.xrate);
+  }
+}
+
+// row u has stopped after `it` iterations: its state goes out, once (one wave)
+template <int R>
+__device__ __forceinline__ void fold_store(const FoldArgs &a, int lane, const FoldRow<R> &r, uint32_t u, uint32_t it)
+{
+  const uint32_t K = a.K;
+  const bool hier = a.hier != 0;
+  const size_t ro = (size_t)u * a.ld;
+#pragma unroll
+  for (int t = 0; t < R; ++t) {
+    const uint32_t c = (uint32_t)lane + 64u * t;
+    if (c >= a.ld) continue;
+    const bool fk = c < K, fb = (int32_t)c == a.bias_col;
+    const double rt = fmax(fk ? r.pr_used + a.csum[c] : a.rate_bias, 1e-30);
+    a.S[ro + c] = (fk || fb) ? r.sh[t] : 0.0;
+    a.E[ro + c] = r.ev[t];
+    a.L[ro + c] = (fk || fb) ? digamma_pos(r.sh[t]) - log(rt) : 0.0;
+    if (fk && hier) a.rate[(size_t)u * K + c] = rt;
+    if (fk && !hier && u == 0) a.rate[c] = rt;
+  }
+  if (lane == 0) {
+    if (hier) {
+      a.xi_shape[u] = a.xi_shape_v; a.xi_rate[u] = r.xrate; a.xi_E[u] = r.pr; a.xi_elog[u] = r.pel;
+      a.xi_used[u] = r.pr_used; a.xi_elog_used[u] = r.pel_used;
+    }
+    if (a.iters_out) a.iters_out[u] = it;
+  }
+}
+
 template <int R>
 __global__ __launch_bounds__(256) void fold_in_kernel(FoldArgs a)
 {
   extern __shared__ double fold_rows[];                  // four slices of a.slice doubles, one per wave
   const int lane = threadIdx.x & 63;
   double *rows = fold_rows + (size_t)(threadIdx.x >> 6) * a.slice;
-  const uint32_t K = a.K, LDF = a.ldf;
-  const double s0 = a.s_prior, r0 = a.r_prior;
-  const bool hier = a.hier != 0;
   bool underflow = false;
   const uint32_t w0 = __builtin_amdgcn_readfirstlane((blockIdx.x * blockDim.x + threadIdx.x) >> 6);
   const uint32_t nw = (gridDim.x * blockDim.x) >> 6;
@@ -1646,129 +1795,84 @@ __global__ __launch_bounds__(256) void fold_in_kernel(FoldArgs a)
   for (uint32_t u = w0; u < a.n; u += nw) {
     const int64_t start = a.rowptr[u];
     const uint32_t len = (uint32_t)(a.rowptr[u + 1] - start);
+    if (len > a.len_max) continue;                       // fold_in_long_kernel's (hpf_fold_in_items)
     const bool held = len <= a.rows_held;
-    double own[R], ev[R], sh[R], acc[R];
-    double pr = hier ? s0 / r0 : r0;                     // E[xi] of the previous step (the constant r_prior without hier)
-    double pr_used = r0, pel = a.elog_prior, pel_used = a.elog_prior, xrate = r0;
+    FoldRow<R> r;
     uint32_t cur_i = 0; float cur_y = 0.0f;
-
-    // shape sums S -> shape, E and the W form of the row; rate = prk + use * c_k (the bias column: rb).  Returns
-    // sum_k E (k < K) and leaves max_k |E - E_before| and max_k E in dmax / emax
-    double dmax = 0.0, emax = 0.0;
-    auto update = [&](double prk, double use, double rb) -> double {
-      double wl[R], wmax = 0.0, rsum = 0.0;
-      dmax = 0.0; emax = 0.0;
-#pragma unroll
-      for (int t = 0; t < R; ++t) {
-        const uint32_t c = (uint32_t)lane + 64u * t;
-        const bool fk = c < K, fb = (int32_t)c == a.bias_col;
-        const double cs = fk ? a.csum[c] : 0.0;
-        const double shp = fmax(s0 + own[t] * acc[t], 1e-30);          // GPBase::make_nonzero, as the sweep has it
-        const double rt = fmax(fk ? fma(cs, use, prk) : rb, 1e-30);
-        const PsiRate ps = psi_parts_rate(shp, rt);
-        const double e = (fk || fb) ? shp / rt : 0.0;
-        const double ek = fk ? e : 0.0;
-        dmax = fmax(dmax, fk ? fabs(e - ev[t]) : 0.0);
-        emax = fmax(emax, ek);
-        rsum += ek;
-        const double w = ps.xs * exp_neg(ps.corr) * ps.ri;             // exp(psi(shape) - log(rate))
-        wl[t] = (fk || fb) ? w : ((int32_t)c == a.junk_col ? 1.0 : 0.0);
-        wmax = fmax(wmax, wl[t]);
-        sh[t] = shp; ev[t] = e;
-      }
-      wmax = group_max<64>(wmax);
-      dmax = group_max<64>(dmax);
-      emax = group_max<64>(emax);
-      const double inv = (wmax > 0.0) ? fast_rcp(wmax) : 0.0;
-#pragma unroll
-      for (int t = 0; t < R; ++t) own[t] = wl[t] * inv;
-      return group_sum<64>(rsum);
-    };
-
-    // the prior: every Gamma object at shape s_prior, rate r_prior
-#pragma unroll
-    for (int t = 0; t < R; ++t) { own[t] = 0.0; acc[t] = 0.0; ev[t] = 0.0; }
-    (void)update(r0, 0.0, r0);
+    fold_start<R>(a, lane, r);
 
     uint32_t it = 0;
     for (;;) {
 #pragma unroll
-      for (int t = 0; t < R; ++t) acc[t] = 0.0;
-      const bool from_lds = held && it > 0;              // wave-uniform
-      auto get = [&](double (&x)[R], uint32_t j, uint32_t jrow) {
-        if (from_lds) {
-#pragma unroll
-          for (int t = 0; t < R; ++t) { const uint32_t c = (uint32_t)lane + 64u * t; x[t] = (c < LDF) ? rows[(size_t)jrow * LDF + c] : 0.0; }
-        } else {
-          const uint32_t in = (uint32_t)__builtin_amdgcn_readlane((int)cur_i, (int)j);
-          const double *p = a.Wb + (size_t)in * LDF;
-#pragma unroll
-          for (int t = 0; t < R; ++t) { const uint32_t c = (uint32_t)lane + 64u * t; x[t] = (c < LDF) ? p[c] : 0.0; }
-          if (held) {
-#pragma unroll
-            for (int t = 0; t < R; ++t) { const uint32_t c = (uint32_t)lane + 64u * t; if (c < LDF) rows[(size_t)jrow * LDF + c] = x[t]; }
-          }
-        }
-      };
-      auto rating = [&](uint32_t j) -> double { return (double)__int_as_float(__builtin_amdgcn_readlane(__float_as_int(cur_y), (int)j)); };
-      for (uint32_t base = 0; base < len; base += 64u) {
-        const uint32_t cnt = (len - base < 64u) ? len - base : 64u;
-        if (!from_lds) {
-          // the factor is yy = (y > 1 ? y : 1), hgaprec.cc:1355-1356, as in the phi pass
-          cur_i = ((uint32_t)lane < cnt) ? a.idx[start + base + lane] : 0u;
-          cur_y = 1.0f;
-          if (a.val && (uint32_t)lane < cnt) { const uint32_t y = a.val[start + base + lane]; cur_y = (y > 1u) ? (float)y : 1.0f; }
-        }
-        uint32_t j = 0;
-        double xa[R], xb[R];
-        for (; j + 1 < cnt; j += 2) {
-          get(xa, j, base + j);
-          get(xb, j + 1, base + j + 1);
-          const double sa = fold_dot<R>(xa, own), sb = fold_dot<R>(xb, own);
-          fold_add<R>(xa, acc, sa, rating(j), underflow);
-          fold_add<R>(xb, acc, sb, rating(j + 1), underflow);
-        }
-        if (j < cnt) {
-          get(xa, j, base + j);
-          fold_add<R>(xa, acc, fold_dot<R>(xa, own), rating(j), underflow);
-        }
-      }
-      // B, D-user: shape and rate of theta and of the bias; E: xi from the new theta
-      pr_used = pr; pel_used = pel;
-      const double rsum = update(pr, 1.0, a.rate_bias);
-      if (hier) {
-        xrate = r0 + rsum;
-        pr = a.xi_shape_v / xrate;
-        pel = a.psi_xi_shape - log(xrate);
-      }
+      for (int t = 0; t < R; ++t) r.acc[t] = 0.0;
+      fold_walk<R>(a, lane, r, start, 0u, len, held, held && it > 0 /* wave-uniform */, rows, cur_i, cur_y, underflow);
+      fold_step<R>(a, lane, r);
       ++it;
       if (it >= a.n_iters) break;
-      if (a.tol > 0.0 && it >= 2 && dmax <= a.tol * emax) break;
+      if (a.tol > 0.0 && it >= 2 && r.dmax <= a.tol * r.emax) break;
     }
-
-    // the user has stopped: its state goes out, once
-    const size_t ro = (size_t)u * a.ld;
-#pragma unroll
-    for (int t = 0; t < R; ++t) {
-      const uint32_t c = (uint32_t)lane + 64u * t;
-      if (c >= a.ld) continue;
-      const bool fk = c < K, fb = (int32_t)c == a.bias_col;
-      const double rt = fmax(fk ? pr_used + a.csum[c] : a.rate_bias, 1e-30);
-      a.S[ro + c] = (fk || fb) ? sh[t] : 0.0;
-      a.E[ro + c] = ev[t];
-      a.L[ro + c] = (fk || fb) ? digamma_pos(sh[t]) - log(rt) : 0.0;
-      if (fk && hier) a.rate[(size_t)u * K + c] = rt;
-      if (fk && !hier && u == 0) a.rate[c] = rt;
-    }
-    if (lane == 0) {
-      if (hier) {
-        a.xi_shape[u] = a.xi_shape_v; a.xi_rate[u] = xrate; a.xi_E[u] = pr; a.xi_elog[u] = pel;
-        a.xi_used[u] = pr_used; a.xi_elog_used[u] = pel_used;
-      }
-      if (a.iters_out) a.iters_out[u] = it;
-    }
+    fold_store<R>(a, lane, r, u, it);
   }
   if (__any(underflow) && lane == 0) atomicOr(a.flags, 1u);
+}
+
+// Long rows (hpf_fold_in_items): one WORKGROUP of WAVES waves owns row long_rows[i] from the prior to
+// its stop.  Every wave keeps the same copy of the row's state (FoldRow).  Per iteration wave w walks its part of the
+// row's nonzeros (hpf_plan::fold_part: contiguous, whole 64-blocks, a function of len and WAVES only) with fold_in_kernel's
+// loop, leaves its sums in its LDS slice, and after a barrier every wave adds the WAVES slices in wave order -- a fixed
+// order, no atomics -- and runs the same update on the same sums.  Whether the row stops is decided ONCE, by wave 0, and
+// read by all from LDS: two barriers per iteration, each reached by every wave (a wave with an empty part adds +0.0), so
+// no wave can leave the loop alone.  Long rows never fit LDS: every iteration gathers from Wb.
+template <int R, int WAVES>
+__global__ __launch_bounds__(64 * WAVES) void fold_in_long_kernel(FoldArgs a)
+{
+  extern __shared__ double fold_part[];                  // [WAVES][R][64] partial sums, then the stop word
+  const int lane = threadIdx.x & 63;
+  const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  volatile uint32_t *stop = (volatile uint32_t *)(fold_part + (size_t)WAVES * R * 64);
+  bool underflow = false;
+
+  for (uint32_t li = blockIdx.x; li < a.n_long; li += gridDim.x) {       // workgroup-uniform
+    const uint32_t u = a.long_rows[li];
+    const int64_t start = a.rowptr[u];
+    const uint32_t len = (uint32_t)(a.rowptr[u + 1] - start);
+    const hpf_plan::FoldPart part = hpf_plan::fold_part(len, (uint32_t)WAVES, wave);
+    FoldRow<R> r;
+    uint32_t cur_i = 0; float cur_y = 0.0f;
+    fold_start<R>(a, lane, r);
+
+    uint32_t it = 0;
+    for (;;) {
+#pragma unroll
+      for (int t = 0; t < R; ++t) r.acc[t] = 0.0;
+      fold_walk<R>(a, lane, r, start, part.begin, part.end, false, false, nullptr, cur_i, cur_y, underflow);
+#pragma unroll
+      for (int t = 0; t < R; ++t) fold_part[((size_t)wave * R + t) * 64 + lane] = r.acc[t];
+      __syncthreads();
+#pragma unroll
+      for (int t = 0; t < R; ++t) {
+        double s = fold_part[(size_t)t * 64 + lane];
+#pragma unroll
+        for (int w = 1; w < WAVES; ++w) s += fold_part[((size_t)w * R + t) * 64 + lane];
+        r.acc[t] = s;
+      }
+      fold_step<R>(a, lane, r);
+      ++it;
+      if (wave == 0 && lane == 0) *stop = (it >= a.n_iters || (a.tol > 0.0 && it >= 2 && r.dmax <= a.tol * r.emax)) ? 1u : 0u;
+      __syncthreads();                                   // ... which also ends the reads of this iteration's partial sums
+      if (__builtin_amdgcn_readfirstlane(*stop)) break;  // the next write of the word lies behind the next barrier
+    }
+    if (wave == 0) fold_store<R>(a, lane, r, u, it);
+  }
+  if (__any(underflow) && lane == 0) atomicOr(a.flags, 1u);
+}
+
+// the rows fold_in_long_kernel owns: those with at least long_min nonzeros, in any order (a row's result does not depend
+// on its place in the list)
+__global__ void fold_long_list_kernel(const int64_t *rowptr, uint32_t n, uint32_t long_min, uint32_t *list, uint32_t *count)
+{
+  for (uint32_t u = blockIdx.x * blockDim.x + threadIdx.x; u < n; u += gridDim.x * blockDim.x)
+    if ((uint64_t)(rowptr[u + 1] - rowptr[u]) >= long_min) list[atomicAdd(count, 1u)] = u;
 }
 
 // the item rows the fold-in kernel gathers: Wb = exp(L - rowmax(L)) over the live columns as plain doubles at stride

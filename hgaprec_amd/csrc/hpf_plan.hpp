@@ -59,7 +59,11 @@ struct Knobs {
   uint32_t phi_wg = 0;
   long long loo_batch = 0;          // HPF_LOO_BATCH: at most so many users per batch of the fused rank calls (<= 0: no limit of its own)
   long long ftop_batch = 0;         // HPF_FACTOR_TOP_BATCH: at most so many columns per transposed batch of hpf_factor_top (<= 0: no limit of its own)
-  int fold_route = 0;               // HPF_FOLD_ROUTE=sweeps: hpf_fold_in through the training kernels (1), for A/B runs; never chosen by the library
+  int fold_route = 0;               // HPF_FOLD_ROUTE=sweeps: hpf_fold_in / hpf_fold_in_items through the training kernels (1), for A/B runs; never chosen by the library
+  // HPF_FOLD_LONG_MIN: hpf_fold_in_items gives an item with at least so many ratings to a workgroup (fold_in_long_kernel), the
+  // others to a wave.  Inside the gate: the route changes the order of a row's sums.  >= 2^32 - 1: every row to the wave
+  // kernel; 1: every non-empty row to the workgroup kernel (tests).  0 = the plan's FOLD_LONG_MIN
+  uint32_t fold_long_min = 0;
   // HPF_FUSED_SWEEP=0|1|2: the user pass writes W of its single-segment rows in its segment epilogue and the user sweep only
   // takes their sums (fused_sweep below).  0: never (the A/B switch), 1: where it was measured to pay (fused_pays), 2: wherever
   // an instance exists (tests, A/B runs of the other shapes).  Every route gives the same bits in every array, so the variable
@@ -95,6 +99,7 @@ inline Knobs read_knobs()
   if (const char *e = getenv("HPF_PHI_BLOCKS")) { int v = atoi(e); if (v >= 1) k.phi_blocks = (uint32_t)v; }
   if (const char *e = getenv("HPF_FACTOR_TOP_BATCH")) k.ftop_batch = atoll(e);
   if (const char *e = getenv("HPF_FOLD_ROUTE")) k.fold_route = !strcmp(e, "sweeps") ? 1 : 0;
+  if (const char *e = getenv("HPF_FOLD_LONG_MIN")) { unsigned long long v = strtoull(e, nullptr, 10); if (v >= 1) k.fold_long_min = (uint32_t)std::min<unsigned long long>(v, 0xffffffffull); }
   if (const char *e = getenv("HPF_PHI_WG")) { int v = atoi(e); if (v == 64 || v == 128 || v == 256) k.phi_wg = (uint32_t)v; }
   return k;
 }
@@ -245,6 +250,45 @@ inline FoldPlan fold_plan(uint32_t K, bool bias)
   p.lds_wave_bytes = FOLD_SLICE_BYTES;
   p.rows_held = std::min<uint32_t>(64u, p.lds_wave_bytes / (p.ld * 8u));
   p.ok = has_fold((int)p.R) && p.rows_held >= 1;
+  return p;
+}
+
+// ---- fold-in of new items (hpf_fold_in_items) ------------------------------------------------------
+// Two kernels share the rows: fold_in_kernel<R> (a wave per row, as above) takes the rows with fewer than long_min
+// nonzeros, fold_in_long_kernel<R, WAVES> (a WORKGROUP per row) the others.  WAVES per R is the largest of {8, 4} whose
+// build uses no scratch: launch_bounds(512) leaves a wave 256 registers (VGPR + AGPR), launch_bounds(256) the whole SIMD's
+// 512 (the compiler's figures: DESIGN.md section 4g).  The workgroup's LDS: WAVES partial rows of R * 64 doubles and the
+// shared stop word.  At most FOLD_LONG_BLOCKS_MAX workgroups, which then stride over the list of long rows.
+// hgaprec_amd/capi.py mirrors the arithmetic (fold_items_plan).
+constexpr uint32_t FOLD_LONG_MIN = 256, FOLD_LONG_BLOCKS_MAX = 4096;   // 256: the best of {128 .. 2048} measured
+constexpr int fold_long_waves(int R) { return R <= 8 ? 8 : 4; }     // <9, 8> spills 96 bytes per lane
+constexpr bool has_fold_long(int R, int WAVES) { return has_fold(R) && WAVES == fold_long_waves(R); }
+// the nonzeros [begin, end) of a row of len that wave w of `waves` walks: the row's 64-blocks dealt in contiguous runs of
+// ceil(blocks / waves); a function of len and waves only.  Empty (begin == end) for the waves beyond the last block.
+struct FoldPart { uint32_t begin, end; };
+constexpr FoldPart fold_part(uint32_t len, uint32_t waves, uint32_t w)
+{
+  const uint64_t blocks = ((uint64_t)len + 63u) / 64u, per = (blocks + waves - 1) / waves;
+  const uint64_t lo = (uint64_t)w * per < blocks ? (uint64_t)w * per : blocks, hi = (uint64_t)(w + 1) * per < blocks ? (uint64_t)(w + 1) * per : blocks;
+  return {(uint32_t)(lo * 64u < len ? lo * 64u : len), (uint32_t)(hi * 64u < len ? hi * 64u : len)};
+}
+struct FoldItemsPlan {
+  FoldPlan wave;                        // fold_in_kernel's shape (the gathered copy, R and the LDS slices are shared)
+  uint32_t waves = 0;                   // waves of a workgroup of fold_in_long_kernel
+  uint32_t long_min = FOLD_LONG_MIN;    // a row with at least so many nonzeros is the workgroup kernel's
+  bool ok = false;
+  uint32_t lds_long_bytes() const { return waves * wave.R * 64u * 8u + 16u; }
+  // workgroups for n_long long rows (0: no launch)
+  uint32_t grid_long(uint32_t n_long) const { return std::min<uint32_t>(n_long, FOLD_LONG_BLOCKS_MAX); }
+};
+inline FoldItemsPlan fold_items_plan(uint32_t K, bool bias, uint32_t long_min = FOLD_LONG_MIN)
+{
+  FoldItemsPlan p;
+  p.wave = fold_plan(K, bias);
+  if (!p.wave.ok) return p;
+  p.waves = (uint32_t)fold_long_waves((int)p.wave.R);
+  p.long_min = long_min;
+  p.ok = has_fold_long((int)p.wave.R, (int)p.waves) && p.lds_long_bytes() <= FOLD_LDS_LIMIT;
   return p;
 }
 

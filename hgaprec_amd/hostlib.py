@@ -34,6 +34,8 @@ def lib():
     L.hg_ratings_read_heldout.argtypes = [vp, C.c_char_p, C.c_int]
     L.hg_ratings_read_fold_in.argtypes = [vp, C.c_char_p, C.POINTER(C.c_uint64), C.POINTER(C.c_int)]
     L.hg_ratings_read_fold_in.restype = vp
+    L.hg_ratings_read_fold_in_items.argtypes = [vp, C.c_char_p, C.POINTER(C.c_uint64), C.POINTER(C.c_int)]
+    L.hg_ratings_read_fold_in_items.restype = vp
     L.hg_ratings_n.argtypes = [vp]; L.hg_ratings_n.restype = C.c_uint32
     L.hg_ratings_m.argtypes = [vp]; L.hg_ratings_m.restype = C.c_uint32
     L.hg_ratings_nnz.argtypes = [vp]; L.hg_ratings_nnz.restype = C.c_uint64
@@ -128,6 +130,18 @@ class Ratings:
         skipped because their item is unknown); (None, -1) when the file cannot be opened, (None, -2) when it is malformed"""
         skipped, rc = C.c_uint64(0), C.c_int(0)
         p = self.L.hg_ratings_read_fold_in(self._r, str(path).encode(), C.byref(skipped), C.byref(rc))
+        if not p:
+            return None, rc.value
+        out = Ratings.__new__(Ratings)
+        out.L, out._r = self.L, C.c_void_p(p)
+        return out, skipped.value
+
+    def read_fold_in_items(self, path):
+        """-fold-in-items FILE: the ratings of new items by this data set's users -> (Ratings of the new items: m, seq2item
+        and a CSR over this data set's users, lines skipped because their user is unknown); (None, -1) / (None, -2) as
+        read_fold_in"""
+        skipped, rc = C.c_uint64(0), C.c_int(0)
+        p = self.L.hg_ratings_read_fold_in_items(self._r, str(path).encode(), C.byref(skipped), C.byref(rc))
         if not p:
             return None, rc.value
         out = Ratings.__new__(Ratings)

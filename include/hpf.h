@@ -482,6 +482,33 @@ int  hpf_factor_top(hpf_handle *h, int side, uint32_t topn,
  * state in registers and its gathered item rows in LDS when they fit. */
 int  hpf_fold_in(hpf_handle *h, uint32_t n_iters, double tol, uint32_t *iters_out /* n_users, may be NULL */);
 
+/* The mirror of hpf_fold_in for a catalogue that grows: the item half of the reference's iteration (hgaprec.cc:1340-1414)
+ * against a frozen user side.  The handle's ITEMS are the NEW items, its users the trained users: the ratings uploaded
+ * with hpf_upload_csr[_device] -- a CSR over the trained users whose columns are new-item ids (val = NULL: every rating
+ * is 1) -- and walked through the item-major view the upload built (users ascending inside an item); the user side handed
+ * in with hpf_set_state -- THETA_E and THETA_ELOG, with bias also UBIAS_E and UBIAS_ELOG; no item-side state is needed or
+ * read.  A missing CSR or user state is HPF_ERR_STATE, n_iters = 0, tol < 0 or a NaN tol HPF_ERR_INVALID, n_ranks > 1
+ * HPF_ERR_UNSUPPORTED (users are sharded across ranks: an item's sums would need an exchange per iteration), all before
+ * anything is launched; zero items is HPF_OK.
+ * Start: every item-side Gamma object (beta; eta with hier; the item bias with bias) at shape s_prior, rate r_prior,
+ * E = s_prior / r_prior, Elog = psi(s_prior) - log(r_prior).  One iteration for item i: phi over the item's nonzeros in
+ * item-major order (K + 2 entries with bias, hgaprec.cc:1347-1353; scaled by y when y > 1), beta shape = s_prior +
+ * sum_u phi_k, bias shape = s_prior + sum_u phi_K+1; beta rate = E[eta_i] of the PREVIOUS step + c_k with c_k = sum over
+ * ALL users of the handle of E[theta_uk] (hier) or the K-vector r_prior + c_k; bias rate r_prior + n_users_total (1393;
+ * 0 => n_users); eta shape s_prior + K s_prior, rate r_prior + sum_k E[beta_ik] of the new beta; E and Elog as
+ * gpbase.hh:248-262.  novb changes nothing here.
+ * tol = 0: every item runs n_iters iterations.  tol > 0: item i stops after the first iteration t >= 2 with
+ * max_k |E_t[beta_ik] - E_t-1[beta_ik]| <= tol max_k E_t[beta_ik], after n_iters at the latest.  iters_out[i] (may be
+ * NULL) is the number of iterations i ran.  An item's result depends on nothing but its own ratings and the user side --
+ * not on its place in the list or on what else the handle holds.
+ * Leaves the item side as hpf_set_state of BETA_* (ETA_*, IBIAS_*) would: every hpf_get_state, the scoring and ranking
+ * calls and a later hpf_iterate see the folded-in state.  The user side is not written (c_k goes into a temporary).
+ * Synchronous.  A softmax denominator that underflows surfaces as HPF_ERR_STATE.
+ * Two kernels share the items: hpf_fold_in's (a wave per item) takes those with fewer than 256 ratings, a second one gives
+ * every longer item to a whole workgroup whose waves walk contiguous parts of it and add their sums in a fixed order
+ * (DESIGN.md section 4g): the same bits from run to run. */
+int  hpf_fold_in_items(hpf_handle *h, uint32_t n_iters, double tol, uint32_t *iters_out /* n_items, may be NULL */);
+
 /* how the uploaded matrix was cut into work (diagnostics, tests, bench):
  * a "segment" is <= 512 consecutive nonzeros of one row; rows longer than that
  * are "long" (their segment sums are combined by a second kernel) and rows with
