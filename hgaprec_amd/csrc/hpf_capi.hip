@@ -14,6 +14,7 @@
 #include "hpf_kernels.hpp"
 #include "hpf_build.hpp"
 #include "hpf_plan.hpp"
+#include "hpf_lazy.hpp"
 
 #include <dlfcn.h>
 
@@ -46,7 +47,6 @@ struct Side {
   uint32_t rows = 0;
   double *S = nullptr, *E = nullptr, *L = nullptr;
   void *W = nullptr;                   // [rows x ld] double, or float in the f32-storage mode; rows of pieces: [rows x pk.row_bytes]
-  bool w_from_sweep = false;           // W was written by a sweep (a W-only repeat of it restores it), not derived from Elog
   double *prior_E = nullptr, *prior_used = nullptr, *prior_rate = nullptr;
   double *prior_elog = nullptr, *prior_elog_used = nullptr;   // Elog xi/eta now / as used by the last rate
   double *colsum = nullptr;       // [ld] sum over this side's rows of E
@@ -79,12 +79,6 @@ struct Side {
   int32_t bias_col = -1, junk_col = -1;
   double bias_rate_add = 0.0;
   uint32_t sweep_blocks = 0;
-  bool have_E = false, have_L = false, have_prior = false;
-  bool have_bias_E = false, have_bias_L = false;   // the bias column of E / L was handed in (hpf_fold_in asks for the item side's)
-  bool bias_rate_known = false;   // hpf_fold_in left the bias at rate r_prior + bias_rate_add (readable before the first sweep)
-  bool w_dirty = false;     // L was handed in by hpf_set_state: W must be derived from it
-  bool l_stale = false;      // a sweep ran since L was last valid: rebuild L on export
-  bool es_stale = false;     // S holds raw phi sums and E predates the last sweep
   // fused sweep epilogue (hpf_plan::fused_sweep): this side's pass writes W of the rows that are one segment -- a bit per row in
   // row_done, set with the work lists -- and its sweep is row_sums_kernel
   bool fused = false;
@@ -106,15 +100,13 @@ struct hpf_handle : Plan, Knobs {
   hipStream_t stream = nullptr;
   bool own_stream = false;
   Side u, it;
+  hpf_lazy::State lz;                   // what is pending on S, E, Elog, W and the start sums: hpf_lazy.hpp
+  int side_of(const Side &s) const { return &s == &it ? hpf_lazy::ITEMS : hpf_lazy::USERS; }
   double *exch = nullptr; size_t exch_count = 0; bool exch_external = false;
   // -novb with -bias and without -hier (vb_bias()'s else-branch, hgaprec.cc:1276-1297): the
   // item rate is built from the sum_u E[theta] of BEFORE this iteration's user sweep
   bool jacobi = false;
   double *u_colsum_prev = nullptr;      // [ld]
-  bool start_sums_done = false;         // jacobi on several ranks: the start state's sum_u E[theta] has been handed to the exchange
-  bool tail_partial = false;            // hpf_start_sums left THIS RANK'S PART of that sum in the tail for a caller that owns the exchange;
-                                        // hpf_work_info.start_sums_pending keeps reading 1 until the first pass of the next iteration, so that a
-                                        // caller may look at it before or after hpf_start_sums
   double *logfact = nullptr;
   int64_t *rowptr_dev = nullptr;   // user CSR row pointers (ranking mask, CSC build)
   int64_t *colptr_dev = nullptr;   // item-major (CSC) column pointers, built on device
@@ -125,10 +117,7 @@ struct hpf_handle : Plan, Knobs {
   void *stage[2] = {nullptr, nullptr};
   hipEvent_t stage_ev[2] = {nullptr, nullptr};
   size_t stage_bytes = 0;
-  bool have_csr = false, derived_dirty = true;
-  bool sums_dirty = true;               // a state array was handed in since the start state's column sums were taken: prepare_derived
-                                        // takes them again.  derived_dirty without it = only W has to be written again (recover_flush):
-                                        // the sums in place -- on several ranks the all-reduced ones -- stay
+  bool have_csr = false;
   uint32_t iterations = 0;
   uint32_t wg_of(bool tiled) const { return wl == WL_PLAIN ? 256u : phi_wg ? phi_wg : (tiled ? 64u : 256u); }   // (plain rows: phi_pass_kernel, always 256)
   uint32_t nz_per_batch() const { return phiG > 0 ? 64u / (uint32_t)phiG : 8u; }
@@ -415,7 +404,7 @@ int recover_flush(hpf_handle *h, uint32_t fl0, uint32_t begun);
 
 // A sweep (or derive_w) met an element the p59 rows cannot hold: move the handle to plain fp64 rows and repeat
 // whatever the passes skipped since (recover_flush).  Synchronises the stream.  Every consumer outside the hot
-// loop comes through here (or through check_flags) before it touches S, E or W.
+// loop comes through here before it touches S, E or W (hpf_lazy::RECOVER, first in the list ready() runs).
 int recover_if_flushed(hpf_handle *h)
 {
   if (h->in_recovery) return HPF_OK;
@@ -426,16 +415,9 @@ int recover_if_flushed(hpf_handle *h)
   return recover_flush(h, f[0], f[1]);
 }
 
-// for an export that reads what only the sweeps write (a rate's column sums, the xi / eta vectors, the exchange buffer): the
-// iterations a fall-back made the passes skip are run first.  Between iterations only -- inside one the item side's S
-// already holds the sums of the iteration in flight, not those its last sweep read.
-int recover_between_iterations(hpf_handle *h) { return h->phase == 0 ? recover_if_flushed(h) : HPF_OK; }
-
-// surfaces a numerical breakdown the kernels flagged (synchronises the stream)
+// surfaces a numerical breakdown the kernels flagged (synchronises the stream; hpf_lazy::REPORT)
 int check_flags(hpf_handle *h)
 {
-  int rc;
-  if ((rc = recover_if_flushed(h))) return rc;
   uint32_t f = 0;
   HIPCHK(h, hipMemcpyAsync(&f, h->flags, 4, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -1166,52 +1148,37 @@ double host_digamma(double x)
 }
 
 // shape (prior added, in place) and E from the raw sums and the rate the last
-// sweep used; needed by every consumer outside the hot loop
+// sweep used; needed by every consumer outside the hot loop (hpf_lazy::ES_*)
 int refresh_es(hpf_handle *h, Side &s)
 {
-  if (!s.es_stale || !s.rows) { s.es_stale = false; return HPF_OK; }
-  { int rc0 = recover_if_flushed(h); if (rc0) return rc0; }       // a repeat of the last sweep needs S as the pass left it
-  const size_t ne = (size_t)s.rows * h->ld;
-  const uint32_t blocks = (uint32_t)std::min<size_t>((ne + 255) / 256, 8192);
-  hipLaunchKernelGGL(materialize_es_kernel, dim3(blocks), dim3(256), 0, h->stream, s.S, s.E, s.prior_used,
-                     s.colsum_used, s.rows, h->ld, h->K, s.bias_col, s.bias_rate_add, h->cfg.s_prior,
-                     h->cfg.r_prior, h->cfg.hier);
-  int rc = check_launch(h, "materialize_es_kernel");
-  if (!rc) s.es_stale = false;
-  return rc;
+  if (s.rows) {
+    const size_t ne = (size_t)s.rows * h->ld;
+    const uint32_t blocks = (uint32_t)std::min<size_t>((ne + 255) / 256, 8192);
+    hipLaunchKernelGGL(materialize_es_kernel, dim3(blocks), dim3(256), 0, h->stream, s.S, s.E, s.prior_used,
+                       s.colsum_used, s.rows, h->ld, h->K, s.bias_col, s.bias_rate_add, h->cfg.s_prior,
+                       h->cfg.r_prior, h->cfg.hier);
+    if (int rc = check_launch(h, "materialize_es_kernel")) return rc;
+  }
+  h->lz.refreshed(h->side_of(s) ? hpf_lazy::ES_ITEMS : hpf_lazy::ES_USERS);
+  return HPF_OK;
 }
 
-// rebuild Elog from shape and the rate the last sweep used (export only)
+// rebuild Elog from shape and the rate the last sweep used (export only; hpf_lazy::ELOG_*)
 int refresh_elog(hpf_handle *h, Side &s)
 {
-  { int rc0 = refresh_es(h, s); if (rc0) return rc0; }
-  if (!s.l_stale || !s.rows) { s.l_stale = false; return HPF_OK; }
-  const size_t ne = (size_t)s.rows * h->ld;
-  const uint32_t blocks = (uint32_t)std::min<size_t>((ne + 255) / 256, 8192);
-  hipLaunchKernelGGL(elog_kernel, dim3(blocks), dim3(256), 0, h->stream, s.S, s.prior_used,
-                     s.colsum_used, s.L, s.rows, h->ld, h->K, s.bias_col, s.bias_rate_add,
-                     h->cfg.r_prior, h->cfg.hier);
-  int rc = check_launch(h, "elog_kernel");
-  if (!rc) s.l_stale = false;
-  return rc;
+  if (s.rows) {
+    const size_t ne = (size_t)s.rows * h->ld;
+    const uint32_t blocks = (uint32_t)std::min<size_t>((ne + 255) / 256, 8192);
+    hipLaunchKernelGGL(elog_kernel, dim3(blocks), dim3(256), 0, h->stream, s.S, s.prior_used,
+                       s.colsum_used, s.L, s.rows, h->ld, h->K, s.bias_col, s.bias_rate_add,
+                       h->cfg.r_prior, h->cfg.hier);
+    if (int rc = check_launch(h, "elog_kernel")) return rc;
+  }
+  h->lz.refreshed(h->side_of(s) ? hpf_lazy::ELOG_ITEMS : hpf_lazy::ELOG_USERS);
+  return HPF_OK;
 }
 
 // ---- what the report-step endpoints share -------------------------------------------------------------------------------
-// E of both sides must have been set, or an iteration must have run
-int need_e(hpf_handle *h)
-{
-  if (!(h->u.have_E && h->it.have_E) && h->iterations == 0) { h->err = "E state not set"; return HPF_ERR_STATE; }
-  return HPF_OK;
-}
-int refresh_e(hpf_handle *h) { const int rc = refresh_es(h, h->u); return rc ? rc : refresh_es(h, h->it); }
-// before a kernel scores pairs from E: E exists, no breakdown is flagged, and E is that of the last sweep.  (A call that
-// validates its arguments in between asks need_e first: which error a bad call gets does not depend on the device.)
-int scoring_ready(hpf_handle *h)
-{
-  int rc;
-  if ((rc = need_e(h)) || (rc = check_flags(h))) return rc;
-  return refresh_e(h);
-}
 // the fields every scoring kernel's argument struct has
 template <class Args>
 void factor_args(const hpf_handle *h, Args &a)
@@ -1266,23 +1233,15 @@ int topn_run(FusedCtx &c, TopnArgs a, uint32_t m, uint32_t n_sel, uint32_t topn,
   return copy_back(h, {{out_items, d_items, (size_t)n_sel * topn * 4}, {out_scores, d_sc, (size_t)n_sel * topn * 8}});
 }
 
+// W of the sides that follow a handed-in Elog (hpf_lazy::DERIVE_W)
 int prepare_derived(hpf_handle *h)
 {
-  if (!h->derived_dirty) return HPF_OK;
-  if (!(h->u.have_L && h->it.have_L && h->it.have_E)) {
-    h->err = "state not initialised: set THETA_ELOG, BETA_ELOG and BETA_E before iterating";
-    return HPF_ERR_STATE;
-  }
-  if (h->cfg.hier && !(h->u.have_prior && h->it.have_prior)) {
-    h->err = "state not initialised: set XI_E and ETA_E (-hier)";
-    return HPF_ERR_STATE;
-  }
   Side *sides[2] = {&h->u, &h->it};
   for (int attempt = 0; attempt < 2; ++attempt) {
     bool derived = false;
     for (Side *s : sides) {
-      if (!s->rows || !s->w_dirty) continue;
-      s->w_dirty = false; s->w_from_sweep = false;
+      if (!h->lz.w_due(h->side_of(*s))) continue;
+      h->lz.w_derived(h->side_of(*s));
       derived = true;
       const uint32_t blocks = std::min<uint32_t>((s->rows + 3) / 4, 4096);
       hipLaunchKernelGGL(derive_w_kernel, dim3(blocks), dim3(256), 0, h->stream, s->L, s->W,
@@ -1297,32 +1256,62 @@ int prepare_derived(hpf_handle *h)
     if (!(f[0] & 2u)) break;
     { int rc0 = recover_flush(h, f[0], f[1]); if (rc0) return rc0; }
   }
-  // c[k] = sum_i E[beta_ik]: consumed by the first user sweep
-  if (h->sums_dirty) {
-    Side &s = h->it;
-    { int rc0 = refresh_es(h, s); if (rc0) return rc0; }
-    const uint32_t nb = s.sweep_blocks;
-    hipLaunchKernelGGL(colsum_partial_kernel, dim3(nb), dim3(256), 0, h->stream, s.E, s.rows,
-                       h->ld, h->K, s.colsum_part);
-    hipLaunchKernelGGL(colsum_finalize_kernel, dim3(h->ld), dim3(256), 0, h->stream,
-                       s.colsum_part, nb, h->ld, s.colsum, h->flags);
-  }
-  if (h->jacobi && h->sums_dirty) {      // sum_u E[theta] of the start state: the first item rate uses it
-    h->start_sums_done = false;           // several ranks: this rank's part only, until hpf_start_sums hands it to the exchange
-    Side &s = h->u;
-    if (!s.have_E) { h->err = "state not initialised: -novb needs THETA_E (the first item rate is built from it)"; return HPF_ERR_STATE; }
-    { int rc0 = refresh_es(h, s); if (rc0) return rc0; }
-    hipLaunchKernelGGL(colsum_partial_kernel, dim3(s.sweep_blocks), dim3(256), 0, h->stream, s.E, s.rows,
-                       h->ld, h->K, s.colsum_part);
-    hipLaunchKernelGGL(colsum_finalize_kernel, dim3(h->ld), dim3(256), 0, h->stream,
-                       s.colsum_part, s.sweep_blocks, h->ld, s.colsum, h->flags);
-  }
-  int rc = check_launch(h, "prepare_derived");
-  if (rc) return rc;
-  h->derived_dirty = false;
-  h->sums_dirty = false;
   return HPF_OK;
 }
+
+// c[k] = sum_i E[beta_ik], consumed by the first user sweep; jacobi: sum_u E[theta] of the start state, which the first
+// item rate uses (hpf_lazy::COLUMN_SUMS)
+void start_column_sums(hpf_handle *h)
+{
+  for (Side *s : {&h->it, &h->u}) {
+    if (s == &h->u && !h->jacobi) break;
+    hipLaunchKernelGGL(colsum_partial_kernel, dim3(s->sweep_blocks), dim3(256), 0, h->stream, s->E, s->rows,
+                       h->ld, h->K, s->colsum_part);
+    hipLaunchKernelGGL(colsum_finalize_kernel, dim3(h->ld), dim3(256), 0, h->stream,
+                       s->colsum_part, s->sweep_blocks, h->ld, s->colsum, h->flags);
+  }
+}
+
+// hpf_lazy::EXCHANGE_START_SUMS
+int exchange_start_sums(hpf_handle *h)
+{
+  if (h->comm) {                        // the library owns the exchange: the [ld] tail, in place, on the kernels' stream
+    const size_t items = (size_t)h->it.rows * h->ld;
+    const int rc2 = g_rccl.AllReduce(h->exch + items, h->exch + items, h->exch_count - items, 8, 0, h->comm, (void *)h->stream);
+    if (rc2 != 0) { h->err = std::string("ncclAllReduce: ") + g_rccl.GetErrorString(rc2); return HPF_ERR_HIP; }
+    if (int rc = check_comm_async(h)) return rc;
+  }
+  HIPCHK(h, hipStreamSynchronize(h->stream));     // the caller's all-reduce may run on another stream
+  h->lz.start_sums_handed(h->comm != nullptr);
+  return HPF_OK;
+}
+
+// The one prologue of a call: what it names is current when this returns HPF_OK.  hpf_lazy::State::ask decides -- the
+// error the call returns, or the deferred jobs and their order --, `validate` (the call's own argument checks) runs between
+// the two, so that which error a bad call gets does not depend on the device, and each job has one executor here.
+template <typename Validate>
+int ready(hpf_handle *h, hpf_lazy::Need need, int side, int kind, Validate &&validate)
+{
+  const hpf_lazy::Todo todo = h->lz.ask(need, {h->phase, h->iterations, h->wl == WL_P59, h->comm != nullptr}, side, kind);
+  if (todo.status) { h->err = todo.error; return todo.status; }
+  int rc = validate();
+  for (int j = 0; j < todo.n && !rc; ++j)
+    switch (todo.job[j]) {
+      case hpf_lazy::RECOVER: rc = recover_if_flushed(h); break;
+      case hpf_lazy::REPORT: rc = check_flags(h); break;
+      case hpf_lazy::ES_USERS: rc = refresh_es(h, h->u); break;
+      case hpf_lazy::ES_ITEMS: rc = refresh_es(h, h->it); break;
+      case hpf_lazy::ELOG_USERS: rc = refresh_elog(h, h->u); break;
+      case hpf_lazy::ELOG_ITEMS: rc = refresh_elog(h, h->it); break;
+      case hpf_lazy::DERIVE_W: rc = prepare_derived(h); break;
+      case hpf_lazy::COLUMN_SUMS: start_column_sums(h); break;
+      case hpf_lazy::DERIVED_DONE: if (!(rc = check_launch(h, "prepare_derived"))) h->lz.derived(); break;
+      case hpf_lazy::EXCHANGE_START_SUMS: rc = exchange_start_sums(h); break;
+      case hpf_lazy::N_JOBS: break;
+    }
+  return rc;
+}
+int ready(hpf_handle *h, hpf_lazy::Need need, int side = -1, int kind = -1) { return ready(h, need, side, kind, [] { return (int)HPF_OK; }); }
 
 // rows of W in 16-byte pieces?
 bool rows_in_pieces(const hpf_handle *h) { return h->wl != WL_PLAIN; }
@@ -1457,15 +1446,12 @@ int enqueue_step(hpf_handle *h, Step step, hipEvent_t *ev)
   return HPF_OK;
 }
 
-// a sweep of s is on the stream: S holds raw sums, E and Elog predate it, W is the sweep's
-void mark_swept(Side &s) { s.l_stale = true; s.es_stale = true; s.w_from_sweep = true; }
-
 void step_done(hpf_handle *h, Step step)
 {
   h->phase = hpf_plan::next_phase(h->phase, step);
-  if (step == Step::USERS_SWEEP) mark_swept(h->u);
+  if (step == Step::USERS_SWEEP) h->lz.swept(hpf_lazy::USERS);
   if (step != Step::ITEMS_SWEEP) return;
-  mark_swept(h->it);
+  h->lz.swept(hpf_lazy::ITEMS);
   h->replaying = false;
   h->ev_count++;
   h->iterations++;
@@ -1533,26 +1519,13 @@ int begin_iteration(hpf_handle *h, Replay want)
 {
   int rc;
   if (!h->have_csr) { h->err = "hpf_upload_csr has not been called"; return HPF_ERR_STATE; }
-  // several ranks: a pass that skipped would leave this rank's sums out of the all-reduce, so the host looks at the flag
-  // before every iteration (one stream synchronisation) and repairs the rows first; one rank lets the passes skip and
-  // catches up at its next synchronisation point (recover_flush)
-  if (h->cfg.n_ranks > 1 && h->wl == WL_P59 && (rc = recover_if_flushed(h))) return rc;
-  // (sums_dirty, not derived_dirty: a rank that only has to write its W again after a fall-back from the packed rows keeps
-  // the all-reduced sums it holds and must not enter a collective the other ranks never issue -- ADVICE r4)
-  if (h->jacobi && h->cfg.n_ranks > 1 && (h->sums_dirty || !h->start_sums_done)) {
-    if (h->comm) { if ((rc = hpf_start_sums(h))) return rc; }
-    else {
-      h->err = "-novb on several ranks: call hpf_start_sums and sum-all-reduce the last ld doubles of the exchange buffer before the first iteration";
-      return HPF_ERR_STATE;
-    }
-  }
-  if ((rc = prepare_derived(h))) return rc;
+  if ((rc = ready(h, hpf_lazy::ITERATION))) return rc;
   if (want == PIECES && !split_graph_on(h)) want = EAGER;
   for (int k = 0; want == PIECES && k < 3; ++k)
     if (!h->split_exec[k] && (rc = capture_steps(h, PIECE[k][0], PIECE[k][1], &h->split_exec[k]))) return rc;
   if (want == WHOLE && !h->graph_exec && (rc = capture_steps(h, Step::ITEMS_PASS, Step::ITEMS_SWEEP, &h->graph_exec))) return rc;
   const uint32_t slot = h->ev_count % hpf_handle::RING;
-  h->tail_partial = false;
+  h->lz.iteration_begun();
   h->ev = h->evr[slot];
   h->ring_graphed[slot] = want == WHOLE;
   h->replaying = want == PIECES;
@@ -1616,12 +1589,12 @@ int redo_in_plain_rows(hpf_handle *h, uint32_t fl0, uint64_t redo)
   h->iters_counted = 0;
   Side *sides[2] = {&h->u, &h->it};
   for (Side *s : sides) {
-    if (!s->rows) continue;
-    if (!s->w_from_sweep || s->w_dirty) { s->w_dirty = true; h->derived_dirty = true; continue; }     // from Elog: prepare_derived
+    const hpf_lazy::Repair how = h->lz.fell_back(h->side_of(*s));
+    if (how == hpf_lazy::REPAIR_NOTHING || how == hpf_lazy::REPAIR_FROM_ELOG) continue;      // from Elog: the next DERIVE_W
     SweepArgs a;
     sweep_args(h, *s, a);
     a.prior_E = s->prior_used; a.colsum_oth = s->colsum_used; a.colsum_used = nullptr;             // what that sweep read
-    if (!s->es_stale) a.s_prior = 0.0;      // an export has turned S into the shape (prior added, in place) since: the same sum, not taken twice
+    if (how == hpf_lazy::REPAIR_REPEAT_ON_SHAPE) a.s_prior = 0.0;      // S is the shape (prior added, in place) already
     if (!launch_sweep(h->sw_mode, h->swG, h->swR, a, s->sweep_blocks, h->stream)) { h->err = "no sweep kernel for this configuration"; return HPF_ERR_UNSUPPORTED; }
   }
   if ((rc = check_launch(h, "repeat of the sweeps in plain rows"))) return rc;
@@ -1758,6 +1731,12 @@ int hpf_create(const hpf_config *cfg, hpf_handle **out)
   h->it.S = h->exch; h->u.colsum = h->exch + (size_t)m * ld;
   if ((rc = dalloc(h, &h->it.colsum, ld))) return fail(rc);
   h->jacobi = jacobi;
+  {
+    hpf_lazy::Config lc;
+    lc.hier = cfg->hier != 0; lc.bias = cfg->bias != 0; lc.jacobi = jacobi; lc.several = cfg->n_ranks > 1;
+    lc.rows[hpf_lazy::USERS] = n != 0; lc.rows[hpf_lazy::ITEMS] = m != 0;
+    h->lz = hpf_lazy::State(lc);
+  }
   if ((rc = dalloc(h, &h->u_colsum_prev, ld))) return fail(rc);
   // log y! as HGAPRec::log_factorial does it (hgaprec.cc:1563-1570)
   {
@@ -1884,26 +1863,13 @@ int hpf_start_sums(hpf_handle *h)
 {
   if (!h) return HPF_ERR_INVALID;
   if (!h->have_csr) { h->err = "hpf_upload_csr has not been called"; return HPF_ERR_STATE; }
-  int rc;
-  if ((rc = prepare_derived(h))) return rc;
-  if (!h->jacobi || h->cfg.n_ranks == 1) return HPF_OK;
-  if (h->start_sums_done) return HPF_OK;
-  if (h->comm) {                        // the library owns the exchange: the [ld] tail, in place, on the kernels' stream
-    const size_t items = (size_t)h->it.rows * h->ld;
-    const int rc2 = g_rccl.AllReduce(h->exch + items, h->exch + items, h->exch_count - items, 8, 0, h->comm, (void *)h->stream);
-    if (rc2 != 0) { h->err = std::string("ncclAllReduce: ") + g_rccl.GetErrorString(rc2); return HPF_ERR_HIP; }
-    if ((rc = check_comm_async(h))) return rc;
-  }
-  HIPCHK(h, hipStreamSynchronize(h->stream));     // the caller's all-reduce may run on another stream
-  h->start_sums_done = true;
-  h->tail_partial = !h->comm;
-  return HPF_OK;
+  return ready(h, hpf_lazy::START_SUMS);
 }
 
 int hpf_exchange_read(hpf_handle *h, double *host, size_t count)
 {
   if (!h || !host || count != h->exch_count) return HPF_ERR_INVALID;
-  { int rc = recover_between_iterations(h); if (rc) return rc; }
+  { int rc = ready(h, hpf_lazy::SWEEP_VECTORS); if (rc) return rc; }
   HIPCHK(h, hipMemcpyAsync(host, h->exch, count * 8, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   return HPF_OK;
@@ -2064,45 +2030,22 @@ static int set_state_impl(hpf_handle *h, hpf_state which, const double *host, si
   const size_t want = (obj == 2 || obj == 3) ? (size_t)rows : gr_rate ? (size_t)h->K : (size_t)rows * cols;
   if (count != want) return HPF_ERR_INVALID;
   if (kind == 1 && obj >= 4) return HPF_OK;   // bias rate is the constant 0.3 + m / 0.3 + n
-  // a new state supersedes whatever the kernels flagged about the old one -- but iterations a flushed entry made the
-  // passes skip are part of the old one: they are run first (recover_flush)
-  if ((rc = recover_if_flushed(h))) return rc;
+  const bool vector = obj == 2 || obj == 3 || kind == 1;      // xi / eta, or a rate
+  if ((rc = ready(h, vector ? hpf_lazy::PATCH_VECTOR : hpf_lazy::PATCH, h->side_of(*s), kind))) return rc;
+  // a new state supersedes whatever the kernels flagged about the old one
   HIPCHK(h, hipMemsetAsync(h->flags, 0, 4, h->stream));
   if (obj == 2 || obj == 3) {                 // xi / eta vectors
-    double **dst = nullptr;
-    switch (kind) {
-      case 0: dst = &s->prior_shape_set; break;
-      case 1: dst = &s->prior_rate; break;
-      case 2: dst = &s->prior_E; s->have_prior = true; break;
-      default: dst = &s->prior_elog; break;
-    }
+    double **dst = kind == 0 ? &s->prior_shape_set : kind == 1 ? &s->prior_rate : kind == 2 ? &s->prior_E : &s->prior_elog;
     if (!*dst && (rc = dalloc(h, dst, rows))) return rc;
-    return put(*dst, host, (size_t)rows * 8);
-  }
-  if (kind == 1) {                            // rate: kept only for export before iteration 0
+    rc = put(*dst, host, (size_t)rows * 8);
+  } else if (kind == 1) {                     // rate: kept only for export before iteration 0
     dfree(s->rate_set); s->rate_set = nullptr;
     if ((rc = dalloc(h, &s->rate_set, want))) return rc;
     s->rate_set_count = want;
-    return put(s->rate_set, host, want * 8);
-  }
-  if ((rc = refresh_es(h, *s))) return rc;     // the rest of S / E must be current before patching
-  double *dev = kind == 0 ? s->S : kind == 2 ? s->E : s->L;
-  if ((kind == 3 || kind == 0) && s->l_stale) {
-    // Elog: the rest of L predates the last sweep, rebuild it before patching in the new part.  Shape: L is rebuilt from
-    // S, and a shape handed in is not the sweep's -- an Elog exported later must not depend on whether one was exported before
-    if ((rc = refresh_elog(h, *s))) return rc;
-  }
-  if ((rc = put2d(dev, (uint32_t)col0))) return rc;
-  if (obj <= 1) {
-    if (kind == 2) s->have_E = true;
-    if (kind == 3) s->have_L = true;
-  } else {
-    if (kind == 2) s->have_bias_E = true;
-    if (kind == 3) s->have_bias_L = true;
-  }
-  if (kind == 3) s->w_dirty = true;          // Elog of theta/beta or of a bias column
-  if (kind != 0) h->derived_dirty = h->sums_dirty = true;
-  return HPF_OK;
+    rc = put(s->rate_set, host, want * 8);
+  } else rc = put2d(kind == 0 ? s->S : kind == 2 ? s->E : s->L, (uint32_t)col0);
+  if (!rc) h->lz.state_set(obj, kind);
+  return rc;
 }
 
 int hpf_set_state(hpf_handle *h, hpf_state which, const double *host, size_t count)
@@ -2135,11 +2078,10 @@ static int get_state_impl(hpf_handle *h, hpf_state which, double *host, size_t c
     return HPF_OK;
   };
   // the exports below read neither S, E nor W, but the xi / eta vectors and the column sums a rate is built from are the
-  // sweeps' too: iterations a fall-back made the passes skip are run first (not check_flags: an underflow report is
-  // about E, and these exports never failed on it)
+  // sweeps' too: iterations a fall-back made the passes skip are run first (hpf_lazy::SWEEP_VECTORS)
   if (obj == 2 || obj == 3) {
     if (count != rows) return HPF_ERR_INVALID;
-    { int rc = recover_between_iterations(h); if (rc) return rc; }
+    { int rc = ready(h, hpf_lazy::SWEEP_VECTORS); if (rc) return rc; }
     if (kind == 2 || kind == 1) return get(host, kind == 2 ? s->prior_E : s->prior_rate, (size_t)rows * 8);
     if (kind == 3) return get(host, s->prior_elog, (size_t)rows * 8);   // set by the host, then maintained by the sweep
     if (h->iterations == 0) {
@@ -2154,11 +2096,8 @@ static int get_state_impl(hpf_handle *h, hpf_state which, double *host, size_t c
     const bool gr = (obj <= 1 && !h->cfg.hier);
     const size_t want = gr ? h->K : (size_t)rows * cols;
     if (count != want) return HPF_ERR_INVALID;
-    { int rc = recover_between_iterations(h); if (rc) return rc; }
-    if (obj >= 4) {                           // gpbase.hh:225-231 via hgaprec.cc:1389,1393
-      if (h->iterations == 0 && !s->bias_rate_known) { h->err = "bias rate is defined after the first sweep"; return HPF_ERR_STATE; }
-      return fill(r0 + s->bias_rate_add, rows);
-    }
+    { int rc = ready(h, obj >= 4 ? hpf_lazy::BIAS_RATE : hpf_lazy::SWEEP_VECTORS, h->side_of(*s)); if (rc) return rc; }
+    if (obj >= 4) return fill(r0 + s->bias_rate_add, rows);      // gpbase.hh:225-231 via hgaprec.cc:1389,1393
     if (h->iterations == 0) {
       if (!s->rate_set || s->rate_set_count != want) { h->err = "state was never set"; return HPF_ERR_STATE; }
       return get(host, s->rate_set, want * 8);
@@ -2184,8 +2123,7 @@ static int get_state_impl(hpf_handle *h, hpf_state which, double *host, size_t c
     return HPF_OK;
   }
   if (count != (size_t)rows * cols) return HPF_ERR_INVALID;
-  { int rc = check_flags(h); if (rc) return rc; }
-  { int rc = kind == 3 ? refresh_elog(h, *s) : refresh_es(h, *s); if (rc) return rc; }
+  { int rc = ready(h, kind == 3 ? hpf_lazy::STATE_ELOG : hpf_lazy::STATE_E, h->side_of(*s)); if (rc) return rc; }
   const double *dev = kind == 0 ? s->S : kind == 2 ? s->E : s->L;
   return on_device ? copy_out_dev(h, dev, h->ld, (uint32_t)col0, host, rows, cols)
                    : copy_out(h, dev, h->ld, (uint32_t)col0, host, rows, cols);
@@ -2212,11 +2150,9 @@ struct SnapHeader {
   uint32_t n_users_total, rank, n_ranks, novb;
   uint64_t nnz;
   double s_prior, r_prior;
-  uint32_t side_flags[2];               // bit 0 have_E, 1 have_L, 2 have_prior, 3 w_dirty, 4 l_stale, 5 es_stale,
-                                        // 6 rate_set present, 7 prior_shape_set present
-  uint32_t derived_dirty;
-  uint32_t more_flags;                  // bit 0 sums_dirty, bit 1 start_sums_done (a handle whose W alone was pending must not
-                                        // come back as one whose start sums are pending -- on several ranks it would enter a collective alone)
+  uint32_t side_flags[2];               // hpf_lazy::State::snap_side_word: what is pending on a side; SNAP_RATE_SET / SNAP_PRIOR_SHAPE_SET: the array follows
+  uint32_t derived_word;                // hpf_lazy::State::snap_derived_dirty
+  uint32_t more_flags;                  // hpf_lazy::State::snap_more_flags
   uint64_t rate_set_count[2];
   uint64_t total_bytes;
 };
@@ -2233,15 +2169,9 @@ void snapshot_sections(hpf_handle *h, const uint64_t rate_cnt[2], const uint32_t
     out->push_back({s.W, w_bytes(h, s.rows)});
     for (double *p : {s.prior_E, s.prior_used, s.prior_rate, s.prior_elog, s.prior_elog_used}) out->push_back({p, vec});
     out->push_back({s.colsum, row}); out->push_back({s.colsum_used, row});
-    if (flags[k] & 64u) out->push_back({s.rate_set, (size_t)rate_cnt[k] * 8});
-    if (flags[k] & 128u) out->push_back({s.prior_shape_set, vec});
+    if (flags[k] & hpf_lazy::SNAP_RATE_SET) out->push_back({s.rate_set, (size_t)rate_cnt[k] * 8});
+    if (flags[k] & hpf_lazy::SNAP_PRIOR_SHAPE_SET) out->push_back({s.prior_shape_set, vec});
   }
-}
-uint32_t side_flag_word(const Side &s)
-{
-  return (s.have_E ? 1u : 0u) | (s.have_L ? 2u : 0u) | (s.have_prior ? 4u : 0u) | (s.w_dirty ? 8u : 0u) |
-         (s.l_stale ? 16u : 0u) | (s.es_stale ? 32u : 0u) | (s.rate_set ? 64u : 0u) | (s.prior_shape_set ? 128u : 0u) |
-         (s.w_from_sweep ? 256u : 0u);
 }
 void fill_snap_header(hpf_handle *h, SnapHeader *hd)
 {
@@ -2252,9 +2182,10 @@ void fill_snap_header(hpf_handle *h, SnapHeader *hd)
   hd->n_users_total = h->cfg.n_users_total; hd->rank = h->cfg.rank; hd->n_ranks = h->cfg.n_ranks;
   hd->novb = h->jacobi ? 1u : 0u; hd->nnz = h->have_csr ? h->nnz : 0;
   hd->s_prior = h->cfg.s_prior; hd->r_prior = h->cfg.r_prior;
-  hd->side_flags[0] = side_flag_word(h->u); hd->side_flags[1] = side_flag_word(h->it);
-  hd->derived_dirty = h->derived_dirty;
-  hd->more_flags = (h->sums_dirty ? 1u : 0u) | (h->start_sums_done ? 2u : 0u);
+  hd->side_flags[0] = h->lz.snap_side_word(hpf_lazy::USERS, h->u.rate_set, h->u.prior_shape_set);
+  hd->side_flags[1] = h->lz.snap_side_word(hpf_lazy::ITEMS, h->it.rate_set, h->it.prior_shape_set);
+  hd->derived_word = h->lz.snap_derived_dirty();
+  hd->more_flags = h->lz.snap_more_flags();
   hd->rate_set_count[0] = h->u.rate_set ? h->u.rate_set_count : 0;
   hd->rate_set_count[1] = h->it.rate_set ? h->it.rate_set_count : 0;
   std::vector<SnapSection> sec;
@@ -2269,7 +2200,7 @@ int hpf_snapshot_size(hpf_handle *h, size_t *bytes)
 {
   if (!h || !bytes) return HPF_ERR_INVALID;
   // a fall-back that is due changes the size of W: it happens here, so that hpf_snapshot_save finds the size it is handed
-  { int rc = recover_between_iterations(h); if (rc) return rc; }
+  { int rc = ready(h, hpf_lazy::SWEEP_VECTORS); if (rc) return rc; }
   SnapHeader hd; fill_snap_header(h, &hd);
   *bytes = (size_t)hd.total_bytes;
   return HPF_OK;
@@ -2279,7 +2210,7 @@ int hpf_snapshot_save(hpf_handle *h, void *host, size_t bytes)
 {
   if (!h || !host) return HPF_ERR_INVALID;
   if (h->phase != 0) { h->err = "snapshot inside an iteration"; return HPF_ERR_STATE; }
-  { int rc = check_flags(h); if (rc) return rc; }
+  { int rc = ready(h, hpf_lazy::FLAGS); if (rc) return rc; }
   SnapHeader hd; fill_snap_header(h, &hd);
   if (bytes != hd.total_bytes) { h->err = "snapshot buffer size differs from hpf_snapshot_size"; return HPF_ERR_INVALID; }
   memcpy(host, &hd, sizeof hd);
@@ -2304,7 +2235,7 @@ int hpf_snapshot_load(hpf_handle *h, const void *host, size_t bytes)
   // handle follows (validated below like everything else, but the layout has to be known to size the sections)
   const bool follow = !memcmp(hd.magic, SNAP_MAGIC, 8) && h->wl == WL_P59 && hd.w32 == (h->cfg.w_storage | ((uint32_t)WL_F64 << 8)) &&
                       hd.n_users == h->u.rows && hd.n_items == h->it.rows && hd.K == h->K && hd.ld == h->ld && hd.total_bytes == bytes;
-  if (follow) { int rc0 = recover_if_flushed(h); if (!rc0 && h->wl == WL_P59) rc0 = set_rows_f64(h); if (rc0) return rc0; h->fallbacks++; }
+  if (follow) { int rc0 = ready(h, hpf_lazy::OVERWRITE_ALL); if (!rc0 && h->wl == WL_P59) rc0 = set_rows_f64(h); if (rc0) return rc0; h->fallbacks++; }
   if (memcmp(hd.magic, SNAP_MAGIC, 8) || hd.total_bytes != bytes || hd.n_users != h->u.rows || hd.n_items != h->it.rows ||
       hd.K != h->K || hd.ld != h->ld || hd.hier != h->cfg.hier || hd.bias != h->cfg.bias || hd.w32 != (h->cfg.w_storage | ((uint32_t)h->wl << 8))) {
     h->err = "not a snapshot of this model (shape, flags or storage differ)"; return HPF_ERR_INVALID;
@@ -2319,7 +2250,7 @@ int hpf_snapshot_load(hpf_handle *h, const void *host, size_t bytes)
   Side *sides[2] = {&h->u, &h->it};
   for (int k = 0; k < 2; ++k) {
     const size_t lim = (size_t)sides[k]->rows * h->K;
-    const bool has = hd.side_flags[k] & 64u;
+    const bool has = hd.side_flags[k] & hpf_lazy::SNAP_RATE_SET;
     if (has != (hd.rate_set_count[k] != 0) || hd.rate_set_count[k] > lim) { h->err = "damaged snapshot header"; return HPF_ERR_INVALID; }
   }
   {
@@ -2327,8 +2258,8 @@ int hpf_snapshot_load(hpf_handle *h, const void *host, size_t bytes)
     for (int k = 0; k < 2; ++k) {
       const size_t mat = (size_t)sides[k]->rows * h->ld * 8, vec = (size_t)sides[k]->rows * 8, row = (size_t)h->ld * 8;
       tot += 3 * mat + w_bytes(h, sides[k]->rows) + 5 * vec + 2 * row;
-      if (hd.side_flags[k] & 64u) tot += (size_t)hd.rate_set_count[k] * 8;
-      if (hd.side_flags[k] & 128u) tot += vec;
+      if (hd.side_flags[k] & hpf_lazy::SNAP_RATE_SET) tot += (size_t)hd.rate_set_count[k] * 8;
+      if (hd.side_flags[k] & hpf_lazy::SNAP_PRIOR_SHAPE_SET) tot += vec;
     }
     if (tot != bytes) { h->err = "damaged snapshot header"; return HPF_ERR_INVALID; }
   }
@@ -2337,8 +2268,8 @@ int hpf_snapshot_load(hpf_handle *h, const void *host, size_t bytes)
   double *new_rate[2] = {nullptr, nullptr}, *new_pss[2] = {nullptr, nullptr};
   for (int k = 0; k < 2; ++k) {                           // optional arrays the snapshot carries
     Side &s = *sides[k];
-    if ((hd.side_flags[k] & 64u) && (rc = sc.alloc(&new_rate[k], (size_t)hd.rate_set_count[k]))) return rc;
-    if ((hd.side_flags[k] & 128u) && !s.prior_shape_set && (rc = sc.alloc(&new_pss[k], s.rows))) return rc;
+    if ((hd.side_flags[k] & hpf_lazy::SNAP_RATE_SET) && (rc = sc.alloc(&new_rate[k], (size_t)hd.rate_set_count[k]))) return rc;
+    if ((hd.side_flags[k] & hpf_lazy::SNAP_PRIOR_SHAPE_SET) && !s.prior_shape_set && (rc = sc.alloc(&new_pss[k], s.rows))) return rc;
   }
   for (int k = 0; k < 2; ++k) {
     Side &s = *sides[k];
@@ -2353,16 +2284,7 @@ int hpf_snapshot_load(hpf_handle *h, const void *host, size_t bytes)
     if ((rc = h2d(h, x.ptr, p, x.bytes))) return rc;
     p += x.bytes;
   }
-  for (int k = 0; k < 2; ++k) {
-    Side &s = *sides[k]; const uint32_t f = hd.side_flags[k];
-    s.have_E = f & 1u; s.have_L = f & 2u; s.have_prior = f & 4u; s.w_dirty = f & 8u; s.l_stale = f & 16u; s.es_stale = f & 32u;
-    s.w_from_sweep = (f & 256u) != 0;
-    s.have_bias_E = s.have_E; s.have_bias_L = s.have_L;      // a snapshot does not say them apart: the whole rows came with it
-    s.bias_rate_known = false;
-  }
-  h->derived_dirty = hd.derived_dirty != 0;
-  h->sums_dirty = (hd.more_flags & 1u) != 0;
-  h->start_sums_done = (hd.more_flags & 2u) != 0;      // the tail of the exchange buffer came with the snapshot
+  h->lz.snapshot_loaded(hd.side_flags, hd.derived_word, hd.more_flags);
   h->iterations = hd.iterations;
   h->phase = 0;
   HIPCHK(h, hipMemsetAsync(h->flags, 0, 8, h->stream));
@@ -2410,17 +2332,6 @@ namespace {
 // item-major view's column pointers), and the rows with at least long_min nonzeros go to fold_in_long_kernel (0: none do).
 struct FoldCall { Side &own, &oth; const int64_t *ptr; uint32_t long_min; const char *who; };
 
-// the folded-in side after the call: what hpf_set_state of every array of that side would leave behind
-void fold_mark_state(hpf_handle *h, Side &s)
-{
-  s.have_E = s.have_L = true;
-  if (h->cfg.hier) s.have_prior = true;
-  if (h->cfg.bias) s.have_bias_E = s.have_bias_L = s.bias_rate_known = true;
-  s.es_stale = s.l_stale = false;
-  s.w_dirty = true; s.w_from_sweep = false;
-  h->derived_dirty = h->sums_dirty = true;
-}
-
 // room for what the rates are exported from before the first sweep (hpf_set_state(THETA_RATE), (XI_SHAPE))
 int fold_export_room(hpf_handle *h, Side &u)
 {
@@ -2443,7 +2354,6 @@ int fold_fused(hpf_handle *h, const FoldCall &fc, uint32_t n_iters, double tol, 
   const uint32_t n = u.rows, m = it.rows, ld = h->ld, ldf = fp.wave.ld;
   const double s0 = h->cfg.s_prior, r0 = h->cfg.r_prior;
   int rc;
-  if ((rc = refresh_elog(h, it))) return rc;                 // E and Elog of the frozen side as of its last sweep
   if ((rc = fold_export_room(h, u))) return rc;
   Scratch sc(h);
   double *Wb = nullptr, *part = nullptr, *csum = nullptr; uint32_t *d_iters = nullptr, *d_long = nullptr, *d_nlong = nullptr;
@@ -2485,7 +2395,7 @@ int fold_fused(hpf_handle *h, const FoldCall &fc, uint32_t n_iters, double tol, 
   }
   // what the rate was built from, where the exports after a sweep look for it
   HIPCHK(h, hipMemcpyAsync(u.colsum_used, csum, (size_t)ld * 8, hipMemcpyDeviceToDevice, h->stream));
-  fold_mark_state(h, u);
+  h->lz.folded(h->side_of(u));
   return copy_back(h, {{iters_out, d_iters, (size_t)n * 4}});
 }
 
@@ -2503,31 +2413,27 @@ int fold_sweeps(hpf_handle *h, const FoldCall &fc, uint32_t n_iters, double tol,
   hipLaunchKernelGGL(fold_prior_kernel, dim3(grid_for((uint64_t)n * ld)), dim3(256), 0, h->stream, u.S, u.E, u.L,
                      h->cfg.hier ? u.prior_E : nullptr, u.prior_elog, n, ld, h->K, u.bias_col, s0, s0 / r0, host_digamma(s0) - std::log(r0));
   if ((rc = check_launch(h, "fold_prior_kernel"))) return rc;
-  fold_mark_state(h, u);
-  const bool prior_given = it.have_prior;
-  it.have_prior = true;                                      // the frozen side's xi / eta is not read by the other half
-  rc = prepare_derived(h);
-  it.have_prior = prior_given;
-  if (rc) return rc;
-  // the sums of the frozen side the sweep's rate reads: the item side's are prepare_derived's; the user side's own are the
+  h->lz.folded(h->side_of(u));
+  if ((rc = ready(h, hpf_lazy::FOLD_SWEEPS_RUN, h->side_of(u)))) return rc;      // the frozen side's xi / eta is not read by the other half
+  // the sums of the frozen side the sweep's rate reads: the item side's are the start sums; the user side's own are the
   // product of a user sweep, so an item call takes them into a temporary
   Scratch sc(h);
   double *csum = it.colsum;
   if (items) {
     double *part = nullptr;
-    if ((rc = refresh_es(h, it)) || (rc = sc.alloc(&part, (size_t)it.sweep_blocks * ld)) || (rc = sc.alloc(&csum, ld))) return rc;
+    if ((rc = sc.alloc(&part, (size_t)it.sweep_blocks * ld)) || (rc = sc.alloc(&csum, ld))) return rc;
     hipLaunchKernelGGL(colsum_partial_kernel, dim3(it.sweep_blocks), dim3(256), 0, h->stream, it.E, it.rows, ld, h->K, part);
     hipLaunchKernelGGL(colsum_finalize_kernel, dim3(ld), dim3(256), 0, h->stream, part, it.sweep_blocks, ld, csum, h->flags);
     if ((rc = check_launch(h, "fold-in set-up"))) return rc;
   }
   for (uint32_t t = 0; t < n_iters; ++t)
     if ((rc = run_phi(h, u, it, nullptr)) || (rc = run_sweep(h, u, csum, u.colsum))) return rc;
-  mark_swept(u);                                             // refresh_elog below rebuilds E and Elog from the sums
+  h->lz.swept(h->side_of(u));                                // FOLD_SWEEPS_END below rebuilds E and Elog from the sums
   uint32_t fl = 0;
   HIPCHK(h, hipMemcpyAsync(&fl, h->flags, 4, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   if (fl & 6u) { h->err = "HPF_FOLD_ROUTE=sweeps: the packed rows cannot hold this state (use w_storage = 3)"; return HPF_ERR_UNSUPPORTED; }
-  if ((rc = refresh_elog(h, u))) return rc;                  // shape, E and Elog from the raw sums
+  if ((rc = ready(h, hpf_lazy::FOLD_SWEEPS_END, h->side_of(u)))) return rc;      // shape, E and Elog from the raw sums
   if (h->cfg.hier) {
     hipLaunchKernelGGL(build_rate_kernel, dim3(1024), dim3(256), 0, h->stream, u.prior_used, u.colsum_used, n, h->K, u.rate_set);
     if ((rc = check_launch(h, "build_rate"))) return rc;
@@ -2540,7 +2446,7 @@ int fold_sweeps(hpf_handle *h, const FoldCall &fc, uint32_t n_iters, double tol,
     for (uint32_t k = 0; k < h->K; ++k) cs[k] += r0;
     if ((rc = h2d(h, u.rate_set, cs.data(), (size_t)h->K * 8))) return rc;
   }
-  fold_mark_state(h, u);
+  h->lz.folded(h->side_of(u));
   if (iters_out) std::fill(iters_out, iters_out + n, n_iters);
   HIPCHK(h, hipStreamSynchronize(h->stream));
   return HPF_OK;
@@ -2550,27 +2456,17 @@ int fold_sweeps(hpf_handle *h, const FoldCall &fc, uint32_t n_iters, double tol,
 int fold_call(hpf_handle *h, const FoldCall &fc, uint32_t n_iters, double tol, uint32_t *iters_out)
 {
   const std::string who = fc.who;
-  const bool items = &fc.own == &h->it;
   if (n_iters == 0) { h->err = who + ": n_iters must be at least 1"; return HPF_ERR_INVALID; }
   if (!(tol >= 0.0)) { h->err = who + ": tol must be a number >= 0"; return HPF_ERR_INVALID; }
   if (!h->have_csr) { h->err = "hpf_upload_csr has not been called"; return HPF_ERR_STATE; }
   if (h->phase != 0) { h->err = who + ": call between iterations"; return HPF_ERR_STATE; }
-  const Side &it = fc.oth;
-  if (h->iterations == 0 && !(it.have_E && it.have_L)) {
-    h->err = items ? "user side not set: hand in THETA_E and THETA_ELOG before folding in" : "item side not set: hand in BETA_E and BETA_ELOG before folding in";
-    return HPF_ERR_STATE;
-  }
-  if (h->iterations == 0 && h->cfg.bias && !(it.have_bias_E && it.have_bias_L)) {
-    h->err = items ? "user side not set: hand in UBIAS_E and UBIAS_ELOG before folding in (-bias)" : "item side not set: hand in IBIAS_E and IBIAS_ELOG before folding in (-bias)";
-    return HPF_ERR_STATE;
-  }
-  if (fc.own.rows == 0) return HPF_OK;
   int rc;
+  if ((rc = ready(h, h->fold_route == 1 ? hpf_lazy::FOLD_SWEEPS : hpf_lazy::FOLD_FUSED, h->side_of(fc.own)))) return rc;
+  if (fc.own.rows == 0) return HPF_OK;
   // the folded-in state supersedes whatever the kernels flagged about the old one, like a state handed in
-  if ((rc = recover_if_flushed(h))) return rc;
   HIPCHK(h, hipMemsetAsync(h->flags, 0, 4, h->stream));
   if ((rc = h->fold_route == 1 ? fold_sweeps(h, fc, n_iters, tol, iters_out) : fold_fused(h, fc, n_iters, tol, iters_out))) return rc;
-  return check_flags(h);
+  return ready(h, hpf_lazy::FLAGS);
 }
 
 }  // namespace
@@ -2592,12 +2488,11 @@ int hpf_fold_in_items(hpf_handle *h, uint32_t n_iters, double tol, uint32_t *ite
 
 namespace {
 // per-pair log-likelihoods of cnt pairs whose indices lie on the device, into hout (host; page-locked for a bound set),
-// summed serially in the order handed in: the map order of hgaprec.cc:1455-1465
+// summed serially in the order handed in: the map order of hgaprec.cc:1455-1465.  The caller has asked for hpf_lazy::SCORING.
 int heldout_run(hpf_handle *h, const uint32_t *du, const uint32_t *di, const int32_t *dy, double *dout, double *hout, size_t cnt,
                 double *sum_out, bool pinned)
 {
   int rc;
-  if ((rc = scoring_ready(h))) return rc;
   LLArgs a;
   factor_args(h, a);
   a.u = du; a.i = di; a.y = dy; a.cnt = cnt; a.logfact = h->logfact; a.out = dout; a.binary = h->cfg.binary;
@@ -2645,9 +2540,11 @@ int hpf_heldout_ll(hpf_handle *h, const uint32_t *u, const uint32_t *i, const in
   if (cnt == 0) return HPF_OK;
   if (!u || !i || !y) return HPF_ERR_INVALID;
   int rc;
-  if ((rc = need_e(h))) return rc;
-  for (size_t p = 0; p < cnt; ++p)
-    if (u[p] >= h->u.rows || i[p] >= h->it.rows) { h->err = "held-out index out of range"; return HPF_ERR_INVALID; }
+  if ((rc = ready(h, hpf_lazy::SCORING, -1, -1, [&] {
+        for (size_t p = 0; p < cnt; ++p)
+          if (u[p] >= h->u.rows || i[p] >= h->it.rows) { h->err = "held-out index out of range"; return (int)HPF_ERR_INVALID; }
+        return (int)HPF_OK;
+      }))) return rc;
   Scratch sc(h);
   uint32_t *du = nullptr, *di = nullptr; int32_t *dy = nullptr; double *dout = nullptr;
   std::vector<double> out(cnt);
@@ -2686,6 +2583,7 @@ int hpf_heldout_ll_bound(hpf_handle *h, int slot, double *sum_out, uint64_t *cnt
   if (!hs.bound) { h->err = "hpf_heldout_ll_bound: nothing bound to this slot"; return HPF_ERR_STATE; }
   *sum_out = 0.0; if (cnt_out) *cnt_out = hs.cnt;
   if (hs.cnt == 0) return HPF_OK;
+  if (int rc = ready(h, hpf_lazy::SCORING)) return rc;
   return heldout_run(h, hs.du, hs.di, hs.dy, hs.dout, hs.hout, hs.cnt, sum_out, true);
 }
 
@@ -2694,9 +2592,11 @@ int hpf_elbo(hpf_handle *h, double *out)
   if (!h || !out) return HPF_ERR_INVALID;
   *out = 0.0;
   if (!h->have_csr || h->iterations == 0) { h->err = "the ELBO is defined after the first iteration"; return HPF_ERR_STATE; }
+  // fp64 W: logsumexp from the hot loop's W and the row maxima of Elog (no exp per
+  // element); the f32-stored W is not precise enough for that, it takes the Elog form
+  const bool from_w = !h->w32 && h->wl == WL_PLAIN && h->nnz;
   int rc;
-  if ((rc = refresh_elog(h, h->u))) return rc;
-  if ((rc = refresh_elog(h, h->it))) return rc;
+  if ((rc = ready(h, from_w ? hpf_lazy::ELBO_FROM_W : hpf_lazy::ELBO))) return rc;
   // per-nonzero term: the user-major work list(s) of the phi pass, one wave per segment
   const uint32_t nb_nnz = (uint32_t)std::min<uint64_t>(((uint64_t)h->u.nseg + 3) / 4 + 1, 16384);
   const uint32_t nb_g = 1024;
@@ -2705,11 +2605,7 @@ int hpf_elbo(hpf_handle *h, double *out)
   const size_t npart = (size_t)2 * nb_nnz + 2 * nb_g;
   if ((rc = sc.alloc(&part, npart))) return rc;
   std::vector<double> hp(npart, 0.0);
-  // fp64 W: logsumexp from the hot loop's W and the row maxima of Elog (no exp per
-  // element); the f32-stored W is not precise enough for that, it takes the Elog form
-  const bool from_w = !h->w32 && h->wl == WL_PLAIN && h->nnz;
   if (from_w) {
-    if ((rc = prepare_derived(h))) return rc;                  // W follows a set_state(ELOG), if any
     if ((rc = sc.alloc(&Mt, h->u.rows)) || (rc = sc.alloc(&Mb, h->it.rows))) return rc;
     hipLaunchKernelGGL(rowmax_elog_kernel, dim3((h->u.rows + 255) / 256), dim3(256), 0, h->stream,
                        h->u.L, Mt, h->u.rows, h->ld, h->K, h->u.bias_col, h->u.junk_col);
@@ -2755,10 +2651,9 @@ int hpf_elbo(hpf_handle *h, double *out)
 
 // ---- ranking evaluation ----------------------------------------------------
 namespace {
-// what every ranking call asks of the handle, of the selected users and of the mask list
+// what every ranking call asks of the handle, of the selected users and of the mask list, once E is known to exist
 int rank_check(hpf_handle *h, const uint32_t *users, uint32_t n_sel, const uint64_t *mask_ptr, const uint32_t *mask_items)
 {
-  if (int rc = need_e(h)) return rc;
   if (!h->have_csr) { h->err = "hpf_upload_csr has not been called"; return HPF_ERR_STATE; }
   for (uint32_t b = 0; b < n_sel; ++b)
     if (users[b] >= h->u.rows) { h->err = "user index out of range"; return HPF_ERR_INVALID; }
@@ -2773,13 +2668,15 @@ int rank_check(hpf_handle *h, const uint32_t *users, uint32_t n_sel, const uint6
 }
 
 // What a fused call (hpf_loo_ranks, hpf_rank_queries, hpf_recommend) settles before it allocates, in the order that decides
-// which error a bad call gets: rank_check, the items q[0 .. nq) it asks about (none for hpf_recommend), scoring_ready
+// which error a bad call gets: E exists, rank_check, the items q[0 .. nq) it asks about (none for hpf_recommend), the jobs
 int fused_ready(hpf_handle *h, const uint32_t *users, uint32_t n_sel, const uint64_t *mask_ptr, const uint32_t *mask_items,
                 const uint32_t *q = nullptr, uint64_t nq = 0)
 {
-  if (int rc = rank_check(h, users, n_sel, mask_ptr, mask_items)) return rc;
-  for (uint64_t k = 0; k < nq; ++k) if (q[k] >= h->it.rows) { h->err = "query item out of range"; return HPF_ERR_INVALID; }
-  return scoring_ready(h);
+  return ready(h, hpf_lazy::SCORING, -1, -1, [&] {
+    if (int rc = rank_check(h, users, n_sel, mask_ptr, mask_items)) return rc;
+    for (uint64_t k = 0; k < nq; ++k) if (q[k] >= h->it.rows) { h->err = "query item out of range"; return (int)HPF_ERR_INVALID; }
+    return (int)HPF_OK;
+  });
 }
 
 // The unfused ranking calls (hpf_scores, hpf_rank_topn, hpf_item_ranks) keep the scores of a batch of users
@@ -2791,7 +2688,7 @@ struct ScoreCtx : FusedCtx {
   int prepare(const uint32_t *users, uint32_t n_sel, const uint64_t *mask_ptr, const uint32_t *mask_items)
   {
     int rc;
-    if ((rc = rank_check(h, users, n_sel, mask_ptr, mask_items)) || (rc = refresh_e(h))) return rc;
+    if ((rc = ready(h, hpf_lazy::SCORES, -1, -1, [&] { return rank_check(h, users, n_sel, mask_ptr, mask_items); }))) return rc;
     batch = hpf_plan::score_batch_rows(h->it.rows, n_sel);
     if ((rc = upload(users, n_sel, mask_ptr, mask_items))) return rc;
     return alloc(&d_scores, (size_t)batch * h->it.rows);
@@ -2878,10 +2775,11 @@ int hpf_predict(hpf_handle *h, const uint32_t *u, const uint32_t *i, size_t cnt,
   if (cnt == 0) return HPF_OK;
   if (!u || !i || !out) return HPF_ERR_INVALID;
   int rc;
-  if ((rc = need_e(h))) return rc;
-  for (size_t p = 0; p < cnt; ++p)
-    if (u[p] >= h->u.rows || i[p] >= h->it.rows) { h->err = "hpf_predict: index out of range"; return HPF_ERR_INVALID; }
-  if ((rc = scoring_ready(h))) return rc;
+  if ((rc = ready(h, hpf_lazy::SCORING, -1, -1, [&] {
+        for (size_t p = 0; p < cnt; ++p)
+          if (u[p] >= h->u.rows || i[p] >= h->it.rows) { h->err = "hpf_predict: index out of range"; return (int)HPF_ERR_INVALID; }
+        return (int)HPF_OK;
+      }))) return rc;
   Scratch sc(h);
   uint32_t *du = nullptr, *di = nullptr; double *dout = nullptr;
   if ((rc = sc.alloc(&du, cnt, u)) || (rc = sc.alloc(&di, cnt, i)) || (rc = sc.alloc(&dout, cnt))) return rc;
@@ -2940,7 +2838,7 @@ int hpf_rank_queries(hpf_handle *h, const uint32_t *users, uint32_t n_sel, const
   const uint64_t nq = q_ptr[n_sel];
   if (nq > 0xffffffffull) { h->err = "hpf_rank_queries: more than 2^32 - 1 queries in one call"; return HPF_ERR_INVALID; }
   if (nq && (!q_items || !out_rank || !out_score)) return HPF_ERR_INVALID;
-  if (!nq) return rank_check(h, users, n_sel, mask_ptr, mask_items);      // nothing asked: only the checks
+  if (!nq) return ready(h, hpf_lazy::E_IS_SET, -1, -1, [&] { return rank_check(h, users, n_sel, mask_ptr, mask_items); });      // nothing asked: only the checks
   if (int rc = fused_ready(h, users, n_sel, mask_ptr, mask_items, q_items, nq)) return rc;
   FusedCtx c(h); int rc;
   if ((rc = c.upload(users, n_sel, mask_ptr, mask_items)) || (rc = c.bit_rows(n_sel))) return rc;
@@ -3021,11 +2919,12 @@ int hpf_similar(hpf_handle *h, int side, const uint32_t *ids, uint32_t n_sel, ui
   Side &s = side ? h->it : h->u;
   const uint32_t m = s.rows;
   if (h->ld & 1u) { h->err = "hpf_similar: odd row stride"; return HPF_ERR_UNSUPPORTED; }
-  if (!s.have_E && h->iterations == 0) { h->err = "E state not set"; return HPF_ERR_STATE; }
-  for (uint32_t b = 0; b < n_sel; ++b)
-    if (ids[b] >= m) { h->err = side ? "item index out of range" : "user index out of range"; return HPF_ERR_INVALID; }
   int rc;
-  if ((rc = check_flags(h)) || (rc = refresh_es(h, s))) return rc;
+  if ((rc = ready(h, hpf_lazy::FACTORS, side, -1, [&] {
+        for (uint32_t b = 0; b < n_sel; ++b)
+          if (ids[b] >= m) { h->err = side ? "item index out of range" : "user index out of range"; return (int)HPF_ERR_INVALID; }
+        return (int)HPF_OK;
+      }))) return rc;
   FusedCtx c(h);
   double *d_unit = nullptr;
   if ((rc = c.upload(ids, n_sel, nullptr, nullptr))) return rc;
@@ -3054,15 +2953,16 @@ int hpf_explain(hpf_handle *h, const uint32_t *u, const uint32_t *i, size_t cnt,
   if (cnt == 0) return HPF_OK;
   if (!u || !i || !out_factor || !out_contrib) { h->err = "hpf_explain: null pointer"; return HPF_ERR_INVALID; }
   int rc;
-  if ((rc = need_e(h))) return rc;
-  for (size_t p = 0; p < cnt; ++p)
-    if (u[p] >= h->u.rows || i[p] >= h->it.rows) { h->err = "hpf_explain: index out of range"; return HPF_ERR_INVALID; }
   const hpf_plan::ExplainPlan ep = hpf_plan::explain_plan(h->K, h->cfg.bias != 0);
-  // the bias terms are numbered by their columns: K the user's, K + 1 the item's (hpf_create)
-  if (!ep.ok || ep.terms > h->ld || (h->cfg.bias && (h->u.bias_col != (int32_t)h->K || h->it.bias_col != (int32_t)h->K + 1))) {
-    h->err = "explain_kernel: no instance for this column count"; return HPF_ERR_UNSUPPORTED;
-  }
-  if ((rc = scoring_ready(h))) return rc;
+  if ((rc = ready(h, hpf_lazy::SCORING, -1, -1, [&] {
+        for (size_t p = 0; p < cnt; ++p)
+          if (u[p] >= h->u.rows || i[p] >= h->it.rows) { h->err = "hpf_explain: index out of range"; return (int)HPF_ERR_INVALID; }
+        // the bias terms are numbered by their columns: K the user's, K + 1 the item's (hpf_create)
+        if (!ep.ok || ep.terms > h->ld || (h->cfg.bias && (h->u.bias_col != (int32_t)h->K || h->it.bias_col != (int32_t)h->K + 1))) {
+          h->err = "explain_kernel: no instance for this column count"; return (int)HPF_ERR_UNSUPPORTED;
+        }
+        return (int)HPF_OK;
+      }))) return rc;
   Scratch sc(h);
   ExplainArgs a;
   factor_args(h, a);
@@ -3084,9 +2984,8 @@ int hpf_factor_top(hpf_handle *h, int side, uint32_t topn, uint32_t *out_ids, do
   if (topn < 1 || topn > hpf_plan::FACTOR_TOP_MAX) { h->err = "hpf_factor_top: topn is 1 .. 1024"; return HPF_ERR_INVALID; }
   if (!out_ids || !out_vals) { h->err = "hpf_factor_top: null pointer"; return HPF_ERR_INVALID; }
   Side &s = side ? h->it : h->u;
-  if (!s.have_E && h->iterations == 0) { h->err = "E state not set"; return HPF_ERR_STATE; }
   int rc;
-  if ((rc = check_flags(h)) || (rc = refresh_es(h, s))) return rc;
+  if ((rc = ready(h, hpf_lazy::FACTORS, side))) return rc;
   const uint32_t rows = s.rows, K = h->K, NP = hpf_plan::pow2_ceil(topn);
   const uint32_t batch = hpf_plan::factor_top_batch(rows, K, h->ftop_batch);
   static_assert(hpf_plan::FACTOR_TOP_TILE == 32, "transpose_cols_kernel's tile");
@@ -3129,7 +3028,7 @@ int hpf_get_work_info(hpf_handle *h, hpf_work_info *out)
   out->heavy_min_nnz_user = h->u.tiles ? h->u.light_below : 0; out->heavy_min_nnz_item = h->it.tiles ? h->it.light_below : 0;
   out->w_fallbacks = h->fallbacks;
   out->notes = h->notes;
-  out->start_sums_pending = (h->jacobi && h->cfg.n_ranks > 1 && (h->sums_dirty || !h->start_sums_done || h->tail_partial)) ? 1u : 0u;
+  out->start_sums_pending = h->lz.start_sums_pending() ? 1u : 0u;
   out->graph_replay = (h->cfg.n_ranks == 1 && !h->comm) ? ((h->have_csr && want_graph(h)) ? 1u : 0u) : (h->have_csr && split_graph_on(h) ? 2u : 0u);
   out->tile_chunk_user = h->u.chunks ? h->u.chunk_segs : 0; out->tile_chunk_item = h->it.chunks ? h->it.chunk_segs : 0;
   return HPF_OK;
@@ -3140,9 +3039,8 @@ int hpf_gather_only(hpf_handle *h, int side, int reps, float *ms_out)
   if (!h || !ms_out || reps < 1 || (side != 0 && side != 1)) return HPF_ERR_INVALID;
   if (!h->have_csr) { h->err = "hpf_upload_csr has not been called"; return HPF_ERR_STATE; }
   if (h->w32 || (h->wl == WL_PLAIN && h->phiV != 2)) { h->err = "gather-only probe: rows of 16-byte pieces only"; return HPF_ERR_UNSUPPORTED; }
-  { int rc0 = recover_if_flushed(h); if (rc0) return rc0; }
   int rc;
-  if ((rc = prepare_derived(h))) return rc;
+  if ((rc = ready(h, hpf_lazy::GATHER_PROBE))) return rc;
   Side &own = side ? h->it : h->u, &oth = side ? h->u : h->it;
   PhiArgs a;
   const PhiLaunch pl = phi_setup(h, own, oth, false, a);         // the pass's own workgroups
@@ -3191,7 +3089,7 @@ int hpf_host_free(void *ptr)
 int hpf_synchronize(hpf_handle *h)
 {
   if (!h) return HPF_ERR_INVALID;
-  return check_flags(h);
+  return ready(h, hpf_lazy::FLAGS);
 }
 
 int hpf_mean_timing(hpf_handle *h, uint32_t n_last, hpf_timing *out)

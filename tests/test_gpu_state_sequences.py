@@ -163,6 +163,47 @@ def _iterate(M, D, P, dims):
     return D, P
 
 
+def _same_on_both(call):
+    """a scoring call as the first consumer: everything it returns, bit for bit on both handles"""
+    def run(M, D, P, dims):
+        a, b = call(D, dims), call(P, dims)
+        a, b = (a, b) if isinstance(a, tuple) else ((a,), (b,))
+        assert len(a) == len(b) and all(x.size for x in a)
+        for k, (x, y) in enumerate(zip(a, b)):
+            assert sm.same_bits(x, y), (k, int(np.sum(x != y)))
+        return D, P
+    return run
+
+
+def _users(dims):
+    return np.array([0, 7, dims[0] // 2, dims[0] - 1], dtype=np.uint32)
+
+
+def _queries(dims):
+    """two queried items for each of _users -> (q_ptr, q_items)"""
+    q = (np.arange(8, dtype=np.uint32) * 37 + 5) % dims[1]
+    return np.arange(0, 9, 2, dtype=np.uint64), q.astype(np.uint32)
+
+
+def _pairs(dims):
+    return heldout_pairs(dims[0], dims[1], 6, seed=8)[:2]
+
+
+SCORING_CONSUMERS = {
+    "scores": lambda X, d: X.scores(_users(d)),
+    "rank_topn": lambda X, d: X.rank_topn(_users(d), topn=10),
+    "item_ranks": lambda X, d: X.item_ranks(_users(d), np.repeat(np.arange(4, dtype=np.uint32), 2), _queries(d)[1]),
+    "loo_ranks": lambda X, d: X.loo_ranks(_users(d), _queries(d)[1][:4]),
+    "rank_queries": lambda X, d: X.rank_queries(_users(d), *_queries(d)),
+    "recommend": lambda X, d: X.recommend(_users(d), topn=10),
+    "similar_users": lambda X, d: X.similar(0, _users(d), 10),
+    "similar_items": lambda X, d: X.similar(1, _queries(d)[1][:4], 10),
+    "explain": lambda X, d: X.explain(*_pairs(d), 4),
+    "factor_top_users": lambda X, d: X.factor_top(0, 10),
+    "factor_top_items": lambda X, d: X.factor_top(1, 10),
+}
+
+
 CONSUMERS = {
     "THETA_RATE": _get("THETA_RATE"), "BETA_RATE": _get("BETA_RATE"), "XI_E": _get("XI_E"), "XI_RATE": _get("XI_RATE"),
     "XI_ELOG": _get("XI_ELOG"), "ETA_E": _get("ETA_E"), "THETA_E": _get("THETA_E"), "BETA_ELOG": _get("BETA_ELOG"),
@@ -170,6 +211,7 @@ CONSUMERS = {
     "heldout_ll_bound": _heldout(True), "elbo": _elbo, "predict": _predict, "snapshot_restore": _snapshot_restore,
     "refused_set_state": _refused_set_state, "iterate": _iterate,
 }
+CONSUMERS.update({name: _same_on_both(call) for name, call in SCORING_CONSUMERS.items()})
 
 
 @pytest.mark.parametrize("consumer", list(CONSUMERS))
