@@ -42,7 +42,7 @@ EXPORTS = [
     "hpf_iteration_times", "hpf_debug_poke_index", "hpf_start_sums", "hpf_host_alloc", "hpf_host_free",
     "hpf_heldout_bind", "hpf_heldout_ll_bound",
     "hpf_predict", "hpf_loo_ranks", "hpf_rank_queries", "hpf_recommend", "hpf_fold_in", "hpf_similar",
-    "hpf_explain", "hpf_factor_top", "hpf_fold_in_items",
+    "hpf_explain", "hpf_factor_top", "hpf_fold_in_items", "hpf_because",
 ]
 
 # hpf_similar: the metrics (hpf_similarity in include/hpf.h) and the largest topn (TOPN_FUSED_MAX: only the fused route exists)
@@ -53,6 +53,9 @@ SIMILAR_MAX = 256
 # factor (hpf_rank_topn's limit)
 EXPLAIN_MAX = 32
 FACTOR_TOP_MAX = 1024
+
+# hpf_because: the most history items it returns per target (HPF_BECAUSE_MAX in include/hpf.h)
+BECAUSE_MAX = 32
 
 # queries of one row of rank_queries_kernel (RQ_QCAP in csrc/hpf_kernels.hpp): hpf_rank_queries cuts a user with more
 # into several rows; tests put their query counts around it
@@ -152,6 +155,28 @@ def explain_grid(cnt):
     """workgroups hpf_explain launches for cnt pairs; a trip of that grid covers grid * EXPLAIN_WAVES * EXPLAIN_RUN pairs"""
     per = EXPLAIN_WAVES * EXPLAIN_RUN
     return max(1, min((cnt + per - 1) // per, EXPLAIN_BLOCKS_MAX))
+
+
+# hpf_because (hpf_plan::because_plan in csrc/hpf_plan.hpp): a wave per selected user, then a wave per target pair with a
+# run of BECAUSE_RUN consecutive pairs per wave and trip; workgroups of BECAUSE_WAVES waves, at most BECAUSE_BLOCKS_MAX
+BECAUSE_WAVES, BECAUSE_RUN, BECAUSE_BLOCKS_MAX = 4, 4, 4096
+
+
+def because_plan(K, bias=False):
+    """shape of hpf_because's kernels for K factors: row stride of the gathered item rows and of D (fold_plan's), columns
+    per lane R"""
+    try:
+        p = fold_plan(K, bias)
+    except ValueError:
+        raise ValueError("no because kernel for this column count") from None
+    return {"ld": p["ld"], "R": p["R"]}
+
+
+def because_grid(n_sel, nt):
+    """workgroups of because_shape_kernel for n_sel users and of because_kernel for nt target pairs"""
+    per = BECAUSE_WAVES * BECAUSE_RUN
+    return (max(1, min((n_sel + BECAUSE_WAVES - 1) // BECAUSE_WAVES, BECAUSE_BLOCKS_MAX)),
+            max(1, min((nt + per - 1) // per, BECAUSE_BLOCKS_MAX)))
 
 
 class _PinnedBlock:
@@ -305,6 +330,8 @@ def load_library(path: os.PathLike | None = None) -> C.CDLL:
     if hasattr(lib, "hpf_explain"):
         lib.hpf_explain.argtypes = [vp, u32p, u32p, C.c_size_t, C.c_uint32, u32p, dp]
         lib.hpf_factor_top.argtypes = [vp, C.c_int, C.c_uint32, u32p, dp]
+    if hasattr(lib, "hpf_because"):
+        lib.hpf_because.argtypes = [vp, u32p, C.c_uint32, u64p, u32p, C.c_uint32, u32p, dp, dp, dp]
     lib.hpf_comm_unique_id.argtypes = [vp]
     lib.hpf_comm_init.argtypes = [vp, vp]
     lib.hpf_allreduce_exchange.argtypes = [vp]
@@ -679,6 +706,29 @@ class Hpf:
         self._check(self.lib.hpf_explain(self._h, _ptr(u, C.c_uint32), _ptr(i, C.c_uint32), u.size, T & 0xffffffff,
                                          _ptr(factors, C.c_uint32), _ptr(contrib, C.c_double)))
         return factors, contrib
+
+    def because(self, users, t_ptr, t_items, T, want_sums=True):
+        """which of a user's own ratings carry a score (hpf_because).  Targets are a CSR over the selected (local) users:
+        user b asks for t_items[t_ptr[b] : t_ptr[b + 1]]
+        -> (items[nt, T] uint32, contrib[nt, T] float64, sums[nt], priors[nt]): per target the T history items with the
+        largest contribution, best first, entries beyond the history (0xffffffff, 0.0); the sum over the whole history in
+        CSR order; the prior's share (sums and priors None with want_sums=False: NULL pointers)"""
+        users = np.ascontiguousarray(users, dtype=np.uint32)
+        t_ptr = np.ascontiguousarray(t_ptr, dtype=np.uint64)
+        t_items = np.ascontiguousarray(t_items, dtype=np.uint32)
+        if users.ndim != 1 or t_ptr.ndim != 1 or t_items.ndim != 1 or t_ptr.size != users.size + 1:
+            raise ValueError("users, t_ptr (len(users) + 1 entries) and t_items: one-dimensional arrays")
+        T = int(T)
+        nt = t_items.size
+        shape = (nt, T if 0 < T <= BECAUSE_MAX else 0)
+        items = np.empty(shape, dtype=np.uint32)
+        contrib = np.empty(shape, dtype=np.float64)
+        sums = np.empty(nt, dtype=np.float64) if want_sums else None
+        priors = np.empty(nt, dtype=np.float64) if want_sums else None
+        self._check(self.lib.hpf_because(self._h, _ptr(users, C.c_uint32), users.size, _ptr(t_ptr, C.c_uint64), _ptr(t_items, C.c_uint32),
+                                         T & 0xffffffff, _ptr(items, C.c_uint32), _ptr(contrib, C.c_double),
+                                         _ptr(sums, C.c_double) if want_sums else None, _ptr(priors, C.c_double) if want_sums else None))
+        return items, contrib, sums, priors
 
     def factor_top(self, side, topn):
         """the topn heaviest rows of every factor column of one side (hpf_factor_top).  side 0: rows of E[theta] (this

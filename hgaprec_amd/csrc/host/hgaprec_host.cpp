@@ -112,6 +112,16 @@ int Env::parse(int argc, char **argv, bool echo, std::string *bad)
       }
       explain = (uint32_t)t;
     }
+    else if (!strcmp(s, "-because")) {                            // extension: the T rated items that carry every recommended item's score
+      const char *v = next(); char *end = nullptr;
+      const long t = strtol(v, &end, 10);
+      if (!*v || *end || t < 1 || t > 32) {
+        usage_error = "-because needs the number of rated items per recommended item, 1 .. 32";
+        if (bad) *bad = s;
+        return 2;
+      }
+      because = (uint32_t)t;
+    }
     else if (!strcmp(s, "-similar-metric")) {
       const char *v = next();
       if (strcmp(v, "cosine") && strcmp(v, "dot")) {
@@ -187,6 +197,11 @@ int Env::parse(int argc, char **argv, bool echo, std::string *bad)
   if (explain && !recommend) {                                    // wherever the two stand on the line
     usage_error = "-explain goes with -recommend N: it explains the recommended items";
     if (bad) *bad = "-explain";
+    return 2;
+  }
+  if (because && !recommend) {
+    usage_error = "-because goes with -recommend N: it traces the recommended items to the user's ratings";
+    if (bad) *bad = "-because";
     return 2;
   }
   return 0;

@@ -89,6 +89,11 @@ struct Env {
   // through hpf_explain, recommend_explain.tsv / .txt beside recommend.tsv.  N outside 1 .. 1024, T outside 1 .. 32, no
   // number, or -explain without -recommend: parse() returns 2 and says why in usage_error
   uint32_t topic_items = 0, topic_users = 0, explain = 0;
+  // extension: -because T goes with -recommend N only (also behind -fold-in, also beside -explain): the T items of the
+  // user's own ratings that contribute most to every recommended item's score through hpf_because,
+  // recommend_because.tsv / .txt beside recommend.tsv.  T outside 1 .. 32, no number, or -because without -recommend:
+  // parse() returns 2 and says why in usage_error
+  uint32_t because = 0;
   std::string usage_error;
   bool score_mode() const {
     return gen_ranking || rmse || msr || eval_all || recommend > 0 || !fold_in.empty() || !fold_in_items.empty() || similar_items > 0 || similar_users > 0 ||

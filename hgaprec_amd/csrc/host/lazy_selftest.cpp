@@ -169,6 +169,7 @@ struct Sim {
       case FOLD_FUSED: return !cfg.rows[sd] || (!t.due && side_ok(oth, true));
       case FOLD_SWEEPS_RUN: return derived_ok() && (sd != ITEMS || side_ok(oth, false));
       case FOLD_SWEEPS_END: return side_ok(sd, true);
+      case BECAUSE: return !t.due && side_ok(USERS, true) && side_ok(ITEMS, true);
       case N_NEEDS: break;
     }
     return false;
@@ -186,7 +187,7 @@ struct Sim {
       if (need == SCORING || need == SCORES || need == E_IS_SET) CHECK(!(t.e_exists[USERS] && t.e_exists[ITEMS]), "%s seed %u: E exists, need %d refused", name, seed, need);
       return false;
     }
-    if (need == SCORING || need == SCORES || need == FACTORS)
+    if (need == SCORING || need == SCORES || need == FACTORS || need == BECAUSE)
       CHECK(need == FACTORS ? t.e_exists[sd] : (t.e_exists[USERS] && t.e_exists[ITEMS]), "%s seed %u: need %d granted though E does not exist", name, seed, need);
     for (int j = 0; j < todo.n; ++j) run(todo.job[j]);
     CHECK(holds(need, sd, kind), "%s seed %u: after the jobs of need %d (side %d, kind %d) not everything it named is current", name, seed, need, sd, kind);
@@ -287,7 +288,7 @@ struct Sim {
 static void sequences(unsigned n_seeds, unsigned long *n_events)
 {
   static const int standalone[] = {FLAGS, SWEEP_VECTORS, BIAS_RATE, STATE_E, STATE_ELOG, SCORING, SCORES, E_IS_SET, FACTORS, ELBO, ELBO_FROM_W,
-                                   ITERATION, DERIVED, GATHER_PROBE, START_SUMS};
+                                   ITERATION, DERIVED, GATHER_PROBE, START_SUMS, BECAUSE};
   for (unsigned seed = 0; seed < n_seeds; ++seed) {
     std::mt19937 rng(seed * 2654435761u + 12345u);
     auto pick = [&](int n) { return (int)(rng() % (unsigned)n); };

@@ -1,4 +1,4 @@
-// score_modes.cpp -- the reports of `hgaprec` on a saved model: -rmse / -msr / -eval-all / -recommend [-explain] /
+// score_modes.cpp -- the reports of `hgaprec` on a saved model: -rmse / -msr / -eval-all / -recommend [-explain] [-because] /
 // -similar-items / -similar-users / -topic-items / -topic-users / -fold-in / -fold-in-items (and -gen-ranking, which is the training run's own ranking on the loaded state).  Each
 // reads the data like a training run, loads the factor files a run has written (from the current directory like the
 // reference, or from -model-dir DIR), writes ONE report and returns.  One GPU; nothing of the training loop is seen here.
@@ -56,6 +56,33 @@ struct ScoreModes : Cli {
     side(false);
     side(true);
     env.lerr("loaded the model from %s", env.model_dir.empty() ? "." : env.model_dir.c_str());
+  }
+
+  // -because T: hpf_because reads Elog beside E, and the E files do not give it.  Both sides' shape and rate files through
+  // the strict readers -- htheta / hbeta or theta / beta, with -bias thetabias / betabias --, Elog = psi(shape) - log(rate)
+  // (gamma_expectations) into the handle's *_ELOG.  E stays what load_model has put: the lists are those of a run without
+  // the flag.  Only a run with the flag reads these files.
+  void load_model_elog() {
+    std::string err;
+    for (int user_side = 0; user_side < 2; ++user_side) {
+      const uint32_t rows = user_side ? n : m;
+      const std::vector<uint32_t> &ids = user_side ? rt.seq2user : rt.seq2item;
+      const std::string base = env.hier ? (user_side ? "htheta" : "hbeta") : (user_side ? "theta" : "beta");
+      std::vector<double> E, L((size_t)rows * k), rate;
+      load(base + "_shape.tsv", E, rows, k, &ids);
+      const std::string rate_path = env.hier ? load(base + "_rate.tsv", rate, rows, k, &ids) : load(base + "_rate.tsv", rate, k, 1, nullptr);
+      if (gamma_expectations(E.data(), L.data(), rate.data(), rows, k, !env.hier, rate_path, &err)) model_die(err);
+      put(user_side ? HPF_THETA_ELOG : HPF_BETA_ELOG, L);
+      if (env.bias) {
+        const std::string bias = user_side ? "thetabias" : "betabias";
+        L.resize(rows);
+        load(bias + "_shape.tsv", E, rows, 1, &ids);
+        const std::string bp = load(bias + "_rate.tsv", rate, rows, 1, &ids);
+        if (gamma_expectations(E.data(), L.data(), rate.data(), rows, 1, false, bp, &err)) model_die(err);
+        put(user_side ? HPF_UBIAS_ELOG : HPF_IBIAS_ELOG, L);
+      }
+    }
+    env.lerr("-because: Elog of both sides formed from the shape and rate files");
   }
 
   // HGAPRec::compute_rmse (hgaprec.cc:1579-1604).  DEVIATION: the reference's -rmse never loads the model (main.cc:254-257
@@ -175,13 +202,17 @@ struct ScoreModes : Cli {
   // item id, factor, contribution (%.8f), pairs in <stem>.tsv's order, each pair's T largest terms best first; with -bias
   // the factors K and K + 1 are the user and the item bias.  <stem>_explain.txt: pairs, lines, T.  <stem>.tsv is written
   // by the same calls as without the flag.
+  // -because T (extension): the same pairs, grouped by user as they are, go to hpf_because; <stem>_because.tsv: user id,
+  // item id, rated item id, contribution (%.8f), pairs in <stem>.tsv's order, each pair's T rated items best first, the
+  // padding of a history shorter than T never printed.  <stem>_because.txt: pairs, lines, T.
   unsigned long long recommend_lists(const Ratings &given, const HeldOut *mask, const std::string &stem) {
-    const uint32_t N = env.recommend, T = env.explain;
-    const std::string rpath = env.file_str(stem + ".tsv"), epath = env.file_str(stem + "_explain.tsv");
-    FILE *f = open_or_die(rpath, "w"), *ef = T ? open_or_die(epath, "w") : nullptr;
-    MaskLists ml; std::vector<uint32_t> items, eu, ei, fac; std::vector<double> scores, con;
+    const uint32_t N = env.recommend, T = env.explain, TB = env.because;
+    const std::string rpath = env.file_str(stem + ".tsv"), epath = env.file_str(stem + "_explain.tsv"), bpath = env.file_str(stem + "_because.tsv");
+    FILE *f = open_or_die(rpath, "w"), *ef = T ? open_or_die(epath, "w") : nullptr, *bf = TB ? open_or_die(bpath, "w") : nullptr;
+    MaskLists ml; std::vector<uint32_t> items, eu, ei, fac, rated; std::vector<double> scores, con;
+    std::vector<uint64_t> tptr;
     const HeldOut none;
-    unsigned long long lines = 0, epairs = 0, elines = 0;
+    unsigned long long lines = 0, epairs = 0, elines = 0, bpairs = 0, blines = 0;
     const std::function<bool(uint32_t, uint32_t)> keep = [&](uint32_t u, uint32_t it) { return given.r(u, it) == 0; };
     for_chunks(given.n, [&](size_t u0, size_t u1) {
       ml.fill(mask ? *mask : none, nullptr, 0, (uint32_t)u0, (uint32_t)u1);
@@ -191,11 +222,23 @@ struct ScoreModes : Cli {
       if (rc) die("hpf_recommend", rc);
       lines += write_topn(f, ml.users.data(), ml.users.size(), items.data(), scores.data(), N, m, given.seq2user.data(),
                           rt.seq2item.data(), keep);
-      if (!ef) return;
-      eu.clear(); ei.clear();
-      for (size_t b = 0; b < ml.users.size(); ++b)
+      if (!ef && !bf) return;
+      eu.clear(); ei.clear(); tptr.assign(1, 0);
+      for (size_t b = 0; b < ml.users.size(); ++b) {
         for (uint32_t j = 0; j < m && j < N; ++j)                 // the entries write_topn has written
           if (keep(ml.users[b], items[b * N + j])) { eu.push_back(ml.users[b]); ei.push_back(items[b * N + j]); }
+        tptr.push_back(ei.size());
+      }
+      if (bf) {
+        rated.resize(eu.size() * (size_t)TB); con.resize(eu.size() * (size_t)TB);
+        rc = hpf_because(h, ml.users.data(), (uint32_t)ml.users.size(), tptr.data(), ei.data(), TB, rated.data(), con.data(), nullptr, nullptr);
+        if (rc) die("hpf_because", rc);
+        for (size_t p = 0; p < eu.size(); ++p)
+          for (uint32_t r = 0; r < TB && rated[p * TB + r] != 0xffffffffu; ++r, ++blines)
+            fprintf(bf, "%d\t%d\t%d\t%.8f\n", given.seq2user[eu[p]], rt.seq2item[ei[p]], rt.seq2item[rated[p * TB + r]], con[p * TB + r]);
+        bpairs += eu.size();
+      }
+      if (!ef) return;
       fac.resize(eu.size() * (size_t)T); con.resize(eu.size() * (size_t)T);
       rc = hpf_explain(h, eu.data(), ei.data(), eu.size(), T, fac.data(), con.data());
       if (rc) die("hpf_explain", rc);
@@ -211,9 +254,15 @@ struct ScoreModes : Cli {
       write_line(env.file_str(stem + "_explain.txt"), "%llu\t%llu\t%u\n", epairs, elines, T);
       env.lerr("-explain: %llu pairs, %llu lines in %s_explain.tsv", epairs, elines, stem.c_str() + 1);
     }
+    if (bf) {
+      close_or_die(bf, bpath);
+      write_line(env.file_str(stem + "_because.txt"), "%llu\t%llu\t%u\n", bpairs, blines, TB);
+      env.lerr("-because: %llu pairs, %llu lines in %s_because.tsv", bpairs, blines, stem.c_str() + 1);
+    }
     return lines;
   }
   void recommend_report() {
+    if (env.because) load_model_elog();
     const unsigned long long lines = recommend_lists(rt, &rt.validation, "/recommend");
     env.lerr("-recommend: %u users, %llu lines in recommend.tsv", n, lines);
   }
@@ -275,7 +324,7 @@ struct ScoreModes : Cli {
   // user).  Output: the user-side files of save_model under the prefix foldin_, through the same writers; foldin.txt
   // (users, nonzeros, lines skipped for an unknown item, T, X, iterations min / mean / max); with -recommend N also
   // foldin_recommend.tsv / .txt, recommend_report's lines for the new users with their given ratings masked (and with -explain T
-  // foldin_recommend_explain.tsv / .txt).
+  // foldin_recommend_explain.tsv / .txt, with -because T foldin_recommend_because.tsv / .txt: the second handle holds all the call reads).
   //
   // -fold-in-items FILE (extension) is the mirror, for a catalogue that grows: the ITEMS of FILE, which need not be in -dir,
   // rated by users of -dir (Ratings::read_fold_in_items).  The USER side comes from -model-dir as shape and rate

@@ -385,6 +385,17 @@ bool launch_explain(int R, const ExplainArgs &a, uint32_t blocks, hipStream_t st
     } else return false;
   });
 }
+// because_shape_kernel / because_kernel: R columns per lane (hpf_plan::because_plan), four waves per workgroup
+bool launch_because(int R, bool pairs, const BecauseArgs &a, uint32_t blocks, hipStream_t st)
+{
+  return pick(R, Counts(), [&](auto r) {
+    if constexpr (hpf_plan::has_because(PICKED(r))) {
+      if (pairs) hipLaunchKernelGGL((because_kernel<PICKED(r)>), dim3(blocks), dim3(64 * hpf_plan::BECAUSE_WAVES), 0, st, a);
+      else hipLaunchKernelGGL((because_shape_kernel<PICKED(r)>), dim3(blocks), dim3(64 * hpf_plan::BECAUSE_WAVES), 0, st, a);
+      return true;
+    } else return false;
+  });
+}
 int check_launch(hpf_handle *h, const char *what);
 // the fused rank kernels, by the chunks of A a column count keeps in registers (hpf_plan::rank_chunks); launch(nch) names
 // the kernel template: loo_rank_kernel<nch>, rank_queries_kernel<nch> or topn_sweep_kernel<nch>.  Fails where the column
@@ -2972,6 +2983,64 @@ int hpf_explain(hpf_handle *h, const uint32_t *u, const uint32_t *i, size_t cnt,
   if (!launch_explain((int)ep.R, a, ep.grid(cnt), h->stream)) { h->err = "explain_kernel: no instance for this column count"; return HPF_ERR_UNSUPPORTED; }
   if ((rc = check_launch(h, "explain_kernel"))) return rc;
   return copy_back(h, {{out_factor, a.out_factor, cnt * T * 4}, {out_contrib, a.out_contrib, cnt * T * 8}});
+}
+
+// Which of the user's own ratings carry a score (because_shape_kernel, because_kernel): the argument checks first -- they
+// depend on nothing but the handle's sizes --, then E and Elog of both sides through the one prologue.  The gathered copy
+// of the item side, D and the underflow word are temporaries of the call: the handle's state and flags are only read.
+static_assert(HPF_BECAUSE_MAX == hpf_plan::BECAUSE_MAX && HPF_BECAUSE_MAX <= 64, "a lane of the wave per returned entry");
+int hpf_because(hpf_handle *h, const uint32_t *users, uint32_t n_sel, const uint64_t *t_ptr, const uint32_t *t_items, uint32_t T,
+                uint32_t *out_item, double *out_contrib, double *out_sum, double *out_prior)
+{
+  if (!h) return HPF_ERR_INVALID;
+  if (T < 1 || T > HPF_BECAUSE_MAX) { h->err = "hpf_because: T is 1 .. 32"; return HPF_ERR_INVALID; }
+  if (!n_sel) return HPF_OK;
+  if (!users || !t_ptr) { h->err = "hpf_because: null pointer"; return HPF_ERR_INVALID; }
+  if (t_ptr[0] != 0) { h->err = "hpf_because: t_ptr[0] must be 0"; return HPF_ERR_INVALID; }
+  for (uint32_t b = 0; b < n_sel; ++b) {
+    if (t_ptr[b + 1] < t_ptr[b]) { h->err = "hpf_because: t_ptr decreases"; return HPF_ERR_INVALID; }
+    if (users[b] >= h->u.rows) { h->err = "hpf_because: user index out of range"; return HPF_ERR_INVALID; }
+  }
+  const uint64_t nt = t_ptr[n_sel];
+  if (nt && (!t_items || !out_item || !out_contrib)) { h->err = "hpf_because: null pointer"; return HPF_ERR_INVALID; }
+  for (uint64_t q = 0; q < nt; ++q)
+    if (t_items[q] >= h->it.rows) { h->err = "hpf_because: item index out of range"; return HPF_ERR_INVALID; }
+  if (!nt) return HPF_OK;
+  if (!h->have_csr) { h->err = "hpf_upload_csr has not been called"; return HPF_ERR_STATE; }
+  if (h->phase != 0) { h->err = "hpf_because: call between iterations"; return HPF_ERR_STATE; }
+  int rc;
+  if ((rc = ready(h, hpf_lazy::BECAUSE))) return rc;
+  const hpf_plan::BecausePlan bp = hpf_plan::because_plan(h->K, h->cfg.bias != 0);
+  if (!bp.ok || bp.ld < h->K + (h->cfg.bias ? 2u : 0u)) { h->err = "because_kernel: no instance for this column count"; return HPF_ERR_UNSUPPORTED; }
+  const uint32_t m = h->it.rows, ld = h->ld, ldf = bp.ld;
+  std::vector<uint32_t> t_sel(nt);
+  for (uint32_t b = 0; b < n_sel; ++b) std::fill(t_sel.begin() + t_ptr[b], t_sel.begin() + t_ptr[b + 1], b);
+  Scratch sc(h);
+  double *Wb = nullptr; uint32_t *d_users = nullptr, *d_sel = nullptr, *d_items = nullptr, *d_flag = nullptr;
+  BecauseArgs a;
+  if ((rc = sc.alloc(&Wb, (size_t)m * ldf)) || (rc = sc.alloc(&a.D, (size_t)n_sel * ldf)) || (rc = sc.alloc(&d_users, n_sel, users)) ||
+      (rc = sc.alloc(&d_sel, nt, t_sel.data())) || (rc = sc.alloc(&d_items, nt, t_items)) || (rc = sc.alloc(&d_flag, 1)) ||
+      (rc = sc.alloc(&a.out_item, nt * T)) || (rc = sc.alloc(&a.out_contrib, nt * T)) || (rc = sc.alloc(&a.out_sum, nt)) || (rc = sc.alloc(&a.out_prior, nt))) return rc;
+  hipLaunchKernelGGL(fold_derive_w_kernel, dim3(std::max<uint32_t>(1, std::min<uint32_t>((m + 3) / 4, 4096))), dim3(256), 0, h->stream, h->it.L, Wb, m, ld, ldf,
+                     h->K, h->it.bias_col, h->it.junk_col);
+  if ((rc = check_launch(h, "hpf_because set-up"))) return rc;
+  a.rowptr = h->rowptr_dev; a.idx = h->u.idx; a.val = h->u.val;
+  a.users = d_users; a.t_sel = d_sel; a.t_item = d_items; a.Wb = Wb;
+  a.Lt = h->u.L; a.Et = h->u.E; a.Eb = h->it.E;
+  a.flags = d_flag; a.nt = nt; a.n_sel = n_sel; a.ld = ld; a.ldf = ldf; a.K = h->K; a.T = T; a.run = hpf_plan::BECAUSE_RUN;
+  a.ubias_col = h->cfg.bias ? h->u.bias_col : -1; a.ujunk_col = h->cfg.bias ? h->u.junk_col : -1;
+  a.s_prior = h->cfg.s_prior;
+  if (!launch_because((int)bp.R, false, a, bp.grid_users(n_sel), h->stream)) { h->err = "because_shape_kernel: no instance for this column count"; return HPF_ERR_UNSUPPORTED; }
+  if ((rc = check_launch(h, "because_shape_kernel"))) return rc;
+  if (!launch_because((int)bp.R, true, a, bp.grid_pairs(nt), h->stream)) { h->err = "because_kernel: no instance for this column count"; return HPF_ERR_UNSUPPORTED; }
+  if ((rc = check_launch(h, "because_kernel"))) return rc;
+  uint32_t fl = 0;
+  if ((rc = copy_back(h, {{&fl, d_flag, 4}}))) return rc;
+  if (fl & 1u) {                                     // before any output reaches the caller
+    h->err = "hpf_because: a softmax denominator underflowed to zero (Elog spread > ~700): the state is not a valid HPF state";
+    return HPF_ERR_STATE;
+  }
+  return copy_back(h, {{out_item, a.out_item, nt * T * 4}, {out_contrib, a.out_contrib, nt * T * 8}, {out_sum, a.out_sum, nt * 8}, {out_prior, a.out_prior, nt * 8}});
 }
 
 // The topn heaviest rows of every factor column of one side: a batch of columns transposed into a temporary of this call

@@ -3277,6 +3277,204 @@ __global__ __launch_bounds__(256) void transpose_cols_kernel(const double *E, do
   }
 }
 
+// ---------------------------------------------------------------------
+// Because you rated (hpf_because; -because).  A user's shape is the prior plus a sum over the user's
+// ratings of yy * phi, so E[theta_uc] and with it every score splits over the user's history:
+//   phi_uic = own_c x_ic / ssum_i ,  ssum_i = sum_c own_c x_ic        own = exp(Elog theta_u - row max), x_i = Wb[i] (the
+//                                                                     fold-in's W forms; K + 2 entries with bias)
+//   D_uc    = s_prior + sum_i yy_i phi_uic                            because_shape_kernel, the sum in CSR order
+//   g_c     = E[theta_uc] E[beta_jc] / D_uc  (c < K),  g_K = E[ubias_u] / D_uK
+//   c(i->j) = yy_i sum_c phi_uic g_c = yy_i / ssum_i * sum_c x_ic (own_c g_c)                    because_kernel
+//   prior(j) = s_prior sum_c g_c
+// Reads E and Elog of both sides and the CSR; writes temporaries and outputs of the call only -- the underflow of a
+// softmax denominator goes to the CALL's flag word, not the handle's.
+// ---------------------------------------------------------------------
+struct BecauseArgs {
+  const int64_t  *rowptr;      // [n + 1] CSR of the users
+  const uint32_t *idx;         // item of each nonzero
+  const uint8_t  *val;         // rating (NULL: all ones)
+  const uint32_t *users;       // [n_sel] selected users
+  const uint32_t *t_sel;       // [nt] which selected user a target pair belongs to
+  const uint32_t *t_item;      // [nt] the target item
+  const double   *Wb;          // [n_items x ldf] exp(Elog - row max) of the item side (fold_derive_w_kernel)
+  const double   *Lt, *Et, *Eb;// [n x ld], [n x ld], [m x ld]
+  double         *D;           // [n_sel x ldf] because_shape_kernel's output
+  uint32_t       *out_item;    // [nt x T]
+  double         *out_contrib; // [nt x T]
+  double         *out_sum, *out_prior;    // [nt]
+  uint32_t       *flags;       // bit 0: a softmax denominator underflowed
+  uint64_t        nt;
+  uint32_t        n_sel, ld, ldf, K, T, run;      // run: consecutive pairs a wave takes per trip (hpf_plan::BECAUSE_RUN)
+  int32_t         ubias_col, ujunk_col;           // of the user side's rows: K and K + 1 with -bias, -1 without
+  double          s_prior;
+};
+
+// the W form of user u's row, lane l its columns l + 64 t: the same bits in both kernels
+template <int R>
+__device__ __forceinline__ void because_own(const BecauseArgs &a, uint32_t lane, uint32_t u, double (&own)[R])
+{
+  const double *lt = a.Lt + (size_t)u * a.ld;
+  double l[R], m = -1.0e308;
+#pragma unroll
+  for (int t = 0; t < R; ++t) {
+    const uint32_t c = lane + 64u * t;
+    const bool live = c < a.K || (int32_t)c == a.ubias_col || (int32_t)c == a.ujunk_col;
+    l[t] = live ? lt[c] : -1.0e308;
+    m = fmax(m, l[t]);
+  }
+  m = group_max<64>(m);
+#pragma unroll
+  for (int t = 0; t < R; ++t) own[t] = (l[t] > -1.0e308) ? exp(l[t] - m) : 0.0;
+}
+
+// sum_c x_c w_c in every lane, the SAME bits in every lane: fold_dot's chains, with the lane's own sum rounded before it
+// meets the other lanes'.  (With one column per lane the compiler otherwise fuses the lane's product into the first
+// cross-lane addition -- fma(own, x, partner's product) on one lane, the mirror image on the partner -- and the two disagree
+// in the last bit; a contribution is handed out by one lane and summed by another.)
+template <int R>
+__device__ __forceinline__ double because_dot(const double (&x)[R], const double (&w)[R])
+{
+#pragma clang fp contract(off)
+  double s[2] = {0.0, 0.0};
+#pragma unroll
+  for (int e = 0; e < R; ++e) s[e & 1] = (e < 2) ? w[e] * x[e] : fma(w[e], x[e], s[e & 1]);
+  const double v = (R > 1) ? s[0] + s[1] : s[0];
+  return group_sum<64>(v);
+}
+
+// One walk over the `len` nonzeros of the row that starts at `start`, in CSR order: visit(x, yy, item) per nonzero with the
+// item's gathered row, the factor yy = (y > 1 ? y : 1) of the phi pass (hgaprec.cc:1355-1356) and the item.  A block of 64
+// indices and ratings sits one per lane; two rows are in flight, visited in order.
+template <int R, typename Visit>
+__device__ __forceinline__ void because_walk(const BecauseArgs &a, uint32_t lane, int64_t start, uint32_t len, Visit &&visit)
+{
+  const uint32_t LDF = a.ldf;
+  for (uint32_t base = 0; base < len; base += 64u) {
+    const uint32_t cnt = (len - base < 64u) ? len - base : 64u;
+    const uint32_t ci = (lane < cnt) ? a.idx[start + base + lane] : 0u;
+    float cy = 1.0f;
+    if (a.val && lane < cnt) { const uint32_t y = a.val[start + base + lane]; cy = (y > 1u) ? (float)y : 1.0f; }
+    auto item = [&](uint32_t j) { return (uint32_t)__builtin_amdgcn_readlane((int)ci, (int)j); };
+    auto rating = [&](uint32_t j) { return (double)__int_as_float(__builtin_amdgcn_readlane(__float_as_int(cy), (int)j)); };
+    auto get = [&](double (&x)[R], uint32_t it) {
+      const double *p = a.Wb + (size_t)it * LDF;
+#pragma unroll
+      for (int t = 0; t < R; ++t) { const uint32_t c = lane + 64u * t; x[t] = (c < LDF) ? p[c] : 0.0; }
+    };
+    uint32_t j = 0;
+    double xa[R], xb[R];
+    for (; j + 1 < cnt; j += 2) {
+      const uint32_t ia = item(j), ib = item(j + 1);
+      get(xa, ia);
+      get(xb, ib);
+      visit(xa, rating(j), ia);
+      visit(xb, rating(j + 1), ib);
+    }
+    if (j < cnt) { const uint32_t ia = item(j); get(xa, ia); visit(xa, rating(j), ia); }
+  }
+}
+
+// D of every selected user: a wave per user, one walk
+template <int R>
+__global__ __launch_bounds__(256) void because_shape_kernel(BecauseArgs a)
+{
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t w0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6));
+  const uint32_t nw = (gridDim.x * blockDim.x) >> 6;
+  bool underflow = false;
+  for (uint32_t b = w0; b < a.n_sel; b += nw) {
+    const uint32_t u = (uint32_t)__builtin_amdgcn_readfirstlane((int)a.users[b]);
+    const int64_t start = a.rowptr[u];
+    const uint32_t len = (uint32_t)(a.rowptr[u + 1] - start);
+    double own[R], acc[R];
+    because_own<R>(a, lane, u, own);
+#pragma unroll
+    for (int t = 0; t < R; ++t) acc[t] = 0.0;
+    because_walk<R>(a, lane, start, len, [&](const double (&x)[R], double yy, uint32_t) {
+      fold_add<R>(x, acc, because_dot<R>(x, own), yy, underflow);
+    });
+#pragma unroll
+    for (int t = 0; t < R; ++t) {
+      const uint32_t c = lane + 64u * t;
+      if (c < a.ldf) a.D[(size_t)b * a.ldf + c] = (c < a.K || (int32_t)c == a.ubias_col) ? a.s_prior + own[t] * acc[t] : 0.0;
+    }
+  }
+  if (__any(underflow) && lane == 0) atomicOr(a.flags, 1u);
+}
+
+// A wave per target pair (a run of consecutive pairs per trip: the user's row is set up again only when the user changes).
+// own_c g_c stays in registers; per history item one wave-wide sum for the softmax denominator and one for the
+// contribution.  The T best so far live in lanes 0 .. T - 1, sorted in ranks_before's order with the empty places
+// (key 0, item 0xffffffff) last: the lanes that rank before a new entry are a prefix, so a ballot counts the insertion
+// place and the lanes behind it take their left neighbour's entry.  out_sum adds every contribution in CSR order.
+template <int R>
+__global__ __launch_bounds__(256) void because_kernel(BecauseArgs a)
+{
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint64_t w0 = (uint64_t)__builtin_amdgcn_readfirstlane((int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6));
+  const uint64_t nw = ((uint64_t)gridDim.x * blockDim.x) >> 6;
+  const uint32_t K = a.K, T = a.T;
+  bool underflow = false;
+  for (uint64_t base = w0 * a.run; base < a.nt; base += nw * a.run) {
+    double own[R], th[R], dd[R];
+    uint32_t cur_sel = 0xffffffffu, len = 0;
+    int64_t start = 0;
+    for (uint32_t r = 0; r < a.run && base + r < a.nt; ++r) {
+      const uint64_t q = base + r;
+      const uint32_t sel = (uint32_t)__builtin_amdgcn_readfirstlane((int)a.t_sel[q]), tj = (uint32_t)__builtin_amdgcn_readfirstlane((int)a.t_item[q]);
+      if (sel != cur_sel) {                                // wave-uniform
+        const uint32_t u = (uint32_t)__builtin_amdgcn_readfirstlane((int)a.users[sel]);
+        start = a.rowptr[u];
+        len = (uint32_t)(a.rowptr[u + 1] - start);
+        because_own<R>(a, lane, u, own);
+#pragma unroll
+        for (int t = 0; t < R; ++t) {
+          const uint32_t c = lane + 64u * t;
+          const bool shaped = c < K || (int32_t)c == a.ubias_col;
+          th[t] = shaped ? a.Et[(size_t)u * a.ld + c] : 0.0;
+          dd[t] = shaped ? a.D[(size_t)sel * a.ldf + c] : 1.0;
+        }
+        cur_sel = sel;
+      }
+      double og[R], gs = 0.0;
+#pragma unroll
+      for (int t = 0; t < R; ++t) {
+        const uint32_t c = lane + 64u * t;
+        const double g = (c < K) ? th[t] * a.Eb[(size_t)tj * a.ld + c] / dd[t] : (int32_t)c == a.ubias_col ? th[t] / dd[t] : 0.0;
+        gs += g;
+        og[t] = own[t] * g;
+      }
+      const double prior = a.s_prior * group_sum<64>(gs);
+      unsigned long long tk = 0ull;
+      uint32_t ti = 0xffffffffu;
+      double sum = 0.0;
+      because_walk<R>(a, lane, start, len, [&](const double (&x)[R], double yy, uint32_t it) {
+        // the contribution handed out is a rounded double and out_sum the sum of THOSE doubles: no multiply fused into the add
+#pragma clang fp contract(off)
+        const double ssum = because_dot<R>(x, own), num = because_dot<R>(x, og);
+        const bool ok = ssum > 0.0;
+        underflow |= !ok;
+        const double contrib = ok ? num * (yy * fast_rcp(ssum)) : 0.0;
+        sum += contrib;
+        const unsigned long long key = score_key(contrib);
+        const uint32_t pos = (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(lane < T && ranks_before(tk, ti, key, it)));
+        if (pos < T) {                                     // wave-uniform
+          const unsigned long long pk = __shfl_up(tk, 1, 64);
+          const uint32_t pi = __shfl_up(ti, 1, 64);
+          if (lane == pos) { tk = key; ti = it; }
+          else if (lane > pos) { tk = pk; ti = pi; }
+        }
+      });
+      if (lane < T) {
+        a.out_item[q * T + lane] = ti;
+        a.out_contrib[q * T + lane] = __longlong_as_double((long long)tk);
+      }
+      if (lane == 0) { a.out_sum[q] = sum; a.out_prior[q] = prior; }
+    }
+  }
+  if (__any(underflow) && lane == 0) atomicOr(a.flags, 1u);
+}
+
 // materialise the per-element rate matrix for export (htheta_rate.tsv):
 // rate[row,k] = prior_used[row] + colsum[k]   (gpbase.hh:163-173,218-223)
 __global__ void build_rate_kernel(const double *prior_used, const double *colsum,

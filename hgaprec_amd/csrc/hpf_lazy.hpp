@@ -68,6 +68,7 @@ enum Need : uint8_t {
   FOLD_SWEEPS,     // (side) the same call through the training kernels: this side is overwritten ...
   FOLD_SWEEPS_RUN, // (side) ... and, once it holds the prior, W, the start sums and E of the other side
   FOLD_SWEEPS_END, // (side) S, E and Elog of the folded-in side from its last sweep
+  BECAUSE,         // E and Elog of both sides, checked: hpf_because evaluates phi per pair from them
   N_NEEDS
 };
 
@@ -241,6 +242,13 @@ class State {
       // product of a user sweep, so an item call takes them from E into a temporary
       case FOLD_SWEEPS_RUN: p.derive(oth); if (sd == ITEMS) p.es(oth); break;
       case FOLD_SWEEPS_END: p.elog(sd); break;
+      case BECAUSE:
+        if (fresh && !(side[USERS].have_E && side[USERS].have_L && side[ITEMS].have_E && side[ITEMS].have_L))
+          return p.refuse("E and Elog state not set: hand in THETA_E, THETA_ELOG, BETA_E and BETA_ELOG, or iterate");
+        if (fresh && cfg.bias && !(side[USERS].have_bias_E && side[USERS].have_bias_L && side[ITEMS].have_bias_E && side[ITEMS].have_bias_L))
+          return p.refuse("E and Elog state not set: hand in E and ELOG of UBIAS and IBIAS (-bias), or iterate");
+        p.report(); p.elog(USERS); p.elog(ITEMS);
+        break;
       case N_NEEDS: break;
     }
     if (p.overflow) return p.refuse("internal: too many deferred jobs");

@@ -332,6 +332,35 @@ inline uint32_t factor_top_batch(uint32_t rows, uint32_t K, long long knob)
   return (uint32_t)std::min<uint64_t>(b, std::max<uint32_t>(K, 1));
 }
 
+// ---- because you rated (hpf_because) ----------------------------------------------------------------
+// because_shape_kernel<R>: a wave per selected user; because_kernel<R>: a wave per target pair, BECAUSE_RUN consecutive
+// pairs per trip (the targets of one user are consecutive: its row is set up once per run).  Lane l holds the columns
+// l + 64 t, t < R.  The item rows are the fold-in's gathered copy (fold_plan's stride: the live columns K + 2 * bias padded
+// to whole 128-byte lines).  Workgroups of BECAUSE_WAVES waves, at most BECAUSE_BLOCKS_MAX of them, which then stride.
+// hgaprec_amd/capi.py mirrors the arithmetic (because_plan).
+constexpr uint32_t BECAUSE_MAX = 32;      // HPF_BECAUSE_MAX of hpf.h (pinned there by hpf_capi.hip): a lane per returned entry
+constexpr uint32_t BECAUSE_WAVES = 4, BECAUSE_RUN = 4, BECAUSE_BLOCKS_MAX = 4096;
+constexpr bool has_because(int R) { return R >= 1 && R <= 16; }
+struct BecausePlan {
+  uint32_t ld = 0, R = 0;               // row stride of the gathered copy and of D, columns; columns per lane
+  bool ok = false;                      // false: no kernel instance for this column count
+  static constexpr uint32_t pairs_per_block() { return BECAUSE_WAVES * BECAUSE_RUN; }
+  // workgroups for n selected users: a wave per user
+  uint32_t grid_users(uint32_t n) const { return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(((uint64_t)n + BECAUSE_WAVES - 1) / BECAUSE_WAVES, BECAUSE_BLOCKS_MAX)); }
+  // workgroups for nt target pairs: a run per wave
+  uint32_t grid_pairs(uint64_t nt) const { return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((nt + pairs_per_block() - 1) / pairs_per_block(), BECAUSE_BLOCKS_MAX)); }
+};
+inline BecausePlan because_plan(uint32_t K, bool bias)
+{
+  BecausePlan p;
+  const FoldPlan f = fold_plan(K, bias);
+  if (f.ld == 0) return p;
+  p.ld = f.ld;
+  p.R = f.R;
+  p.ok = has_because((int)p.R);
+  return p;
+}
+
 // ---- the tiled phi pass: what is tiled, and where its segments run --------------------------------
 // Policy of one side, decided before anything is allocated.  The gathered matrix (rows_oth rows of row_bytes) is cut into
 // tiles of T consecutive rows; owner rows with at least light_below nonzeros are heavy (their nonzeros are regrouped by

@@ -458,6 +458,45 @@ int  hpf_explain(hpf_handle *h, const uint32_t *u, const uint32_t *i, size_t cnt
 int  hpf_factor_top(hpf_handle *h, int side, uint32_t topn,
                     uint32_t *out_ids /* K x topn */, double *out_vals /* K x topn */);
 
+/* (an extension; the reference has no counterpart.)  "Because you rated": which of the user's OWN ratings carry a score.
+ * All quantities are those hpf_get_state would export at the moment of the call.  For a local user u, hist(u) is the
+ * nonzeros of u's CSR row in CSR order, each with the factor yy of the phi pass (y if y > 1, otherwise 1; 1 throughout when
+ * the ratings were uploaded with val = NULL).  For a history item i
+ *   phi_uic = exp(Elog theta_uc + Elog beta_ic) / sum_c' exp(...)
+ * over the K factor entries and, with bias, the two bias entries of the reference's K + 2 layout (hgaprec.cc:1347-1353):
+ * entry K is Elog ubias_u, entry K + 1 is Elog ibias_i and takes part in the denominator only.  With
+ *   D_uc = s_prior + sum_{i in hist(u)} yy_i phi_uic      (c < K; with bias also c = K) -- the shape the user half of one
+ *                                                          iteration would give row u from the current Elog --
+ *   g_c  = E[theta_uc] E[beta_jc] / D_uc  (c < K),  g_K = E[ubias_u] / D_uK   for a target item j,
+ * history item i contributes c(i -> j) = yy_i sum_c phi_uic g_c to the score of (u, j); prior(j) = s_prior sum_c g_c is the
+ * prior's share and E[ibias_j] (with bias) belongs to nobody.  In exact arithmetic
+ *   sum_i c(i -> j) + prior(j) + E[ibias_j] = sum_k E[theta_uk] E[beta_jk] + E[ubias_u] + E[ibias_j],
+ * the score hpf_predict returns.  The definition reads E and Elog only -- no rate -- so it holds with and without hier.
+ * Targets are a CSR over the selected users like the queries of hpf_rank_queries: selected user b asks for the items
+ * t_items[t_ptr[b] .. t_ptr[b+1]); nt = t_ptr[n_sel].  Row q of out_item / out_contrib (q indexes t_items) holds the T
+ * history items of the target's user with the largest c(i -> j), in the ranking calls' one order taken on the bit pattern:
+ * the larger contribution first, ascending item among equal ones; entries beyond the history's length are
+ * (0xffffffff, 0.0).  out_sum[q] (may be NULL) is the sum over the WHOLE history, added in CSR order; out_prior[q] (may be
+ * NULL) is prior(j).  A target may be in the user's own history, a user may be selected twice, a target asked twice: equal
+ * requests give equal rows, and a pair's result depends on nothing but the user's history, the state and the target.  Two
+ * history items whose item rows and ratings are bit-identical get bit-identical contributions.
+ * T outside 1 .. HPF_BECAUSE_MAX, a user or an item out of range, t_ptr[0] != 0, a decreasing t_ptr or a null pointer with
+ * work to do is HPF_ERR_INVALID before anything is launched; n_sel = 0 or nt = 0 is HPF_OK; no CSR, or no E or Elog on
+ * either side (with bias: of either bias), is HPF_ERR_STATE.  A softmax denominator that underflows is HPF_ERR_STATE too;
+ * it is reported by this call alone and the handle stays usable.  Any n_ranks: the local users only, nothing is
+ * exchanged.  Synchronous.  The model state is not written: every hpf_get_state returns the same bits before and after,
+ * and a following hpf_iterate the bits it returns without the call.
+ * A returned contribution and out_prior are within (4 S + H + 64) 2^-53 relative of the exact value, H the history's
+ * length and S the largest Elog spread inside the user's row or a gathered item row.
+ * Two kernels: a wave per selected user writes D, a wave per target pair walks the history again with g in registers and
+ * the T best in its lanes.  Device memory beyond inputs and outputs, freed when the call returns: a plain fp64 copy of
+ * exp(Elog beta - row max) (n_items x the padded column count) and D (n_sel x the same). */
+#define HPF_BECAUSE_MAX 32
+int  hpf_because(hpf_handle *h, const uint32_t *users, uint32_t n_sel,
+                 const uint64_t *t_ptr, const uint32_t *t_items, uint32_t T,
+                 uint32_t *out_item   /* nt x T */, double *out_contrib /* nt x T */,
+                 double *out_sum      /* nt, may be NULL */, double *out_prior /* nt, may be NULL */);
+
 /* replaces: HGAPRec::test() (hgaprec.cc:2257-2346) -- load the item factors, put the user at the prior
  * (set_to_prior + set_to_prior_curr, 2278-2279), run user-side CAVI iterations over the user's ratings with the item
  * side untouched.  The handle's users are the NEW users: their ratings uploaded with hpf_upload_csr[_device] (val = NULL:
