@@ -42,7 +42,7 @@ EXPORTS = [
     "hpf_iteration_times", "hpf_debug_poke_index", "hpf_start_sums", "hpf_host_alloc", "hpf_host_free",
     "hpf_heldout_bind", "hpf_heldout_ll_bound",
     "hpf_predict", "hpf_loo_ranks", "hpf_rank_queries", "hpf_recommend", "hpf_fold_in", "hpf_similar",
-    "hpf_explain", "hpf_factor_top", "hpf_fold_in_items", "hpf_because",
+    "hpf_explain", "hpf_factor_top", "hpf_fold_in_items", "hpf_because", "hpf_audience",
 ]
 
 # hpf_similar: the metrics (hpf_similarity in include/hpf.h) and the largest topn (TOPN_FUSED_MAX: only the fused route exists)
@@ -332,6 +332,8 @@ def load_library(path: os.PathLike | None = None) -> C.CDLL:
         lib.hpf_factor_top.argtypes = [vp, C.c_int, C.c_uint32, u32p, dp]
     if hasattr(lib, "hpf_because"):
         lib.hpf_because.argtypes = [vp, u32p, C.c_uint32, u64p, u32p, C.c_uint32, u32p, dp, dp, dp]
+    if hasattr(lib, "hpf_audience"):
+        lib.hpf_audience.argtypes = [vp, u32p, C.c_uint32, u64p, u32p, C.c_uint32, u32p, dp]
     lib.hpf_comm_unique_id.argtypes = [vp]
     lib.hpf_comm_init.argtypes = [vp, vp]
     lib.hpf_allreduce_exchange.argtypes = [vp]
@@ -671,6 +673,24 @@ class Hpf:
         self._check(self.lib.hpf_recommend(self._h, _ptr(users, C.c_uint32), users.size, pmp, pmi, topn & 0xffffffff,
                                            _ptr(items, C.c_uint32), _ptr(sc, C.c_double)))
         return items, sc
+
+    def audience(self, items, topn=100, mask_ptr=None, mask_users=None):
+        """the topn best LOCAL users of every selected item (hpf_audience): recommend transposed, the scores bit for bit
+        those of scores(); masked are the item's training users (rating > 0) and mask_users, a CSR over the selected items
+        -> (users, scores), each [len(items), topn]; entries beyond n_users are (0xffffffff, 0.0)"""
+        items = np.ascontiguousarray(items, dtype=np.uint32)
+        if items.ndim != 1:
+            raise ValueError("items: a one-dimensional array")
+        mp, mu, pmp, pmu = self._mask(mask_ptr, mask_users)
+        if mp is not None and mp.size != items.size + 1:
+            raise ValueError("mask_ptr must have len(items) + 1 entries")
+        topn = int(topn)
+        shape = (items.size, topn if 0 < topn <= RECOMMEND_FUSED_MAX else 0)
+        users = np.empty(shape, dtype=np.uint32)
+        sc = np.empty(shape, dtype=np.float64)
+        self._check(self.lib.hpf_audience(self._h, _ptr(items, C.c_uint32), items.size, pmp, pmu, topn & 0xffffffff,
+                                          _ptr(users, C.c_uint32), _ptr(sc, C.c_double)))
+        return users, sc
 
     def similar(self, side, ids, topn, metric="cosine"):
         """the topn nearest OTHER rows of one side for every selected row (hpf_similar).  side 0: rows of E[theta] (this

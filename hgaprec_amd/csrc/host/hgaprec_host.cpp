@@ -122,6 +122,16 @@ int Env::parse(int argc, char **argv, bool echo, std::string *bad)
       }
       because = (uint32_t)t;
     }
+    else if (!strcmp(s, "-audience")) {                           // extension: the N best users of every item, from a saved model
+      const char *v = next(); char *end = nullptr;
+      const long na = strtol(v, &end, 10);
+      if (!*v || *end || na < 1 || na > 256) {
+        usage_error = "-audience needs the number of users per item, 1 .. 256";
+        if (bad) *bad = s;
+        return 2;
+      }
+      audience = (uint32_t)na;
+    }
     else if (!strcmp(s, "-similar-metric")) {
       const char *v = next();
       if (strcmp(v, "cosine") && strcmp(v, "dot")) {
@@ -194,7 +204,13 @@ int Env::parse(int argc, char **argv, bool echo, std::string *bad)
     if (bad) *bad = "-fold-in-items";
     return 2;
   }
-  if (explain && !recommend) {                                    // wherever the two stand on the line
+  if (audience && (gen_ranking || rmse || msr || eval_all || recommend || !fold_in.empty() || similar_items || similar_users ||
+                   topic_items || topic_users)) {
+    usage_error = "-audience runs alone or behind -fold-in-items";
+    if (bad) *bad = "-audience";
+    return 2;
+  }
+  if (explain && !recommend && !audience) {                       // wherever the two stand on the line
     usage_error = "-explain goes with -recommend N: it explains the recommended items";
     if (bad) *bad = "-explain";
     return 2;
@@ -1585,6 +1601,18 @@ void MaskLists::fill(const HeldOut &ho, const uint32_t *list, size_t cnt, uint32
   };
   if (!list) for (uint32_t u = lo; u < hi; ++u) add(u);
   else for (size_t j = 0; j < cnt; ++j) if (list[j] >= lo && list[j] < hi) add(list[j]);
+}
+
+void ItemMaskLists::fill(const HeldOut &ho, uint32_t lo, uint32_t hi)
+{
+  const size_t cnt = hi > lo ? hi - lo : 0;
+  items.resize(cnt); ptr.assign(cnt + 1, 0);
+  for (size_t b = 0; b < cnt; ++b) items[b] = lo + (uint32_t)b;
+  for (uint32_t it : ho.i) if (it >= lo && it < hi) ptr[it - lo + 1]++;
+  for (size_t b = 0; b < cnt; ++b) ptr[b + 1] += ptr[b];
+  users.resize(ptr[cnt]);
+  std::vector<uint64_t> at(ptr.begin(), ptr.end() - 1);
+  for (size_t a = 0; a < ho.i.size(); ++a) if (ho.i[a] >= lo && ho.i[a] < hi) users[at[ho.i[a] - lo]++] = ho.u[a];
 }
 
 uint64_t write_topn(FILE *f, const uint32_t *sel, size_t n_sel, const uint32_t *items, const double *scores, uint32_t N, uint32_t real,

@@ -85,19 +85,26 @@ struct Env {
   std::string similar_metric = "cosine";
   // extension: -topic-items N / -topic-users N write the N heaviest items (users) of every factor of a saved model through
   // hpf_factor_top: topic_items.tsv / .txt, topic_users.tsv / .txt.  Score modes too; both may be given in one run.
-  // -explain T goes with -recommend N only (also behind -fold-in): the T largest terms of every recommended item's score
-  // through hpf_explain, recommend_explain.tsv / .txt beside recommend.tsv.  N outside 1 .. 1024, T outside 1 .. 32, no
-  // number, or -explain without -recommend: parse() returns 2 and says why in usage_error
+  // -explain T goes with -recommend N (also behind -fold-in) or with -audience N: the T largest terms of every listed
+  // pair's score through hpf_explain, recommend_explain.tsv / .txt beside recommend.tsv.  N outside 1 .. 1024, T outside
+  // 1 .. 32, no number, or -explain without -recommend and without -audience: parse() returns 2 and says why in usage_error
   uint32_t topic_items = 0, topic_users = 0, explain = 0;
   // extension: -because T goes with -recommend N only (also behind -fold-in, also beside -explain): the T items of the
   // user's own ratings that contribute most to every recommended item's score through hpf_because,
   // recommend_because.tsv / .txt beside recommend.tsv.  T outside 1 .. 32, no number, or -because without -recommend:
   // parse() returns 2 and says why in usage_error
   uint32_t because = 0;
+  // extension: -audience N writes the N best users of EVERY item of a saved model (audience.tsv: item id, user id, score;
+  // audience.txt) through hpf_audience: -recommend transposed, the item's training users with a rating > 0 and its
+  // validation users zeroed.  A score mode that runs alone or behind -fold-in-items FILE (foldin_audience.tsv / .txt: the
+  // audience of the new items); -explain T may go with it (audience_explain.tsv / .txt); -because is not offered: tracing
+  // an audience to histories is another question.  N outside 1 .. 256, no N, or -audience with -fold-in or another score
+  // mode: parse() returns 2 and says why in usage_error
+  uint32_t audience = 0;
   std::string usage_error;
   bool score_mode() const {
     return gen_ranking || rmse || msr || eval_all || recommend > 0 || !fold_in.empty() || !fold_in_items.empty() || similar_items > 0 || similar_users > 0 ||
-           topic_items > 0 || topic_users > 0;
+           topic_items > 0 || topic_users > 0 || audience > 0;
   }
 
   std::string prefix;          // output directory (Env::prefix)
@@ -334,6 +341,14 @@ struct MaskLists {
   std::vector<uint32_t> users, items;
   std::vector<uint64_t> ptr;
   void fill(const HeldOut &ho, const uint32_t *list, size_t cnt, uint32_t lo, uint32_t hi, uint32_t rebase = 0);
+};
+// The transpose of MaskLists::fill, for the calls that select ITEMS (hpf_audience): the held-out users of the items
+// [lo, hi) as (mask_ptr, mask_users) -- items holds lo .. hi - 1, item b's users are users[ptr[b] .. ptr[b + 1]), ascending
+// (the pairs of a HeldOut are in (user, item) order and are visited in that order).  One pass over the pairs per call.
+struct ItemMaskLists {
+  std::vector<uint32_t> items, users;
+  std::vector<uint64_t> ptr;
+  void fill(const HeldOut &ho, uint32_t lo, uint32_t hi);
 };
 // Top-N lists as lines "row id \t entry id \t %.5f" (`digits` decimals: 5 unless given): list b belongs to row sel[b] and has items[b * N + j], scores[b * N + j],
 // j < N, of which the first `real` exist (the rest is padding and never printed); ids through row_ids / item_ids.  Only

@@ -200,6 +200,22 @@ uint64_t hg_mask_lists_get(const MaskLists *ml, int part, const void **p)
   *p = v.data();
   return v.size();
 }
+// ItemMaskLists::fill over the validation (which = 0) or test pairs for the items [lo, hi)
+ItemMaskLists *hg_item_mask_lists_new(const Ratings *r, int which, uint32_t lo, uint32_t hi)
+{
+  ItemMaskLists *ml = new ItemMaskLists();
+  ml->fill(which ? r->test : r->validation, lo, hi);
+  return ml;
+}
+void hg_item_mask_lists_free(ItemMaskLists *ml) { delete ml; }
+// part 0 items (uint32), 1 ptr (uint64), 2 users (uint32): the elements, *p their address
+uint64_t hg_item_mask_lists_get(const ItemMaskLists *ml, int part, const void **p)
+{
+  if (part == 1) { *p = ml->ptr.data(); return ml->ptr.size(); }
+  const std::vector<uint32_t> &v = part ? ml->users : ml->items;
+  *p = v.data();
+  return v.size();
+}
 // write_topn into a new file; given != NULL: only the entries with given->r(row, item) == 0, the rule of recommend.tsv.
 // Returns the lines, -1 when the file cannot be written
 int64_t hg_write_topn(const char *path, const Ratings *given, const uint32_t *sel, uint64_t n_sel, const uint32_t *items,

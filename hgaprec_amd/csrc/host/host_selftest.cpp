@@ -531,6 +531,36 @@ static void test_reports()
           (ml.ptr == std::vector<uint64_t>{0, 2, 4, 4}));
   }
 
+  // the transposed lists (-audience): the validation users of every item, ascending; chunk by chunk == the one-chunk result
+  {
+    std::vector<std::vector<uint32_t>> by_item(m);
+    for (uint32_t u = 0; u < n; ++u) for (uint32_t it : valid[u]) by_item[it].push_back(u);
+    ItemMaskLists one;
+    one.fill(rt.validation, 0, m);
+    CHECK(one.items.size() == m && one.ptr.size() == (size_t)m + 1 && one.ptr[0] == 0 && one.ptr.back() == one.users.size());
+    for (uint32_t it = 0; it < m && it < one.items.size(); ++it) {
+      CHECK(one.items[it] == it);
+      CHECK(std::vector<uint32_t>(one.users.begin() + one.ptr[it], one.users.begin() + one.ptr[it + 1]) == by_item[it]);
+    }
+    for (size_t ch : {(size_t)1, (size_t)3, (size_t)5, (size_t)64}) {
+      ItemMaskLists cat, ml;
+      cat.ptr.assign(1, 0);
+      for_chunks(m, [&](size_t i0, size_t i1) {
+        ml.fill(rt.validation, (uint32_t)i0, (uint32_t)i1);
+        CHECK(ml.ptr.size() == i1 - i0 + 1 && ml.ptr[0] == 0 && ml.ptr.back() == ml.users.size());
+        cat.items.insert(cat.items.end(), ml.items.begin(), ml.items.end());
+        for (size_t j = 1; j < ml.ptr.size(); ++j) cat.ptr.push_back(cat.users.size() + ml.ptr[j]);
+        cat.users.insert(cat.users.end(), ml.users.begin(), ml.users.end());
+      }, ch);
+      CHECK(cat.items == one.items && cat.ptr == one.ptr && cat.users == one.users);
+    }
+    ItemMaskLists none;
+    none.fill(HeldOut(), 2, 5);                             // no pairs, and an empty range
+    CHECK(none.items == (std::vector<uint32_t>{2, 3, 4}) && none.users.empty() && none.ptr == (std::vector<uint64_t>{0, 0, 0, 0}));
+    none.fill(rt.validation, 4, 4);
+    CHECK(none.items.empty() && none.users.empty() && none.ptr == (std::vector<uint64_t>{0}));
+  }
+
   // the list writer: only the real entries, only what the predicate keeps, the line count
   {
     const uint32_t N = 4, bad = 0xffffffffu;

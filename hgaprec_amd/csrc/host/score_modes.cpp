@@ -1,5 +1,5 @@
 // score_modes.cpp -- the reports of `hgaprec` on a saved model: -rmse / -msr / -eval-all / -recommend [-explain] [-because] /
-// -similar-items / -similar-users / -topic-items / -topic-users / -fold-in / -fold-in-items (and -gen-ranking, which is the training run's own ranking on the loaded state).  Each
+// -similar-items / -similar-users / -topic-items / -topic-users / -audience [-explain] / -fold-in / -fold-in-items (and -gen-ranking, which is the training run's own ranking on the loaded state).  Each
 // reads the data like a training run, loads the factor files a run has written (from the current directory like the
 // reference, or from -model-dir DIR), writes ONE report and returns.  One GPU; nothing of the training loop is seen here.
 #include "hgaprec_cli.hpp"
@@ -267,6 +267,55 @@ struct ScoreModes : Cli {
     env.lerr("-recommend: %u users, %llu lines in recommend.tsv", n, lines);
   }
 
+  // -audience N (extension): whom to show an item to -- the N best users of EVERY item, the item's training users with a
+  // rating > 0 and its validation users zeroed: -recommend transposed, through hpf_audience.  <stem>.tsv: item id, user id,
+  // score -- items in seq order, each list best first, printed by write_topn under the rule that mirrors recommend.tsv's
+  // (given.r(user, item) == 0; the padding beyond n users is never printed); <stem>.txt items, lines and N.  The validation
+  // pairs are regrouped per item for each chunk (ItemMaskLists); a chunk of items is written before the next is ranked.
+  // -fold-in-items' tail is the same report for the new items: their own handle and ratings, and no list beyond the given
+  // ratings, which the call masks itself (mask == nullptr).
+  // -explain T: as behind -recommend, the (user, item) pairs of the lines just written go to hpf_explain;
+  // <stem>_explain.tsv: item id, user id, factor, contribution (%.8f); <stem>_explain.txt: pairs, lines, T.
+  unsigned long long audience_lists(const Ratings &given, const HeldOut *mask, const std::string &stem) {
+    const uint32_t N = env.audience, T = env.explain, nu = given.n;
+    const std::string rpath = env.file_str(stem + ".tsv"), epath = env.file_str(stem + "_explain.tsv");
+    FILE *f = open_or_die(rpath, "w"), *ef = T ? open_or_die(epath, "w") : nullptr;
+    ItemMaskLists ml; std::vector<uint32_t> users, eu, ei, fac; std::vector<double> scores, con;
+    const HeldOut none;
+    unsigned long long lines = 0, epairs = 0, elines = 0;
+    const std::function<bool(uint32_t, uint32_t)> keep = [&](uint32_t it, uint32_t u) { return given.r(u, it) == 0; };
+    for_chunks(given.m, [&](size_t i0, size_t i1) {
+      ml.fill(mask ? *mask : none, (uint32_t)i0, (uint32_t)i1);
+      users.resize(ml.items.size() * (size_t)N); scores.resize(ml.items.size() * (size_t)N);
+      int rc = hpf_audience(h, ml.items.data(), (uint32_t)ml.items.size(), ml.ptr.data(), mask ? ml.users.data() : nullptr, N,
+                            users.data(), scores.data());
+      if (rc) die("hpf_audience", rc);
+      lines += write_topn(f, ml.items.data(), ml.items.size(), users.data(), scores.data(), N, nu, given.seq2item.data(),
+                          given.seq2user.data(), keep);
+      if (!ef) return;
+      eu.clear(); ei.clear();
+      for (size_t b = 0; b < ml.items.size(); ++b)
+        for (uint32_t j = 0; j < nu && j < N; ++j)                // the entries write_topn has written
+          if (keep(ml.items[b], users[b * N + j])) { eu.push_back(users[b * N + j]); ei.push_back(ml.items[b]); }
+      fac.resize(eu.size() * (size_t)T); con.resize(eu.size() * (size_t)T);
+      rc = hpf_explain(h, eu.data(), ei.data(), eu.size(), T, fac.data(), con.data());
+      if (rc) die("hpf_explain", rc);
+      for (size_t p = 0; p < eu.size(); ++p)
+        for (uint32_t r = 0; r < T && fac[p * T + r] != 0xffffffffu; ++r, ++elines)
+          fprintf(ef, "%d\t%d\t%d\t%.8f\n", given.seq2item[ei[p]], given.seq2user[eu[p]], fac[p * T + r], con[p * T + r]);
+      epairs += eu.size();
+    });
+    close_or_die(f, rpath);
+    write_line(env.file_str(stem + ".txt"), "%u\t%llu\t%u\n", given.m, lines, N);
+    if (ef) {
+      close_or_die(ef, epath);
+      write_line(env.file_str(stem + "_explain.txt"), "%llu\t%llu\t%u\n", epairs, elines, T);
+      env.lerr("-explain: %llu pairs, %llu lines in %s_explain.tsv", epairs, elines, stem.c_str() + 1);
+    }
+    env.lerr("-audience: %u items, %llu lines in %s.tsv", given.m, lines, stem.c_str() + 1);
+    return lines;
+  }
+
   // -similar-items N / -similar-users N (extension): "more like this item" and "users like this one" -- the N nearest other
   // rows of E[beta] (E[theta]) to every row, by cosine or dot product over the K factor columns, through hpf_similar.
   // similar_items.tsv: item id, neighbour item id, score -- items in seq order, each list best first, ids and score printed
@@ -331,7 +380,8 @@ struct ScoreModes : Cli {
   // (htheta / theta, with -bias thetabias), the second handle holds the n users x the new items, hpf_fold_in_items runs
   // the iterations.  Output: the item-side files of save_model under foldin_ (foldin_hbeta*.tsv, foldin_betarate*.tsv,
   // foldin_betabias*.tsv) and foldin_items.txt (items, ratings, lines skipped for an unknown user, T, X, iterations
-  // min / mean / max).
+  // min / mean / max); with -audience N also foldin_audience.tsv / .txt, audience_lists' lines for the new items with their
+  // given ratings masked (and with -explain T foldin_audience_explain.tsv / .txt).
   void fold_in_report(bool items) {
     const char *flag = items ? "-fold-in-items" : "-fold-in";
     const std::string &file = items ? env.fold_in_items : env.fold_in;
@@ -402,6 +452,7 @@ struct ScoreModes : Cli {
     env.lerr("%s: %u %s, %llu ratings, %llu lines skipped (unknown %s), iterations %u .. %u", flag, rows, items ? "items" : "users",
              (unsigned long long)nu.col.size(), (unsigned long long)skipped, items ? "user" : "item", imin, imax);
     if (!items && env.recommend) f.recommend_lists(nu, nullptr, "/foldin_recommend");
+    if (items && env.audience) f.audience_lists(nu, nullptr, "/foldin_audience");
     if (f.h) hpf_destroy(f.h);
   }
 };
@@ -418,6 +469,7 @@ void score(Cli &c, const std::function<void()> &gen_ranking)
   else if (c.env.msr) s.gen_msr_csv();
   else if (c.env.eval_all) s.eval_all_report();
   else if (c.env.recommend) s.recommend_report();
+  else if (c.env.audience) s.audience_lists(c.rt, &c.rt.validation, "/audience");
   else if (c.env.similar_items || c.env.similar_users) {
     if (c.env.similar_items) s.similar_report(true);
     if (c.env.similar_users) s.similar_report(false);

@@ -621,7 +621,7 @@ struct Scratch {
 };
 
 // Device side of a ranking call: the selected users and the mask list (upload) and, for the fused calls (hpf_loo_ranks,
-// hpf_rank_queries, hpf_recommend), the bit rows of one batch of users (bit_rows; hpf_plan::rank_batch_users)
+// hpf_rank_queries, hpf_recommend, hpf_audience), the bit rows of one batch of selected rows (bit_rows; hpf_plan::rank_batch_users)
 struct FusedCtx : Scratch {
   uint32_t *d_users = nullptr, *d_mitems = nullptr; uint64_t *d_mptr = nullptr, *d_bits = nullptr;
   uint32_t words = 0, batch = 0;       // 64-bit words of a bit row; users per batch
@@ -634,18 +634,24 @@ struct FusedCtx : Scratch {
     if ((rc = alloc(&d_mptr, (size_t)n_sel + 1, mask_ptr))) return rc;
     return alloc(&d_mitems, (size_t)mask_ptr[n_sel], mask_ptr[n_sel] ? mask_items : nullptr);
   }
-  int bit_rows(uint32_t n_sel)
+  // the bit rows of a batch over the `swept` rows the call ranks: the items for the calls that select users, the users for
+  // hpf_audience
+  int bit_rows(uint32_t n_sel, uint32_t swept)
   {
-    words = (h->it.rows + 63) / 64;
-    batch = hpf_plan::rank_batch_users(h->it.rows, n_sel, h->loo_batch);
+    words = (swept + 63) / 64;
+    batch = hpf_plan::rank_batch_users(swept, n_sel, h->loo_batch);
     return alloc(&d_bits, (size_t)batch * words);
   }
-  // the bit rows of the selected users [b0, b0 + rows): cleared (alloc left them zero for the first batch) and set
-  int mask_batch(uint32_t b0, uint32_t rows)
+  // the bit rows of the selected rows [b0, b0 + rows): cleared (alloc left them zero for the first batch) and set from the
+  // view whose rows the selected ids name -- (rowptr_dev, u.idx, u.val) for users, (colptr_dev, it.idx, it.val) for items
+  using MaskKernel = void (*)(const uint32_t *, uint32_t, const int64_t *, const uint32_t *, const uint8_t *, const uint64_t *,
+                              const uint32_t *, uint32_t *, uint32_t);
+  int mask_batch(uint32_t b0, uint32_t rows, const int64_t *ptr, const uint32_t *idx, const uint8_t *val,
+                 MaskKernel kernel = loo_mask_kernel)
   {
     if (b0) HIPCHK(h, hipMemsetAsync(d_bits, 0, (size_t)rows * words * 8, h->stream));
-    hipLaunchKernelGGL(loo_mask_kernel, dim3(std::min<uint32_t>((rows + 3) / 4, 4096)), dim3(256), 0, h->stream,
-                       d_users + b0, rows, h->rowptr_dev, h->u.idx, h->u.val, d_mptr ? d_mptr + b0 : nullptr, d_mitems,
+    hipLaunchKernelGGL(kernel, dim3(std::min<uint32_t>((rows + 3) / 4, 4096)), dim3(256), 0, h->stream,
+                       d_users + b0, rows, ptr, idx, val, d_mptr ? d_mptr + b0 : nullptr, d_mitems,
                        (uint32_t *)d_bits, words);
     return HPF_OK;
   }
@@ -2816,11 +2822,11 @@ int hpf_loo_ranks(hpf_handle *h, const uint32_t *users, uint32_t n_sel, const ui
   if (int rc = fused_ready(h, users, n_sel, mask_ptr, mask_items, q_item, n_sel)) return rc;
   FusedCtx c(h); int rc;
   uint32_t *d_q = nullptr, *d_rank = nullptr, *d_masked = nullptr; double *d_sc = nullptr;
-  if ((rc = c.upload(users, n_sel, mask_ptr, mask_items)) || (rc = c.bit_rows(n_sel)) || (rc = c.alloc(&d_q, n_sel, q_item)) || (rc = c.alloc(&d_rank, n_sel)) ||
+  if ((rc = c.upload(users, n_sel, mask_ptr, mask_items)) || (rc = c.bit_rows(n_sel, h->it.rows)) || (rc = c.alloc(&d_q, n_sel, q_item)) || (rc = c.alloc(&d_rank, n_sel)) ||
       (rc = c.alloc(&d_masked, n_sel)) || (rc = c.alloc(&d_sc, n_sel))) return rc;
   for (uint32_t b0 = 0; b0 < n_sel; b0 += c.batch) {
     const uint32_t rows = std::min(n_sel - b0, c.batch);
-    if ((rc = c.mask_batch(b0, rows))) return rc;
+    if ((rc = c.mask_batch(b0, rows, h->rowptr_dev, h->u.idx, h->u.val))) return rc;
     LooArgs a;
     factor_args(h, a);
     a.users = c.d_users + b0; a.q_item = d_q + b0; a.bits = c.d_bits;
@@ -2852,7 +2858,7 @@ int hpf_rank_queries(hpf_handle *h, const uint32_t *users, uint32_t n_sel, const
   if (!nq) return ready(h, hpf_lazy::E_IS_SET, -1, -1, [&] { return rank_check(h, users, n_sel, mask_ptr, mask_items); });      // nothing asked: only the checks
   if (int rc = fused_ready(h, users, n_sel, mask_ptr, mask_items, q_items, nq)) return rc;
   FusedCtx c(h); int rc;
-  if ((rc = c.upload(users, n_sel, mask_ptr, mask_items)) || (rc = c.bit_rows(n_sel))) return rc;
+  if ((rc = c.upload(users, n_sel, mask_ptr, mask_items)) || (rc = c.bit_rows(n_sel, h->it.rows))) return rc;
   // rows: a selected user with at most RQ_QCAP of its queries (a query's rank does not depend on the user's other
   // queries, so cutting a user is exact); in the order of the selected users, so a batch owns a run of them
   std::vector<uint32_t> row_sel, row_q0, row_nq, first_row;   // first_row[batch index] -> its first row
@@ -2875,7 +2881,7 @@ int hpf_rank_queries(hpf_handle *h, const uint32_t *users, uint32_t n_sel, const
   for (uint32_t b0 = 0; b0 < n_sel; b0 += c.batch, ++bi) {
     const uint32_t r0 = first_row[bi], rows = first_row[bi + 1] - r0;
     if (!rows) continue;
-    if ((rc = c.mask_batch(b0, std::min(n_sel - b0, c.batch)))) return rc;
+    if ((rc = c.mask_batch(b0, std::min(n_sel - b0, c.batch), h->rowptr_dev, h->u.idx, h->u.val))) return rc;
     RqArgs a;
     factor_args(h, a);
     a.users = c.d_users + b0; a.row_sel = d_rsel + r0; a.row_q0 = d_rq0 + r0; a.row_nq = d_rnq + r0; a.q_item = d_q;
@@ -2904,12 +2910,12 @@ int hpf_recommend(hpf_handle *h, const uint32_t *users, uint32_t n_sel, const ui
   if (h->ld & 1u) { h->err = "hpf_recommend: odd row stride"; return HPF_ERR_UNSUPPORTED; }
   if (int rc = fused_ready(h, users, n_sel, mask_ptr, mask_items)) return rc;
   FusedCtx c(h); int rc;
-  if ((rc = c.upload(users, n_sel, mask_ptr, mask_items)) || (rc = c.bit_rows(n_sel))) return rc;
+  if ((rc = c.upload(users, n_sel, mask_ptr, mask_items)) || (rc = c.bit_rows(n_sel, h->it.rows))) return rc;
   TopnArgs a;
   factor_args(h, a);
   a.bits = c.d_bits; a.words = c.words;
   return topn_run(c, a, m, n_sel, topn, std::min(topn, m), "topn_sweep_kernel",
-                  [&](uint32_t b0, uint32_t rows) { return c.mask_batch(b0, rows); },
+                  [&](uint32_t b0, uint32_t rows) { return c.mask_batch(b0, rows, h->rowptr_dev, h->u.idx, h->u.val); },
                   [&](auto nch, dim3 grid, const TopnArgs &ta) {
                     hipLaunchKernelGGL(topn_sweep_kernel<decltype(nch)::value>, grid, dim3(256), 0, h->stream, ta);
                   }, out_items, out_scores);
@@ -2952,6 +2958,46 @@ int hpf_similar(hpf_handle *h, int side, const uint32_t *ids, uint32_t n_sel, ui
                   [&](auto nch, dim3 grid, const TopnArgs &ta) {
                     hipLaunchKernelGGL(similar_sweep_kernel<decltype(nch)::value>, grid, dim3(256), 0, h->stream, ta);
                   }, out_ids, out_scores);
+}
+
+// The topn users of every selected item: hpf_recommend transposed.  TopnArgs with the sides exchanged -- the selected items'
+// rows of E[beta] are the query rows, the m = n_users rows of E[theta] are swept, the bias columns change places -- behind the
+// bit rows of a batch of ITEMS, one bit per user, set from the item-major view (audience_mask_kernel).  Only the fused route.
+int hpf_audience(hpf_handle *h, const uint32_t *items, uint32_t n_sel, const uint64_t *mask_ptr,
+                 const uint32_t *mask_users, uint32_t topn, uint32_t *out_users, double *out_scores)
+{
+  if (!h) return HPF_ERR_INVALID;
+  if (!hpf_plan::topn_fused(topn)) { h->err = "hpf_audience: topn is 1 .. 256"; return HPF_ERR_INVALID; }
+  if (n_sel && (!items || !out_users || !out_scores)) { h->err = "hpf_audience: null pointer"; return HPF_ERR_INVALID; }
+  if (!n_sel) return HPF_OK;
+  const uint32_t n = h->u.rows;
+  if (h->ld & 1u) { h->err = "hpf_audience: odd row stride"; return HPF_ERR_UNSUPPORTED; }
+  int rc;
+  if ((rc = ready(h, hpf_lazy::SCORING, -1, -1, [&] {
+        if (!h->have_csr) { h->err = "hpf_upload_csr has not been called"; return (int)HPF_ERR_STATE; }
+        for (uint32_t b = 0; b < n_sel; ++b)
+          if (items[b] >= h->it.rows) { h->err = "item index out of range"; return (int)HPF_ERR_INVALID; }
+        if (mask_ptr) {
+          const uint64_t nmask = mask_ptr[n_sel];
+          if (mask_ptr[0] != 0) { h->err = "mask_ptr[0] must be 0"; return (int)HPF_ERR_INVALID; }
+          for (uint32_t b = 0; b < n_sel; ++b) if (mask_ptr[b + 1] < mask_ptr[b]) { h->err = "mask_ptr not monotone"; return (int)HPF_ERR_INVALID; }
+          if (nmask && !mask_users) { h->err = "hpf_audience: null pointer"; return (int)HPF_ERR_INVALID; }
+          for (uint64_t j = 0; j < nmask; ++j) if (mask_users[j] >= n) { h->err = "mask user out of range"; return (int)HPF_ERR_INVALID; }
+        }
+        return (int)HPF_OK;
+      }))) return rc;
+  FusedCtx c(h);
+  if ((rc = c.upload(items, n_sel, mask_ptr, mask_users)) || (rc = c.bit_rows(n_sel, n))) return rc;
+  TopnArgs a;
+  a.Et = h->it.E; a.Eb = h->u.E; a.ld = h->ld; a.K = h->K;
+  a.ubias_col = h->cfg.bias ? h->it.bias_col : -1;       // of the query rows: E_ibias
+  a.ibias_col = h->cfg.bias ? h->u.bias_col : -1;        // of the swept rows: E_ubias
+  a.bits = c.d_bits; a.words = c.words;
+  return topn_run(c, a, n, n_sel, topn, std::min(topn, n), "audience_sweep_kernel",
+                  [&](uint32_t b0, uint32_t rows) { return c.mask_batch(b0, rows, h->colptr_dev, h->it.idx, h->it.val, audience_mask_kernel); },
+                  [&](auto nch, dim3 grid, const TopnArgs &ta) {
+                    hipLaunchKernelGGL(audience_sweep_kernel<decltype(nch)::value>, grid, dim3(256), 0, h->stream, ta);
+                  }, out_users, out_scores);
 }
 
 // The T largest terms of every pair's score (explain_kernel): hpf_predict's readiness path and argument checks, no CSR,

@@ -3085,6 +3085,57 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void s
   topn_sweep_body<NCH, SimilarEpi>(a);
 }
 
+// ---------------------------------------------------------------------
+// The top-N users of every item (hpf_audience, -audience).
+//   audience_mask_kernel   training (rating > 0) and mask-list USERS of a batch of items as bits: loo_mask_kernel over the
+//                          item-major view, a long column walked by a whole workgroup
+//   audience_sweep_kernel  topn_sweep_kernel's sweep and selection with the sides exchanged: the caller fills TopnArgs with
+//                          Et = E[beta] (query rows: the selected items), Eb = E[theta] (swept rows: the users), m = n_users
+//                          and the bias columns exchanged; topn_merge_kernel follows
+// ---------------------------------------------------------------------
+// The policy needs nothing beyond what RecommendEpi has: with the sides exchanged `ubias` reads E_ibias of the query item,
+// `ibias` E_ubias of the swept user, epilogue_key adds their ONE parenthesised sum (commutative, so the bits of hpf_scores)
+// and the mask word is the item's word of USER bits.  The type and the kernel carry their own names for launch_rank's
+// error text and for profiles.
+struct AudienceEpi : RecommendEpi {};
+
+template <int NCH>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void audience_sweep_kernel(TopnArgs a)
+{
+  topn_sweep_body<NCH, AudienceEpi>(a);
+}
+
+constexpr uint32_t AUDIENCE_LONG_MIN = 4096;     // users of a column from which a workgroup walks it, not a wave
+
+// Bit u of row b is set when user u is masked for item items[b]: masked_items over the item-major view (colptr, usr, val)
+// and the caller's list.  Workgroups of four waves.  First a wave per item of the batch: its list and, where the column has
+// fewer than AUDIENCE_LONG_MIN users, its column.  Then a workgroup per item: the long columns, 256 users a step (item
+// columns are heavy-tailed: a wave alone would walk the longest in thousands of dependent steps while the rest of the
+// launch has long finished).  Rows are `words` 64-bit words, written as dwords; every usr[j] is below 64 words.
+__global__ __launch_bounds__(256) void audience_mask_kernel(const uint32_t *items, uint32_t n_sel, const int64_t *colptr,
+                                                            const uint32_t *usr, const uint8_t *val, const uint64_t *mask_ptr,
+                                                            const uint32_t *mask_users, uint32_t *bits, uint32_t words)
+{
+  const int lane = threadIdx.x & 63;
+  const uint32_t wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  const uint32_t nwaves = (gridDim.x * blockDim.x) >> 6;
+  for (uint32_t b = wave; b < n_sel; b += nwaves) {
+    uint32_t *row = bits + (size_t)b * words * 2;
+    const uint32_t i = items[b];
+    const bool is_long = colptr[i + 1] - colptr[i] >= (int64_t)AUDIENCE_LONG_MIN;
+    masked_items(i, b, lane, is_long ? nullptr : colptr, usr, val, mask_ptr, mask_users,
+                 [&](uint32_t u) { atomicOr(&row[u >> 5], 1u << (u & 31u)); });
+  }
+  for (uint32_t b = blockIdx.x; b < n_sel; b += gridDim.x) {
+    const uint32_t i = items[b];
+    const int64_t j0 = colptr[i], j1 = colptr[i + 1];
+    if (j1 - j0 < (int64_t)AUDIENCE_LONG_MIN) continue;
+    uint32_t *row = bits + (size_t)b * words * 2;
+    for (int64_t j = j0 + threadIdx.x; j < j1; j += blockDim.x)
+      if (!val || val[j] > 0) atomicOr(&row[usr[j] >> 5], 1u << (usr[j] & 31u));
+  }
+}
+
 constexpr int UNIT_G = 16;            // lanes per row: one DPP row; 16 lanes x 16 bytes = two 128-byte lines per step
 
 // U[r, k] = x_k / sqrt(sum_k x_k^2), x_k = E[r, k] 2^-e with 2^e the power of two of the row's largest entry: x_k is exact

@@ -84,6 +84,10 @@ def lib():
     L.hg_mask_lists_new.restype = vp
     L.hg_mask_lists_free.argtypes = [vp]; L.hg_mask_lists_free.restype = None
     L.hg_mask_lists_get.argtypes = [vp, C.c_int, C.POINTER(vp)]; L.hg_mask_lists_get.restype = C.c_uint64
+    L.hg_item_mask_lists_new.argtypes = [vp, C.c_int, C.c_uint32, C.c_uint32]
+    L.hg_item_mask_lists_new.restype = vp
+    L.hg_item_mask_lists_free.argtypes = [vp]; L.hg_item_mask_lists_free.restype = None
+    L.hg_item_mask_lists_get.argtypes = [vp, C.c_int, C.POINTER(vp)]; L.hg_item_mask_lists_get.restype = C.c_uint64
     L.hg_write_topn.argtypes = [C.c_char_p, vp, u32p, C.c_uint64, u32p, dp, C.c_uint32, C.c_uint32, u32p, u32p]
     L.hg_write_topn.restype = C.c_int64
     _lib = L
@@ -219,6 +223,22 @@ class Ratings:
             return tuple(out)
         finally:
             self.L.hg_mask_lists_free(ml)
+
+    def item_mask_lists(self, which=0, lo=0, hi=None):
+        """ItemMaskLists::fill over the validation (which = 0) or test pairs: the held-out users of the items [lo, hi)
+        -> (items, mask_ptr, mask_users)"""
+        hi = self.m if hi is None else hi
+        ml = C.c_void_p(self.L.hg_item_mask_lists_new(self._r, which, lo, hi))
+        try:
+            out = []
+            for part, dt in enumerate((np.uint32, np.uint64, np.uint32)):
+                p = C.c_void_p()
+                cnt = self.L.hg_item_mask_lists_get(ml, part, C.byref(p))
+                out.append(np.ctypeslib.as_array(C.cast(p, C.POINTER(np.ctypeslib.as_ctypes_type(dt))), shape=(cnt,)).copy()
+                           if cnt else np.zeros(0, dt))
+            return tuple(out)
+        finally:
+            self.L.hg_item_mask_lists_free(ml)
 
     def __del__(self):
         try:

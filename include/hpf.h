@@ -427,6 +427,33 @@ typedef enum { HPF_SIM_COSINE = 0, HPF_SIM_DOT = 1 } hpf_similarity;
 int  hpf_similar(hpf_handle *h, int side, const uint32_t *ids, uint32_t n_sel,
                  uint32_t topn, int metric, uint32_t *out_ids, double *out_scores);
 
+/* (an extension; the reference has no counterpart.)  Whom to show an item to: hpf_recommend transposed.  For selected item
+ * items[b] the topn LOCAL users of this handle (with several ranks the local users only; nothing is exchanged, as for
+ * hpf_similar side 0), in the ranking calls' one order, taken on the bit pattern: score descending, ties by ascending
+ * user: out_users[b x topn + j] / out_scores[b x topn + j].
+ * The score of (u, i) is, bit for bit, the double hpf_scores returns for that pair: the sweep issues the same MFMA chain
+ * over k = 0, 4, 8, ... with the same zero padding, the item rows as the A operand and the user rows as the B operand --
+ * a product does not depend on which operand is which -- and with bias the epilogue adds (E_ibias_i + E_ubias_u) as ONE
+ * parenthesised sum, as the other fused calls do; that sum is commutative too.
+ * Masking: a user's score is replaced by +0.0 when the user has a stored training rating > 0 for the item (ALL users of
+ * the item's column when the handle has no values; a uint8-wrapped 0 is NOT masked, as for the users' calls), or when the
+ * user is in the caller's mask list -- a CSR over the selected items, item b's entries mask_users[mask_ptr[b] ..
+ * mask_ptr[b+1]) being local user ids: the validation pairs of that item.  mask_ptr = NULL: no list.  Masked users stay
+ * candidates at +0.0 and tie with every other zero score by user id, like masked items in hpf_recommend.
+ * Entries beyond n_users are (0xffffffff, 0.0).  topn is 1 .. 256 (only the fused route exists, as for hpf_similar).  An
+ * item may be selected twice; both output rows are then equal.  Domain: the ranking calls' -- E finite and >= +0.0.
+ * topn outside 1 .. 256, an item or a mask user out of range, mask_ptr[0] != 0, a decreasing mask_ptr, or a null pointer
+ * with work to do is HPF_ERR_INVALID before anything is launched; n_sel = 0 is HPF_OK; no CSR, or no E on either side, is
+ * HPF_ERR_STATE; an odd row stride is HPF_ERR_UNSUPPORTED, as for the other fused calls.
+ * Synchronous.  The model state is not written.  The call waits for what hpf_recommend waits for: right after
+ * hpf_iterate or hpf_fold_in_items it sees what hpf_get_state would export.
+ * Device memory beyond inputs and outputs: the bit rows of a batch of items, one bit per USER (<= 256 MB; HPF_LOO_BATCH
+ * makes the batches smaller), and the candidate buffers of the batch as in hpf_recommend (<= 512 MB: 10^6 users, topn =
+ * 100: 2 112 items x 32 splits x 256 entries = 208 MB beside 264 MB of bit rows).  Nothing of size n_sel x n_users. */
+int  hpf_audience(hpf_handle *h, const uint32_t *items, uint32_t n_sel,
+                  const uint64_t *mask_ptr, const uint32_t *mask_users, uint32_t topn,
+                  uint32_t *out_users /* n_sel x topn */, double *out_scores /* n_sel x topn */);
+
 /* (an extension; the reference has no counterpart.)  Why a score is what it is: the T largest of the terms whose sum a
  * pair's score is.  For pair p the terms are c_k = E[theta_u k] * E[beta_i k], k < K -- each ONE IEEE fp64 multiplication,
  * nothing fused into it and no reciprocal: the double returned is, bit for bit, the product a host forms from the two
