@@ -43,6 +43,7 @@ EXPORTS = [
     "hpf_heldout_bind", "hpf_heldout_ll_bound",
     "hpf_predict", "hpf_loo_ranks", "hpf_rank_queries", "hpf_recommend", "hpf_fold_in", "hpf_similar",
     "hpf_explain", "hpf_factor_top", "hpf_fold_in_items", "hpf_because", "hpf_audience",
+    "hpf_score_moments", "hpf_recommend_ucb",
 ]
 
 # hpf_similar: the metrics (hpf_similarity in include/hpf.h) and the largest topn (TOPN_FUSED_MAX: only the fused route exists)
@@ -177,6 +178,28 @@ def because_grid(n_sel, nt):
     per = BECAUSE_WAVES * BECAUSE_RUN
     return (max(1, min((n_sel + BECAUSE_WAVES - 1) // BECAUSE_WAVES, BECAUSE_BLOCKS_MAX)),
             max(1, min((nt + per - 1) // per, BECAUSE_BLOCKS_MAX)))
+
+
+# hpf_score_moments / hpf_recommend_ucb (hpf_plan::moments_plan in csrc/hpf_plan.hpp): the derived rows X, Y have
+# C = 2 K + 2 * bias columns at a stride of whole MFMA steps; pair_moments_kernel takes MOMENTS_PAIRS pairs per wave,
+# MOMENTS_WAVES waves per workgroup, at most MOMENTS_BLOCKS_MAX workgroups
+MOMENTS_WAVES, MOMENTS_PAIRS, MOMENTS_BLOCKS_MAX = 4, 16, 4096
+
+
+def moments_plan(K, bias=False):
+    """shape of the moment kernels for K factors: columns C and stride ldx of the derived rows, the column at which the
+    derived columns begin in ucb_sweep_kernel's concatenation, and the MFMAs of the mean and of the variance chain"""
+    C_ = 2 * K + (2 if bias else 0)
+    if K < 1 or C_ > 1024:
+        raise ValueError("the derived columns exceed HPF_MAX_COLUMNS")
+    ldx, mean_cols = (C_ + 3) & ~3, (K + 3) & ~3
+    return {"C": C_, "ldx": ldx, "mean_cols": mean_cols, "mean_steps": mean_cols // 4, "var_steps": ldx // 4}
+
+
+def moments_grid(cnt, rows, ldx):
+    """workgroups of pair_moments_kernel for cnt pairs and of moment_rows_kernel for `rows` derived rows of stride ldx"""
+    per = MOMENTS_WAVES * MOMENTS_PAIRS
+    return (max(1, min((cnt + per - 1) // per, MOMENTS_BLOCKS_MAX)), max(1, min((rows * ldx + 255) // 256, MOMENTS_BLOCKS_MAX)))
 
 
 class _PinnedBlock:
@@ -334,6 +357,9 @@ def load_library(path: os.PathLike | None = None) -> C.CDLL:
         lib.hpf_because.argtypes = [vp, u32p, C.c_uint32, u64p, u32p, C.c_uint32, u32p, dp, dp, dp]
     if hasattr(lib, "hpf_audience"):
         lib.hpf_audience.argtypes = [vp, u32p, C.c_uint32, u64p, u32p, C.c_uint32, u32p, dp]
+    if hasattr(lib, "hpf_score_moments"):
+        lib.hpf_score_moments.argtypes = [vp, u32p, u32p, C.c_size_t, dp, dp]
+        lib.hpf_recommend_ucb.argtypes = [vp, u32p, C.c_uint32, u64p, u32p, C.c_uint32, C.c_double, u32p, dp, dp, dp]
     lib.hpf_comm_unique_id.argtypes = [vp]
     lib.hpf_comm_init.argtypes = [vp, vp]
     lib.hpf_allreduce_exchange.argtypes = [vp]
@@ -691,6 +717,37 @@ class Hpf:
         self._check(self.lib.hpf_audience(self._h, _ptr(items, C.c_uint32), items.size, pmp, pmu, topn & 0xffffffff,
                                           _ptr(users, C.c_uint32), _ptr(sc, C.c_double)))
         return users, sc
+
+    def score_moments(self, u, i):
+        """posterior mean and variance of the score of every pair (hpf_score_moments): the mean bit for bit what scores()
+        returns, the variance sum_k Var(theta_uk beta_ik) (+ the bias variances) from E and the shapes; u is a local user
+        index -> (mean[cnt], var[cnt])"""
+        u = np.ascontiguousarray(u, dtype=np.uint32)
+        i = np.ascontiguousarray(i, dtype=np.uint32)
+        if u.shape != i.shape or u.ndim != 1:
+            raise ValueError("u and i: one-dimensional arrays of the same length")
+        mean = np.empty(u.size, dtype=np.float64)
+        var = np.empty(u.size, dtype=np.float64)
+        self._check(self.lib.hpf_score_moments(self._h, _ptr(u, C.c_uint32), _ptr(i, C.c_uint32), u.size,
+                                               _ptr(mean, C.c_double), _ptr(var, C.c_double)))
+        return mean, var
+
+    def recommend_ucb(self, users, topn=100, z=1.0, mask_ptr=None, mask_items=None):
+        """recommend() ordered by the optimistic score mean + z sd of the Gamma posterior (hpf_recommend_ucb), z >= 0
+        -> (items, ucb, mean, var), each [len(users), topn]; entries beyond n_items are (0xffffffff, 0.0, 0.0, 0.0)"""
+        users = np.ascontiguousarray(users, dtype=np.uint32)
+        if users.ndim != 1:
+            raise ValueError("users: a one-dimensional array")
+        mp, mi, pmp, pmi = self._mask(mask_ptr, mask_items)
+        if mp is not None and mp.size != users.size + 1:
+            raise ValueError("mask_ptr must have len(users) + 1 entries")
+        topn = int(topn)
+        shape = (users.size, topn if 0 < topn <= RECOMMEND_FUSED_MAX else 0)
+        items = np.empty(shape, dtype=np.uint32)
+        ucb, mean, var = (np.empty(shape, dtype=np.float64) for _ in range(3))
+        self._check(self.lib.hpf_recommend_ucb(self._h, _ptr(users, C.c_uint32), users.size, pmp, pmi, topn & 0xffffffff, float(z),
+                                               _ptr(items, C.c_uint32), _ptr(ucb, C.c_double), _ptr(mean, C.c_double), _ptr(var, C.c_double)))
+        return items, ucb, mean, var
 
     def similar(self, side, ids, topn, metric="cosine"):
         """the topn nearest OTHER rows of one side for every selected row (hpf_similar).  side 0: rows of E[theta] (this

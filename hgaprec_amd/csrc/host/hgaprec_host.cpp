@@ -132,6 +132,16 @@ int Env::parse(int argc, char **argv, bool echo, std::string *bad)
       }
       audience = (uint32_t)na;
     }
+    else if (!strcmp(s, "-ucb")) {                                // extension: beside -recommend, the lists by mean + Z sd
+      const char *v = next(); char *end = nullptr;
+      const double z = strtod(v, &end);
+      if (!*v || end == v || *end || !(z >= 0.0) || !std::isfinite(z)) {
+        usage_error = "-ucb needs the number of standard deviations added to the mean, a number >= 0";
+        if (bad) *bad = s;
+        return 2;
+      }
+      ucb_set = true; ucb = z;
+    }
     else if (!strcmp(s, "-similar-metric")) {
       const char *v = next();
       if (strcmp(v, "cosine") && strcmp(v, "dot")) {
@@ -218,6 +228,13 @@ int Env::parse(int argc, char **argv, bool echo, std::string *bad)
   if (because && !recommend) {
     usage_error = "-because goes with -recommend N: it traces the recommended items to the user's ratings";
     if (bad) *bad = "-because";
+    return 2;
+  }
+  if (ucb_set && (audience || !recommend || recommend > 256)) {
+    usage_error = audience ? "-ucb goes with -recommend N, not with -audience"
+                : !recommend ? "-ucb goes with -recommend N: it orders the recommended items by mean + Z sd"
+                             : "-ucb needs -recommend N with N <= 256";
+    if (bad) *bad = "-ucb";
     return 2;
   }
   return 0;

@@ -101,6 +101,13 @@ struct Env {
   // an audience to histories is another question.  N outside 1 .. 256, no N, or -audience with -fold-in or another score
   // mode: parse() returns 2 and says why in usage_error
   uint32_t audience = 0;
+  // extension: -ucb Z goes with -recommend N, N <= 256 (also behind -fold-in): beside recommend.tsv, which is written byte
+  // for byte as without the flag, the N best items of every user by the optimistic score mean + Z sd of the Gamma
+  // posterior through hpf_recommend_ucb -- recommend_ucb.tsv (user id, item id, ucb, mean, sd) / .txt (users, lines, N, Z).
+  // The run reads the shape files of both sides (with -bias of the biases) from -model-dir.  Z negative or no number,
+  // -ucb without -recommend, with N > 256 or with -audience: parse() returns 2 and says why in usage_error
+  bool ucb_set = false;
+  double ucb = 0.0;
   std::string usage_error;
   bool score_mode() const {
     return gen_ranking || rmse || msr || eval_all || recommend > 0 || !fold_in.empty() || !fold_in_items.empty() || similar_items > 0 || similar_users > 0 ||

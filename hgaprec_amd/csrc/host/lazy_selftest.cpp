@@ -37,6 +37,7 @@ struct Truth {
   bool s_raw[2] = {false, false}, e_cur[2] = {true, true}, l_cur[2] = {true, true};
   int w[2] = {W_OUTDATED, W_OUTDATED};
   bool e_exists[2] = {false, false};
+  bool s_exists[2] = {false, false}, bs_exists[2] = {false, false}, be_exists[2] = {false, false};   // a shape, a bias shape, a bias E is in place
   bool unpackable[2] = {false, false};     // the Elog handed in has a spread the packed rows cannot hold
   bool due = false; int skipped = 0;       // a fall-back is due; iterations the passes have skipped since
   bool packed = false;
@@ -45,7 +46,8 @@ struct Truth {
   bool same(const Truth &o) const
   {
     for (int k = 0; k < 2; ++k)
-      if (s_raw[k] != o.s_raw[k] || e_cur[k] != o.e_cur[k] || l_cur[k] != o.l_cur[k] || w[k] != o.w[k] || e_exists[k] != o.e_exists[k]) return false;
+      if (s_raw[k] != o.s_raw[k] || e_cur[k] != o.e_cur[k] || l_cur[k] != o.l_cur[k] || w[k] != o.w[k] || e_exists[k] != o.e_exists[k] ||
+          s_exists[k] != o.s_exists[k] || bs_exists[k] != o.bs_exists[k] || be_exists[k] != o.be_exists[k]) return false;
     return due == o.due && packed == o.packed && sums_cur == o.sums_cur && exchanged == o.exchanged && phase == o.phase && iterations == o.iterations;
   }
 };
@@ -67,7 +69,7 @@ struct Sim {
   Now now() const { return {t.phase, t.iterations, t.packed, comm}; }
 
   // ---- the executors, as the model sees them
-  void sweep(int sd) { st.swept(sd); t.e_exists[sd] = true; if (cfg.rows[sd]) { t.s_raw[sd] = true; t.e_cur[sd] = t.l_cur[sd] = false; t.w[sd] = W_SWEEP; } }
+  void sweep(int sd) { st.swept(sd); t.e_exists[sd] = t.s_exists[sd] = t.bs_exists[sd] = t.be_exists[sd] = true; if (cfg.rows[sd]) { t.s_raw[sd] = true; t.e_cur[sd] = t.l_cur[sd] = false; t.w[sd] = W_SWEEP; } }
   bool iterate()
   {
     if (!request(ITERATION)) return false;
@@ -170,10 +172,14 @@ struct Sim {
       case FOLD_SWEEPS_RUN: return derived_ok() && (sd != ITEMS || side_ok(oth, false));
       case FOLD_SWEEPS_END: return side_ok(sd, true);
       case BECAUSE: return !t.due && side_ok(USERS, true) && side_ok(ITEMS, true);
+      case MOMENTS: return !t.due && side_ok(USERS, false) && side_ok(ITEMS, false);
       case N_NEEDS: break;
     }
     return false;
   }
+
+  // E and the shape of a side, with -bias of its bias too, are in place: handed in, folded in or a sweep's
+  bool moments_exist(int sd) const { return t.e_exists[sd] && t.s_exists[sd] && (!cfg.bias || (t.be_exists[sd] && t.bs_exists[sd])); }
 
   // a call's prologue -> it was not refused
   bool request(Need need, int sd = -1, int kind = -1)
@@ -185,8 +191,11 @@ struct Sim {
     if (todo.status) {
       CHECK(todo.status == HPF_ERR_STATE && todo.error && todo.n == 0, "%s seed %u: a refusal of %d without a message", name, seed, need);
       if (need == SCORING || need == SCORES || need == E_IS_SET) CHECK(!(t.e_exists[USERS] && t.e_exists[ITEMS]), "%s seed %u: E exists, need %d refused", name, seed, need);
+      if (need == MOMENTS)
+        CHECK(!(moments_exist(USERS) && moments_exist(ITEMS)), "%s seed %u: E and shape exist, need %d refused", name, seed, need);
       return false;
     }
+    if (need == MOMENTS) CHECK(moments_exist(USERS) && moments_exist(ITEMS), "%s seed %u: need %d granted though E or a shape does not exist", name, seed, need);
     if (need == SCORING || need == SCORES || need == FACTORS || need == BECAUSE)
       CHECK(need == FACTORS ? t.e_exists[sd] : (t.e_exists[USERS] && t.e_exists[ITEMS]), "%s seed %u: need %d granted though E does not exist", name, seed, need);
     for (int j = 0; j < todo.n; ++j) run(todo.job[j]);
@@ -198,6 +207,7 @@ struct Sim {
   {
     st.folded(sd);
     t.s_raw[sd] = false; t.e_cur[sd] = t.l_cur[sd] = true; t.w[sd] = W_OUTDATED; t.e_exists[sd] = true; t.unpackable[sd] = false; t.sums_cur = false;
+    t.s_exists[sd] = true; if (cfg.bias) t.bs_exists[sd] = t.be_exists[sd] = true;
   }
 
   // -> the event happened (false: refused, or not a call for this moment)
@@ -211,6 +221,8 @@ struct Sim {
       if ((done = request(vector ? PATCH_VECTOR : PATCH, sd, kind))) {
         st.state_set(obj, kind);
         if (!vector && kind == 2 && obj <= 1) t.e_exists[sd] = true;
+        if (!vector && kind == 2 && obj >= 4) t.be_exists[sd] = true;
+        if (!vector && kind == 0) (obj <= 1 ? t.s_exists : t.bs_exists)[sd] = true;
         if (!vector && cfg.rows[sd]) {
           if (kind == 2) t.sums_cur = false;
           if (kind == 3) { t.w[sd] = W_OUTDATED; if (obj <= 1) t.unpackable[sd] = e.flag; }
@@ -263,6 +275,10 @@ struct Sim {
               loaded.snap_derived_dirty() == dd && loaded.snap_more_flags() == more, "%s seed %u: the snapshot words do not round-trip", name, seed);
         CHECK(loaded.ask(ITERATION, now()).n == st.ask(ITERATION, now()).n, "%s seed %u: a restored handle begins its iteration otherwise", name, seed);
         st = loaded;
+        for (int k = 0; k < 2; ++k) {
+          if (t.iterations == 0) t.s_exists[k] = t.bs_exists[k] = false;     // the snapshot does not say that a shape was handed in
+          if (t.e_exists[k]) t.be_exists[k] = true;                          // ... nor the bias column apart: the whole rows came with it
+        }
         done = true;
         break;
       }
@@ -288,7 +304,7 @@ struct Sim {
 static void sequences(unsigned n_seeds, unsigned long *n_events)
 {
   static const int standalone[] = {FLAGS, SWEEP_VECTORS, BIAS_RATE, STATE_E, STATE_ELOG, SCORING, SCORES, E_IS_SET, FACTORS, ELBO, ELBO_FROM_W,
-                                   ITERATION, DERIVED, GATHER_PROBE, START_SUMS, BECAUSE};
+                                   ITERATION, DERIVED, GATHER_PROBE, START_SUMS, BECAUSE, MOMENTS};
   for (unsigned seed = 0; seed < n_seeds; ++seed) {
     std::mt19937 rng(seed * 2654435761u + 12345u);
     auto pick = [&](int n) { return (int)(rng() % (unsigned)n); };

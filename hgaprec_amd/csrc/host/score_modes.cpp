@@ -1,4 +1,4 @@
-// score_modes.cpp -- the reports of `hgaprec` on a saved model: -rmse / -msr / -eval-all / -recommend [-explain] [-because] /
+// score_modes.cpp -- the reports of `hgaprec` on a saved model: -rmse / -msr / -eval-all / -recommend [-explain] [-because] [-ucb] /
 // -similar-items / -similar-users / -topic-items / -topic-users / -audience [-explain] / -fold-in / -fold-in-items (and -gen-ranking, which is the training run's own ranking on the loaded state).  Each
 // reads the data like a training run, loads the factor files a run has written (from the current directory like the
 // reference, or from -model-dir DIR), writes ONE report and returns.  One GPU; nothing of the training loop is seen here.
@@ -83,6 +83,26 @@ struct ScoreModes : Cli {
       }
     }
     env.lerr("-because: Elog of both sides formed from the shape and rate files");
+  }
+
+  // -ucb Z: hpf_recommend_ucb reads the shapes beside E.  The shape files of both sides through the strict readers --
+  // htheta / hbeta or theta / beta, with -bias thetabias / betabias -- into the handle's *_SHAPE.  E stays what load_model
+  // has put: recommend.tsv is that of a run without the flag.  Only a run with the flag reads these files here.
+  // only_items: the handle of a fold-in, whose user side the fold-in has left with its shapes.
+  void load_model_shapes(bool only_items) {
+    for (int user_side = 0; user_side < (only_items ? 1 : 2); ++user_side) {
+      const uint32_t rows = user_side ? n : m;
+      const std::vector<uint32_t> &ids = user_side ? rt.seq2user : rt.seq2item;
+      const std::string base = env.hier ? (user_side ? "htheta" : "hbeta") : (user_side ? "theta" : "beta");
+      std::vector<double> S;
+      load(base + "_shape.tsv", S, rows, k, &ids);
+      put(user_side ? HPF_THETA_SHAPE : HPF_BETA_SHAPE, S);
+      if (env.bias) {
+        load(std::string(user_side ? "thetabias" : "betabias") + "_shape.tsv", S, rows, 1, &ids);
+        put(user_side ? HPF_UBIAS_SHAPE : HPF_IBIAS_SHAPE, S);
+      }
+    }
+    env.lerr("-ucb: the shapes of %s from the shape files", only_items ? "the item side" : "both sides");
   }
 
   // HGAPRec::compute_rmse (hgaprec.cc:1579-1604).  DEVIATION: the reference's -rmse never loads the model (main.cc:254-257
@@ -205,14 +225,19 @@ struct ScoreModes : Cli {
   // -because T (extension): the same pairs, grouped by user as they are, go to hpf_because; <stem>_because.tsv: user id,
   // item id, rated item id, contribution (%.8f), pairs in <stem>.tsv's order, each pair's T rated items best first, the
   // padding of a history shorter than T never printed.  <stem>_because.txt: pairs, lines, T.
+  // -ucb Z (extension): behind each chunk's lists the same users and mask lists go to hpf_recommend_ucb; <stem>_ucb.tsv:
+  // user id, item id, ucb, mean, sd = sqrt(var) (%.5f each) under <stem>.tsv's rule, users in seq order, each list best
+  // first by mean + Z sd.  <stem>_ucb.txt: users, lines, N, Z.  <stem>.tsv is written by the same calls as without the flag.
   unsigned long long recommend_lists(const Ratings &given, const HeldOut *mask, const std::string &stem) {
     const uint32_t N = env.recommend, T = env.explain, TB = env.because;
     const std::string rpath = env.file_str(stem + ".tsv"), epath = env.file_str(stem + "_explain.tsv"), bpath = env.file_str(stem + "_because.tsv");
     FILE *f = open_or_die(rpath, "w"), *ef = T ? open_or_die(epath, "w") : nullptr, *bf = TB ? open_or_die(bpath, "w") : nullptr;
-    MaskLists ml; std::vector<uint32_t> items, eu, ei, fac, rated; std::vector<double> scores, con;
+    const std::string upath = env.file_str(stem + "_ucb.tsv");
+    FILE *uf = env.ucb_set ? open_or_die(upath, "w") : nullptr;
+    MaskLists ml; std::vector<uint32_t> items, eu, ei, fac, rated, uitems; std::vector<double> scores, con, ucb, mean, var;
     std::vector<uint64_t> tptr;
     const HeldOut none;
-    unsigned long long lines = 0, epairs = 0, elines = 0, bpairs = 0, blines = 0;
+    unsigned long long lines = 0, epairs = 0, elines = 0, bpairs = 0, blines = 0, ulines = 0;
     const std::function<bool(uint32_t, uint32_t)> keep = [&](uint32_t u, uint32_t it) { return given.r(u, it) == 0; };
     for_chunks(given.n, [&](size_t u0, size_t u1) {
       ml.fill(mask ? *mask : none, nullptr, 0, (uint32_t)u0, (uint32_t)u1);
@@ -222,6 +247,20 @@ struct ScoreModes : Cli {
       if (rc) die("hpf_recommend", rc);
       lines += write_topn(f, ml.users.data(), ml.users.size(), items.data(), scores.data(), N, m, given.seq2user.data(),
                           rt.seq2item.data(), keep);
+      if (uf) {
+        const size_t cnt = ml.users.size() * (size_t)N;
+        uitems.resize(cnt); ucb.resize(cnt); mean.resize(cnt); var.resize(cnt);
+        rc = hpf_recommend_ucb(h, ml.users.data(), (uint32_t)ml.users.size(), ml.ptr.data(), mask ? ml.items.data() : nullptr, N, env.ucb,
+                               uitems.data(), ucb.data(), mean.data(), var.data());
+        if (rc) die("hpf_recommend_ucb", rc);
+        for (size_t b = 0; b < ml.users.size(); ++b)
+          for (uint32_t j = 0; j < m && j < N; ++j) {               // write_topn's rule: no padding, no given item
+            const size_t e = b * N + j;
+            if (!keep(ml.users[b], uitems[e])) continue;
+            fprintf(uf, "%d\t%d\t%.5f\t%.5f\t%.5f\n", given.seq2user[ml.users[b]], rt.seq2item[uitems[e]], ucb[e], mean[e], sqrt(var[e]));
+            ++ulines;
+          }
+      }
       if (!ef && !bf) return;
       eu.clear(); ei.clear(); tptr.assign(1, 0);
       for (size_t b = 0; b < ml.users.size(); ++b) {
@@ -249,6 +288,11 @@ struct ScoreModes : Cli {
     });
     close_or_die(f, rpath);
     write_line(env.file_str(stem + ".txt"), "%u\t%llu\t%u\n", given.n, lines, N);
+    if (uf) {
+      close_or_die(uf, upath);
+      write_line(env.file_str(stem + "_ucb.txt"), "%u\t%llu\t%u\t%g\n", given.n, ulines, N, env.ucb);
+      env.lerr("-ucb: %llu lines in %s_ucb.tsv, z = %g", ulines, stem.c_str() + 1, env.ucb);
+    }
     if (ef) {
       close_or_die(ef, epath);
       write_line(env.file_str(stem + "_explain.txt"), "%llu\t%llu\t%u\n", epairs, elines, T);
@@ -263,6 +307,7 @@ struct ScoreModes : Cli {
   }
   void recommend_report() {
     if (env.because) load_model_elog();
+    if (env.ucb_set) load_model_shapes(false);
     const unsigned long long lines = recommend_lists(rt, &rt.validation, "/recommend");
     env.lerr("-recommend: %u users, %llu lines in recommend.tsv", n, lines);
   }
@@ -373,7 +418,8 @@ struct ScoreModes : Cli {
   // user).  Output: the user-side files of save_model under the prefix foldin_, through the same writers; foldin.txt
   // (users, nonzeros, lines skipped for an unknown item, T, X, iterations min / mean / max); with -recommend N also
   // foldin_recommend.tsv / .txt, recommend_report's lines for the new users with their given ratings masked (and with -explain T
-  // foldin_recommend_explain.tsv / .txt, with -because T foldin_recommend_because.tsv / .txt: the second handle holds all the call reads).
+  // foldin_recommend_explain.tsv / .txt, with -because T foldin_recommend_because.tsv / .txt: the second handle holds all the call reads;
+  // with -ucb Z foldin_recommend_ucb.tsv / .txt: the item side's shapes are handed in too, the new users' the fold-in has left).
   //
   // -fold-in-items FILE (extension) is the mirror, for a catalogue that grows: the ITEMS of FILE, which need not be in -dir,
   // rated by users of -dir (Ratings::read_fold_in_items).  The USER side comes from -model-dir as shape and rate
@@ -451,6 +497,7 @@ struct ScoreModes : Cli {
                (unsigned long long)skipped, env.fold_iters, env.fold_tol, imin, rows ? isum / rows : 0.0, imax);
     env.lerr("%s: %u %s, %llu ratings, %llu lines skipped (unknown %s), iterations %u .. %u", flag, rows, items ? "items" : "users",
              (unsigned long long)nu.col.size(), (unsigned long long)skipped, items ? "user" : "item", imin, imax);
+    if (!items && env.recommend && env.ucb_set && f.h) f.load_model_shapes(true);     // after the files: the fold-in's output is that of a run without -ucb
     if (!items && env.recommend) f.recommend_lists(nu, nullptr, "/foldin_recommend");
     if (items && env.audience) f.audience_lists(nu, nullptr, "/foldin_audience");
     if (f.h) hpf_destroy(f.h);

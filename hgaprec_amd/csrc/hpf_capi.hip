@@ -1219,9 +1219,10 @@ int copy_back(hpf_handle *h, std::initializer_list<HostOut> outs)
 // launches the caller's kernel) and a merge of each row's splits (topn_merge_kernel) -- per batch the candidate buffers
 // (hpf_plan::topn_batch_users), nothing of n_sel x m.  `a` comes with the factor pointers, the bias columns and the bit rows
 // of the caller; batch(b0, rows) readies the bit rows of a batch.  A list has `real` entries; the rest is padding.
+// lists_dev: where a caller that goes on with the lists on the device (hpf_recommend_ucb) finds the items; c owns them.
 template <typename Batch, typename Sweep>
 int topn_run(FusedCtx &c, TopnArgs a, uint32_t m, uint32_t n_sel, uint32_t topn, uint32_t real, const char *kernel,
-             Batch &&batch, Sweep &&sweep, uint32_t *out_items, double *out_scores)
+             Batch &&batch, Sweep &&sweep, uint32_t *out_items, double *out_scores, uint32_t **lists_dev = nullptr)
 {
   hpf_handle *h = c.h; int rc;
   const uint32_t ntiles = (m + 63) / 64, cap = hpf_plan::topn_cap(topn), NP = hpf_plan::pow2_ceil(topn);
@@ -1233,6 +1234,7 @@ int topn_run(FusedCtx &c, TopnArgs a, uint32_t m, uint32_t n_sel, uint32_t topn,
   uint32_t *d_items = nullptr; double *d_sc = nullptr;
   if ((rc = c.alloc(&a.ckey, nseg * cap)) || (rc = c.alloc(&a.citem, nseg * cap)) || (rc = c.alloc(&a.ccount, nseg)) ||
       (rc = c.alloc(&d_items, (size_t)n_sel * topn)) || (rc = c.alloc(&d_sc, (size_t)n_sel * topn))) return rc;
+  if (lists_dev) *lists_dev = d_items;
   a.m = m; a.topn = topn; a.cap = cap; a.lg_cap = hpf_plan::log2_of(cap);
   const std::string what = std::string(kernel) + "/topn_merge_kernel";
   for (uint32_t b0 = 0; b0 < n_sel; b0 += c.batch) {
@@ -2998,6 +3000,105 @@ int hpf_audience(hpf_handle *h, const uint32_t *items, uint32_t n_sel, const uin
                   [&](auto nch, dim3 grid, const TopnArgs &ta) {
                     hipLaunchKernelGGL(audience_sweep_kernel<decltype(nch)::value>, grid, dim3(256), 0, h->stream, ta);
                   }, out_users, out_scores);
+}
+
+// ---- posterior moments of a score, the optimistic top-N ----
+namespace {
+// what both calls settle before they allocate: the derived columns fit, the row stride is even
+int moments_shape(hpf_handle *h, const char *call, hpf_plan::MomentsPlan *mp)
+{
+  *mp = hpf_plan::moments_plan(h->K, h->cfg.bias != 0);
+  if (!mp->ok) { h->err = std::string(call) + ": 2 K + 2 * bias derived columns exceed HPF_MAX_COLUMNS"; return HPF_ERR_UNSUPPORTED; }
+  if (h->ld & 1u) { h->err = std::string(call) + ": odd row stride"; return HPF_ERR_UNSUPPORTED; }
+  return HPF_OK;
+}
+void pair_moment_args(const hpf_handle *h, const hpf_plan::MomentsPlan &mp, PairMomentArgs &a)
+{
+  factor_args(h, a);
+  a.St = h->u.S; a.Sb = h->it.S; a.C = mp.C; a.mean_steps = mp.mean_steps; a.var_steps = mp.var_steps;
+}
+}  // namespace
+
+// Mean and variance of every pair (pair_moments_kernel): hpf_predict's argument checks behind E and the shapes of both
+// sides (hpf_lazy::MOMENTS); no CSR, no temporaries beyond the pairs, the state only read.
+int hpf_score_moments(hpf_handle *h, const uint32_t *u, const uint32_t *i, size_t cnt, double *out_mean, double *out_var)
+{
+  if (!h) return HPF_ERR_INVALID;
+  if (cnt == 0) return HPF_OK;
+  if (!u || !i) { h->err = "hpf_score_moments: null pointer"; return HPF_ERR_INVALID; }
+  hpf_plan::MomentsPlan mp; int rc;
+  if ((rc = moments_shape(h, "hpf_score_moments", &mp))) return rc;
+  if ((rc = ready(h, hpf_lazy::MOMENTS, -1, -1, [&] {
+        for (size_t p = 0; p < cnt; ++p)
+          if (u[p] >= h->u.rows || i[p] >= h->it.rows) { h->err = "hpf_score_moments: index out of range"; return (int)HPF_ERR_INVALID; }
+        return (int)HPF_OK;
+      }))) return rc;
+  Scratch sc(h);
+  uint32_t *du = nullptr, *di = nullptr;
+  PairMomentArgs a;
+  pair_moment_args(h, mp, a);
+  a.out_ucb = nullptr; a.z = 0.0; a.per = 0; a.cnt = cnt;
+  if ((rc = sc.alloc(&du, cnt, u)) || (rc = sc.alloc(&di, cnt, i)) || (rc = sc.alloc(&a.out_mean, cnt)) || (rc = sc.alloc(&a.out_var, cnt))) return rc;
+  a.u = du; a.i = di;
+  hipLaunchKernelGGL(pair_moments_kernel, dim3(mp.grid_pairs(cnt)), dim3(256), 0, h->stream, a);
+  if ((rc = check_launch(h, "pair_moments_kernel"))) return rc;
+  return copy_back(h, {{out_mean, a.out_mean, cnt * 8}, {out_var, a.out_var, cnt * 8}});
+}
+
+// hpf_recommend ordered by mean + z sd: its checks, bit rows, batches, candidate buffers and merge (topn_run) around
+// ucb_sweep_kernel.  Y (every item's derived row) is built once, X for the users of each batch (moment_rows_kernel); both
+// are temporaries of the call.  The lists' means, variances and values then come from pair_moments_kernel over the listed
+// pairs: the merge's decoded keys are not handed out, a masked item that was listed at +0.0 reports its own value.
+int hpf_recommend_ucb(hpf_handle *h, const uint32_t *users, uint32_t n_sel, const uint64_t *mask_ptr, const uint32_t *mask_items,
+                      uint32_t topn, double z, uint32_t *out_items, double *out_ucb, double *out_mean, double *out_var)
+{
+  if (!h) return HPF_ERR_INVALID;
+  if (!hpf_plan::topn_fused(topn)) { h->err = "hpf_recommend_ucb: topn is 1 .. 256"; return HPF_ERR_INVALID; }
+  if (!(z >= 0.0) || !std::isfinite(z)) { h->err = "hpf_recommend_ucb: z is finite and >= 0 (the key order covers no negative score)"; return HPF_ERR_INVALID; }
+  if (n_sel && (!users || !out_items || !out_ucb)) { h->err = "hpf_recommend_ucb: null pointer"; return HPF_ERR_INVALID; }
+  if (!n_sel) return HPF_OK;
+  const uint32_t m = h->it.rows;
+  hpf_plan::MomentsPlan mp; int rc;
+  if ((rc = moments_shape(h, "hpf_recommend_ucb", &mp))) return rc;
+  if ((rc = ready(h, hpf_lazy::MOMENTS, -1, -1, [&] { return rank_check(h, users, n_sel, mask_ptr, mask_items); }))) return rc;
+  FusedCtx c(h);
+  if ((rc = c.upload(users, n_sel, mask_ptr, mask_items)) || (rc = c.bit_rows(n_sel, m))) return rc;
+  const uint32_t x_rows = mp.x_rows(m, n_sel, topn, h->loo_batch);          // topn_run's batch
+  double *X = nullptr, *Y = nullptr;
+  if ((rc = c.alloc(&Y, (size_t)m * mp.ldx)) || (rc = c.alloc(&X, (size_t)x_rows * mp.ldx))) return rc;
+  MomentRowsArgs ra;
+  ra.ld = h->ld; ra.ldx = mp.ldx; ra.K = h->K;
+  ra.E = h->it.E; ra.S = h->it.S; ra.sel = nullptr; ra.out = Y; ra.rows = m; ra.item_side = 1;
+  ra.bias_col = h->cfg.bias ? h->it.bias_col : -1;
+  hipLaunchKernelGGL(moment_rows_kernel, dim3(mp.grid_rows(m)), dim3(256), 0, h->stream, ra);
+  if ((rc = check_launch(h, "moment_rows_kernel"))) return rc;
+  ra.E = h->u.E; ra.S = h->u.S; ra.out = X; ra.item_side = 0;
+  ra.bias_col = h->cfg.bias ? h->u.bias_col : -1;
+  TopnArgs a;
+  factor_args(h, a);
+  a.bits = c.d_bits; a.words = c.words;
+  uint32_t *d_items = nullptr;
+  if ((rc = topn_run(c, a, m, n_sel, topn, std::min(topn, m), "ucb_sweep_kernel",
+                     [&](uint32_t b0, uint32_t rows) {
+                       if (rows > x_rows) { h->err = "hpf_recommend_ucb: a batch beyond the derived rows"; return (int)HPF_ERR_HIP; }
+                       ra.sel = c.d_users + b0; ra.rows = rows;
+                       hipLaunchKernelGGL(moment_rows_kernel, dim3(mp.grid_rows(rows)), dim3(256), 0, h->stream, ra);
+                       return c.mask_batch(b0, rows, h->rowptr_dev, h->u.idx, h->u.val);
+                     },
+                     [&](auto, dim3 grid, const TopnArgs &ta) {
+                       UcbArgs ua;
+                       static_cast<TopnArgs &>(ua) = ta;
+                       ua.X = X; ua.Y = Y; ua.ldx = mp.ldx; ua.C = mp.C; ua.mean_steps = mp.mean_steps; ua.z = z;
+                       hipLaunchKernelGGL(ucb_sweep_kernel, grid, dim3(256), 0, h->stream, ua);
+                     }, out_items, nullptr, &d_items))) return rc;
+  const size_t cnt = (size_t)n_sel * topn;
+  PairMomentArgs pa;
+  pair_moment_args(h, mp, pa);
+  pa.u = c.d_users; pa.i = d_items; pa.per = topn; pa.cnt = cnt; pa.z = z;
+  if ((rc = c.alloc(&pa.out_ucb, cnt)) || (rc = c.alloc(&pa.out_mean, cnt)) || (rc = c.alloc(&pa.out_var, cnt))) return rc;
+  hipLaunchKernelGGL(pair_moments_kernel, dim3(mp.grid_pairs(cnt)), dim3(256), 0, h->stream, pa);
+  if ((rc = check_launch(h, "pair_moments_kernel"))) return rc;
+  return copy_back(h, {{out_ucb, pa.out_ucb, cnt * 8}, {out_mean, pa.out_mean, cnt * 8}, {out_var, pa.out_var, cnt * 8}});
 }
 
 // The T largest terms of every pair's score (explain_kernel): hpf_predict's readiness path and argument checks, no CSR,

@@ -3203,6 +3203,305 @@ __global__ __launch_bounds__(256) void topn_merge_kernel(TopnArgs a, uint32_t NP
 }
 
 // ---------------------------------------------------------------------
+// Posterior moments of a score and the optimistic top-N (hpf_score_moments, hpf_recommend_ucb).
+// Under the mean-field posterior Var(theta_uk beta_ik) = vt s + q vb with q = E[theta]^2, vt = q / shape(theta),
+// p = E[beta]^2, vb = p / shape(beta), s = p + vb: the variance of a score is the dot product of the derived rows
+//   X_u = [ vt_0 .. vt_{K-1} | q_0 .. q_{K-1}   | (bias:) Var ubias_u, 1.0 ]
+//   Y_i = [ s_0 .. s_{K-1}   | vb_0 .. vb_{K-1} | (bias:) 1.0, Var ibias_i ]
+// taken by the chain hpf_scores issues for C = 2 K + 2 * bias columns.  Every operation is one fp64 operation, nothing is
+// contracted, / and sqrt are the correctly rounded ones.
+//   moment_rows_kernel   X of a batch of selected users, or Y of every item
+//   ucb_sweep_kernel     topn_sweep_kernel's sweep and selection with two chains per output, ordered by mean + z sd
+//   pair_moments_kernel  mean and variance of single pairs, from the sweep's arithmetic
+// ---------------------------------------------------------------------
+// e^2 / shape: the variance of a Gamma from its expectation and its shape; *sq = e^2
+__device__ __forceinline__ double gamma_var(double e, double shape, double *sq)
+{
+#pragma clang fp contract(off)
+  const double q = e * e;
+  *sq = q;
+  return q / shape;
+}
+// Column c of the derived row of a row of E and S (shapes): X where item_side is false, Y where it is true.  bias_col < 0:
+// no bias columns.  Columns from C on are the padding: 0.0.
+__device__ __forceinline__ double moment_column(const double *e, const double *s, uint32_t c, uint32_t K, int32_t bias_col, bool item_side)
+{
+#pragma clang fp contract(off)
+  double q;
+  if (c < 2 * K) {
+    const uint32_t k = c < K ? c : c - K;
+    const double v = gamma_var(e[k], s[k], &q);
+    if (!item_side) return c < K ? v : q;                        // vt | q
+    if (c >= K) return v;                                        // vb
+    const double sum = q + v;                                    // s = p + vb
+    return sum;
+  }
+  if (bias_col < 0 || c > 2 * K + 1) return 0.0;
+  const bool own = (c == 2 * K) != item_side;                    // X: Var ubias, 1.0; Y: 1.0, Var ibias
+  return own ? gamma_var(e[bias_col], s[bias_col], &q) : 1.0;
+}
+
+struct MomentRowsArgs {
+  const double   *E, *S;     // [side rows x ld] expectations and shapes of the side
+  const uint32_t *sel;       // [rows] the side's rows to derive from, or null: rows 0 .. rows - 1
+  double         *out;       // [rows x ldx]
+  uint32_t        rows, ld, ldx, K;
+  int32_t         bias_col;  // -1 without -bias
+  uint32_t        item_side;
+};
+
+// a thread per element of the derived rows, the padding columns included
+__global__ __launch_bounds__(256) void moment_rows_kernel(MomentRowsArgs a)
+{
+  const uint64_t n = (uint64_t)a.rows * a.ldx;
+  for (uint64_t e = (uint64_t)blockIdx.x * 256 + threadIdx.x; e < n; e += (uint64_t)gridDim.x * 256) {
+    const uint32_t r = (uint32_t)(e / a.ldx), c = (uint32_t)(e % a.ldx);
+    const size_t src = (size_t)(a.sel ? a.sel[r] : r) * a.ld;
+    a.out[e] = moment_column(a.E + src, a.S + src, c, a.K, a.bias_col, a.item_side != 0);
+  }
+}
+
+// mean + z sd of a score, three operations
+__device__ __forceinline__ double ucb_value(double mean, double var, double z)
+{
+#pragma clang fp contract(off)
+  const double sd = sqrt(var);
+  const double t = z * sd;
+  return mean + t;
+}
+
+struct UcbArgs : TopnArgs {
+  const double *X;          // [n_sel x ldx] derived rows of this batch's users
+  const double *Y;          // [m x ldx] derived rows of the items
+  uint32_t      ldx, C;     // stride and columns of the derived rows
+  uint32_t      mean_steps; // MFMAs of the mean chain: the derived columns begin at column 4 mean_steps of the concatenation
+  double        z;
+};
+
+// rank_sweep over the concatenation [the K columns of E, zeros up to 4 mean_steps | the C derived columns]: the same LDS
+// staging and MFMA order, the A rows read per step (rank_sweep's NCH == 0 route: K + C columns do not fit in registers).
+// After mean_steps MFMAs the accumulators are the scores hpf_scores returns; they are set aside and the chain starts again
+// from zero over the derived columns.  epi(tl, mean, var) gets both sets in rank_sweep's register layout.  A function of
+// its own, not a parameter of rank_sweep: the kernels that call that one keep their code.
+template <typename Epi>
+__device__ __forceinline__ void moment_sweep(const UcbArgs &a, const double *pa, const double *px, bool row_ok, double *tile, Epi &&epi)
+{
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int r16 = lane & 15, kq = lane >> 4;
+  const uint32_t K = a.K, K4 = 4u * a.mean_steps, KT = K4 + a.C;
+  const uint32_t nsteps = (KT + 3) / 4;
+  const uint32_t ntiles = (a.m + 63) / 64;
+  const uint32_t t0 = blockIdx.y * a.tiles_per_split, t1 = min(ntiles, t0 + a.tiles_per_split);
+  const uint32_t nchunks = (KT + LOO_KC - 1) / LOO_KC;
+
+  // this thread's four 16-byte pieces of a 64 x 32 chunk, as in rank_sweep; K4, C, ld and ldx are even: a piece lies in one part
+  double2 pre[4];
+  auto fetch = [&](uint32_t tile_i, uint32_t chunk) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const uint32_t p = (uint32_t)tid + 256u * j, row = p >> 4, c = chunk * LOO_KC + 2u * (p & 15u);
+      const uint32_t it = tile_i * 64 + row;
+      double2 v = make_double2(0.0, 0.0);
+      if (it < a.m) {
+        if (c < K) {
+          v = *(const double2 *)(a.Eb + (size_t)it * a.ld + c);
+          if (c + 1 >= K) v.y = 0.0;
+        } else if (c >= K4 && c < KT) v = *(const double2 *)(a.Y + (size_t)it * a.ldx + (c - K4));
+      }
+      pre[j] = v;
+    }
+  };
+  auto a_load = [&](uint32_t s) {
+    const uint32_t k = 4u * s + kq;
+    if (!row_ok) return 0.0;
+    if (k < K4) return k < K ? pa[k] : 0.0;
+    return k < KT ? px[k - K4] : 0.0;
+  };
+  if (t0 < t1) fetch(t0, 0);
+  for (uint32_t tl = t0; tl < t1; ++tl) {
+    double4_t acc[4], mean[4];
+#pragma unroll
+    for (int t = 0; t < 4; ++t) acc[t] = mean[t] = (double4_t){0.0, 0.0, 0.0, 0.0};
+    for (uint32_t ch = 0; ch < nchunks; ++ch) {
+      __syncthreads();                                         // the previous chunk has been read
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const uint32_t p = (uint32_t)tid + 256u * j;
+        *(double2 *)&tile[(p >> 4) * LOO_LDS_STRIDE + 2u * (p & 15u)] = pre[j];
+      }
+      __syncthreads();
+      if (ch + 1 < nchunks) fetch(tl, ch + 1);
+      else if (tl + 1 < t1) fetch(tl + 1, 0);
+      for (uint32_t s = 0; s < 8 && ch * 8 + s < nsteps; ++s) {
+        if (ch * 8 + s == a.mean_steps) {                      // the mean chain has ended
+#pragma unroll
+          for (int t = 0; t < 4; ++t) { mean[t] = acc[t]; acc[t] = (double4_t){0.0, 0.0, 0.0, 0.0}; }
+        }
+        const double av = a_load(ch * 8 + s);
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+          const double bv = tile[(16 * t + r16) * LOO_LDS_STRIDE + 4 * s + kq];
+          acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(av, bv, acc[t], 0, 0, 0);
+        }
+      }
+    }
+    epi(tl, mean, acc);
+  }
+}
+
+// hpf_recommend_ucb's sweep: topn_sweep_body's selection (candidate buffers, compaction, lo, a wave owning 16 users;
+// topn_merge_kernel follows) behind moment_sweep.  A candidate's key is that of mean + z sd, with the mean's
+// + (E_ubias + E_ibias) as epilogue_key adds it and +0.0 for a masked item.  z >= 0 and both moments >= +0.0: the key
+// order is the order of the values.  The body is topn_sweep_body's with the second accumulator set, spelled out so that
+// the three kernels built from that one keep their code.
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void ucb_sweep_kernel(UcbArgs a)
+{
+  __shared__ double tile[64 * LOO_LDS_STRIDE];
+  __shared__ unsigned long long scr_k[4 * TOPN_CAP_MAX];          // per wave: the entries being sorted
+  __shared__ uint32_t scr_i[4 * TOPN_CAP_MAX];
+  __shared__ unsigned long long s_lo[64];
+  __shared__ uint32_t s_cnt[64];
+  __shared__ double s_ub[64];                                       // E_ubias of the user
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int r16 = lane & 15, kq = lane >> 4;
+  const uint32_t ub0 = blockIdx.x * 64;                          // first user of this workgroup
+  const uint32_t usel = ub0 + wv * 16 + r16;
+  const bool uok = usel < a.n_sel;
+  const double *pa = a.Et + (size_t)(uok ? a.users[usel] : 0u) * a.ld;
+  const double *px = a.X + (size_t)(uok ? usel : 0u) * a.ldx;
+  unsigned long long *sk = scr_k + wv * TOPN_CAP_MAX;
+  uint32_t *si = scr_i + wv * TOPN_CAP_MAX;
+
+  if (tid < 64) {
+    const uint32_t us = ub0 + tid;
+    s_cnt[tid] = 0u; s_lo[tid] = 0ull;
+    s_ub[tid] = user_bias(a, us, us < a.n_sel);
+  }
+  __syncthreads();
+
+  moment_sweep(a, pa, px, uok, tile, [&](uint32_t tl, const double4_t (&mean)[4], const double4_t (&var)[4]) {
+    // epilogue: register r of tile t holds local user wv 16 + kq + 4 r, item 64 tl + 16 t + r16
+    const uint32_t i0 = tl * 64;
+    double bi[4];
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      const uint32_t it = i0 + 16 * t + r16;
+      bi[t] = item_bias(a, it, it < a.m);
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const uint32_t lr = wv * 16 + kq + 4 * r, us = ub0 + lr;
+      const bool live = us < a.n_sel;
+      const unsigned long long w = live ? a.bits[(size_t)us * a.words + tl] : 0ull;
+      const unsigned long long lo = s_lo[lr];
+      const double ub = s_ub[lr];
+      uint32_t cnt = s_cnt[lr];                                  // <= cap - 64: the 64 items of a tile fit
+      const uint32_t e0 = live ? (us * a.splits + blockIdx.y) << a.lg_cap : 0u;
+#pragma unroll
+      for (int t = 0; t < 4; ++t) {
+        const uint32_t it = i0 + 16 * t + r16;
+        double mu = mean[t][r];
+        if (a.ubias_col >= 0) mu += ub + bi[t];                  // s += Eb_u + Eb_i
+        double v = ucb_value(mu, var[t][r], a.z);
+        if ((w >> (16 * t + r16)) & 1ull) v = 0.0;
+        const unsigned long long k = score_key(v);
+        const bool take = live && it < a.m && k >= lo;
+        const uint32_t grp = (uint32_t)(__ballot(take) >> (16 * kq)) & 0xffffu;   // the 16 lanes that share this user
+        if (take) {
+          const uint32_t slot = cnt + (uint32_t)__popc(grp & ((1u << r16) - 1u));
+          a.ckey[e0 + slot] = k; a.citem[e0 + slot] = it;
+        }
+        cnt += (uint32_t)__popc(grp);
+      }
+      if (r16 == 0) s_cnt[lr] = cnt;
+    }
+    wave_sync();
+    // users of this wave whose buffer might not hold another tile: the whole wave compacts them, one after the other
+    const uint32_t c16 = lane < 16 ? s_cnt[wv * 16 + lane] : 0u;
+    unsigned long long full = __ballot(c16 > a.cap - 64u);
+    while (full) {
+      const uint32_t lr = wv * 16 + (uint32_t)__ffsll((long long)full) - 1u;
+      full &= full - 1ull;
+      const size_t seg = (size_t)(ub0 + lr) * a.splits + blockIdx.y;
+      const uint32_t c = (uint32_t)__builtin_amdgcn_readfirstlane((int)s_cnt[lr]);
+      unsigned long long worst;
+      const uint32_t keep = topn_compact(a.ckey + (seg << a.lg_cap), a.citem + (seg << a.lg_cap), c, a.topn, sk, si, (uint32_t)lane, &worst);
+      if (lane == 0) { s_cnt[lr] = keep; s_lo[lr] = worst + 1ull; }    // c > cap - 64 >= topn: keep == topn
+      wave_sync();
+    }
+  });
+
+  // the end of the split: every segment sorted and cut to its best topn
+  wave_sync();
+  for (uint32_t uu = 0; uu < 16; ++uu) {
+    const uint32_t lr = wv * 16 + uu, us = ub0 + lr;
+    if (us >= a.n_sel) break;
+    const size_t seg = (size_t)us * a.splits + blockIdx.y;
+    const uint32_t c = (uint32_t)__builtin_amdgcn_readfirstlane((int)s_cnt[lr]);
+    unsigned long long worst;
+    const uint32_t keep = topn_compact(a.ckey + (seg << a.lg_cap), a.citem + (seg << a.lg_cap), c, a.topn, sk, si, (uint32_t)lane, &worst);
+    if (lane == 0) a.ccount[seg] = keep;
+  }
+}
+
+struct PairMomentArgs {
+  const uint32_t *u, *i;       // [cnt] the pairs; per > 0: pair p is (u[p / per], i[p]) -- the lists of hpf_recommend_ucb -- and
+  uint32_t        per;         //   an item 0xffffffff is a list's padding: 0.0 in every output
+  uint64_t        cnt;
+  const double   *Et, *Eb, *St, *Sb;   // [n x ld], [m x ld] expectations and shapes
+  double         *out_mean, *out_var, *out_ucb;   // [cnt]; each may be null
+  double          z;           // out_ucb = mean + z sd
+  uint32_t        ld, K, C;
+  uint32_t        mean_steps, var_steps;
+  int32_t         ubias_col, ibias_col;   // -1 without -bias
+};
+
+// A wave takes 16 pairs: the A rows are the pairs' user rows, the B rows their item rows, and of the 16 x 16 tile the
+// diagonal is kept (as loo_rank_kernel takes its threshold) -- the MFMAs, operands and order of the sweep, so a pair's
+// mean and variance are the sweep's bits and those of hpf_scores.  The derived columns are formed on the way
+// (moment_column: the operations of moment_rows_kernel, so the same bits).
+__global__ __launch_bounds__(256) void pair_moments_kernel(PairMomentArgs a)
+{
+  const int lane = threadIdx.x & 63, r16 = lane & 15, kq = lane >> 4;
+  const uint64_t wave = ((uint64_t)blockIdx.x * 256 + threadIdx.x) >> 6, nwaves = ((uint64_t)gridDim.x * 256) >> 6;
+  for (uint64_t p0 = wave * 16; p0 < a.cnt; p0 += nwaves * 16) {
+    const uint64_t p = p0 + r16;
+    uint32_t it = p < a.cnt ? a.i[p] : 0xffffffffu;
+    const bool ok = p < a.cnt && !(a.per && it == 0xffffffffu);
+    const uint32_t u = ok ? a.u[a.per ? p / a.per : p] : 0u;
+    if (!ok) it = 0u;
+    const double *et = a.Et + (size_t)u * a.ld, *st = a.St + (size_t)u * a.ld;
+    const double *eb = a.Eb + (size_t)it * a.ld, *sb = a.Sb + (size_t)it * a.ld;
+    double4_t mean = (double4_t){0.0, 0.0, 0.0, 0.0}, var = mean;
+    for (uint32_t s = 0; s < a.mean_steps; ++s) {
+      const uint32_t k = 4u * s + kq;
+      const bool in = ok && k < a.K;
+      mean = __builtin_amdgcn_mfma_f64_16x16x4f64(in ? et[k] : 0.0, in ? eb[k] : 0.0, mean, 0, 0, 0);
+    }
+    for (uint32_t s = 0; s < a.var_steps; ++s) {
+      const uint32_t c = 4u * s + kq;
+      const bool in = ok && c < a.C;
+      const double xv = in ? moment_column(et, st, c, a.K, a.ubias_col, false) : 0.0;
+      const double yv = in ? moment_column(eb, sb, c, a.K, a.ibias_col, true) : 0.0;
+      var = __builtin_amdgcn_mfma_f64_16x16x4f64(xv, yv, var, 0, 0, 0);
+    }
+    // D[i][i] for i = kq + 4 r sits in register r of lane i + 16 kq: the lanes with r16 % 4 == kq hold their own pair's
+    if ((r16 & 3) == kq) {
+      const int r = r16 >> 2;
+      double mu = r == 0 ? mean[0] : r == 1 ? mean[1] : r == 2 ? mean[2] : mean[3];
+      double vr = r == 0 ? var[0] : r == 1 ? var[1] : r == 2 ? var[2] : var[3];
+      if (ok && a.ubias_col >= 0) mu += et[a.ubias_col] + eb[a.ibias_col];        // s += Eb_u + Eb_i
+      if (!ok) mu = vr = 0.0;
+      if (p < a.cnt) {
+        if (a.out_mean) a.out_mean[p] = mu;
+        if (a.out_var) a.out_var[p] = vr;
+        if (a.out_ucb) a.out_ucb[p] = ok ? ucb_value(mu, vr, a.z) : 0.0;
+      }
+    }
+  }
+}
+
+// ---------------------------------------------------------------------
 // Why a score is what it is (hpf_explain, hpf_factor_top; -explain, -topic-items / -topic-users).
 //   explain_kernel      the T largest of the K (+ 2) non-negative terms of a pair's score, a wave per pair
 //   transpose_cols_kernel  a batch of columns of E as rows, through LDS; topn_kernel (block_topn) then takes the heaviest

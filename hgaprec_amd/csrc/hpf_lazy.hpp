@@ -69,6 +69,7 @@ enum Need : uint8_t {
   FOLD_SWEEPS_RUN, // (side) ... and, once it holds the prior, W, the start sums and E of the other side
   FOLD_SWEEPS_END, // (side) S, E and Elog of the folded-in side from its last sweep
   BECAUSE,         // E and Elog of both sides, checked: hpf_because evaluates phi per pair from them
+  MOMENTS,         // E and shape of both sides, checked: hpf_score_moments / hpf_recommend_ucb take Var = E^2 / shape from them
   N_NEEDS
 };
 
@@ -111,9 +112,11 @@ class State {
     if (obj == 2 || obj == 3) { if (kind == 2) s.have_prior = true; return; }
     if (kind == 1) return;
     if (obj <= 1) {
+      if (kind == 0) s.have_S = true;
       if (kind == 2) s.have_E = true;
       if (kind == 3) s.have_L = true;
     } else {
+      if (kind == 0) s.have_bias_S = true;
       if (kind == 2) s.have_bias_E = true;
       if (kind == 3) s.have_bias_L = true;
     }
@@ -134,9 +137,9 @@ class State {
   void folded(int sd)
   {
     Flags &s = side[sd];
-    s.have_E = s.have_L = true;
+    s.have_E = s.have_L = s.have_S = true;            // a fold-in leaves shapes
     if (cfg.hier) s.have_prior = true;
-    if (cfg.bias) s.have_bias_E = s.have_bias_L = s.bias_rate_known = true;
+    if (cfg.bias) s.have_bias_E = s.have_bias_L = s.have_bias_S = s.bias_rate_known = true;
     s.es_stale = s.l_stale = false;
     s.w_dirty = true; s.w_from_sweep = false;
     derived_dirty = sums_dirty = true;
@@ -249,6 +252,14 @@ class State {
           return p.refuse("E and Elog state not set: hand in E and ELOG of UBIAS and IBIAS (-bias), or iterate");
         p.report(); p.elog(USERS); p.elog(ITEMS);
         break;
+      // after a sweep S is the shape once ES_* has run; before the first one only what was handed in (or folded in) exists
+      case MOMENTS:
+        if (fresh && !(side[USERS].have_E && side[USERS].have_S && side[ITEMS].have_E && side[ITEMS].have_S))
+          return p.refuse("E and shape state not set: hand in THETA_E, THETA_SHAPE, BETA_E and BETA_SHAPE, or iterate");
+        if (fresh && cfg.bias && !(side[USERS].have_bias_E && side[USERS].have_bias_S && side[ITEMS].have_bias_E && side[ITEMS].have_bias_S))
+          return p.refuse("E and shape state not set: hand in E and SHAPE of UBIAS and IBIAS (-bias), or iterate");
+        p.report(); p.es(USERS); p.es(ITEMS);
+        break;
       case N_NEEDS: break;
     }
     if (p.overflow) return p.refuse("internal: too many deferred jobs");
@@ -262,8 +273,9 @@ class State {
     for (int k = 0; k < 2; ++k) {
       const Flags &s = side[k];
       const uint32_t w = (s.have_E ? 1u : 0u) | (s.have_L ? 2u : 0u) | (s.have_prior ? 4u : 0u) | (s.have_bias_E ? 8u : 0u) | (s.have_bias_L ? 16u : 0u) |
-                         (s.bias_rate_known ? 32u : 0u) | (s.w_dirty ? 64u : 0u) | (s.w_from_sweep ? 128u : 0u) | (s.l_stale ? 256u : 0u) | (s.es_stale ? 512u : 0u);
-      f |= w << (4 + 10 * k);
+                         (s.bias_rate_known ? 32u : 0u) | (s.w_dirty ? 64u : 0u) | (s.w_from_sweep ? 128u : 0u) | (s.l_stale ? 256u : 0u) | (s.es_stale ? 512u : 0u) |
+                         (s.have_S ? 1024u : 0u) | (s.have_bias_S ? 2048u : 0u);
+      f |= w << (4 + 12 * k);
     }
     return f;
   }
@@ -288,6 +300,7 @@ class State {
       s.have_E = f & SNAP_HAVE_E; s.have_L = f & SNAP_HAVE_L; s.have_prior = f & SNAP_HAVE_PRIOR; s.w_dirty = f & SNAP_W_DIRTY;
       s.l_stale = f & SNAP_L_STALE; s.es_stale = f & SNAP_ES_STALE; s.w_from_sweep = f & SNAP_W_FROM_SWEEP;
       s.have_bias_E = s.have_E; s.have_bias_L = s.have_L;      // a snapshot does not say them apart: the whole rows came with it
+      s.have_S = s.have_bias_S = false;     // HPFSNAP4 has no word for them: a handle restored before its first sweep is handed the shapes again
       s.bias_rate_known = false;
     }
     derived_dirty = derived_word != 0;
@@ -299,6 +312,7 @@ class State {
   struct Flags {
     bool have_E = false, have_L = false, have_prior = false;
     bool have_bias_E = false, have_bias_L = false;   // the bias column of E / L was handed in (a fold-in asks for the other side's)
+    bool have_S = false, have_bias_S = false;        // a shape was handed in or folded in (MOMENTS asks for it before the first sweep)
     bool bias_rate_known = false;   // a fold-in left the bias at rate r_prior + bias_rate_add (readable before the first sweep)
     bool w_dirty = false;           // L was handed in by hpf_set_state: W must be derived from it
     bool w_from_sweep = false;      // W was written by a sweep (a W-only repeat of it restores it), not derived from Elog

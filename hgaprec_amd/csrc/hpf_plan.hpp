@@ -361,6 +361,44 @@ inline BecausePlan because_plan(uint32_t K, bool bias)
   return p;
 }
 
+// ---- posterior moments of a score (hpf_score_moments, hpf_recommend_ucb) ----------------------------
+// var(u, i) = X_u . Y_i over C = 2 K + 2 * bias derived columns (moment_rows_kernel).  ucb_sweep_kernel sweeps the
+// concatenation [the K columns of E padded to whole MFMA steps | the C derived columns] with the A rows read per step: the
+// mean chain ends after mean_steps MFMAs, the variance chain takes the other var_steps.  The derived rows have the stride
+// ldx: C padded to a whole MFMA step (32-byte rows, the padding zero).  X is built for the selected users of one batch
+// (topn_batch_users: the batches are hpf_recommend's), Y once for every item.  pair_moments_kernel: a wave per MOMENTS_PAIRS
+// pairs, workgroups of MOMENTS_WAVES waves, at most MOMENTS_BLOCKS_MAX of them, which then stride; moment_rows_kernel: a
+// thread per element, the same cap.  hgaprec_amd/capi.py mirrors the arithmetic (moments_plan).
+constexpr uint32_t MOMENTS_WAVES = 4, MOMENTS_PAIRS = 16, MOMENTS_BLOCKS_MAX = 4096;
+struct MomentsPlan {
+  uint32_t C = 0, ldx = 0;              // columns and row stride of the derived rows
+  uint32_t mean_cols = 0;               // K padded to a whole MFMA step: where the derived columns begin in the concatenation
+  uint32_t mean_steps = 0, var_steps = 0;   // MFMAs of the two chains of one output: those hpf_scores issues for K and for C columns
+  bool ok = false;                      // false: C does not fit HPF_MAX_COLUMNS
+  static constexpr uint32_t pairs_per_block() { return MOMENTS_WAVES * MOMENTS_PAIRS; }
+  // selected users whose X rows are built at once: the users of a batch of the top-N sweep
+  uint32_t x_rows(uint32_t m, uint32_t n_sel, uint32_t topn, long long knob) const { return topn_batch_users(m, n_sel, topn_cap(topn), knob); }
+  // bytes of the call's derived rows: Y of every item and X of a batch
+  uint64_t derived_bytes(uint32_t m, uint32_t x_rows_) const { return ((uint64_t)m + x_rows_) * ldx * 8; }
+  // workgroups of pair_moments_kernel for cnt pairs
+  uint32_t grid_pairs(uint64_t cnt) const { return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((cnt + pairs_per_block() - 1) / pairs_per_block(), MOMENTS_BLOCKS_MAX)); }
+  // workgroups of moment_rows_kernel for `rows` derived rows
+  uint32_t grid_rows(uint32_t rows) const { return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(((uint64_t)rows * ldx + 255) / 256, MOMENTS_BLOCKS_MAX)); }
+};
+inline MomentsPlan moments_plan(uint32_t K, bool bias)
+{
+  MomentsPlan p;
+  const uint64_t C = 2ull * K + (bias ? 2u : 0u);
+  if (K < 1 || C > HPF_MAX_COLUMNS) return p;
+  p.C = (uint32_t)C;
+  p.ldx = (p.C + 3u) & ~3u;
+  p.mean_cols = (K + 3u) & ~3u;
+  p.mean_steps = p.mean_cols / 4;
+  p.var_steps = p.ldx / 4;
+  p.ok = true;
+  return p;
+}
+
 // ---- the tiled phi pass: what is tiled, and where its segments run --------------------------------
 // Policy of one side, decided before anything is allocated.  The gathered matrix (rows_oth rows of row_bytes) is cut into
 // tiles of T consecutive rows; owner rows with at least light_below nonzeros are heavy (their nonzeros are regrouped by

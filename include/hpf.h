@@ -454,6 +454,55 @@ int  hpf_audience(hpf_handle *h, const uint32_t *items, uint32_t n_sel,
                   const uint64_t *mask_ptr, const uint32_t *mask_users, uint32_t topn,
                   uint32_t *out_users /* n_sel x topn */, double *out_scores /* n_sel x topn */);
 
+/* (an extension; the reference has no counterpart.)  How sure the model is of a score.  Every theta_uk, beta_ik and bias
+ * is a Gamma with a shape and a rate; under the mean-field posterior the factors are independent, so per factor
+ *   Var(theta beta) = vt * s + q * vb,   q = m * m, vt = q / a, p = n * n, vb = p / b, s = p + vb
+ * with m = E[theta_uk], a = shape(theta_uk), n = E[beta_ik], b = shape(beta_ik) -- the doubles hpf_get_state would export
+ * at the moment of the call; each of the five is ONE IEEE fp64 operation, nothing contracted into an FMA, no reciprocal,
+ * the division correctly rounded.  The variance of a score is the sum over k, with bias plus Var(ubias_u) + Var(ibias_i),
+ * each E * E / shape formed the same way.  It is taken as ONE dot product of C = 2 K + 2 * bias columns,
+ *   X_u = [ vt_0 .. vt_{K-1} | q_0 .. q_{K-1}   | (bias:) Var ubias_u , 1.0         ]
+ *   Y_i = [ s_0  .. s_{K-1}  | vb_0 .. vb_{K-1} | (bias:) 1.0         , Var ibias_i ]
+ * by the chain hpf_scores issues (one MFMA accumulator per output over c = 0, 4, 8, ..., the tail padded by zeros): out_var
+ * is, bit for bit, the double hpf_scores returns on a handle with K' = C, no bias, E[theta] = X and E[beta] = Y.  All terms
+ * are >= 0, an element of X carries at most 2 roundings and one of Y at most 3: |var - exact| <= (C + 9) 2^-53 exact where
+ * no intermediate is subnormal.  out_mean is, bit for bit, what hpf_scores returns for the pair on this handle.
+ * Either output may be NULL.  A pair may be given twice.  Domain: the ranking calls' (E finite and >= +0.0) and shapes
+ * finite and > 0; the library does not scan them.
+ * C must fit HPF_MAX_COLUMNS -- K <= 511 with bias, K <= 512 without --, else HPF_ERR_UNSUPPORTED, as for an odd row
+ * stride; an index out of range or a null u or i is HPF_ERR_INVALID; cnt = 0 is HPF_OK.  HPF_ERR_STATE: before the first
+ * iteration E or the SHAPE of either side (with bias: of either bias) was not handed in with hpf_set_state or left by a
+ * fold-in.  A snapshot does not record that a shape was handed in: a handle that loads a snapshot taken before any
+ * iteration has to be handed the shapes again.  All of these are returned before anything is launched.
+ * Synchronous.  The model state is not written (after a sweep S becomes the shape, as for an export: the same bits
+ * hpf_get_state returns before and after, and a following hpf_iterate returns what it returns without the call).  Any
+ * n_ranks: local users only, nothing exchanged.  No CSR is needed.  Device memory beyond inputs and outputs: none (the
+ * derived columns are formed on the way). */
+int  hpf_score_moments(hpf_handle *h, const uint32_t *u, const uint32_t *i, size_t cnt,
+                       double *out_mean, double *out_var);
+
+/* (an extension.)  What to show when a guess is worth trying: hpf_recommend ordered by the optimistic score
+ *   sd = sqrt(var), t = z * sd, ucb = mean + t        (three fp64 operations, sqrt correctly rounded, nothing contracted)
+ * of the two moments above.  Arguments, masking (a masked item scores +0.0 and stays a candidate), order (ucb descending
+ * on the bit pattern, ties by ascending item), padding (0xffffffff, 0.0), batches and error cases are hpf_recommend's;
+ * topn is 1 .. 256 (only the fused route exists, as for hpf_similar / hpf_audience).  With z = 0 ucb is mean bit for bit
+ * and the lists are hpf_recommend's.
+ * For a listed item out_mean and out_var (n_sel x topn each; either may be NULL) are the pair's hpf_score_moments values
+ * bit for bit, and out_ucb is the three-operation expression of them -- also for a masked item that got listed at +0.0:
+ * the list says where it was ranked, out_ucb what it would have scored.  Padding entries are 0.0 in all three.
+ * HPF_ERR_INVALID: z < 0, NaN or infinite (a negative z gives negative scores, which the key order does not cover), topn
+ * outside 1 .. 256, a user or mask item out of range, a malformed mask_ptr, a null pointer with work to do.
+ * HPF_ERR_UNSUPPORTED: C > HPF_MAX_COLUMNS or an odd row stride.  HPF_ERR_STATE: no CSR, or no E or no shape as for
+ * hpf_score_moments.  n_sel = 0 is HPF_OK.  All returned before anything is launched.
+ * Synchronous; the model state is not written; any n_ranks (local users only).
+ * Device memory beyond inputs and outputs: hpf_recommend's bit rows and candidate buffers, and two temporaries freed when
+ * the call returns: Y, n_items x ldx doubles, and X, (users of a batch) x ldx doubles, ldx = C padded to a multiple of 4
+ * (10^5 items, K = 100: 10^5 x 200 x 8 B = 160 MB for Y). */
+int  hpf_recommend_ucb(hpf_handle *h, const uint32_t *users, uint32_t n_sel,
+                       const uint64_t *mask_ptr, const uint32_t *mask_items, uint32_t topn, double z,
+                       uint32_t *out_items /* n_sel x topn */, double *out_ucb /* n_sel x topn */,
+                       double *out_mean /* n_sel x topn, may be NULL */, double *out_var /* may be NULL */);
+
 /* (an extension; the reference has no counterpart.)  Why a score is what it is: the T largest of the terms whose sum a
  * pair's score is.  For pair p the terms are c_k = E[theta_u k] * E[beta_i k], k < K -- each ONE IEEE fp64 multiplication,
  * nothing fused into it and no reciprocal: the double returned is, bit for bit, the product a host forms from the two
