@@ -89,13 +89,20 @@ enum Repair : uint8_t {
 };
 
 // the snapshot's flag words (HPFSNAP4).  Bits 6 and 7 of a side word say which optional arrays follow: the caller's.
+// Bits 9 .. 13 say what was handed in (or folded in) before the first sweep beyond E and Elog of the factors -- a shape, the
+// bias column of E / Elog / the shape apart, the bias rate -- and bit 14 that the word says so at all: a blob written before
+// these bits existed has none of them and loads as it always did (the bias columns as the factors', no shape, no bias rate).
 enum : uint32_t {
   SNAP_HAVE_E = 1, SNAP_HAVE_L = 2, SNAP_HAVE_PRIOR = 4, SNAP_W_DIRTY = 8, SNAP_L_STALE = 16, SNAP_ES_STALE = 32,
   SNAP_RATE_SET = 64, SNAP_PRIOR_SHAPE_SET = 128, SNAP_W_FROM_SWEEP = 256,
+  SNAP_HAVE_S = 512, SNAP_HAVE_BIAS_S = 1024, SNAP_HAVE_BIAS_E = 2048, SNAP_HAVE_BIAS_L = 4096, SNAP_BIAS_RATE_KNOWN = 8192,
+  SNAP_SAYS_HANDED_IN = 16384,
   SNAP_SUMS_DIRTY = 1, SNAP_START_SUMS_DONE = 2
 };
 static_assert(SNAP_HAVE_E == 1u && SNAP_HAVE_L == 2u && SNAP_HAVE_PRIOR == 4u && SNAP_W_DIRTY == 8u && SNAP_L_STALE == 16u &&
               SNAP_ES_STALE == 32u && SNAP_RATE_SET == 64u && SNAP_PRIOR_SHAPE_SET == 128u && SNAP_W_FROM_SWEEP == 256u, "HPFSNAP4 side word");
+static_assert(SNAP_HAVE_S == 512u && SNAP_HAVE_BIAS_S == 1024u && SNAP_HAVE_BIAS_E == 2048u && SNAP_HAVE_BIAS_L == 4096u &&
+              SNAP_BIAS_RATE_KNOWN == 8192u && SNAP_SAYS_HANDED_IN == 16384u, "HPFSNAP4 side word: what was handed in");
 static_assert(SNAP_SUMS_DIRTY == 1u && SNAP_START_SUMS_DONE == 2u, "HPFSNAP4 more_flags");
 
 class State {
@@ -286,7 +293,9 @@ class State {
     const Flags &s = side[sd];
     return (s.have_E ? SNAP_HAVE_E : 0u) | (s.have_L ? SNAP_HAVE_L : 0u) | (s.have_prior ? SNAP_HAVE_PRIOR : 0u) |
            (s.w_dirty ? SNAP_W_DIRTY : 0u) | (s.l_stale ? SNAP_L_STALE : 0u) | (s.es_stale ? SNAP_ES_STALE : 0u) |
-           (rate_set ? SNAP_RATE_SET : 0u) | (prior_shape_set ? SNAP_PRIOR_SHAPE_SET : 0u) | (s.w_from_sweep ? SNAP_W_FROM_SWEEP : 0u);
+           (rate_set ? SNAP_RATE_SET : 0u) | (prior_shape_set ? SNAP_PRIOR_SHAPE_SET : 0u) | (s.w_from_sweep ? SNAP_W_FROM_SWEEP : 0u) |
+           (s.have_S ? SNAP_HAVE_S : 0u) | (s.have_bias_S ? SNAP_HAVE_BIAS_S : 0u) | (s.have_bias_E ? SNAP_HAVE_BIAS_E : 0u) |
+           (s.have_bias_L ? SNAP_HAVE_BIAS_L : 0u) | (s.bias_rate_known ? SNAP_BIAS_RATE_KNOWN : 0u) | SNAP_SAYS_HANDED_IN;
   }
   uint32_t snap_derived_dirty() const { return derived_dirty ? 1u : 0u; }
   // (a handle whose W alone was pending must not come back as one whose start sums are pending -- on several ranks it
@@ -299,9 +308,17 @@ class State {
       Flags &s = side[k]; const uint32_t f = side_words[k];
       s.have_E = f & SNAP_HAVE_E; s.have_L = f & SNAP_HAVE_L; s.have_prior = f & SNAP_HAVE_PRIOR; s.w_dirty = f & SNAP_W_DIRTY;
       s.l_stale = f & SNAP_L_STALE; s.es_stale = f & SNAP_ES_STALE; s.w_from_sweep = f & SNAP_W_FROM_SWEEP;
-      s.have_bias_E = s.have_E; s.have_bias_L = s.have_L;      // a snapshot does not say them apart: the whole rows came with it
-      s.have_S = s.have_bias_S = false;     // HPFSNAP4 has no word for them: a handle restored before its first sweep is handed the shapes again
-      s.bias_rate_known = false;
+      // The arrays came with the blob, S among them: what was handed in before the first sweep is still there, and a restored
+      // handle answers what the old one answered.  A blob from before the word said so: the whole rows count as the factors'
+      // columns do, and the shapes have to be handed in again
+      if (f & SNAP_SAYS_HANDED_IN) {
+        s.have_S = f & SNAP_HAVE_S; s.have_bias_S = f & SNAP_HAVE_BIAS_S; s.have_bias_E = f & SNAP_HAVE_BIAS_E;
+        s.have_bias_L = f & SNAP_HAVE_BIAS_L; s.bias_rate_known = f & SNAP_BIAS_RATE_KNOWN;
+      } else {
+        s.have_bias_E = s.have_E; s.have_bias_L = s.have_L;
+        s.have_S = s.have_bias_S = false;
+        s.bias_rate_known = false;
+      }
     }
     derived_dirty = derived_word != 0;
     sums_dirty = (more_flags & SNAP_SUMS_DIRTY) != 0;

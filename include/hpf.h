@@ -472,8 +472,9 @@ int  hpf_audience(hpf_handle *h, const uint32_t *items, uint32_t n_sel,
  * C must fit HPF_MAX_COLUMNS -- K <= 511 with bias, K <= 512 without --, else HPF_ERR_UNSUPPORTED, as for an odd row
  * stride; an index out of range or a null u or i is HPF_ERR_INVALID; cnt = 0 is HPF_OK.  HPF_ERR_STATE: before the first
  * iteration E or the SHAPE of either side (with bias: of either bias) was not handed in with hpf_set_state or left by a
- * fold-in.  A snapshot does not record that a shape was handed in: a handle that loads a snapshot taken before any
- * iteration has to be handed the shapes again.  All of these are returned before anything is launched.
+ * fold-in.  A snapshot records what was handed in: a handle that loads one taken before any iteration answers as the
+ * handle it was taken from (a blob written by an earlier build of the library does not say so, and the shapes have to be
+ * handed in again).  All of these are returned before anything is launched.
  * Synchronous.  The model state is not written (after a sweep S becomes the shape, as for an export: the same bits
  * hpf_get_state returns before and after, and a following hpf_iterate returns what it returns without the call).  Any
  * n_ranks: local users only, nothing exchanged.  No CSR is needed.  Device memory beyond inputs and outputs: none (the

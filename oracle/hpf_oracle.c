@@ -988,6 +988,26 @@ int orc_model_set_state(orc_model *M, int which, const double *src, size_t count
   return 0;
 }
 
+/* What theta (side 0) or beta (side 1) kept of its rate prior at the last rate update, for the ELBO (gp_set_prior_rate):
+   not one of the four arrays of a Gamma object, so a test that moves a whole side from one model into another -- a fold-in
+   run on a model of its own -- takes it along with these two. */
+size_t orc_model_prior_kept(const orc_model *M, int side, const double **ev, const double **elogv)
+{
+  const gp *g = side ? &M->beta : &M->theta;
+  if (!M->hier) { *ev = *elogv = NULL; return 0; }
+  *ev = g->hier_rprior; *elogv = g->hier_log_rprior;
+  return g->n;
+}
+
+int orc_model_set_prior_kept(orc_model *M, int side, const double *ev, const double *elogv, size_t count)
+{
+  gp *g = side ? &M->beta : &M->theta;
+  if (!M->hier || count != g->n) return -1;
+  memcpy(g->hier_rprior, ev, count * sizeof(double));
+  memcpy(g->hier_log_rprior, elogv, count * sizeof(double));
+  return 0;
+}
+
 /* ------------------------------------------------------------------ */
 /* TSV writers: D2Array<double>::save matrix.hh:1140-1166,              */
 /*              D1Array<double>::save matrix.hh:725-744                 */

@@ -117,6 +117,10 @@ size_t orc_model_state(const orc_model *M, int which, const double **ptr);
 /* overwrite E/Elog/shape state (used to start oracle and device from the
  * same arbitrary point) */
 int orc_model_set_state(orc_model *M, int which, const double *src, size_t count);
+/* E and E[log] of the rate prior of every row of theta (side 0) or beta (side 1) as the last rate update kept them for
+ * the ELBO (-hier; 0 / -1 without): state beside the four arrays, for a test that moves a whole side between models */
+size_t orc_model_prior_kept(const orc_model *M, int side, const double **ev, const double **elogv);
+int orc_model_set_prior_kept(orc_model *M, int side, const double *ev, const double *elogv, size_t count);
 orc_rng *orc_model_rng(orc_model *M);
 
 /* ---- end-to-end run mirroring main.cc + HGAPRec::vb*() ----

@@ -109,6 +109,9 @@ def lib() -> C.CDLL:
     L.orc_model_state.argtypes = [vp, C.c_int, C.POINTER(dp)]
     L.orc_model_state.restype = C.c_size_t
     L.orc_model_set_state.argtypes = [vp, C.c_int, dp, C.c_size_t]
+    L.orc_model_prior_kept.argtypes = [vp, C.c_int, C.POINTER(dp), C.POINTER(dp)]
+    L.orc_model_prior_kept.restype = C.c_size_t
+    L.orc_model_set_prior_kept.argtypes = [vp, C.c_int, dp, dp, C.c_size_t]
     L.orc_model_rng.argtypes = [vp]
     L.orc_model_rng.restype = vp
     L.orc_run.argtypes = [C.POINTER(RunArgs)]
@@ -306,6 +309,21 @@ class Model:
                                         a.ctypes.data_as(C.POINTER(C.c_double)), a.size)
         if rc:
             raise ValueError(which)
+
+    def prior_kept(self, side):
+        """-hier: (E, Elog) of the rate prior of every row of theta (side 0) or beta (side 1) as the last rate update kept
+        them for the ELBO; None without hier"""
+        e, l = C.POINTER(C.c_double)(), C.POINTER(C.c_double)()
+        cnt = self.L.orc_model_prior_kept(self._m, int(side), C.byref(e), C.byref(l))
+        if cnt == 0:
+            return None
+        return np.ctypeslib.as_array(e, shape=(cnt,)).copy(), np.ctypeslib.as_array(l, shape=(cnt,)).copy()
+
+    def set_prior_kept(self, side, kept):
+        e, l = (np.ascontiguousarray(a, dtype=np.float64) for a in kept)
+        dp = C.POINTER(C.c_double)
+        if e.shape != l.shape or self.L.orc_model_set_prior_kept(self._m, int(side), e.ctypes.data_as(dp), l.ctypes.data_as(dp), e.size):
+            raise ValueError(side)
 
     def rng_u32(self):
         return self.L.orc_rng_u32(self.L.orc_model_rng(self._m))

@@ -1,9 +1,9 @@
 """-m gpu: hpf_fold_in -- new users folded in against a frozen item side (fold_in_kernel: one launch, a wave per user, the
 user's state in registers and its gathered item rows in LDS when they fit, a stopping time per user).
 
-The CPU reference is the oracle itself: oracle.orc.Model on the same CSR, the user side at the prior, the item side a random
-trained-like state; per iteration iterate(1), then every item-side array is put back.  The oracle's user half reads only the
-OLD item side, so that is one fold-in iteration -- test_oracle_loop_is_the_fold_in_equations checks the claim against a
+The CPU reference is the oracle itself (tests/fold_ref.py): oracle.orc.Model on the same CSR, the user side at the prior,
+the item side a random trained-like state; per iteration iterate(1), then every item-side array is put back.  The oracle's
+user half reads only the OLD item side, so that is one fold-in iteration -- test_oracle_loop_is_the_fold_in_equations checks the claim against a
 numpy restatement of the equations of include/hpf.h at 1e-12.  The bar is test_gpu_parity.py's: rel_err < 1e-9 on every
 user-side array of compare_states."""
 import os
@@ -17,6 +17,7 @@ import pytest
 from hgaprec_amd import capi
 from hgaprec_amd.capi import Hpf, HpfError
 from oracle import orc
+from tests.fold_ref import item_states, oracle_fold, psi, user_states  # noqa: F401  (test_gpu_fold_in_items.py takes them from here)
 from tests.util import compare_states, rel_err
 
 pytestmark = pytest.mark.gpu
@@ -25,21 +26,8 @@ RTOL = 1e-9
 S0 = R0 = 0.3
 
 
-def psi(x):
-    x = np.asarray(x, np.float64)
-    return orc.psi(x.ravel()).reshape(x.shape)
-
-
 def _bits(a):
     return np.ascontiguousarray(a, np.float64).view(np.uint64)
-
-
-def user_states(hier, bias):
-    return [w for w in compare_states(hier, bias) if w.split("_")[0] in ("THETA", "XI", "UBIAS")]
-
-
-def item_states(hier, bias):
-    return [w for w in compare_states(hier, bias) if w.split("_")[0] in ("BETA", "ETA", "IBIAS")]
 
 
 def item_side(n, m, K, hier, bias, seed):
@@ -67,30 +55,6 @@ def make_csr(m, degs, seed, binary=False):
     col = np.concatenate(rows).astype(np.uint32) if rows else np.zeros(0, np.uint32)
     val = None if binary else rng.integers(1, 6, col.size).astype(np.uint8)
     return rowptr, col, val
-
-
-def oracle_fold(n, m, K, hier, bias, rowptr, col, val, item, T, trace=False):
-    """T fold-in iterations on the oracle -> the user-side states (trace: THETA_E after every iteration as well)"""
-    M = orc.Model(n, m, K, hier, bias, val is None)
-    M.set_csr(rowptr, col, val)
-    M.initialize(0)                                            # (the accumulators at their priors)
-    e0, l0 = S0 / R0, float(psi(S0)) - np.log(R0)
-    objs = [("THETA", (n, K), (n, K) if hier else (K,))] + ([("XI", (n,), (n,))] if hier else []) + ([("UBIAS", (n,), (n,))] if bias else [])
-    for o, shp, rshp in objs:
-        M.set_state(o + "_SHAPE", np.full(shp, S0)); M.set_state(o + "_RATE", np.full(rshp, R0))
-        M.set_state(o + "_E", np.full(shp, e0)); M.set_state(o + "_ELOG", np.full(shp, l0))
-    put_back = [w for w in item_states(hier, bias)]
-    for w in put_back:
-        M.set_state(w, item[w])
-    steps = []
-    for _ in range(T):
-        M.iterate(1)
-        for w in put_back:
-            M.set_state(w, item[w])
-        if trace:
-            steps.append(M.state("THETA_E"))
-    out = {w: M.state(w) for w in user_states(hier, bias)}
-    return (out, steps) if trace else out
 
 
 def numpy_fold(n, K, hier, bias, rowptr, col, val, item, T):

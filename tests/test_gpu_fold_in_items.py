@@ -2,7 +2,7 @@
 items with fewer than FOLD_LONG_MIN ratings; fold_in_long_kernel, a workgroup per item, for the others).
 
 The reference.  Item fold-in of (R, user side U) IS user fold-in of (R^T, item side := U) with the names exchanged, so the
-oracle is tests.test_gpu_fold_in.oracle_fold on the item-major lists (users ascending inside an item, as the upload builds
+oracle is tests.fold_ref.oracle_fold on the item-major lists (users ascending inside an item, as the upload builds
 them) with THETA <-> BETA, XI <-> ETA, UBIAS <-> IBIAS swapped.  test_oracle_loop_is_the_item_equations checks the claim
 against a numpy restatement of the item equations of include/hpf.h at 1e-12.  The bar everywhere else is the project's:
 rel_err < 1e-9 on every item-side array.
@@ -20,21 +20,16 @@ import pytest
 import tests.test_gpu_fold_in as t
 from hgaprec_amd import capi
 from hgaprec_amd.capi import Hpf, HpfError
+from tests.fold_ref import SWAP, oracle_items, swap  # noqa: F401
 from tests.util import compare_states, rel_err
 
 pytestmark = pytest.mark.gpu
 ROOT = Path(__file__).resolve().parent.parent
 RTOL = 1e-9
 S0 = R0 = t.S0
-SWAP = {"THETA": "BETA", "BETA": "THETA", "XI": "ETA", "ETA": "XI", "UBIAS": "IBIAS", "IBIAS": "UBIAS"}
 _bits = t._bits
 item_states = t.item_states
 user_states = t.user_states
-
-
-def swap(w):
-    o, _, rest = w.partition("_")
-    return SWAP[o] + "_" + rest
 
 
 def user_side(n, m, K, hier, bias, seed):
@@ -74,15 +69,6 @@ def from_lists(n, lists):
     rowptr = np.zeros(n + 1, np.int64)
     rowptr[1:] = np.cumsum(np.bincount(usr, minlength=n))
     return (colptr, usr, val), (rowptr, item_of[o], val[o])
-
-
-def oracle_items(n, m, K, hier, bias, imajor, users, T, trace=False):
-    """T item fold-in iterations on the oracle -> the item-side states (trace: BETA_E after every iteration as well)"""
-    colptr, usr, val = imajor
-    as_items = {swap(w): a for w, a in users.items()}
-    r = t.oracle_fold(m, n, K, hier, bias, colptr, usr, val, as_items, T, trace=trace)
-    out = {swap(w): a for w, a in (r[0] if trace else r).items()}
-    return (out, r[1]) if trace else out
 
 
 def numpy_items(n, m, K, hier, bias, imajor, users, T):

@@ -3,15 +3,18 @@
 The library keeps its model lazily: what a call finds pending depends on the calls before it.  Here the same
 operations run on the oracle (independent arrays: the semantics), on a handle that does exactly them, and on a twin
 that exports everything after every operation so that nothing is ever pending on it.  lazy and twin agree bit for bit;
-both agree with the oracle at the bars of tests/test_gpu_parity.py.  The directed tests pin the call orders the random
-ones led to: the first consumer after a fall-back from the packed rows, a refused call, an export before a set."""
+both agree with the oracle at the bars of tests/test_gpu_parity.py.  test_random_call_orders draws what the library
+could do when the model was written; test_random_serving_call_orders adds the two fold-ins, which write a whole side, and
+every scoring call (lists and ranks against numpy on the oracle's arrays through tests/toplist.py).  The directed tests pin
+the call orders the random ones led to: the first consumer after a fall-back from the packed rows, a refused call, an
+export before a set, a snapshot taken before the first sweep."""
 import ctypes as C
 
 import numpy as np
 import pytest
 
 from tests import statemodel as sm
-from tests.test_state_sequences_host import PACKED_SEEDS, STATE_SEEDS
+from tests.test_state_sequences_host import PACKED_SEEDS, SERVING_PACKED, SERVING_SEEDS, STATE_SEEDS
 from tests.util import compare_states, copy_state, heldout_pairs, init_states, make_problem, rel_err
 
 pytestmark = pytest.mark.gpu
@@ -35,6 +38,32 @@ def test_random_call_orders_around_a_fall_back(orc, monkeypatch, seed):
     ops = sm.with_fall_back(seed, ops)
     sm.set_env(monkeypatch, config)
     lazy, twin, _ = sm.run_three(orc, config, ops, f"seed {seed} (packed)")
+    try:
+        for D in (lazy.D, twin.D):
+            wi = D.work_info()
+            assert wi["w_fallbacks"] == 1 and wi["w_layout"] == 4, (seed, wi)
+    finally:
+        lazy.close(); twin.close()
+
+
+@pytest.mark.parametrize("seed", SERVING_SEEDS)
+def test_random_serving_call_orders(orc, monkeypatch, seed):
+    """the fold-ins and the scoring calls among the operations of test_random_call_orders: whatever a call returns is the
+    same bits on lazy and twin, and within 1e-9 of numpy on the oracle's arrays (prints the worst error per call)"""
+    config, ops = sm.serving_sequence(seed)
+    sm.set_env(monkeypatch, config)
+    lazy, twin, _ = sm.run_three(orc, config, ops, f"serving seed {seed}")
+    lazy.close(); twin.close()
+
+
+@pytest.mark.parametrize("seed", SERVING_PACKED)
+def test_random_serving_call_orders_around_a_fall_back(orc, monkeypatch, seed):
+    """the serving sequences whose config is K = 100 in packed rows, with the fall-back of
+    test_random_call_orders_around_a_fall_back woven in: a fold-in or a scoring call may be its first consumer"""
+    config, ops = sm.serving_sequence(seed)
+    ops = sm.with_fall_back(seed, ops)
+    sm.set_env(monkeypatch, config)
+    lazy, twin, _ = sm.run_three(orc, config, ops, f"serving seed {seed} (packed)")
     try:
         for D in (lazy.D, twin.D):
             wi = D.work_info()
@@ -201,7 +230,23 @@ SCORING_CONSUMERS = {
     "explain": lambda X, d: X.explain(*_pairs(d), 4),
     "factor_top_users": lambda X, d: X.factor_top(0, 10),
     "factor_top_items": lambda X, d: X.factor_top(1, 10),
+    "audience": lambda X, d: X.audience(_queries(d)[1][:4], topn=10),
+    "because": lambda X, d: X.because(_users(d), *_queries(d), 4),
+    "score_moments": lambda X, d: X.score_moments(*_pairs(d)),
+    "recommend_ucb": lambda X, d: X.recommend_ucb(_users(d), topn=10, z=1.5),
 }
+
+
+def _fold(items):
+    """a fold-in as the first consumer: the whole side replaced on both handles and in the oracle (the final comparison
+    of the test holds all three together)"""
+    def run(M, D, P, dims):
+        n, m, K, prob = dims
+        a, b = ((X.fold_in_items if items else X.fold_in)(2, 0.0) for X in (D, P))
+        assert np.array_equal(a, b) and np.all(a == 2)
+        sm.oracle_fold_into(M, n, m, K, True, False, prob, items, 2)
+        return D, P
+    return run
 
 
 CONSUMERS = {
@@ -209,7 +254,7 @@ CONSUMERS = {
     "XI_ELOG": _get("XI_ELOG"), "ETA_E": _get("ETA_E"), "THETA_E": _get("THETA_E"), "BETA_ELOG": _get("BETA_ELOG"),
     "THETA_RATE_device": _get_device("THETA_RATE"), "exchange_read": _exchange_read, "heldout_ll": _heldout(False),
     "heldout_ll_bound": _heldout(True), "elbo": _elbo, "predict": _predict, "snapshot_restore": _snapshot_restore,
-    "refused_set_state": _refused_set_state, "iterate": _iterate,
+    "refused_set_state": _refused_set_state, "iterate": _iterate, "fold_in": _fold(False), "fold_in_items": _fold(True),
 }
 CONSUMERS.update({name: _same_on_both(call) for name, call in SCORING_CONSUMERS.items()})
 
@@ -235,6 +280,87 @@ def test_first_consumer_after_a_fall_back(orc, monkeypatch, scenario, consumer):
         assert wd["w_fallbacks"] == 1 and wd["w_layout"] == 4 and wp["w_fallbacks"] == 0, (wd, wp)
     finally:
         D.close(); P.close()
+
+
+# ---- a snapshot before the first sweep hides nothing -------------------------------------------------------------------
+
+def _same_answer(call, A, B, what):
+    """a call on two handles: the same status and message, or the same bits"""
+    from hgaprec_amd.capi import HpfError
+    out = []
+    for X in (A, B):
+        try:
+            r = call(X)
+            out.append(r if isinstance(r, tuple) else (r,))
+        except HpfError as e:
+            out.append(str(e))
+    a, b = out
+    if isinstance(a, str) or isinstance(b, str):
+        assert a == b, f"{what}: the old handle answers {a if isinstance(a, str) else 'HPF_OK'!r}, the restored one {b if isinstance(b, str) else 'HPF_OK'!r}"
+    else:
+        assert sm.same_results(a, b), f"{what}: the old and the restored handle return different bits"
+    return a
+
+
+@pytest.mark.parametrize("fold", ["fold_in", "fold_in_items"])
+@pytest.mark.parametrize("hier", [False, True], ids=["flat", "hier"])
+@pytest.mark.parametrize("bias", [False, True], ids=["nobias", "bias"])
+def test_a_snapshot_before_the_first_sweep_hides_nothing(orc, bias, hier, fold):
+    """A fresh handle is handed E, Elog and the shapes and folds one side in; then snapshot, restore into a fresh handle
+    with the same CSR.  Every export of compare_states, the bias rates, score_moments, because and recommend_ucb answer
+    alike on the old and on the restored handle -- the same status and message, or the same bits -- and what the fold-in
+    left exportable (the shapes and rates of its side, the moments) is answered, not refused."""
+    from hgaprec_amd.capi import Hpf
+    n, m, K = 150, 120, 21
+    prob = make_problem(n, m, 3000, 11)
+    M = orc.Model(n, m, K, hier, bias, False)
+    M.set_csr(*prob); M.initialize(11)
+    users, pairs = _users((n, m)), _pairs((n, m))
+    q_ptr, q_items = _queries((n, m))
+    old, new = Hpf(n, m, K, hier=hier, bias=bias), Hpf(n, m, K, hier=hier, bias=bias)
+    try:
+        for X in (old, new):
+            X.upload_csr(*prob)
+        copy_state(M, old, hier, bias)
+        getattr(old, fold)(2, 0.0)
+        new.restore(old.snapshot())
+        mine = ("THETA", "XI", "UBIAS") if fold == "fold_in" else ("BETA", "ETA", "IBIAS")
+        for w in compare_states(hier, bias):
+            r = _same_answer(lambda X: X.get_state(w), old, new, w)
+            if w.split("_")[0] in mine:
+                assert not isinstance(r, str), f"{w} after {fold}: {r}"
+        calls = {"score_moments": lambda X: X.score_moments(*pairs), "because": lambda X: X.because(users, q_ptr, q_items, 4),
+                 "recommend_ucb": lambda X: X.recommend_ucb(users, topn=10, z=1.5), "recommend": lambda X: X.recommend(users, topn=10)}
+        for name, call in calls.items():
+            r = _same_answer(call, old, new, name)
+            assert not isinstance(r, str), f"{name} after {fold}: {r}"
+        # and both go on alike
+        old.iterate(1); new.iterate(1)
+        for w in compare_states(hier, bias):
+            assert sm.same_bits(old.get_state(w), new.get_state(w)), w
+    finally:
+        old.close(); new.close()
+
+
+def test_a_snapshot_does_not_grant_a_bias_column_that_was_never_handed_in(orc):
+    """-bias, THETA_E and THETA_ELOG handed in but no UBIAS_*: hpf_fold_in_items is refused, with the same message before
+    and after a snapshot round trip"""
+    from hgaprec_amd.capi import Hpf
+    n, m, K = 60, 40, 5
+    prob = make_problem(n, m, 1000, 5)
+    M = orc.Model(n, m, K, True, True, False)
+    M.set_csr(*prob); M.initialize(5)
+    old, new = Hpf(n, m, K, hier=True, bias=True), Hpf(n, m, K, hier=True, bias=True)
+    try:
+        for X in (old, new):
+            X.upload_csr(*prob)
+        for w in ("THETA_E", "THETA_ELOG"):
+            old.set_state(w, M.state(w))
+        new.restore(old.snapshot())
+        r = _same_answer(lambda X: X.fold_in_items(2, 0.0), old, new, "fold_in_items without UBIAS_*")
+        assert isinstance(r, str) and "UBIAS_E" in r, r
+    finally:
+        old.close(); new.close()
 
 
 # ---- a refused call hides nothing ---------------------------------------------------------------------------------------
