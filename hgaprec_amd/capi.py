@@ -43,7 +43,7 @@ EXPORTS = [
     "hpf_heldout_bind", "hpf_heldout_ll_bound",
     "hpf_predict", "hpf_loo_ranks", "hpf_rank_queries", "hpf_recommend", "hpf_fold_in", "hpf_similar",
     "hpf_explain", "hpf_factor_top", "hpf_fold_in_items", "hpf_because", "hpf_audience",
-    "hpf_score_moments", "hpf_recommend_ucb",
+    "hpf_score_moments", "hpf_recommend_ucb", "hpf_sample_state", "hpf_recommend_thompson",
 ]
 
 # hpf_similar: the metrics (hpf_similarity in include/hpf.h) and the largest topn (TOPN_FUSED_MAX: only the fused route exists)
@@ -360,6 +360,9 @@ def load_library(path: os.PathLike | None = None) -> C.CDLL:
     if hasattr(lib, "hpf_score_moments"):
         lib.hpf_score_moments.argtypes = [vp, u32p, u32p, C.c_size_t, dp, dp]
         lib.hpf_recommend_ucb.argtypes = [vp, u32p, C.c_uint32, u64p, u32p, C.c_uint32, C.c_double, u32p, dp, dp, dp]
+    if hasattr(lib, "hpf_sample_state"):
+        lib.hpf_sample_state.argtypes = [vp, C.c_int, u32p, C.c_uint32, C.c_uint64, C.c_uint32, dp]
+        lib.hpf_recommend_thompson.argtypes = [vp, u32p, C.c_uint32, u64p, u32p, C.c_uint32, C.c_uint64, C.c_uint32, u32p, dp]
     lib.hpf_comm_unique_id.argtypes = [vp]
     lib.hpf_comm_init.argtypes = [vp, vp]
     lib.hpf_allreduce_exchange.argtypes = [vp]
@@ -748,6 +751,45 @@ class Hpf:
         self._check(self.lib.hpf_recommend_ucb(self._h, _ptr(users, C.c_uint32), users.size, pmp, pmi, topn & 0xffffffff, float(z),
                                                _ptr(items, C.c_uint32), _ptr(ucb, C.c_double), _ptr(mean, C.c_double), _ptr(var, C.c_double)))
         return items, ucb, mean, var
+
+    def sample_state(self, side, seed=0, draw=0, ids=None, n_sel=None):
+        """one posterior draw of a side's rows (hpf_sample_state): side 0 users, 1 items; ids the rows (default: rows
+        0 .. n_sel - 1, n_sel defaulting to all of the side's) -> [rows, K + bias]: the K factor columns, then with bias the
+        side's own bias.  The (seed, draw) contract: a sample is a pure function of (seed, draw, side, row, column) -- the
+        same pair gives the same bits in every call, whatever the selection, the batches or the calls before; another draw
+        or another seed is an independent model.  seed is a uint64, draw a uint32."""
+        if ids is not None:
+            ids = np.ascontiguousarray(ids, dtype=np.uint32)
+            if ids.ndim != 1:
+                raise ValueError("ids: a one-dimensional array")
+            n_sel = ids.size
+        elif n_sel is None:
+            n_sel = self.n_items if side else self.n_users
+        out = np.empty((int(n_sel), self.K + (1 if self.bias else 0)), dtype=np.float64)
+        self._check(self.lib.hpf_sample_state(self._h, int(side), _ptr(ids, C.c_uint32) if ids is not None else None, int(n_sel),
+                                              int(seed) & 0xffffffffffffffff, int(draw) & 0xffffffff, _ptr(out, C.c_double)))
+        return out
+
+    def recommend_thompson(self, users, topn=100, seed=0, draw=0, mask_ptr=None, mask_items=None):
+        """recommend() on ONE posterior draw of both sides (hpf_recommend_thompson): Thompson sampling.  The (seed, draw)
+        contract is sample_state()'s: the lists are, bit for bit, recommend() of a handle whose E are sample_state(0, seed,
+        draw) and sample_state(1, seed, draw), and do not depend on the selection, the batches or the call order.  The item
+        side's draw is shared by all users of a (seed, draw): lists of different users are correlated through it.
+        -> (items, scores), each [len(users), topn]; entries beyond n_items are (0xffffffff, 0.0)"""
+        users = np.ascontiguousarray(users, dtype=np.uint32)
+        if users.ndim != 1:
+            raise ValueError("users: a one-dimensional array")
+        mp, mi, pmp, pmi = self._mask(mask_ptr, mask_items)
+        if mp is not None and mp.size != users.size + 1:
+            raise ValueError("mask_ptr must have len(users) + 1 entries")
+        topn = int(topn)
+        shape = (users.size, topn if 0 < topn <= RECOMMEND_FUSED_MAX else 0)
+        items = np.empty(shape, dtype=np.uint32)
+        scores = np.empty(shape, dtype=np.float64)
+        self._check(self.lib.hpf_recommend_thompson(self._h, _ptr(users, C.c_uint32), users.size, pmp, pmi, topn & 0xffffffff,
+                                                    int(seed) & 0xffffffffffffffff, int(draw) & 0xffffffff,
+                                                    _ptr(items, C.c_uint32), _ptr(scores, C.c_double)))
+        return items, scores
 
     def similar(self, side, ids, topn, metric="cosine"):
         """the topn nearest OTHER rows of one side for every selected row (hpf_similar).  side 0: rows of E[theta] (this

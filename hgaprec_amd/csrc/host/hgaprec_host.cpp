@@ -142,6 +142,27 @@ int Env::parse(int argc, char **argv, bool echo, std::string *bad)
       }
       ucb_set = true; ucb = z;
     }
+    else if (!strcmp(s, "-thompson")) {                           // extension: beside -recommend, the lists of D posterior draws
+      const char *v = next(); char *end = nullptr;
+      const long nd = strtol(v, &end, 10);
+      if (!*v || *end || nd < 1 || nd > 64) {
+        usage_error = "-thompson needs the number of posterior draws per user, 1 .. 64";
+        if (bad) *bad = s;
+        return 2;
+      }
+      thompson = (uint32_t)nd;
+    }
+    else if (!strcmp(s, "-thompson-seed")) {
+      const char *v = next(); char *end = nullptr;
+      errno = 0;
+      const unsigned long long sd = strtoull(v, &end, 10);
+      if (!isdigit((unsigned char)*v) || *end || errno == ERANGE) {
+        usage_error = "-thompson-seed needs the seed of the draws, an integer 0 .. 2^64 - 1";
+        if (bad) *bad = s;
+        return 2;
+      }
+      thompson_seed_set = true; thompson_seed = (uint64_t)sd;
+    }
     else if (!strcmp(s, "-similar-metric")) {
       const char *v = next();
       if (strcmp(v, "cosine") && strcmp(v, "dot")) {
@@ -235,6 +256,18 @@ int Env::parse(int argc, char **argv, bool echo, std::string *bad)
                 : !recommend ? "-ucb goes with -recommend N: it orders the recommended items by mean + Z sd"
                              : "-ucb needs -recommend N with N <= 256";
     if (bad) *bad = "-ucb";
+    return 2;
+  }
+  if (thompson_seed_set && !thompson) {
+    usage_error = "-thompson-seed goes with -thompson D: it seeds the posterior draws";
+    if (bad) *bad = "-thompson-seed";
+    return 2;
+  }
+  if (thompson && (audience || !recommend || recommend > 256)) {
+    usage_error = audience ? "-thompson goes with -recommend N, not with -audience"
+                : !recommend ? "-thompson goes with -recommend N: it recommends from D draws of the model from its posterior"
+                             : "-thompson needs -recommend N with N <= 256";
+    if (bad) *bad = "-thompson";
     return 2;
   }
   return 0;
@@ -1643,6 +1676,21 @@ uint64_t write_topn(FILE *f, const uint32_t *sel, size_t n_sel, const uint32_t *
       fprintf(f, "%d\t%d\t%.*f\n", row_ids[sel[b]], item_ids[it], digits, scores[b * N + j]);
       ++lines;
     }
+  return lines;
+}
+
+uint64_t write_thompson(FILE *f, const uint32_t *sel, size_t n_sel, const uint32_t *items, const double *scores, uint32_t D, uint32_t N, uint32_t real,
+                        const uint32_t *row_ids, const uint32_t *item_ids, const std::function<bool(uint32_t, uint32_t)> &keep)
+{
+  uint64_t lines = 0;
+  for (size_t b = 0; b < n_sel; ++b)
+    for (uint32_t t = 0; t < D; ++t)
+      for (uint32_t j = 0; j < real && j < N; ++j) {
+        const size_t e = ((size_t)t * n_sel + b) * N + j;
+        if (keep && !keep(sel[b], items[e])) continue;
+        fprintf(f, "%d\t%d\t%u\t%.5f\n", row_ids[sel[b]], item_ids[items[e]], t, scores[e]);
+        ++lines;
+      }
   return lines;
 }
 

@@ -108,6 +108,15 @@ struct Env {
   // -ucb without -recommend, with N > 256 or with -audience: parse() returns 2 and says why in usage_error
   bool ucb_set = false;
   double ucb = 0.0;
+  // extension: -thompson D (D = 1 .. 64 draws) goes with -recommend N, N <= 256 (also behind -fold-in); -thompson-seed S (a
+  // uint64, 0 unless given) goes with it.  Beside recommend.tsv, which is written byte for byte as without the flag, the N
+  // best items of every user in D draws of the model from its Gamma posterior through hpf_recommend_thompson(seed = S,
+  // draw = t), t < D -- recommend_thompson.tsv (user id, item id, draw, score) / .txt (users, lines, N, D, S).  The run reads
+  // the shape files as -ucb does.  D outside 1 .. 64 or no number, S no uint64, -thompson-seed without -thompson, -thompson
+  // without -recommend, with N > 256 or with -audience: parse() returns 2 and says why in usage_error
+  uint32_t thompson = 0;
+  bool thompson_seed_set = false;
+  uint64_t thompson_seed = 0;
   std::string usage_error;
   bool score_mode() const {
     return gen_ranking || rmse || msr || eval_all || recommend > 0 || !fold_in.empty() || !fold_in_items.empty() || similar_items > 0 || similar_users > 0 ||
@@ -363,6 +372,12 @@ struct ItemMaskLists {
 uint64_t write_topn(FILE *f, const uint32_t *sel, size_t n_sel, const uint32_t *items, const double *scores, uint32_t N,
                     uint32_t real, const uint32_t *row_ids, const uint32_t *item_ids,
                     const std::function<bool(uint32_t, uint32_t)> &keep = nullptr, int digits = 5);
+// The lists of D draws (-thompson) as lines "row id \t entry id \t draw \t %.5f": items / scores hold draw t's lists of the
+// n_sel rows at [t * n_sel * N ...), each as for write_topn.  Rows in the order of sel, within a row the draws ascending,
+// each list best first, under write_topn's rule (no padding, only what keep accepts).  Returns the number of lines.
+uint64_t write_thompson(FILE *f, const uint32_t *sel, size_t n_sel, const uint32_t *items, const double *scores, uint32_t D, uint32_t N,
+                        uint32_t real, const uint32_t *row_ids, const uint32_t *item_ids,
+                        const std::function<bool(uint32_t, uint32_t)> &keep = nullptr);
 
 // ------------------------------------------------------------- Comm --------
 // Host-side collectives of a multi-process run (one process per GPU): a TCP

@@ -1,4 +1,4 @@
-// score_modes.cpp -- the reports of `hgaprec` on a saved model: -rmse / -msr / -eval-all / -recommend [-explain] [-because] [-ucb] /
+// score_modes.cpp -- the reports of `hgaprec` on a saved model: -rmse / -msr / -eval-all / -recommend [-explain] [-because] [-ucb] [-thompson] /
 // -similar-items / -similar-users / -topic-items / -topic-users / -audience [-explain] / -fold-in / -fold-in-items (and -gen-ranking, which is the training run's own ranking on the loaded state).  Each
 // reads the data like a training run, loads the factor files a run has written (from the current directory like the
 // reference, or from -model-dir DIR), writes ONE report and returns.  One GPU; nothing of the training loop is seen here.
@@ -85,7 +85,7 @@ struct ScoreModes : Cli {
     env.lerr("-because: Elog of both sides formed from the shape and rate files");
   }
 
-  // -ucb Z: hpf_recommend_ucb reads the shapes beside E.  The shape files of both sides through the strict readers --
+  // -ucb Z, -thompson D: hpf_recommend_ucb and hpf_recommend_thompson read the shapes beside E.  The shape files of both sides through the strict readers --
   // htheta / hbeta or theta / beta, with -bias thetabias / betabias -- into the handle's *_SHAPE.  E stays what load_model
   // has put: recommend.tsv is that of a run without the flag.  Only a run with the flag reads these files here.
   // only_items: the handle of a fold-in, whose user side the fold-in has left with its shapes.
@@ -102,7 +102,7 @@ struct ScoreModes : Cli {
         put(user_side ? HPF_UBIAS_SHAPE : HPF_IBIAS_SHAPE, S);
       }
     }
-    env.lerr("-ucb: the shapes of %s from the shape files", only_items ? "the item side" : "both sides");
+    env.lerr("%s: the shapes of %s from the shape files", env.ucb_set ? "-ucb" : "-thompson", only_items ? "the item side" : "both sides");
   }
 
   // HGAPRec::compute_rmse (hgaprec.cc:1579-1604).  DEVIATION: the reference's -rmse never loads the model (main.cc:254-257
@@ -228,12 +228,21 @@ struct ScoreModes : Cli {
   // -ucb Z (extension): behind each chunk's lists the same users and mask lists go to hpf_recommend_ucb; <stem>_ucb.tsv:
   // user id, item id, ucb, mean, sd = sqrt(var) (%.5f each) under <stem>.tsv's rule, users in seq order, each list best
   // first by mean + Z sd.  <stem>_ucb.txt: users, lines, N, Z.  <stem>.tsv is written by the same calls as without the flag.
+  // -thompson D (extension): behind each chunk's lists the same users and mask lists go to hpf_recommend_thompson once per
+  // draw t < D with seed = -thompson-seed; <stem>_thompson.tsv: user id, item id, draw, score (%.5f) under <stem>.tsv's rule
+  // (write_thompson: users in seq order, within a user the draws ascending, each list best first).  <stem>_thompson.txt:
+  // users, lines, N, D, seed.
   unsigned long long recommend_lists(const Ratings &given, const HeldOut *mask, const std::string &stem) {
     const uint32_t N = env.recommend, T = env.explain, TB = env.because;
     const std::string rpath = env.file_str(stem + ".tsv"), epath = env.file_str(stem + "_explain.tsv"), bpath = env.file_str(stem + "_because.tsv");
     FILE *f = open_or_die(rpath, "w"), *ef = T ? open_or_die(epath, "w") : nullptr, *bf = TB ? open_or_die(bpath, "w") : nullptr;
     const std::string upath = env.file_str(stem + "_ucb.tsv");
     FILE *uf = env.ucb_set ? open_or_die(upath, "w") : nullptr;
+    const uint32_t D = env.thompson;
+    const std::string tpath = env.file_str(stem + "_thompson.tsv");
+    FILE *tf = D ? open_or_die(tpath, "w") : nullptr;
+    std::vector<uint32_t> titems; std::vector<double> tscores;
+    unsigned long long tlines = 0;
     MaskLists ml; std::vector<uint32_t> items, eu, ei, fac, rated, uitems; std::vector<double> scores, con, ucb, mean, var;
     std::vector<uint64_t> tptr;
     const HeldOut none;
@@ -260,6 +269,17 @@ struct ScoreModes : Cli {
             fprintf(uf, "%d\t%d\t%.5f\t%.5f\t%.5f\n", given.seq2user[ml.users[b]], rt.seq2item[uitems[e]], ucb[e], mean[e], sqrt(var[e]));
             ++ulines;
           }
+      }
+      if (tf) {
+        const size_t cnt = ml.users.size() * (size_t)N;
+        titems.resize(cnt * D); tscores.resize(cnt * D);
+        for (uint32_t t = 0; t < D; ++t) {
+          rc = hpf_recommend_thompson(h, ml.users.data(), (uint32_t)ml.users.size(), ml.ptr.data(), mask ? ml.items.data() : nullptr, N,
+                                      env.thompson_seed, t, titems.data() + cnt * t, tscores.data() + cnt * t);
+          if (rc) die("hpf_recommend_thompson", rc);
+        }
+        tlines += write_thompson(tf, ml.users.data(), ml.users.size(), titems.data(), tscores.data(), D, N, m, given.seq2user.data(),
+                                 rt.seq2item.data(), keep);
       }
       if (!ef && !bf) return;
       eu.clear(); ei.clear(); tptr.assign(1, 0);
@@ -293,6 +313,11 @@ struct ScoreModes : Cli {
       write_line(env.file_str(stem + "_ucb.txt"), "%u\t%llu\t%u\t%g\n", given.n, ulines, N, env.ucb);
       env.lerr("-ucb: %llu lines in %s_ucb.tsv, z = %g", ulines, stem.c_str() + 1, env.ucb);
     }
+    if (tf) {
+      close_or_die(tf, tpath);
+      write_line(env.file_str(stem + "_thompson.txt"), "%u\t%llu\t%u\t%u\t%llu\n", given.n, tlines, N, D, (unsigned long long)env.thompson_seed);
+      env.lerr("-thompson: %llu lines in %s_thompson.tsv, %u draws, seed %llu", tlines, stem.c_str() + 1, D, (unsigned long long)env.thompson_seed);
+    }
     if (ef) {
       close_or_die(ef, epath);
       write_line(env.file_str(stem + "_explain.txt"), "%llu\t%llu\t%u\n", epairs, elines, T);
@@ -307,7 +332,7 @@ struct ScoreModes : Cli {
   }
   void recommend_report() {
     if (env.because) load_model_elog();
-    if (env.ucb_set) load_model_shapes(false);
+    if (env.ucb_set || env.thompson) load_model_shapes(false);
     const unsigned long long lines = recommend_lists(rt, &rt.validation, "/recommend");
     env.lerr("-recommend: %u users, %llu lines in recommend.tsv", n, lines);
   }
@@ -419,7 +444,8 @@ struct ScoreModes : Cli {
   // (users, nonzeros, lines skipped for an unknown item, T, X, iterations min / mean / max); with -recommend N also
   // foldin_recommend.tsv / .txt, recommend_report's lines for the new users with their given ratings masked (and with -explain T
   // foldin_recommend_explain.tsv / .txt, with -because T foldin_recommend_because.tsv / .txt: the second handle holds all the call reads;
-  // with -ucb Z foldin_recommend_ucb.tsv / .txt: the item side's shapes are handed in too, the new users' the fold-in has left).
+  // with -ucb Z foldin_recommend_ucb.tsv / .txt: the item side's shapes are handed in too, the new users' the fold-in has left;
+  // with -thompson D foldin_recommend_thompson.tsv / .txt from the same shapes).
   //
   // -fold-in-items FILE (extension) is the mirror, for a catalogue that grows: the ITEMS of FILE, which need not be in -dir,
   // rated by users of -dir (Ratings::read_fold_in_items).  The USER side comes from -model-dir as shape and rate
@@ -497,7 +523,7 @@ struct ScoreModes : Cli {
                (unsigned long long)skipped, env.fold_iters, env.fold_tol, imin, rows ? isum / rows : 0.0, imax);
     env.lerr("%s: %u %s, %llu ratings, %llu lines skipped (unknown %s), iterations %u .. %u", flag, rows, items ? "items" : "users",
              (unsigned long long)nu.col.size(), (unsigned long long)skipped, items ? "user" : "item", imin, imax);
-    if (!items && env.recommend && env.ucb_set && f.h) f.load_model_shapes(true);     // after the files: the fold-in's output is that of a run without -ucb
+    if (!items && env.recommend && (env.ucb_set || env.thompson) && f.h) f.load_model_shapes(true);     // after the files: the fold-in's output is that of a run without -ucb
     if (!items && env.recommend) f.recommend_lists(nu, nullptr, "/foldin_recommend");
     if (items && env.audience) f.audience_lists(nu, nullptr, "/foldin_audience");
     if (f.h) hpf_destroy(f.h);

@@ -3101,6 +3101,94 @@ int hpf_recommend_ucb(hpf_handle *h, const uint32_t *users, uint32_t n_sel, cons
   return copy_back(h, {{out_ucb, pa.out_ucb, cnt * 8}, {out_mean, pa.out_mean, cnt * 8}, {out_var, pa.out_var, cnt * 8}});
 }
 
+// ---- one posterior draw: its rows, and the top-N of it ----
+namespace {
+// gamma_rows_kernel over `rows` rows of one side into out [rows x ld]: sel names the rows (and the counter's row ids), or
+// null for rows 0 .. rows - 1
+void launch_gamma_rows(hpf_handle *h, int side, const uint32_t *sel, uint32_t rows, uint64_t seed, uint32_t draw, double *out)
+{
+  const Side &s = side ? h->it : h->u;
+  GammaRowsArgs ga;
+  ga.E = s.E; ga.S = s.S; ga.sel = sel; ga.out = out; ga.seed = seed; ga.rows = rows; ga.ld = h->ld; ga.K = h->K;
+  ga.bias_col = h->cfg.bias ? s.bias_col : -1; ga.object = side ? 1u : 0u; ga.draw = draw;
+  hipLaunchKernelGGL(gamma_rows_kernel, dim3(hpf_plan::sample_plan(rows, h->ld).grid), dim3(256), 0, h->stream, ga);
+}
+}  // namespace
+
+// One draw of a side's rows, dense: gamma_rows_kernel into rows of the handle's stride, sample_pack_kernel into the host
+// layout, piece by piece (hpf_plan::sample_piece_rows).  E and the shapes of both sides as for the other posterior calls
+// (hpf_lazy::MOMENTS); no CSR, the state only read.
+int hpf_sample_state(hpf_handle *h, int side, const uint32_t *ids, uint32_t n_sel, uint64_t seed, uint32_t draw, double *out)
+{
+  if (!h) return HPF_ERR_INVALID;
+  if (side != 0 && side != 1) { h->err = "hpf_sample_state: side is 0 (users) or 1 (items)"; return HPF_ERR_INVALID; }
+  if (!n_sel) return HPF_OK;
+  if (!out) { h->err = "hpf_sample_state: null pointer"; return HPF_ERR_INVALID; }
+  const Side &s = side ? h->it : h->u;
+  int rc;
+  if ((rc = ready(h, hpf_lazy::MOMENTS, -1, -1, [&] {
+        bool ok = ids || n_sel <= s.rows;
+        for (uint32_t b = 0; ids && ok && b < n_sel; ++b) ok = ids[b] < s.rows;
+        if (!ok) { h->err = side ? "item index out of range" : "user index out of range"; return (int)HPF_ERR_INVALID; }
+        return (int)HPF_OK;
+      }))) return rc;
+  const uint32_t C = h->K + (h->cfg.bias ? 1u : 0u), piece = hpf_plan::sample_piece_rows(n_sel, h->ld);
+  std::vector<uint32_t> own;                                     // rows 0 .. n_sel - 1 in several pieces: their ids spelled out
+  if (!ids && n_sel > piece) { own.resize(n_sel); for (uint32_t b = 0; b < n_sel; ++b) own[b] = b; ids = own.data(); }
+  Scratch sc(h);
+  uint32_t *d_ids = nullptr; double *rows_ld = nullptr, *dense = nullptr;
+  if ((ids && (rc = sc.alloc(&d_ids, n_sel, ids))) || (rc = sc.alloc(&rows_ld, (size_t)piece * h->ld)) || (rc = sc.alloc(&dense, (size_t)piece * C))) return rc;
+  for (uint32_t b0 = 0; b0 < n_sel; b0 += piece) {
+    const uint32_t rows = std::min(piece, n_sel - b0);
+    launch_gamma_rows(h, side, d_ids ? d_ids + b0 : nullptr, rows, seed, draw, rows_ld);
+    hipLaunchKernelGGL(sample_pack_kernel, dim3(grid_for((uint64_t)rows * C)), dim3(256), 0, h->stream, rows_ld, dense, (uint64_t)rows, h->ld, h->K,
+                       h->cfg.bias ? s.bias_col : -1);
+    if ((rc = check_launch(h, "gamma_rows_kernel/sample_pack_kernel"))) return rc;
+    if ((rc = copy_back(h, {{out + (size_t)b0 * C, dense, (size_t)rows * C * 8}}))) return rc;
+  }
+  return HPF_OK;
+}
+
+// hpf_recommend on one posterior draw: its checks, bit rows, batches, candidate buffers and merge (topn_run) and its sweep
+// kernel, topn_sweep_kernel, over two temporaries of the call in the place of E -- the item side's draw, built once, and the
+// draw of the users of each batch, whose rows the sweep addresses as 0 .. rows - 1 while the counters carry the users' ids.
+int hpf_recommend_thompson(hpf_handle *h, const uint32_t *users, uint32_t n_sel, const uint64_t *mask_ptr, const uint32_t *mask_items,
+                           uint32_t topn, uint64_t seed, uint32_t draw, uint32_t *out_items, double *out_scores)
+{
+  if (!h) return HPF_ERR_INVALID;
+  if (!hpf_plan::topn_fused(topn)) { h->err = "hpf_recommend_thompson: topn is 1 .. 256"; return HPF_ERR_INVALID; }
+  if (n_sel && (!users || !out_items || !out_scores)) { h->err = "hpf_recommend_thompson: null pointer"; return HPF_ERR_INVALID; }
+  if (!n_sel) return HPF_OK;
+  const uint32_t m = h->it.rows;
+  if (h->ld & 1u) { h->err = "hpf_recommend_thompson: odd row stride"; return HPF_ERR_UNSUPPORTED; }
+  int rc;
+  if ((rc = ready(h, hpf_lazy::MOMENTS, -1, -1, [&] { return rank_check(h, users, n_sel, mask_ptr, mask_items); }))) return rc;
+  FusedCtx c(h);
+  if ((rc = c.upload(users, n_sel, mask_ptr, mask_items)) || (rc = c.bit_rows(n_sel, m))) return rc;
+  const uint32_t t_rows = hpf_plan::topn_batch_users(m, n_sel, hpf_plan::topn_cap(topn), h->loo_batch);     // topn_run's batch
+  std::vector<uint32_t> own(t_rows);
+  for (uint32_t b = 0; b < t_rows; ++b) own[b] = b;
+  double *Tt = nullptr, *Bt = nullptr; uint32_t *d_own = nullptr;
+  if ((rc = c.alloc(&Bt, (size_t)m * h->ld)) || (rc = c.alloc(&Tt, (size_t)t_rows * h->ld)) || (rc = c.alloc(&d_own, t_rows, own.data()))) return rc;
+  launch_gamma_rows(h, 1, nullptr, m, seed, draw, Bt);
+  if ((rc = check_launch(h, "gamma_rows_kernel"))) return rc;
+  TopnArgs a;
+  factor_args(h, a);
+  a.Et = Tt; a.Eb = Bt;
+  a.bits = c.d_bits; a.words = c.words;
+  return topn_run(c, a, m, n_sel, topn, std::min(topn, m), "topn_sweep_kernel",
+                  [&](uint32_t b0, uint32_t rows) {
+                    if (rows > t_rows) { h->err = "hpf_recommend_thompson: a batch beyond the sampled rows"; return (int)HPF_ERR_HIP; }
+                    launch_gamma_rows(h, 0, c.d_users + b0, rows, seed, draw, Tt);
+                    return c.mask_batch(b0, rows, h->rowptr_dev, h->u.idx, h->u.val);
+                  },
+                  [&](auto nch, dim3 grid, const TopnArgs &ta) {
+                    TopnArgs sa = ta;
+                    sa.users = d_own;                            // row b of the batch's draw belongs to selected user b0 + b
+                    hipLaunchKernelGGL(topn_sweep_kernel<decltype(nch)::value>, grid, dim3(256), 0, h->stream, sa);
+                  }, out_items, out_scores);
+}
+
 // The T largest terms of every pair's score (explain_kernel): hpf_predict's readiness path and argument checks, no CSR,
 // the state only read.
 static_assert(HPF_EXPLAIN_MAX == hpf_plan::EXPLAIN_MAX && HPF_EXPLAIN_MAX <= 64, "a lane of the wave per returned term");

@@ -21,6 +21,7 @@
 #include <type_traits>
 
 #include "hpf_plan.hpp"   // plain C++: the constexpr arithmetic a kernel shares with its plan (fold_part)
+#include "hpf_rng.hpp"    // host and device: Philox4x32-10 and the Gamma sampler of gamma_rows_kernel
 
 // Build-time switches (A/B builds of tools/ and profiles/ only; the library ships the defaults)
 #ifndef HPF_REDUCE_SCATTER
@@ -3498,6 +3499,54 @@ __global__ __launch_bounds__(256) void pair_moments_kernel(PairMomentArgs a)
         if (a.out_ucb) a.out_ucb[p] = ok ? ucb_value(mu, vr, a.z) : 0.0;
       }
     }
+  }
+}
+
+// ---------------------------------------------------------------------
+// One posterior draw of a side's rows (hpf_sample_state, hpf_recommend_thompson).
+//   gamma_rows_kernel   out[r][c] = a Gamma(S, S / E) variate (hpf_rng::gamma_sample) for the K factor columns and the
+//                       side's own bias column, 0.0 for every other column of the row: the junk column and the padding up
+//                       to ld.  The rows stand in for rows of E behind topn_sweep_kernel, whose chain is padded with zeros.
+//                       A variate is a function of (seed, draw, object, the row's id on its side, column) alone.
+//   sample_pack_kernel  the sampled rows as hpf_sample_state hands them out: K factor columns, then the bias
+// The rejection loop of the sampler diverges inside a wave (about one lane in twenty tries again): a plain bounded loop in
+// registers, nothing crosses lanes, no LDS.
+// ---------------------------------------------------------------------
+struct GammaRowsArgs {
+  const double   *E, *S;     // [side rows x ld] expectations and shapes of the side
+  const uint32_t *sel;       // [rows] the side's rows to draw, also the counter's row ids; or null: rows 0 .. rows - 1
+  double         *out;       // [rows x ld]
+  uint64_t        seed;
+  uint32_t        rows, ld, K;
+  int32_t         bias_col;  // the side's own bias column, -1 without -bias
+  uint32_t        object;    // 0: user side, 1: item side
+  uint32_t        draw;
+};
+
+// a thread per element of the output rows, the columns that are not sampled included
+__global__ __launch_bounds__(256) void gamma_rows_kernel(GammaRowsArgs a)
+{
+  const uint64_t n = (uint64_t)a.rows * a.ld;
+  for (uint64_t e = (uint64_t)blockIdx.x * 256 + threadIdx.x; e < n; e += (uint64_t)gridDim.x * 256) {
+    const uint32_t r = (uint32_t)(e / a.ld), c = (uint32_t)(e % a.ld);
+    double v = 0.0;
+    if (c < a.K || (int32_t)c == a.bias_col) {
+      const uint32_t id = a.sel ? a.sel[r] : r;
+      const size_t src = (size_t)id * a.ld + c;
+      v = hpf_rng::gamma_sample(a.seed, a.draw, a.object, id, c, a.E[src], a.S[src], nullptr);
+    }
+    a.out[e] = v;
+  }
+}
+
+// dense [rows x C], C = K + (bias_col >= 0): columns 0 .. K - 1 of a sampled row, then its bias column
+__global__ __launch_bounds__(256) void sample_pack_kernel(const double *rows_ld, double *out, uint64_t rows, uint32_t ld, uint32_t K, int32_t bias_col)
+{
+  const uint32_t C = K + (bias_col >= 0 ? 1u : 0u);
+  const uint64_t n = rows * C;
+  for (uint64_t e = (uint64_t)blockIdx.x * 256 + threadIdx.x; e < n; e += (uint64_t)gridDim.x * 256) {
+    const uint64_t r = e / C; const uint32_t c = (uint32_t)(e % C);
+    out[e] = rows_ld[r * ld + (c < K ? c : (uint32_t)bias_col)];
   }
 }
 

@@ -399,6 +399,31 @@ inline MomentsPlan moments_plan(uint32_t K, bool bias)
   return p;
 }
 
+// ---- one posterior draw of a side's rows (hpf_sample_state, hpf_recommend_thompson) -----------------
+// gamma_rows_kernel: a thread per element of rows x ld output doubles (the padding columns are written too, as zeros), 256
+// threads a workgroup, at most SAMPLE_BLOCKS_MAX workgroups, which then stride -- MomentsPlan::grid_rows' cap.
+// hpf_recommend_thompson keeps the item side's draw (n_items x ld doubles) for the call and the user side's per batch of
+// the top-N sweep (topn_batch_users: the batches are hpf_recommend's); hpf_sample_state works through its rows in pieces
+// of at most SAMPLE_PIECE_BYTES of sampled rows.
+constexpr uint32_t SAMPLE_BLOCKS_MAX = MOMENTS_BLOCKS_MAX;
+constexpr uint64_t SAMPLE_PIECE_BYTES = 256ull << 20;
+struct SamplePlan {
+  uint64_t elements = 0;                // rows x ld
+  uint32_t grid = 1;                    // workgroups of gamma_rows_kernel
+};
+inline SamplePlan sample_plan(uint64_t rows, uint32_t ld)
+{
+  SamplePlan p;
+  p.elements = rows * ld;
+  p.grid = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((p.elements + 255) / 256, SAMPLE_BLOCKS_MAX));
+  return p;
+}
+// rows of one piece of hpf_sample_state
+inline uint32_t sample_piece_rows(uint32_t n_sel, uint32_t ld)
+{
+  return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(n_sel, SAMPLE_PIECE_BYTES / ((uint64_t)std::max(ld, 1u) * 8)));
+}
+
 // ---- the tiled phi pass: what is tiled, and where its segments run --------------------------------
 // Policy of one side, decided before anything is allocated.  The gathered matrix (rows_oth rows of row_bytes) is cut into
 // tiles of T consecutive rows; owner rows with at least light_below nonzeros are heavy (their nonzeros are regrouped by

@@ -90,6 +90,9 @@ def lib():
     L.hg_item_mask_lists_get.argtypes = [vp, C.c_int, C.POINTER(vp)]; L.hg_item_mask_lists_get.restype = C.c_uint64
     L.hg_write_topn.argtypes = [C.c_char_p, vp, u32p, C.c_uint64, u32p, dp, C.c_uint32, C.c_uint32, u32p, u32p]
     L.hg_write_topn.restype = C.c_int64
+    if hasattr(L, "hg_write_thompson"):
+        L.hg_write_thompson.argtypes = [C.c_char_p, vp, u32p, C.c_uint64, u32p, dp, C.c_uint32, C.c_uint32, C.c_uint32, u32p, u32p]
+        L.hg_write_thompson.restype = C.c_int64
     _lib = L
     return L
 
@@ -388,6 +391,25 @@ def write_topn(path, sel, items, scores, real, row_ids, item_ids, given=None) ->
     n = lib().hg_write_topn(str(path).encode(), None if given is None else given._r, s.ctypes.data_as(u32p), s.size,
                             it.ctypes.data_as(u32p), sc.ctypes.data_as(C.POINTER(C.c_double)), it.shape[1], int(real),
                             ri.ctypes.data_as(u32p), ii.ctypes.data_as(u32p))
+    if n < 0:
+        raise OSError(f"cannot write {path}")
+    return n
+
+
+def write_thompson(path, sel, items, scores, real, row_ids, item_ids, given=None) -> int:
+    """the writer of recommend_thompson.tsv: items / scores are (D, len(sel), N), draw t's lists of the selected rows; the
+    lines are user id, item id, draw, score -- rows in the order of sel, within a row the draws ascending, under
+    write_topn's rule.  Returns the number of lines"""
+    s = np.ascontiguousarray(sel, np.uint32)
+    it = np.ascontiguousarray(items, np.uint32)
+    sc = np.ascontiguousarray(scores, np.float64)
+    if it.ndim != 3 or it.shape[1] != s.size or sc.shape != it.shape:
+        raise ValueError("items and scores: (draws, len(sel), N)")
+    ri, ii = np.ascontiguousarray(row_ids, np.uint32), np.ascontiguousarray(item_ids, np.uint32)
+    u32p = C.POINTER(C.c_uint32)
+    n = lib().hg_write_thompson(str(path).encode(), None if given is None else given._r, s.ctypes.data_as(u32p), s.size,
+                                it.ctypes.data_as(u32p), sc.ctypes.data_as(C.POINTER(C.c_double)), it.shape[0], it.shape[2], int(real),
+                                ri.ctypes.data_as(u32p), ii.ctypes.data_as(u32p))
     if n < 0:
         raise OSError(f"cannot write {path}")
     return n

@@ -504,6 +504,48 @@ int  hpf_recommend_ucb(hpf_handle *h, const uint32_t *users, uint32_t n_sel,
                        uint32_t *out_items /* n_sel x topn */, double *out_ucb /* n_sel x topn */,
                        double *out_mean /* n_sel x topn, may be NULL */, double *out_var /* may be NULL */);
 
+/* (an extension.)  Thompson sampling: one draw of the model from its posterior, and the top-N of that draw.  Every
+ * theta_uk, beta_ik and bias is a Gamma(shape, rate) with E = shape / rate; an element's sample is g * (E / shape) with g a
+ * Gamma(shape, 1) variate, so the rate is never read.  The variate is a pure function of (seed, draw, side, row, column):
+ * Philox4x32-10 (multipliers D2511F53 / CD9E8D57, key increments 9E3779B9 / BB67AE85) with the key (seed low, seed high) and,
+ * for block b of attempt j, the counter (column, row, draw, side | b << 4 | j << 8) -- side 0 users, 1 items; row the LOCAL
+ * user index or the item index; column the element's column in the handle's row layout (factor k at k; with bias the user
+ * bias at K, the item bias at K + 1).  Two words x, y give u = ((x >> 6) 2^26 + (y >> 6) + 0.5) 2^-52; block 0 gives u1, u2,
+ * block 1 u3, u4.  Marsaglia-Tsang with a' = a < 1 ? a + 1 : a, d = a' - 1/3, cc = 1 / sqrt(9 d), for j = 0 .. 31:
+ *   z = sqrt(-2 log u1) cos(2 pi u2); w = cc z; w > -1 and log u3 < z^2 / 2 + d (3 log1p(w) - w (3 + w (3 + w))) accepts
+ *   g = d (1 + w)^3; for a < 1 then g = g exp(log(u4) / a).
+ * Each line is one fp64 operation or one ocml call, nothing contracted (hgaprec_amd/csrc/hpf_rng.hpp compiles for host and
+ * device; tests/thompson_ref.py is the numpy statement).  It does not depend on batches, grid, selection or call order:
+ * the same (seed, draw) gives the same bits in every call, another draw or seed an independent model.
+ * Domain: E finite and >= +0.0, shapes finite and > 0 (not scanned): every sample is finite and >= +0.0 (E = +0.0 gives
+ * +0.0; a tiny shape may give +0.0), so the key order of the ranking calls covers a draw.
+ *
+ * hpf_sample_state: the draw of rows ids[0 .. n_sel) of one side (ids NULL: rows 0 .. n_sel - 1), out[n_sel x C], C = K +
+ * bias, dense row-major: the K factor columns, then (bias) the side's own bias -- the host layout hpf_get_state uses for
+ * THETA_E / BETA_E with UBIAS_E / IBIAS_E appended.  A row may be named twice.
+ *
+ * hpf_recommend_thompson: hpf_recommend on ONE draw (seed, draw) of both sides -- bit for bit, items and scores, what
+ * hpf_recommend returns on a handle whose E are the two hpf_sample_state outputs: score = theta~ . beta~ (+ ubias~ + ibias~),
+ * masking (a masked item scores +0.0 and stays a candidate), order, padding (0xffffffff, 0.0) and batches hpf_recommend's.
+ * The item side is drawn ONCE per (seed, draw) and shared by all users of the call (and of every call with that pair): each
+ * user's list is marginally a Thompson draw, the lists of different users are correlated through beta~.  topn is 1 .. 256
+ * (only the fused route exists).
+ *
+ * HPF_ERR_INVALID: a side other than 0 or 1, an index out of range, a null pointer with work to do, and for the recommend
+ * call hpf_recommend's cases (topn outside 1 .. 256 here).  HPF_ERR_STATE: no CSR (the recommend call), or no E or no shape
+ * as for hpf_score_moments.  HPF_ERR_UNSUPPORTED: an odd row stride (the recommend call).  n_sel = 0 is HPF_OK.  All
+ * returned before anything is launched.
+ * Synchronous; the model state is not written (as for hpf_score_moments); any n_ranks (local users only).
+ * Device memory beyond inputs and outputs, freed when the call returns: hpf_sample_state a piece of at most 256 MB of
+ * sampled rows and its dense copy; hpf_recommend_thompson hpf_recommend's bit rows and candidate buffers, beta~ of n_items x
+ * ld doubles and theta~ of (users of a batch) x ld doubles, ld the handle's row stride. */
+int  hpf_sample_state(hpf_handle *h, int side, const uint32_t *ids, uint32_t n_sel,   /* ids NULL: rows 0 .. n_sel-1 */
+                      uint64_t seed, uint32_t draw, double *out /* n_sel x (K + bias) */);
+int  hpf_recommend_thompson(hpf_handle *h, const uint32_t *users, uint32_t n_sel,
+                            const uint64_t *mask_ptr, const uint32_t *mask_items, uint32_t topn,
+                            uint64_t seed, uint32_t draw,
+                            uint32_t *out_items /* n_sel x topn */, double *out_scores /* n_sel x topn */);
+
 /* (an extension; the reference has no counterpart.)  Why a score is what it is: the T largest of the terms whose sum a
  * pair's score is.  For pair p the terms are c_k = E[theta_u k] * E[beta_i k], k < K -- each ONE IEEE fp64 multiplication,
  * nothing fused into it and no reciprocal: the double returned is, bit for bit, the product a host forms from the two
