@@ -44,6 +44,7 @@ EXPORTS = [
     "hpf_predict", "hpf_loo_ranks", "hpf_rank_queries", "hpf_recommend", "hpf_fold_in", "hpf_similar",
     "hpf_explain", "hpf_factor_top", "hpf_fold_in_items", "hpf_because", "hpf_audience",
     "hpf_score_moments", "hpf_recommend_ucb", "hpf_sample_state", "hpf_recommend_thompson",
+    "hpf_recommend_diverse",
 ]
 
 # hpf_similar: the metrics (hpf_similarity in include/hpf.h) and the largest topn (TOPN_FUSED_MAX: only the fused route exists)
@@ -64,6 +65,9 @@ RANK_QUERIES_QCAP = 32
 
 # largest topn hpf_recommend runs fused (TOPN_FUSED_MAX in csrc/hpf_plan.hpp); above it, up to 1024, hpf_rank_topn's route
 RECOMMEND_FUSED_MAX = 256
+
+# largest pool (and topn) of hpf_recommend_diverse (HPF_DIVERSE_POOL_MAX in include/hpf.h)
+DIVERSE_POOL_MAX = 256
 
 
 def recommend_cap(topn):
@@ -363,6 +367,8 @@ def load_library(path: os.PathLike | None = None) -> C.CDLL:
     if hasattr(lib, "hpf_sample_state"):
         lib.hpf_sample_state.argtypes = [vp, C.c_int, u32p, C.c_uint32, C.c_uint64, C.c_uint32, dp]
         lib.hpf_recommend_thompson.argtypes = [vp, u32p, C.c_uint32, u64p, u32p, C.c_uint32, C.c_uint64, C.c_uint32, u32p, dp]
+    if hasattr(lib, "hpf_recommend_diverse"):
+        lib.hpf_recommend_diverse.argtypes = [vp, u32p, C.c_uint32, u64p, u32p, C.c_uint32, C.c_uint32, C.c_double, u32p, dp, dp, dp]
     lib.hpf_comm_unique_id.argtypes = [vp]
     lib.hpf_comm_init.argtypes = [vp, vp]
     lib.hpf_allreduce_exchange.argtypes = [vp]
@@ -790,6 +796,33 @@ class Hpf:
                                                     int(seed) & 0xffffffffffffffff, int(draw) & 0xffffffff,
                                                     _ptr(items, C.c_uint32), _ptr(scores, C.c_double)))
         return items, scores
+
+    def recommend_diverse(self, users, topn, pool=None, lam=0.7, mask_ptr=None, mask_items=None):
+        """recommend() re-ranked for diversity (hpf_recommend_diverse): greedy maximal marginal relevance over the pool of
+        the user's `pool` best items with a score > 0 (default min(256, 4 topn); topn <= pool <= 256).  Pick t is the
+        unpicked pool entry with the largest lam * score / best score - (1 - lam) * maxsim, maxsim the largest cosine (over
+        the K factor columns of E[beta], as similar(1, ..., "cosine") defines it) to an item picked before; ties go to the
+        entry recommend() lists first.  Every step is one fp64 operation: the result depends only on the user's pool, not on
+        the selection, the batches or the call order.
+        The lambda = 1 identity: with lam = 1 the lists are, bit for bit, the entries of recommend(users, topn) with a
+        score > 0, then padding; with pool == topn a list is a permutation of them.  The first pick is always recommend()'s.
+        -> (items, scores, maxsim, mmr), each [len(users), topn]: the item, its recommend() score, its maxsim when it was
+        picked and its key; entries beyond the pool are (0xffffffff, 0.0, 0.0, 0.0)"""
+        users = np.ascontiguousarray(users, dtype=np.uint32)
+        if users.ndim != 1:
+            raise ValueError("users: a one-dimensional array")
+        mp, mi, pmp, pmi = self._mask(mask_ptr, mask_items)
+        if mp is not None and mp.size != users.size + 1:
+            raise ValueError("mask_ptr must have len(users) + 1 entries")
+        topn = int(topn)
+        pool = min(DIVERSE_POOL_MAX, 4 * topn) if pool is None else int(pool)
+        shape = (users.size, topn if 0 < topn <= DIVERSE_POOL_MAX else 0)
+        items = np.empty(shape, dtype=np.uint32)
+        scores, maxsim, mmr = (np.empty(shape, dtype=np.float64) for _ in range(3))
+        self._check(self.lib.hpf_recommend_diverse(self._h, _ptr(users, C.c_uint32), users.size, pmp, pmi, topn & 0xffffffff,
+                                                   pool & 0xffffffff, float(lam), _ptr(items, C.c_uint32), _ptr(scores, C.c_double),
+                                                   _ptr(maxsim, C.c_double), _ptr(mmr, C.c_double)))
+        return items, scores, maxsim, mmr
 
     def similar(self, side, ids, topn, metric="cosine"):
         """the topn nearest OTHER rows of one side for every selected row (hpf_similar).  side 0: rows of E[theta] (this

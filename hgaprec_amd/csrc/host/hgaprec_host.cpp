@@ -163,6 +163,26 @@ int Env::parse(int argc, char **argv, bool echo, std::string *bad)
       }
       thompson_seed_set = true; thompson_seed = (uint64_t)sd;
     }
+    else if (!strcmp(s, "-diverse")) {                            // extension: beside -recommend, the lists re-ranked by greedy MMR
+      const char *v = next(); char *end = nullptr;
+      const double l = strtod(v, &end);
+      if (!*v || end == v || *end || !(l >= 0.0 && l <= 1.0)) {
+        usage_error = "-diverse needs the weight of relevance against similarity, a number in [0, 1]";
+        if (bad) *bad = s;
+        return 2;
+      }
+      diverse_set = true; diverse = l;
+    }
+    else if (!strcmp(s, "-diverse-pool")) {
+      const char *v = next(); char *end = nullptr;
+      const long np = strtol(v, &end, 10);
+      if (!*v || *end || np < 1 || np > 256) {
+        usage_error = "-diverse-pool needs the number of candidates per user, N .. 256";
+        if (bad) *bad = s;
+        return 2;
+      }
+      diverse_pool = (uint32_t)np;
+    }
     else if (!strcmp(s, "-similar-metric")) {
       const char *v = next();
       if (strcmp(v, "cosine") && strcmp(v, "dot")) {
@@ -270,6 +290,25 @@ int Env::parse(int argc, char **argv, bool echo, std::string *bad)
     if (bad) *bad = "-thompson";
     return 2;
   }
+  if (diverse_pool && !diverse_set) {
+    usage_error = "-diverse-pool goes with -diverse L: it sizes the pool the lists are re-ranked from";
+    if (bad) *bad = "-diverse-pool";
+    return 2;
+  }
+  if (diverse_set && (audience || !recommend || recommend > 256 || ngpus > 1)) {
+    usage_error = audience ? "-diverse goes with -recommend N, not with -audience"
+                : !recommend ? "-diverse goes with -recommend N: it re-ranks the recommended items by relevance minus similarity to what is already picked"
+                : recommend > 256 ? "-diverse needs -recommend N with N <= 256"
+                                  : "-diverse scores a saved model on one GPU: run it without -ngpus";
+    if (bad) *bad = "-diverse";
+    return 2;
+  }
+  if (diverse_set && diverse_pool && diverse_pool < recommend) {
+    usage_error = "-diverse-pool needs the number of candidates per user, N .. 256";
+    if (bad) *bad = "-diverse-pool";
+    return 2;
+  }
+  if (diverse_set && !diverse_pool) diverse_pool = std::min<uint32_t>(256, 4 * recommend);
   return 0;
 }
 
@@ -1691,6 +1730,22 @@ uint64_t write_thompson(FILE *f, const uint32_t *sel, size_t n_sel, const uint32
         fprintf(f, "%d\t%d\t%u\t%.5f\n", row_ids[sel[b]], item_ids[items[e]], t, scores[e]);
         ++lines;
       }
+  return lines;
+}
+
+uint64_t write_diverse(FILE *f, const uint32_t *sel, size_t n_sel, const uint32_t *items, const double *scores, const double *maxsim, uint32_t N,
+                       const uint32_t *row_ids, const uint32_t *item_ids, const std::function<bool(uint32_t, uint32_t)> &keep, double *maxsim_sum)
+{
+  uint64_t lines = 0;
+  for (size_t b = 0; b < n_sel; ++b)
+    for (uint32_t j = 0; j < N; ++j) {
+      const size_t e = b * N + j;
+      if (items[e] == 0xffffffffu) break;                          // padding: the list is over
+      if (keep && !keep(sel[b], items[e])) continue;
+      fprintf(f, "%d\t%d\t%.5f\t%.5f\n", row_ids[sel[b]], item_ids[items[e]], scores[e], maxsim[e]);
+      if (maxsim_sum) *maxsim_sum += maxsim[e];
+      ++lines;
+    }
   return lines;
 }
 

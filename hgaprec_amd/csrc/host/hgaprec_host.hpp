@@ -117,6 +117,16 @@ struct Env {
   uint32_t thompson = 0;
   bool thompson_seed_set = false;
   uint64_t thompson_seed = 0;
+  // extension: -diverse L (L in [0, 1]) goes with -recommend N, N <= 256 (also behind -fold-in); -diverse-pool P (N <= P <=
+  // 256, min(256, 4 N) unless given) goes with it.  Beside recommend.tsv, which is written byte for byte as without the flag,
+  // every user's list re-ranked by greedy MMR from a pool of P candidates through hpf_recommend_diverse(topn = N, pool = P,
+  // lambda = L) -- recommend_diverse.tsv (user id, item id, score, maxsim) / .txt (users, lines, N, P, L, mean maxsim).
+  // L no number or outside [0, 1], P outside N .. 256, -diverse-pool without -diverse, -diverse without -recommend, with
+  // N > 256, with -audience or with -ngpus: parse() returns 2 and says why in usage_error.  After parse() diverse_pool is
+  // the pool of the run
+  bool diverse_set = false;
+  double diverse = 0.0;
+  uint32_t diverse_pool = 0;
   std::string usage_error;
   bool score_mode() const {
     return gen_ranking || rmse || msr || eval_all || recommend > 0 || !fold_in.empty() || !fold_in_items.empty() || similar_items > 0 || similar_users > 0 ||
@@ -378,6 +388,13 @@ uint64_t write_topn(FILE *f, const uint32_t *sel, size_t n_sel, const uint32_t *
 uint64_t write_thompson(FILE *f, const uint32_t *sel, size_t n_sel, const uint32_t *items, const double *scores, uint32_t D, uint32_t N,
                         uint32_t real, const uint32_t *row_ids, const uint32_t *item_ids,
                         const std::function<bool(uint32_t, uint32_t)> &keep = nullptr);
+// The re-ranked lists (-diverse) as lines "row id \t entry id \t %.5f \t %.5f" (score, maxsim): items / scores / maxsim as
+// hpf_recommend_diverse returns them, [n_sel x N].  Rows in the order of sel, each list in pick order up to its first
+// padding entry (0xffffffff), only what keep accepts.  Returns the number of lines; maxsim_sum, where given, grows by the
+// maxsim of every line written.
+uint64_t write_diverse(FILE *f, const uint32_t *sel, size_t n_sel, const uint32_t *items, const double *scores, const double *maxsim,
+                       uint32_t N, const uint32_t *row_ids, const uint32_t *item_ids,
+                       const std::function<bool(uint32_t, uint32_t)> &keep = nullptr, double *maxsim_sum = nullptr);
 
 // ------------------------------------------------------------- Comm --------
 // Host-side collectives of a multi-process run (one process per GPU): a TCP

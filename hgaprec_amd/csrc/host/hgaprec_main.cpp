@@ -13,7 +13,7 @@
 // stand-in (`-comm host`, for tests on a single GPU).  The output files are
 // the same as in a single-GPU run.
 //
-// Scoring a saved model (-gen-ranking / -rmse / -msr / -eval-all / -recommend [-explain] [-because] [-ucb] [-thompson] / -fold-in / -fold-in-items / -similar-items /
+// Scoring a saved model (-gen-ranking / -rmse / -msr / -eval-all / -recommend [-explain] [-because] [-ucb] [-thompson] [-diverse] / -fold-in / -fold-in-items / -similar-items /
 // -similar-users / -topic-items / -topic-users / -audience [-explain]) sets the run up the same way and then writes ONE report instead of training: score(), score_modes.cpp.
 // What both halves share -- flags, ratings, handle, the ways to fail -- is struct Cli (hgaprec_cli.hpp).
 //
@@ -838,7 +838,7 @@ int main(int argc, char **argv)
     fprintf(stderr, "error: option %s selects a mode outside the MI355X hot-path build "
                     "(supported: -dir -n -m -k -hier -bias -binary-data -rfreq -max-iterations "
                     "-seed -label -rating-threshold -logl -novb -a -b -c -d, -gen-ranking -rmse -msr -eval-all -recommend -fold-in -fold-in-items -fold-iters -fold-tol "
-                    "-similar-items -similar-users -similar-metric -topic-items -topic-users -explain -because -audience -ucb -thompson -thompson-seed -model-dir, "
+                    "-similar-items -similar-users -similar-metric -topic-items -topic-users -explain -because -audience -ucb -thompson -thompson-seed -diverse -diverse-pool -model-dir, "
                     "-ngpus -comm -single-allreduce -device)\n", env.unsupported.c_str());
     return 2;
   }

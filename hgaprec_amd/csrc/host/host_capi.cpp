@@ -239,6 +239,20 @@ int64_t hg_write_thompson(const char *path, const Ratings *given, const uint32_t
   const uint64_t lines = write_thompson(f, sel, (size_t)n_sel, items, scores, D, N, real, row_ids, item_ids, keep);
   return (ferror(f) | fclose(f)) ? -1 : (int64_t)lines;
 }
+// write_diverse into a new file, as hg_write_topn: items / scores / maxsim are [n_sel x N]; *maxsim_sum (may be null) the sum
+// of the maxsim column
+int64_t hg_write_diverse(const char *path, const Ratings *given, const uint32_t *sel, uint64_t n_sel, const uint32_t *items,
+                         const double *scores, const double *maxsim, uint32_t N, const uint32_t *row_ids, const uint32_t *item_ids,
+                         double *maxsim_sum)
+{
+  FILE *f = fopen(path, "w");
+  if (!f) return -1;
+  std::function<bool(uint32_t, uint32_t)> keep;
+  if (given) keep = [given](uint32_t u, uint32_t it) { return given->r(u, it) == 0; };
+  if (maxsim_sum) *maxsim_sum = 0.0;
+  const uint64_t lines = write_diverse(f, sel, (size_t)n_sel, items, scores, maxsim, N, row_ids, item_ids, keep, maxsim_sum);
+  return (ferror(f) | fclose(f)) ? -1 : (int64_t)lines;
+}
 
 // -eval-all's arithmetic from ranks to metrics.  per_user: n_users x 6 integers (ntest, hits10, hits100, best_rank,
 // sum_rank, nranked as given); means: users, pairs, precision@10, precision@100, recall@100, mrr, meanrank

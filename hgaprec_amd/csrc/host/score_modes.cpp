@@ -1,4 +1,4 @@
-// score_modes.cpp -- the reports of `hgaprec` on a saved model: -rmse / -msr / -eval-all / -recommend [-explain] [-because] [-ucb] [-thompson] /
+// score_modes.cpp -- the reports of `hgaprec` on a saved model: -rmse / -msr / -eval-all / -recommend [-explain] [-because] [-ucb] [-thompson] [-diverse] /
 // -similar-items / -similar-users / -topic-items / -topic-users / -audience [-explain] / -fold-in / -fold-in-items (and -gen-ranking, which is the training run's own ranking on the loaded state).  Each
 // reads the data like a training run, loads the factor files a run has written (from the current directory like the
 // reference, or from -model-dir DIR), writes ONE report and returns.  One GPU; nothing of the training loop is seen here.
@@ -232,6 +232,9 @@ struct ScoreModes : Cli {
   // draw t < D with seed = -thompson-seed; <stem>_thompson.tsv: user id, item id, draw, score (%.5f) under <stem>.tsv's rule
   // (write_thompson: users in seq order, within a user the draws ascending, each list best first).  <stem>_thompson.txt:
   // users, lines, N, D, seed.
+  // -diverse L (extension): behind each chunk's lists the same users and mask lists go to hpf_recommend_diverse(topn = N, pool
+  // = -diverse-pool, lambda = L); <stem>_diverse.tsv: user id, item id, score, maxsim (%.5f each; write_diverse: users in seq
+  // order, each list in pick order, no padding).  <stem>_diverse.txt: users, lines, N, P, L, the mean maxsim of the lines.
   unsigned long long recommend_lists(const Ratings &given, const HeldOut *mask, const std::string &stem) {
     const uint32_t N = env.recommend, T = env.explain, TB = env.because;
     const std::string rpath = env.file_str(stem + ".tsv"), epath = env.file_str(stem + "_explain.tsv"), bpath = env.file_str(stem + "_because.tsv");
@@ -243,6 +246,10 @@ struct ScoreModes : Cli {
     FILE *tf = D ? open_or_die(tpath, "w") : nullptr;
     std::vector<uint32_t> titems; std::vector<double> tscores;
     unsigned long long tlines = 0;
+    const std::string dpath = env.file_str(stem + "_diverse.tsv");
+    FILE *df = env.diverse_set ? open_or_die(dpath, "w") : nullptr;
+    std::vector<uint32_t> ditems; std::vector<double> dscores, dmaxsim;
+    unsigned long long dlines = 0; double dsum = 0.0;
     MaskLists ml; std::vector<uint32_t> items, eu, ei, fac, rated, uitems; std::vector<double> scores, con, ucb, mean, var;
     std::vector<uint64_t> tptr;
     const HeldOut none;
@@ -281,6 +288,15 @@ struct ScoreModes : Cli {
         tlines += write_thompson(tf, ml.users.data(), ml.users.size(), titems.data(), tscores.data(), D, N, m, given.seq2user.data(),
                                  rt.seq2item.data(), keep);
       }
+      if (df) {
+        const size_t cnt = ml.users.size() * (size_t)N;
+        ditems.resize(cnt); dscores.resize(cnt); dmaxsim.resize(cnt);
+        rc = hpf_recommend_diverse(h, ml.users.data(), (uint32_t)ml.users.size(), ml.ptr.data(), mask ? ml.items.data() : nullptr, N,
+                                   env.diverse_pool, env.diverse, ditems.data(), dscores.data(), dmaxsim.data(), nullptr);
+        if (rc) die("hpf_recommend_diverse", rc);
+        dlines += write_diverse(df, ml.users.data(), ml.users.size(), ditems.data(), dscores.data(), dmaxsim.data(), N, given.seq2user.data(),
+                                rt.seq2item.data(), keep, &dsum);
+      }
       if (!ef && !bf) return;
       eu.clear(); ei.clear(); tptr.assign(1, 0);
       for (size_t b = 0; b < ml.users.size(); ++b) {
@@ -312,6 +328,13 @@ struct ScoreModes : Cli {
       close_or_die(uf, upath);
       write_line(env.file_str(stem + "_ucb.txt"), "%u\t%llu\t%u\t%g\n", given.n, ulines, N, env.ucb);
       env.lerr("-ucb: %llu lines in %s_ucb.tsv, z = %g", ulines, stem.c_str() + 1, env.ucb);
+    }
+    if (df) {
+      close_or_die(df, dpath);
+      write_line(env.file_str(stem + "_diverse.txt"), "%u\t%llu\t%u\t%u\t%g\t%.5f\n", given.n, dlines, N, env.diverse_pool, env.diverse,
+                 dlines ? dsum / (double)dlines : 0.0);
+      env.lerr("-diverse: %llu lines in %s_diverse.tsv, pool %u, lambda %g, mean maxsim %.5f", dlines, stem.c_str() + 1, env.diverse_pool,
+               env.diverse, dlines ? dsum / (double)dlines : 0.0);
     }
     if (tf) {
       close_or_die(tf, tpath);
@@ -445,7 +468,8 @@ struct ScoreModes : Cli {
   // foldin_recommend.tsv / .txt, recommend_report's lines for the new users with their given ratings masked (and with -explain T
   // foldin_recommend_explain.tsv / .txt, with -because T foldin_recommend_because.tsv / .txt: the second handle holds all the call reads;
   // with -ucb Z foldin_recommend_ucb.tsv / .txt: the item side's shapes are handed in too, the new users' the fold-in has left;
-  // with -thompson D foldin_recommend_thompson.tsv / .txt from the same shapes).
+  // with -thompson D foldin_recommend_thompson.tsv / .txt from the same shapes; with -diverse L foldin_recommend_diverse.tsv /
+  // .txt, which needs nothing beyond E).
   //
   // -fold-in-items FILE (extension) is the mirror, for a catalogue that grows: the ITEMS of FILE, which need not be in -dir,
   // rated by users of -dir (Ratings::read_fold_in_items).  The USER side comes from -model-dir as shape and rate

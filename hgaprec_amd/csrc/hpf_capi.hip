@@ -1220,9 +1220,11 @@ int copy_back(hpf_handle *h, std::initializer_list<HostOut> outs)
 // (hpf_plan::topn_batch_users), nothing of n_sel x m.  `a` comes with the factor pointers, the bias columns and the bit rows
 // of the caller; batch(b0, rows) readies the bit rows of a batch.  A list has `real` entries; the rest is padding.
 // lists_dev: where a caller that goes on with the lists on the device (hpf_recommend_ucb) finds the items; c owns them.
+// scores_dev: the same for the scores (hpf_recommend_diverse).
 template <typename Batch, typename Sweep>
 int topn_run(FusedCtx &c, TopnArgs a, uint32_t m, uint32_t n_sel, uint32_t topn, uint32_t real, const char *kernel,
-             Batch &&batch, Sweep &&sweep, uint32_t *out_items, double *out_scores, uint32_t **lists_dev = nullptr)
+             Batch &&batch, Sweep &&sweep, uint32_t *out_items, double *out_scores, uint32_t **lists_dev = nullptr,
+             double **scores_dev = nullptr)
 {
   hpf_handle *h = c.h; int rc;
   const uint32_t ntiles = (m + 63) / 64, cap = hpf_plan::topn_cap(topn), NP = hpf_plan::pow2_ceil(topn);
@@ -1235,6 +1237,7 @@ int topn_run(FusedCtx &c, TopnArgs a, uint32_t m, uint32_t n_sel, uint32_t topn,
   if ((rc = c.alloc(&a.ckey, nseg * cap)) || (rc = c.alloc(&a.citem, nseg * cap)) || (rc = c.alloc(&a.ccount, nseg)) ||
       (rc = c.alloc(&d_items, (size_t)n_sel * topn)) || (rc = c.alloc(&d_sc, (size_t)n_sel * topn))) return rc;
   if (lists_dev) *lists_dev = d_items;
+  if (scores_dev) *scores_dev = d_sc;
   a.m = m; a.topn = topn; a.cap = cap; a.lg_cap = hpf_plan::log2_of(cap);
   const std::string what = std::string(kernel) + "/topn_merge_kernel";
   for (uint32_t b0 = 0; b0 < n_sel; b0 += c.batch) {
@@ -3187,6 +3190,70 @@ int hpf_recommend_thompson(hpf_handle *h, const uint32_t *users, uint32_t n_sel,
                     sa.users = d_own;                            // row b of the batch's draw belongs to selected user b0 + b
                     hipLaunchKernelGGL(topn_sweep_kernel<decltype(nch)::value>, grid, dim3(256), 0, h->stream, sa);
                   }, out_items, out_scores);
+}
+
+// ---- diversified top-N: greedy MMR over the pool hpf_recommend finds ----
+static_assert(HPF_DIVERSE_POOL_MAX == hpf_plan::DIVERSE_POOL_MAX && HPF_DIVERSE_POOL_MAX <= hpf_plan::TOPN_FUSED_MAX,
+              "the pool is a list of the fused top-N route, a thread of the workgroup per entry");
+namespace {
+// compute units of the handle's device: what diverse_plan sizes the persistent grid by (speed only, never results)
+uint32_t device_cus(const hpf_handle *h)
+{
+  int cus = 0;
+  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->cfg.device) != hipSuccess || cus < 1) return 256;
+  return (uint32_t)cus;
+}
+}  // namespace
+
+// hpf_recommend at topn = pool with the lists left on the device (topn_run), the unit rows of E[beta] as hpf_similar makes
+// them, then mmr_kernel per batch of users: the pool's Gram matrix into the workgroups' slabs and the greedy selection.
+int hpf_recommend_diverse(hpf_handle *h, const uint32_t *users, uint32_t n_sel, const uint64_t *mask_ptr, const uint32_t *mask_items,
+                          uint32_t topn, uint32_t pool, double lambda, uint32_t *out_items, double *out_scores, double *out_maxsim,
+                          double *out_mmr)
+{
+  if (!h) return HPF_ERR_INVALID;
+  if (topn < 1 || topn > HPF_DIVERSE_POOL_MAX) { h->err = "hpf_recommend_diverse: topn is 1 .. 256"; return HPF_ERR_INVALID; }
+  if (pool < topn || pool > HPF_DIVERSE_POOL_MAX) { h->err = "hpf_recommend_diverse: pool is topn .. 256"; return HPF_ERR_INVALID; }
+  if (!(lambda >= 0.0 && lambda <= 1.0)) { h->err = "hpf_recommend_diverse: lambda is in [0, 1]"; return HPF_ERR_INVALID; }
+  if (n_sel && (!users || !out_items || !out_scores)) { h->err = "hpf_recommend_diverse: null pointer"; return HPF_ERR_INVALID; }
+  if (!n_sel) return HPF_OK;
+  const uint32_t m = h->it.rows;
+  if (h->ld & 1u) { h->err = "hpf_recommend_diverse: odd row stride"; return HPF_ERR_UNSUPPORTED; }
+  int rc;
+  if ((rc = fused_ready(h, users, n_sel, mask_ptr, mask_items))) return rc;
+  FusedCtx c(h);
+  if ((rc = c.upload(users, n_sel, mask_ptr, mask_items)) || (rc = c.bit_rows(n_sel, m))) return rc;
+  double *d_unit = nullptr;
+  if ((rc = c.alloc(&d_unit, (size_t)m * h->ld))) return rc;
+  hipLaunchKernelGGL(unit_rows_kernel, dim3(std::min<uint32_t>((m + 15) / 16, 16384)), dim3(256), 0, h->stream, h->it.E, d_unit, m, h->ld, h->K);
+  if ((rc = check_launch(h, "unit_rows_kernel"))) return rc;
+  TopnArgs a;
+  factor_args(h, a);
+  a.bits = c.d_bits; a.words = c.words;
+  uint32_t *d_pool = nullptr; double *d_pool_sc = nullptr;
+  if ((rc = topn_run(c, a, m, n_sel, pool, std::min(pool, m), "topn_sweep_kernel",
+                     [&](uint32_t b0, uint32_t rows) { return c.mask_batch(b0, rows, h->rowptr_dev, h->u.idx, h->u.val); },
+                     [&](auto nch, dim3 grid, const TopnArgs &ta) {
+                       hipLaunchKernelGGL(topn_sweep_kernel<decltype(nch)::value>, grid, dim3(256), 0, h->stream, ta);
+                     }, nullptr, nullptr, &d_pool, &d_pool_sc))) return rc;
+  const uint32_t per = std::min(std::max(c.batch, 1u), n_sel);
+  const hpf_plan::DiversePlan dp = hpf_plan::diverse_plan(pool, per, h->K, device_cus(h));
+  if (!dp.ok) { h->err = "hpf_recommend_diverse: no plan"; return HPF_ERR_INVALID; }
+  const size_t cnt = (size_t)n_sel * topn;
+  MmrArgs ma;
+  ma.U = d_unit; ma.rows = m; ma.ld = h->ld; ma.K = h->K; ma.pool = pool; ma.topn = topn; ma.Pp = dp.Pp; ma.lambda = lambda;
+  if ((rc = c.alloc(&ma.slab, (size_t)dp.workgroups * dp.Pp * dp.Pp)) || (rc = c.alloc(&ma.out_items, cnt)) || (rc = c.alloc(&ma.out_scores, cnt)) ||
+      (rc = c.alloc(&ma.out_maxsim, cnt)) || (rc = c.alloc(&ma.out_mmr, cnt))) return rc;
+  uint32_t *d_items = ma.out_items; double *d_sc = ma.out_scores, *d_ms = ma.out_maxsim, *d_mmr = ma.out_mmr;
+  for (uint32_t b0 = 0; b0 < n_sel; b0 += per) {
+    const uint32_t rows = std::min(n_sel - b0, per);
+    ma.pool_items = d_pool + (size_t)b0 * pool; ma.pool_scores = d_pool_sc + (size_t)b0 * pool; ma.n_sel = rows;
+    ma.out_items = d_items + (size_t)b0 * topn; ma.out_scores = d_sc + (size_t)b0 * topn;
+    ma.out_maxsim = d_ms + (size_t)b0 * topn; ma.out_mmr = d_mmr + (size_t)b0 * topn;
+    hipLaunchKernelGGL(mmr_kernel, dim3(std::min(dp.workgroups, rows)), dim3(256), 0, h->stream, ma);
+    if ((rc = check_launch(h, "mmr_kernel"))) return rc;
+  }
+  return copy_back(h, {{out_items, d_items, cnt * 4}, {out_scores, d_sc, cnt * 8}, {out_maxsim, d_ms, cnt * 8}, {out_mmr, d_mmr, cnt * 8}});
 }
 
 // The T largest terms of every pair's score (explain_kernel): hpf_predict's readiness path and argument checks, no CSR,

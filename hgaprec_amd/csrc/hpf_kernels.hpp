@@ -3551,6 +3551,129 @@ __global__ __launch_bounds__(256) void sample_pack_kernel(const double *rows_ld,
 }
 
 // ---------------------------------------------------------------------
+// Diversified top-N: greedy maximal marginal relevance over a user's candidate pool (hpf_recommend_diverse; DESIGN.md
+// section 4l).
+//   mmr_kernel   a workgroup per selected user, a persistent grid.  Gram phase: the cosines of the pool's items -- rows of U
+//                (unit_rows_kernel) gathered by id, the MFMA chain of score_tile_kernel per output -- into the workgroup's
+//                slab of device memory.  Selection phase: thread j owns pool entry j; per round a key, an arg-max over the
+//                workgroup (ties to the smaller j) and one row of the slab.
+// Every line of the selection is one fp64 operation, nothing contracted, the division the correctly rounded one.
+// ---------------------------------------------------------------------
+struct MmrArgs {
+  const double   *U;            // [rows x ld] unit rows of E[beta]
+  const uint32_t *pool_items;   // [n_sel x pool] hpf_recommend's lists at topn = pool
+  const double   *pool_scores;  // [n_sel x pool]
+  double         *slab;         // [gridDim.x x Pp x Pp]
+  uint32_t       *out_items;    // [n_sel x topn]
+  double         *out_scores, *out_maxsim, *out_mmr;
+  double          lambda;
+  uint32_t        rows, ld, K, n_sel, pool, topn, Pp;
+};
+
+__global__ __launch_bounds__(256) void mmr_kernel(MmrArgs a)
+{
+#pragma clang fp contract(off)
+  constexpr uint32_t W = hpf_plan::DIVERSE_WAVES, STRIP = hpf_plan::DIVERSE_STRIP;
+  static_assert(W * 64 == hpf_plan::DIVERSE_POOL_MAX, "a thread per pool entry");
+  __shared__ uint32_t s_item[hpf_plan::DIVERSE_POOL_MAX];
+  __shared__ uint32_t s_P;
+  __shared__ double   s_r0;
+  __shared__ double   s_key[2][W];
+  __shared__ uint32_t s_pos[2][W];
+  static_assert(sizeof(s_item) + sizeof(s_P) + 4 /* s_r0 is aligned to 8 */ + sizeof(s_r0) + sizeof(s_key) + sizeof(s_pos) == hpf_plan::DIVERSE_LDS_BYTES, "DiversePlan::lds_bytes");
+  const uint32_t j = threadIdx.x, lane = j & 63u, wv = j >> 6, r16 = lane & 15u, kq = lane >> 4;
+  double *G = a.slab + (size_t)blockIdx.x * a.Pp * a.Pp;
+  const double om = 1.0 - a.lambda;
+  for (uint32_t b = blockIdx.x; b < a.n_sel; b += gridDim.x) {
+    // ---- the pool: the prefix of the list whose scores are > +0.0 (and whose items exist: nothing is gathered out of U)
+    uint32_t c = 0xffffffffu; double r = 0.0;
+    if (j < a.pool) { c = a.pool_items[(size_t)b * a.pool + j]; r = a.pool_scores[(size_t)b * a.pool + j]; }
+    const bool in = j < a.pool && r > 0.0 && c < a.rows;
+    __syncthreads();                                             // the user before is over: its P, its slab, its last round
+    if (j == 0) { s_P = a.pool; s_r0 = r; }
+    __syncthreads();
+    if (!in && j < a.pool) atomicMin(&s_P, j);
+    s_item[j] = in ? c : 0u;
+    __syncthreads();
+    const uint32_t P = s_P, side = (P + 15u) / 16u;
+
+    // ---- Gram phase: tile (ti, tj) = U[pool rows of ti] x U[pool rows of tj]^T, strips of STRIP tiles of one tile row
+    for (uint32_t s = wv; s < hpf_plan::diverse_strips(side); s += W) {
+      const hpf_plan::DiverseStrip st = hpf_plan::diverse_strip(s, side);
+      const uint32_t ti = st.ti, tj0 = st.tj0;
+      const uint32_t ja = ti * 16 + r16;
+      const bool oka = ja < P;
+      const double *pa = a.U + (size_t)s_item[ja & (hpf_plan::DIVERSE_POOL_MAX - 1)] * a.ld;
+      const double *pb[STRIP]; bool okb[STRIP];
+#pragma unroll
+      for (uint32_t t = 0; t < STRIP; ++t) {
+        const uint32_t jb = (tj0 + t) * 16 + r16;
+        okb[t] = tj0 + t < side && jb < P;
+        pb[t] = a.U + (size_t)s_item[jb & (hpf_plan::DIVERSE_POOL_MAX - 1)] * a.ld;
+      }
+      double4_t acc[STRIP];
+#pragma unroll
+      for (uint32_t t = 0; t < STRIP; ++t) acc[t] = (double4_t){0.0, 0.0, 0.0, 0.0};
+      for (uint32_t k0 = 0; k0 < a.K; k0 += 4) {
+        const uint32_t k = k0 + kq;
+        const bool okk = k < a.K;
+        const double av = (okk && oka) ? pa[k] : 0.0;              // A[i = lane%16][k = lane/16]
+#pragma unroll
+        for (uint32_t t = 0; t < STRIP; ++t) {
+          const double bv = (okk && okb[t]) ? pb[t][k] : 0.0;     // B[k = lane/16][j = lane%16]
+          acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(av, bv, acc[t], 0, 0, 0);
+        }
+      }
+      // register q holds D[i = lane/16 + 4 q][j = lane%16]; rows and columns < side * 16 <= Pp stay inside the slab
+#pragma unroll
+      for (uint32_t t = 0; t < STRIP; ++t) {
+        if (tj0 + t >= side) continue;
+#pragma unroll
+        for (uint32_t q = 0; q < 4; ++q)
+          G[(size_t)(ti * 16 + kq + 4 * q) * a.Pp + (tj0 + t) * 16 + r16] = acc[t][q];
+      }
+    }
+    __syncthreads();
+
+    // ---- selection phase
+    bool alive = j < P;
+    const double rel = alive ? r / s_r0 : 0.0;
+    double pen = 0.0;
+    const uint32_t picks = a.topn < P ? a.topn : P;
+    const size_t o0 = (size_t)b * a.topn;
+    for (uint32_t t = 0; t < picks; ++t) {
+      const double lr = a.lambda * rel;
+      const double op = om * pen;
+      const double key = lr - op;
+      double bk = alive ? key : -INFINITY; uint32_t bj = alive ? j : 0xffffffffu;
+#pragma unroll
+      for (int d = 1; d < 64; d <<= 1) {
+        const double ok = __shfl_xor(bk, d, 64);
+        const uint32_t oj = (uint32_t)__shfl_xor((int)bj, d, 64);
+        if (oj != 0xffffffffu && (bj == 0xffffffffu || ok > bk || (ok == bk && oj < bj))) { bk = ok; bj = oj; }
+      }
+      const uint32_t buf = t & 1u;
+      if (lane == 0) { s_key[buf][wv] = bk; s_pos[buf][wv] = bj; }
+      __syncthreads();                                           // two buffers: round t + 1 writes the other one
+      bk = s_key[buf][0]; bj = s_pos[buf][0];
+#pragma unroll
+      for (uint32_t w = 1; w < W; ++w) {
+        const double ok = s_key[buf][w]; const uint32_t oj = s_pos[buf][w];
+        if (oj != 0xffffffffu && (bj == 0xffffffffu || ok > bk || (ok == bk && oj < bj))) { bk = ok; bj = oj; }
+      }
+      if (j == bj) {
+        a.out_items[o0 + t] = c; a.out_scores[o0 + t] = r; a.out_maxsim[o0 + t] = pen; a.out_mmr[o0 + t] = key;
+        alive = false;
+      }
+      if (alive && bj < P) pen = fmax(pen, G[(size_t)bj * a.Pp + j]);   // one entry at least is alive in every round: bj < P
+    }
+    for (uint32_t t = picks + j; t < a.topn; t += 256) {
+      a.out_items[o0 + t] = 0xffffffffu; a.out_scores[o0 + t] = 0.0; a.out_maxsim[o0 + t] = 0.0; a.out_mmr[o0 + t] = 0.0;
+    }
+  }
+}
+
+// ---------------------------------------------------------------------
 // Why a score is what it is (hpf_explain, hpf_factor_top; -explain, -topic-items / -topic-users).
 //   explain_kernel      the T largest of the K (+ 2) non-negative terms of a pair's score, a wave per pair
 //   transpose_cols_kernel  a batch of columns of E as rows, through LDS; topn_kernel (block_topn) then takes the heaviest

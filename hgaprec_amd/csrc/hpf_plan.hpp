@@ -424,6 +424,61 @@ inline uint32_t sample_piece_rows(uint32_t n_sel, uint32_t ld)
   return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(n_sel, SAMPLE_PIECE_BYTES / ((uint64_t)std::max(ld, 1u) * 8)));
 }
 
+// ---- diversified top-N (hpf_recommend_diverse) -------------------------------------------------------
+// mmr_kernel: a workgroup of DIVERSE_WAVES waves per selected user, a persistent grid that strides over the users of a
+// launch.  The pool of a user (at most `pool` entries) is padded to Pp, whole 16 x 16 MFMA tiles; its Gram matrix has
+// side^2 tiles of `steps` MFMAs each (K columns, four a step, the tail padded by zeros).  A wave takes strips of up to
+// DIVERSE_STRIP tiles of one tile row (one A fragment, DIVERSE_STRIP accumulators), the strips dealt round-robin to the
+// waves.  Every workgroup owns a slab of Pp x Pp doubles in device memory for the matrix; the slabs of one launch total at
+// most DIVERSE_SLABS_BYTES, which caps the grid beside DIVERSE_WGS_PER_CU workgroups a CU and the users of the launch.
+// LDS: the pool's item ids, the prefix length and two buffers of the waves' arg-max (key, position).
+constexpr uint32_t DIVERSE_POOL_MAX = 256;      // HPF_DIVERSE_POOL_MAX of hpf.h (pinned there by hpf_capi.hip): a thread per pool entry
+constexpr uint32_t DIVERSE_WAVES = 4, DIVERSE_STRIP = 4, DIVERSE_WGS_PER_CU = 8;
+constexpr uint64_t DIVERSE_SLABS_BYTES = 256ull << 20;
+constexpr uint32_t DIVERSE_LDS_BYTES = DIVERSE_POOL_MAX * 4 + 16 + 2 * DIVERSE_WAVES * (8 + 4);   // ids, P and r_0, two arg-max buffers
+// Strip s of a Gram matrix of `side` tiles a side: its tile row and its first tile column.  Strips 0 .. side - 1 are the
+// first DIVERSE_STRIP tile columns of every tile row, the next `side` strips the next columns, ...: the short strips of a
+// ragged side come last.  Wave w of a workgroup takes strips w, w + DIVERSE_WAVES, ...  mmr_kernel walks with this very
+// function, so what the selftest checks of the walk is the kernel's walk.
+struct DiverseStrip { uint32_t ti, tj0; };
+constexpr DiverseStrip diverse_strip(uint32_t s, uint32_t side) { return DiverseStrip{s % side, (s / side) * DIVERSE_STRIP}; }
+constexpr uint32_t diverse_strips(uint32_t side) { return side * ((side + DIVERSE_STRIP - 1) / DIVERSE_STRIP); }
+// tiles, steps, strips, tiles_per_wave and lds_bytes are not launch parameters (the kernel derives its walk from each
+// user's own P through diverse_strip, and its LDS is static): they describe the work for DESIGN.md's estimates and let the
+// selftest hold the walk and the kernel's static LDS (a static_assert in hpf_kernels.hpp) to the committed table.
+struct DiversePlan {
+  uint32_t Pp = 0;                      // the pool padded to whole tiles; also the slab's row stride, doubles
+  uint32_t side = 0, tiles = 0;         // tiles along one side of the Gram matrix; side^2
+  uint32_t steps = 0;                   // MFMAs of one tile: those hpf_scores issues for K columns
+  uint32_t strips = 0;                  // side x ceil(side / DIVERSE_STRIP)
+  uint32_t tiles_per_wave = 0;          // the most tiles a wave computes: its strips' tiles, those past the side left out
+  uint64_t slab_bytes = 0;              // Pp x Pp doubles: at most 512 KB
+  uint32_t workgroups = 0;              // the grid of one launch
+  uint32_t lds_bytes = 0;
+  bool ok = false;                      // false: pool outside 1 .. DIVERSE_POOL_MAX, K = 0 or nobody selected
+};
+inline DiversePlan diverse_plan(uint32_t pool, uint32_t n_sel, uint32_t K, uint32_t CUs)
+{
+  DiversePlan p;
+  if (pool < 1 || pool > DIVERSE_POOL_MAX || K < 1 || n_sel < 1) return p;
+  p.Pp = (pool + 15u) & ~15u;
+  p.side = p.Pp / 16;
+  p.tiles = p.side * p.side;
+  p.steps = (K + 3u) / 4;
+  p.strips = diverse_strips(p.side);
+  for (uint32_t w = 0; w < DIVERSE_WAVES; ++w) {
+    uint32_t t = 0;
+    for (uint32_t s = w; s < p.strips; s += DIVERSE_WAVES) t += std::min(DIVERSE_STRIP, p.side - diverse_strip(s, p.side).tj0);
+    p.tiles_per_wave = std::max(p.tiles_per_wave, t);
+  }
+  p.slab_bytes = (uint64_t)p.Pp * p.Pp * 8;
+  const uint64_t by_mem = DIVERSE_SLABS_BYTES / p.slab_bytes, by_cus = (uint64_t)std::max(CUs, 1u) * DIVERSE_WGS_PER_CU;
+  p.workgroups = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(n_sel, std::min(by_mem, by_cus)));
+  p.lds_bytes = DIVERSE_LDS_BYTES;
+  p.ok = true;
+  return p;
+}
+
 // ---- the tiled phi pass: what is tiled, and where its segments run --------------------------------
 // Policy of one side, decided before anything is allocated.  The gathered matrix (rows_oth rows of row_bytes) is cut into
 // tiles of T consecutive rows; owner rows with at least light_below nonzeros are heavy (their nonzeros are regrouped by

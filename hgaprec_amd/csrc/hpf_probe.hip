@@ -11,7 +11,8 @@
 //
 // The second half launches the report kernels themselves -- heldout_ll_kernel, elbo_nnz_kernel, elbo_nnz_w_kernel,
 // rowmax_elog_kernel, elbo_gamma_kernel -- on the caller's arrays and grid (tests/test_gpu_report_terms.py), and
-// unit_rows_kernel as hpf_similar launches it (probe_unit_rows; tests/test_gpu_similar.py).
+// unit_rows_kernel as hpf_similar launches it (probe_unit_rows; tests/test_gpu_similar.py), and mmr_kernel as
+// hpf_recommend_diverse launches it, on a pool and unit rows of the test's (probe_mmr; tests/test_gpu_diverse.py).
 #include "hpf_kernels.hpp"
 
 #include <algorithm>
@@ -530,5 +531,42 @@ PROBE_API int probe_elbo_gamma(int grid_blocks, const double *S, const double *E
   hipLaunchKernelGGL(elbo_gamma_kernel, dim3((unsigned)grid_blocks), dim3(256), 0, 0, g);
   if (const int rc = finish_launch()) return rc;
   PROBE_TRY(hipMemcpy(partial, dpart.p, (size_t)grid_blocks * sizeof(double), hipMemcpyDeviceToHost));
+  return 0;
+}
+
+// mmr_kernel as hpf_recommend_diverse launches it, for ONE user, on the caller's pool and unit rows: U [rows x ld] (K factor
+// columns), pool_items / pool_scores [P] in list order (the kernel takes the prefix with a score > +0.0), out_* [topn]
+PROBE_API int probe_mmr(const double *U, uint32_t rows, uint32_t ld, uint32_t K, const uint32_t *pool_items, const double *pool_scores,
+                        uint32_t P, uint32_t topn, double lambda, uint32_t *out_items, double *out_scores, double *out_maxsim,
+                        double *out_mmr)
+{
+  if (!mat_ok(rows, ld) || K < 1 || K > ld || topn < 1 || topn > hpf_plan::DIVERSE_POOL_MAX || !(lambda >= 0.0 && lambda <= 1.0))
+    return (int)hipErrorInvalidValue;
+  const hpf_plan::DiversePlan dp = hpf_plan::diverse_plan(P, 1, K, 256);
+  if (!dp.ok) return (int)hipErrorInvalidValue;
+  DevBuf du, dpi, dps, dslab, doi, dos, dom, dok;
+  if (int rc = to_device(du, U, (size_t)rows * ld)) return rc;
+  if (int rc = to_device(dpi, pool_items, (size_t)P)) return rc;
+  if (int rc = to_device(dps, pool_scores, (size_t)P)) return rc;
+  PROBE_TRY(dslab.alloc((size_t)dp.workgroups * dp.slab_bytes));
+  PROBE_TRY(doi.alloc((size_t)topn * 4));
+  PROBE_TRY(dos.alloc((size_t)topn * 8));
+  PROBE_TRY(dom.alloc((size_t)topn * 8));
+  PROBE_TRY(dok.alloc((size_t)topn * 8));
+  PROBE_TRY(hipMemset(dslab.p, 0xff, (size_t)dp.workgroups * dp.slab_bytes));    // a cosine the Gram phase skipped reads back as NaN
+  PROBE_TRY(hipMemset(doi.p, 0xee, (size_t)topn * 4));
+  PROBE_TRY(hipMemset(dos.p, 0xff, (size_t)topn * 8));
+  PROBE_TRY(hipMemset(dom.p, 0xff, (size_t)topn * 8));
+  PROBE_TRY(hipMemset(dok.p, 0xff, (size_t)topn * 8));
+  MmrArgs a;
+  a.U = du.as<double>(); a.pool_items = dpi.as<uint32_t>(); a.pool_scores = dps.as<double>(); a.slab = dslab.as<double>();
+  a.out_items = doi.as<uint32_t>(); a.out_scores = dos.as<double>(); a.out_maxsim = dom.as<double>(); a.out_mmr = dok.as<double>();
+  a.lambda = lambda; a.rows = rows; a.ld = ld; a.K = K; a.n_sel = 1; a.pool = P; a.topn = topn; a.Pp = dp.Pp;
+  hipLaunchKernelGGL(mmr_kernel, dim3(dp.workgroups), dim3(256), 0, 0, a);
+  if (const int rc = finish_launch()) return rc;
+  PROBE_TRY(hipMemcpy(out_items, doi.p, (size_t)topn * 4, hipMemcpyDeviceToHost));
+  PROBE_TRY(hipMemcpy(out_scores, dos.p, (size_t)topn * 8, hipMemcpyDeviceToHost));
+  PROBE_TRY(hipMemcpy(out_maxsim, dom.p, (size_t)topn * 8, hipMemcpyDeviceToHost));
+  PROBE_TRY(hipMemcpy(out_mmr, dok.p, (size_t)topn * 8, hipMemcpyDeviceToHost));
   return 0;
 }

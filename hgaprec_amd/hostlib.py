@@ -93,6 +93,9 @@ def lib():
     if hasattr(L, "hg_write_thompson"):
         L.hg_write_thompson.argtypes = [C.c_char_p, vp, u32p, C.c_uint64, u32p, dp, C.c_uint32, C.c_uint32, C.c_uint32, u32p, u32p]
         L.hg_write_thompson.restype = C.c_int64
+    if hasattr(L, "hg_write_diverse"):
+        L.hg_write_diverse.argtypes = [C.c_char_p, vp, u32p, C.c_uint64, u32p, dp, dp, C.c_uint32, u32p, u32p, dp]
+        L.hg_write_diverse.restype = C.c_int64
     _lib = L
     return L
 
@@ -413,6 +416,28 @@ def write_thompson(path, sel, items, scores, real, row_ids, item_ids, given=None
     if n < 0:
         raise OSError(f"cannot write {path}")
     return n
+
+
+def write_diverse(path, sel, items, scores, maxsim, row_ids, item_ids, given=None):
+    """the writer of recommend_diverse.tsv: items / scores / maxsim are (len(sel), N) as Hpf.recommend_diverse returns
+    them; the lines are user id, item id, score, maxsim -- rows in the order of sel, each list in pick order up to its
+    first padding entry, under write_topn's rule for given items.  Returns (the number of lines, the sum of the maxsim
+    column)"""
+    s = np.ascontiguousarray(sel, np.uint32)
+    it = np.ascontiguousarray(items, np.uint32)
+    sc = np.ascontiguousarray(scores, np.float64)
+    ms = np.ascontiguousarray(maxsim, np.float64)
+    if it.ndim != 2 or it.shape[0] != s.size or sc.shape != it.shape or ms.shape != it.shape:
+        raise ValueError("items, scores and maxsim: (len(sel), N)")
+    ri, ii = np.ascontiguousarray(row_ids, np.uint32), np.ascontiguousarray(item_ids, np.uint32)
+    u32p, dp = C.POINTER(C.c_uint32), C.POINTER(C.c_double)
+    total = C.c_double(0.0)
+    n = lib().hg_write_diverse(str(path).encode(), None if given is None else given._r, s.ctypes.data_as(u32p), s.size,
+                               it.ctypes.data_as(u32p), sc.ctypes.data_as(dp), ms.ctypes.data_as(dp), it.shape[1],
+                               ri.ctypes.data_as(u32p), ii.ctypes.data_as(u32p), C.byref(total))
+    if n < 0:
+        raise OSError(f"cannot write {path}")
+    return n, total.value
 
 
 def format_fixed8(values):

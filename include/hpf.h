@@ -546,6 +546,49 @@ int  hpf_recommend_thompson(hpf_handle *h, const uint32_t *users, uint32_t n_sel
                             uint64_t seed, uint32_t draw,
                             uint32_t *out_items /* n_sel x topn */, double *out_scores /* n_sel x topn */);
 
+/* (an extension.)  Diversified top-N: greedy maximal marginal relevance (MMR) over a pool of hpf_recommend's candidates --
+ * pick the next item by relevance minus its similarity to what is already picked, so that the head of a list is not filled
+ * by the near-duplicates that load on the user's strongest factor.
+ *
+ * Pool.  For a selected user the pool is the entries (c_j, r_j), j = 0 .. P - 1, of the list hpf_recommend returns for the
+ * same user, mask list and topn = pool whose score is > +0.0 (no padding, no masked item, no true zero): a prefix of that
+ * list, in its order, items and scores bit for bit hpf_recommend's.  P may be 0 and may be less than topn.
+ *
+ * Similarity.  G(a, b) is the cosine of rows a and b of E[beta] over the K factor columns as hpf_similar(side 1,
+ * HPF_SIM_COSINE) defines it: the rows at unit length U (overflow-free, a row scaled by a power of two has the same U),
+ * then the chain hpf_scores issues -- one MFMA accumulator per output over c = 0, 4, 8, ..., the tail padded by zeros.  Bit
+ * for bit it is the double hpf_scores returns for (a, b) on a handle without bias whose E[theta] and E[beta] are both U.
+ * Bias columns take no part.  G is symmetric bit for bit (a product does not depend on which operand is which).
+ *
+ * Greedy selection.  Every step is ONE IEEE fp64 operation, nothing contracted into an FMA, no reciprocal:
+ *   rel_j = r_j / r_0 (correctly rounded);  om = 1.0 - lambda;  pen_j = 0.0
+ *   for t = 0 .. min(topn, P) - 1:
+ *     key_j = lambda * rel_j - om * pen_j            for every pool entry not yet picked
+ *     j* = the entry with the largest key, compared as values (keys may be negative); among equal keys the smallest j
+ *     out_items[t] = c_j*, out_scores[t] = r_j*, out_maxsim[t] = pen_j*, out_mmr[t] = key_j*
+ *     pen_j = max(pen_j, G(c_j, c_j*))               for every entry still unpicked
+ * Positions from min(topn, P) on are (0xffffffff, 0.0, 0.0, 0.0).
+ * So: with lambda = 1 the lists are the entries of hpf_recommend(topn) with a positive score, bit for bit, then padding;
+ * with pool == topn a list is a permutation of that set; the first pick is always c_0; a user's result depends only on the
+ * user's pool and the rows of U of the pool's items -- not on batches, selection, grid or call order; a user selected
+ * twice gives two equal rows.
+ *
+ * HPF_ERR_INVALID: topn outside 1 .. 256, pool outside topn .. HPF_DIVERSE_POOL_MAX, lambda NaN or outside [0, 1], and
+ * hpf_recommend's cases (a user or mask item out of range, a malformed mask_ptr, a null pointer with work to do).
+ * HPF_ERR_STATE: no CSR, or no E on either side.  HPF_ERR_UNSUPPORTED: an odd row stride.  n_sel = 0 is HPF_OK.  All
+ * returned before anything is launched.
+ * Synchronous; the model state is not written; any n_ranks (local users only).
+ * Device memory beyond inputs and outputs, freed when the call returns: hpf_recommend's bit rows and candidate buffers, the
+ * pool lists (n_sel x pool), U of n_items x ld doubles, and per workgroup of the persistent grid a slab of Pp x Pp doubles
+ * for the Gram matrix (Pp = pool rounded up to 16; at most 512 KB each, 256 MB in all). */
+#define HPF_DIVERSE_POOL_MAX 256
+int  hpf_recommend_diverse(hpf_handle *h, const uint32_t *users, uint32_t n_sel,
+                           const uint64_t *mask_ptr, const uint32_t *mask_items,
+                           uint32_t topn, uint32_t pool, double lambda,
+                           uint32_t *out_items /* n_sel x topn */, double *out_scores /* n_sel x topn */,
+                           double *out_maxsim /* n_sel x topn, may be NULL */,
+                           double *out_mmr /* n_sel x topn, may be NULL */);
+
 /* (an extension; the reference has no counterpart.)  Why a score is what it is: the T largest of the terms whose sum a
  * pair's score is.  For pair p the terms are c_k = E[theta_u k] * E[beta_i k], k < K -- each ONE IEEE fp64 multiplication,
  * nothing fused into it and no reciprocal: the double returned is, bit for bit, the product a host forms from the two
